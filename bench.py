@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: 40 ms packets/s, encode + decode round trip.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: it sets up, runs W warm-up steps, times exactly K steps and prints the result line
+(value, ms_per_step, ...).  --dump-outputs DIR also writes what the timed path computed in its last step as DIR/<name>.npy
+(dump_outputs below).  --full adds everything else the line can carry, each measured or checked after the timed steps as before:
+the reference-hashed parity of the first and third steps, the per-kernel timings and the roofline / VALU-issue figures built on
+them, the shader clock, the extra legs (N = 1) and the CPU baseline.  Of the fields listed below, a plain run's line holds `value`.
 
 N > 1 runs ONE RANK PER GPU.  Started under a launcher (the driver's `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N`) it reads RANK / LOCAL_RANK / WORLD_SIZE; started plainly (`python bench.py --gpus N`) it launches the N ranks itself
@@ -222,6 +228,11 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=0, help="streams per GPU (default: 4096 = configs[2] at N = 1, 8192 = configs[4] at N > 1)")
     ap.add_argument("--first-stream", type=int, default=-1, help="global index of this process's first stream (default: rank * streams)")
     ap.add_argument("--packets", type=int, default=50, help="40 ms packets per stream per step (SURVEY 8(d): P >= 50 = 2 s of audio)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: parity against the reference hashes, per-kernel timings, "
+                                                        "roofline / VALU issue, shader clock, the extra legs and the CPU baseline (the --no-* options "
+                                                        "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, "
+                                                                        "at most 64 MB: a fixed sample of the streams)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] / configs[3] legs (N = 1 only)")
     ap.add_argument("--no-hash", action="store_true", help="skip the hashes of the first step (saves the device-to-host copies; parity_checked = null)")
@@ -231,6 +242,43 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-packets-per-stream", type=int, default=400)
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this many bytes in all
+DUMP_SEED = 20261015           # the fixed sample of streams whose payloads and PCM are written in full
+
+
+def dump_outputs(path, nb, bits, pcm, first_stream):
+    """What the timed path hands its caller for the last timed step, as .npy files under `path`:
+      nbytes       float32 [n, P, 2]        nBytesOut of every packet (total, MD2 + 8)
+      pcm_energy   float64 [n, P]           sum of squares of the decoded samples of every packet (exact: < 2^53)
+      streams_all  float64 [n]              global indices of the streams in nbytes / pcm_energy: every stream (n = N) unless
+                                            N x P passes 1 M packets
+      streams      float64 [k]              global indices of the sampled streams, ascending
+      payload      float32 [k, P, slot]     payload bytes of the sampled streams (bytes past nBytesOut[0] set to 0: the slots keep
+                                            stale tails of earlier steps, which are no output)
+      pcm          float32 [k, P, 640]      decoded PCM of the sampled streams
+    nb / bits / pcm are the device tensors.  The sample (numpy default_rng(DUMP_SEED)) depends on N and P only; k and, for very
+    long steps, the trailing packets kept are chosen so that the files stay within DUMP_BYTES."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    N, P, slot = bits.shape
+    S = pcm.shape[2]
+    n_all = min(N, max(1, (DUMP_BYTES // 4) // (P * 16)))          # nbytes + pcm_energy: 16 bytes per packet
+    p_keep = min(P, max(1, (DUMP_BYTES // 2) // ((slot + S) * 4)))  # one sampled stream must fit in the other half
+    k = min(N, max(1, (DUMP_BYTES // 2) // (p_keep * (slot + S) * 4)))
+    rng = np.random.default_rng(DUMP_SEED)
+    rows_all = np.arange(N) if n_all == N else np.sort(rng.choice(N, n_all, replace=False))
+    rows = np.arange(N) if k == N else np.sort(rng.choice(N, k, replace=False))
+    ia, ik = torch.from_numpy(rows_all).to(bits.device), torch.from_numpy(rows).to(bits.device)
+    energy = torch.cat([pcm.index_select(0, ia[a:a + 256]).double().square().sum(-1) for a in range(0, n_all, 256)])
+    nb_k, bits_k = nb.index_select(0, ik)[:, P - p_keep:], bits.index_select(0, ik)[:, P - p_keep:]
+    bits_k = torch.where(torch.arange(slot, device=bits.device)[None, None, :] < nb_k[:, :, 0:1].long(), bits_k, torch.zeros_like(bits_k))
+    out = {"nbytes": nb.index_select(0, ia).float(), "pcm_energy": energy, "streams_all": torch.from_numpy(rows_all + first_stream).double(),
+           "streams": torch.from_numpy(rows + first_stream).double(),
+           "payload": bits_k.float(), "pcm": pcm.index_select(0, ik)[:, P - p_keep:].float()}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def timed_loop(fn, steps, warmup, barrier):
@@ -253,6 +301,8 @@ def main():
     from solo_amd import dist as sdist
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     launched = "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
         # plain `python bench.py --gpus N`: become the launcher of N ranks (never silently time one GPU)
@@ -344,59 +394,67 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # The first step after a reset is the one the compiled reference reproduces bit for bit from the same input: hash its outputs
-    # per block of 4096 streams (outside the timed region).  Later steps continue the streams' state with the same input.
-    step()
-    drain()
-    torch.cuda.synchronize()
-    mean_payload = float(nb[:, :, 0].float().mean().item())
-    first_step = (None, None, None) if args.no_hash else (nb.cpu().numpy(), bits.cpu().numpy(), out.cpu().numpy())
-    # Steps 2 and 3 run under the TIMED schedule (pipelined: the encode of step 3 is issued before the decode of step 2) and continue the
-    # streams' state; the third step's payloads and PCM are hashed as well (the reference encoded the same 50 packets three times in a row)
-    step()
-    step()
-    jl = (step_no[0] - 1) & 1 if overlap else 0
-    drain()
-    torch.cuda.synchronize()
-    third_step = (None, None, None) if args.no_hash else (nb2[jl].cpu().numpy(), bits2[jl].cpu().numpy(), out.cpu().numpy())
-    for _ in range(max(0, args.warmup - 3)):
+    # Warm-up: W steps (--full: at least 3).  Under --full the first step after a reset, the one the compiled reference reproduces bit
+    # for bit from the same input, is hashed per block of 4096 streams (outside the timed region); steps 2 and 3 run under the TIMED
+    # schedule (pipelined: the encode of step 3 is issued before the decode of step 2) and continue the streams' state, and the third
+    # step's payloads and PCM are hashed as well (the reference encoded the same 50 packets three times in a row).  The drains in
+    # between change when the decodes are issued, not what they compute.
+    first_step = third_step = (None, None, None)
+    mean_payload = None
+    for w in range(max(3, args.warmup) if args.full else args.warmup):
         step()
+        if args.full and w in (0, 2):
+            jl = (step_no[0] - 1) & 1 if overlap else 0
+            drain()
+            torch.cuda.synchronize()
+            if w == 0:
+                mean_payload = float(nb[:, :, 0].float().mean().item())
+            if not args.no_hash:
+                host = (nb2[jl].cpu().numpy(), bits2[jl].cpu().numpy(), out.cpu().numpy())
+                first_step, third_step = (host, third_step) if w == 0 else (first_step, host)
     drain()
     barrier()
     payload_acc.zero_()
     t0 = time.perf_counter()
     for k in range(args.steps):
         step()
+    jl = (step_no[0] - 1) & 1 if overlap else 0           # (the buffers the last timed step encoded into)
     drain()                                               # (the last step's decode: every packet is encoded AND decoded in the timed region)
     barrier()
     dt_local = time.perf_counter() - t0
     payload_bytes_timed = int(payload_acc.item())
-    # effective shader clock under vector load, right after the timed steps (the boxes of a pool differ by ~10 %: lines are comparable
-    # only with it); a ~1 ms probe kernel of the library, outside the timed region
-    sclk_mhz = solo_amd.shader_clock_mhz()
-    # per-kernel durations: a few extra steps outside the timed region (reading the events synchronises the stream)
-    if overlap:
-        batch.set_async_join(False)
-        overlap = False
-    batch.set_timing(True)
-    for _ in range(min(3, args.steps)):
-        step()
-        for name, v in batch.last_kernel_ms().items():
-            kms[name].append(v)
-    batch.set_timing(False)
-    enc_chunks = max(1, batch.last_encode_chunks())
-    dt = sdist.max_over_ranks(dt_local, dist, dev) if use_dist else dt_local
-    assert int(st_e.abs().max()) == 0 and int(st_d.abs().max()) == 0, "codec status != 0"
-    kavg = {n: float(np.mean(v)) for n, v in kms.items()}
     packets_step = N * P
+    if mean_payload is None:
+        mean_payload = payload_bytes_timed / float(packets_step * args.steps)
+    assert int(st_e.abs().max()) == 0 and int(st_d.abs().max()) == 0, "codec status != 0"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nb2[jl], bits2[jl], out, first)
+    dt = sdist.max_over_ranks(dt_local, dist, dev) if use_dist else dt_local
     value = world * packets_step * args.steps / dt
+    sclk_mhz, checked, detail, checked3 = None, None, [], None
+    if args.full:
+        # effective shader clock under vector load, right after the timed steps (the boxes of a pool differ by ~10 %: lines are comparable
+        # only with it); a ~1 ms probe kernel of the library, outside the timed region
+        sclk_mhz = solo_amd.shader_clock_mhz()
+        # per-kernel durations: a few extra steps outside the timed region (reading the events synchronises the stream)
+        if overlap:
+            batch.set_async_join(False)
+            overlap = False
+        batch.set_timing(True)
+        for _ in range(min(3, args.steps)):
+            step()
+            for name, v in batch.last_kernel_ms().items():
+                kms[name].append(v)
+        batch.set_timing(False)
+        enc_chunks = max(1, batch.last_encode_chunks())
+        assert int(st_e.abs().max()) == 0 and int(st_d.abs().max()) == 0, "codec status != 0"
+        kavg = {n: float(np.mean(v)) for n, v in kms.items()}
 
-    gold, gmap = golden_blocks()
-    hashes = None if args.no_hash else sdist.block_hashes(*first_step)
-    checked, detail = check_blocks(first, hashes, gold, gmap, P, RATE, SLOT)
+        gold, gmap = golden_blocks()
+        hashes = None if args.no_hash else sdist.block_hashes(*first_step)
+        checked, detail = check_blocks(first, hashes, gold, gmap, P, RATE, SLOT)
     # the state-continued third step under the pipelined schedule (reference hashes exist for block 0)
-    checked3 = None
-    if not args.no_hash and gold is not None and first == 0 and gmap.get(0, {}).get("step3_payload_md5"):
+    if args.full and not args.no_hash and gold is not None and first == 0 and gmap.get(0, {}).get("step3_payload_md5"):
         b3 = third_step[1][:4096]
         b3 = np.where(np.arange(b3.shape[2])[None, None, :] < third_step[0][:4096, :, 0:1].astype(np.int64), b3, 0).astype(np.uint8)   # (the slots still hold the tails of step 1's payloads)
         h3 = sdist.block_hashes(third_step[0][:4096], b3, third_step[2][:4096])[0]
@@ -406,7 +464,7 @@ def main():
 
     # ---- extra legs (N = 1): BASELINE configs[1] and configs[3], each its own timed loop ------------------------------------
     extra = {}
-    if world == 1 and not args.no_extra and not args.no_overlap:
+    if args.full and world == 1 and not args.no_extra and not args.no_overlap:
         # the same round trip with the strictly sequential schedule (decode of a step done before the next encode is issued)
         def seq_step():
             batch.encode(pcm, bits, nb, st_e)
@@ -415,7 +473,7 @@ def main():
         dt_s = timed_loop(seq_step, ns, 1, barrier)
         extra["sequential_schedule"] = {"workload": "the headline round trip, encode then decode on one stream (--no-overlap)", "steps": ns, "warmup": 1,
                                         "value": round(packets_step * ns / dt_s, 1), "unit": "40ms packets/s (encode+decode)", "ms_per_step": round(dt_s / ns * 1e3, 3)}
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         # configs[1]: the same 4096 streams, encode only
         dt_e = timed_loop(lambda: batch.encode(pcm, bits, nb, st_e), args.steps, max(1, args.warmup), barrier)
         assert int(st_e.abs().max()) == 0
@@ -474,7 +532,7 @@ def main():
                                                     "on one GPU: tests/test_gpu_fullsize.py::test_config4_all_blocks_on_one_gpu"}
         del b8, bits8, nb8, out8, pcm8, recv
 
-    if world == 1 and not args.no_extra and P % 2 == 0:
+    if args.full and world == 1 and not args.no_extra and P % 2 == 0:
         # the 32 kHz mode (`samplerate = 32000`: 1280-sample packets, SILK wide band inside, 24 kbps): the same input
         # samples taken as 32 kHz audio, P / 2 packets per stream per step, sequential encode then decode
         bw = solo_amd.SoloBatch(N, rate=24000, encoder=True, decoder=True, slot_bytes=SLOT, samplerate=32000)
@@ -513,51 +571,52 @@ def main():
     records = sdist.gather_records(record, dist) if use_dist else [record]
 
     if rank == 0:
-        all_checked = [r["parity_checked"] for r in records]
-        parity = (all(c is True for c in all_checked) if all(c is not None for c in all_checked) else (False if any(c is False for c in all_checked) else None))
-        # ALGORITHMIC bytes per packet: what crosses the boundary, with the run's mean payload
-        enc_alg = PCM_BYTES + mean_payload + 4.0
-        dec_alg = mean_payload + 4.0 + PCM_BYTES
-        # the three encoder kernels are stages of ONE pass over the boundary data of a packet (PCM in, payload + lengths out): each
-        # is priced with the encode-only boundary bytes of the packets it handles per launch; the hand-over records between them are
-        # implementation traffic
-        alg = {"analysis": enc_alg, "quantiser": enc_alg, "coding": enc_alg, "decode": dec_alg}
-        split_dec = os.environ.get("SOLO_DEC_SPLIT", "1") != "0"
-        stage_kernels = {"analysis": ["solo_enc_analysis_kernel"], "quantiser": ["solo_nsq_kernel"],
-                         "coding": ["solo_enc_coding_kernel", "solo_enc_rc_kernel"],
-                         "decode": ["solo_dec_synth_kernel", "solo_dec_extract_kernel"] if split_dec else ["solo_decode_kernel"]}
-        kname = {n: v[0] for n, v in stage_kernels.items()}
-        traffic = _profile_json("hbm_traffic.json") or {}
-        insts = _profile_json("wave_instructions.json") or {}
         src_hash = solo_amd.kernel_source_hash()
-        prof_hash = {"hbm_traffic.json": traffic.get("kernel_source_sha16"), "wave_instructions.json": insts.get("kernel_source_sha16")}
-        prof_ok = all(v == src_hash for v in prof_hash.values())
-        dec_chunk = int(os.environ.get("SOLO_DEC_CHUNK", "64"))       # (solo_api.hip: one chunk up to 64 packets)
-        dec_first = int(os.environ.get("SOLO_DEC_FIRST_CHUNK", "64"))
-        if split_dec and dec_chunk > 0:
-            cp = min(P, dec_chunk)
-            c0 = dec_first if (P > 2 * dec_first and cp > dec_first) else cp
-            dec_chunks = 1 + (P - c0 + cp - 1) // cp
-        else:
-            dec_chunks = 1
-        nl = {n: (enc_chunks if n != "decode" else dec_chunks) for n in kavg}
+        if args.full:
+            all_checked = [r["parity_checked"] for r in records]
+            parity = (all(c is True for c in all_checked) if all(c is not None for c in all_checked) else (False if any(c is False for c in all_checked) else None))
+            # ALGORITHMIC bytes per packet: what crosses the boundary, with the run's mean payload
+            enc_alg = PCM_BYTES + mean_payload + 4.0
+            dec_alg = mean_payload + 4.0 + PCM_BYTES
+            # the three encoder kernels are stages of ONE pass over the boundary data of a packet (PCM in, payload + lengths out): each
+            # is priced with the encode-only boundary bytes of the packets it handles per launch; the hand-over records between them are
+            # implementation traffic
+            alg = {"analysis": enc_alg, "quantiser": enc_alg, "coding": enc_alg, "decode": dec_alg}
+            split_dec = os.environ.get("SOLO_DEC_SPLIT", "1") != "0"
+            stage_kernels = {"analysis": ["solo_enc_analysis_kernel"], "quantiser": ["solo_nsq_kernel"],
+                             "coding": ["solo_enc_coding_kernel", "solo_enc_rc_kernel"],
+                             "decode": ["solo_dec_synth_kernel", "solo_dec_extract_kernel"] if split_dec else ["solo_decode_kernel"]}
+            kname = {n: v[0] for n, v in stage_kernels.items()}
+            traffic = _profile_json("hbm_traffic.json") or {}
+            insts = _profile_json("wave_instructions.json") or {}
+            prof_hash = {"hbm_traffic.json": traffic.get("kernel_source_sha16"), "wave_instructions.json": insts.get("kernel_source_sha16")}
+            prof_ok = all(v == src_hash for v in prof_hash.values())
+            dec_chunk = int(os.environ.get("SOLO_DEC_CHUNK", "64"))       # (solo_api.hip: one chunk up to 64 packets)
+            dec_first = int(os.environ.get("SOLO_DEC_FIRST_CHUNK", "64"))
+            if split_dec and dec_chunk > 0:
+                cp = min(P, dec_chunk)
+                c0 = dec_first if (P > 2 * dec_first and cp > dec_first) else cp
+                dec_chunks = 1 + (P - c0 + cp - 1) // cp
+            else:
+                dec_chunks = 1
+            nl = {n: (enc_chunks if n != "decode" else dec_chunks) for n in kavg}
 
-        def tr_launch(n):
-            v = [traffic.get(k + "_bytes_per_packet") for k in stage_kernels[n]]
-            return None if any(x is None for x in v) else int(sum(v) * packets_step / nl[n])
-        kernels = {kname[n]: {"launches_per_step": nl[n], "avg_launch_ms": round(kavg[n] / nl[n], 4),
-                              "kernels_of_the_stage": stage_kernels[n],
-                              "packets_per_launch": packets_step // nl[n],
-                              "algorithmic_bytes_per_launch": int(alg[n] * packets_step / nl[n]),
-                              "achieved_GBps": round(alg[n] * packets_step / (kavg[n] * 1e-3) / 1e9, 4),
-                              "frac_of_hbm_peak": round(alg[n] * packets_step / (kavg[n] * 1e-3) / 1e9 / HBM_PEAK_GBS, 7),
-                              "traffic_bytes_per_launch": tr_launch(n),
-                              "valu_lane_utilisation": {k: (insts.get("valu_lane_utilisation") or {}).get(k) for k in stage_kernels[n]}} for n in kavg}
-        dom = max(kavg, key=kavg.get)
-        alg_launch = alg[dom] * packets_step / nl[dom]
-        achieved = alg_launch / (kavg[dom] / nl[dom] * 1e-3) / 1e9
-        step_alg = (enc_alg + dec_alg) * packets_step
-        step_gbs = step_alg / (dt / args.steps) / 1e9
+            def tr_launch(n):
+                v = [traffic.get(k + "_bytes_per_packet") for k in stage_kernels[n]]
+                return None if any(x is None for x in v) else int(sum(v) * packets_step / nl[n])
+            kernels = {kname[n]: {"launches_per_step": nl[n], "avg_launch_ms": round(kavg[n] / nl[n], 4),
+                                  "kernels_of_the_stage": stage_kernels[n],
+                                  "packets_per_launch": packets_step // nl[n],
+                                  "algorithmic_bytes_per_launch": int(alg[n] * packets_step / nl[n]),
+                                  "achieved_GBps": round(alg[n] * packets_step / (kavg[n] * 1e-3) / 1e9, 4),
+                                  "frac_of_hbm_peak": round(alg[n] * packets_step / (kavg[n] * 1e-3) / 1e9 / HBM_PEAK_GBS, 7),
+                                  "traffic_bytes_per_launch": tr_launch(n),
+                                  "valu_lane_utilisation": {k: (insts.get("valu_lane_utilisation") or {}).get(k) for k in stage_kernels[n]}} for n in kavg}
+            dom = max(kavg, key=kavg.get)
+            alg_launch = alg[dom] * packets_step / nl[dom]
+            achieved = alg_launch / (kavg[dom] / nl[dom] * 1e-3) / 1e9
+            step_alg = (enc_alg + dec_alg) * packets_step
+            step_gbs = step_alg / (dt / args.steps) / 1e9
         res = {
             "metric": "40 ms frames/sec (encode+decode) per GPU; concurrent real-time WB streams @1/2/4/8 MI355X",
             "value": round(value, 1), "unit": "40ms packets/s (encode+decode)", "n_gpus": world, "steps": args.steps,
@@ -574,70 +633,73 @@ def main():
                        "schedule": ("consecutive steps pipelined: encode of step k+1 issued before the decode of step k "
                                     "(solo_batch_set_async_join, double-buffered bitstreams); every packet is encoded AND decoded inside the timed region" if not args.no_overlap
                                     else "encode then decode on one stream")},
-            "parity_checked": parity,
-            "parity": {"what": "first step (freshly reset streams) hashed per block of 4096 streams: md5(nBytes || payload slots) and md5(decoded PCM), "
-                               "compared with the compiled reference's hashes of the same streams (tests/golden/bench_blocks.json); block 0 also after "
-                               "steps 2 and 3 run under the timed (pipelined) schedule: the third, state-continued step against the reference's third pass",
-                       "third_step_pipelined_checked": checked3,
-                       "ranks": [{"rank": r["rank"], "first_stream": r["first_stream"], "checked": r["parity_checked"], "blocks": r["blocks"]} for r in records]},
-            "shader_clock_mhz_under_vector_load": None if sclk_mhz is None else round(sclk_mhz, 1),
-            "clock_note": "effective shader clock of rank 0 right after the timed steps while every SIMD runs vector instructions (solo_debug_clock: shader-clock "
-                          "counter ticks per 100 MHz tick); boxes of a pool differ, compare lines at equal clock",
             "realtime_streams": round(value / 25.0, 1),
             "per_gpu_packets_per_s": [r["packets_per_s"] for r in records],
             "whole_node_packets_per_s": round(value, 1),
             "rccl_ranks": world if use_dist else 0,
             "ranks": [{k: v for k, v in r.items() if k != "blocks"} for r in records],
-            "roofline": {"kernel": kname[dom], "bound": "hbm", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 7), "traffic": tr_launch(dom),
-                         "traffic_is": "L2 memory-side (fabric) bytes per launch, rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE: Infinity-Cache hits are included (no counter "
-                                       "behind the Infinity Cache is exposed), so an UPPER bound of the HBM bytes; the 32 MB quantiser ring lives in the 256 MiB Infinity Cache",
-                         "avg_launch_ms": round(kavg[dom] / nl[dom], 4), "launches_per_step": nl[dom],
-                         "packets_per_launch": packets_step // nl[dom],
-                         "algorithmic_bytes_per_packet": round(alg[dom], 2),
-                         "algorithmic_bytes_per_launch": int(alg_launch),
-                         "formula": "achieved = packets_per_launch x (1280 + mean_payload + 4) B / avg_launch_ms; frac = achieved / 8 TB/s "
-                                    "(SURVEY 8(d); hand-over records and stream state count as traffic, not as algorithmic bytes).  Every encoder "
-                                    "stage in `kernels` is priced with the full encode boundary bytes of its packets (the stages are one pass over "
-                                    "a packet): their achieved_GBps are per stage, not additive",
-                         "whole_step": {"algorithmic_bytes_per_packet": round(enc_alg + dec_alg, 2), "achieved": round(step_gbs, 4),
-                                        "frac": round(step_gbs / HBM_PEAK_GBS, 7)},
-                         "note": "serial fixed-point recursions: instruction-issue / latency bound, not HBM bound -- see valu_issue"},
-            "kernels": kernels,
-            "launches_per_step": {k: nl[n] for n, ks in stage_kernels.items() for k in ks},
             "kernel_source_sha16": src_hash,
-            "profile_matches_head": prof_ok,
-            "profile_source": {"files": prof_hash, "git_head_of_profile": traffic.get("git_head"), "summary": insts.get("source")},
         }
-        if extra:
-            res["extra"] = extra
-        peak_issue = N_SIMD * CLOCK_HZ / CYCLES_PER_VALU
-        if insts.get("valu_per_packet_round_trip"):
-            v = insts["valu_per_packet_round_trip"] * (value / world)
-            # share of the time a SIMD's vector unit is executing: VALU wave-instructions of this run per SIMD and second (SQ_INSTS_VALU of the
-            # committed counter pass x this run's packet rate) x the measured cost of an instruction of this path's class mix (a third of them
-            # full rate at 1.15 ns, two thirds half rate at 1.85 ns per SIMD: profiles/r05_issue_model.txt, tools/debug/nsq_row_mix.py)
-            busy = v / N_SIMD * (1.15e-9 / 3.0 + 2.0 * 1.85e-9 / 3.0)
-            res["valu_issue"] = {"bound": "valu_issue", "achieved": round(v / 1e9, 2), "peak": round(peak_issue / 1e9, 1), "valu_busy_frac": round(busy, 3),
-                                 "unit": "G wave-instructions/s (VALU)", "frac": round(v / peak_issue, 4),
-                                 "valu_wave_instructions_per_packet": insts.get("valu_per_packet"),
-                                 "all_wave_instructions_per_packet": insts.get("all_per_packet"),
-                                 "valu_lane_utilisation": insts.get("valu_lane_utilisation"),
-                                 "lane_utilisation_is": "SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU): lanes switched on (EXEC) while a vector instruction executes",
-                                 "source": insts.get("source"), "from_this_build": prof_ok,
-                                 "note": "SQ_INSTS_VALU per packet of each kernel (rocprofv3 --pmc pass) x packets/s of this run, per GPU; "
-                                         "peak = 1024 SIMD-32 x 2.4 GHz / 2 cycles per wave64 VALU instruction (nominal).  Measured on gfx950 "
-                                         "(tools/debug/mb_mix.hip, profiles/r05_issue_model.txt; round 4: mb_valu.hip, r04_valu_microbench.txt): a SIMD retires one "
-                                         "add / sub / logic / arithmetic-shift instruction with register operands per 1.1 - 1.2 ns and one multiply / left shift / "
-                                         "min / max / select / DPP / 3-operand / SGPR-operand instruction per 1.8 - 1.9 ns (a v_mul_hi + v_add pair 3.0, v_mad_i64_i32 2.1); "
-                                         "scalar and LDS instructions of OTHER waves overlap with them (a type mix costs ~ the maximum, not the sum); one wave issues "
-                                         "a dependent instruction every 3.6 - 4.0 ns, two waves interleave perfectly, four saturate the unit.  The encoder pipeline "
-                                         "holds 5 waves per SIMD (registers and LDS full) and keeps the vector unit ~65 % busy: time follows the instruction count"}
-        if world == 1 and not args.no_cpu_baseline:
-            cb = cpu_baseline(args.cpu_seconds, args.cpu_packets_per_stream)
-            if cb and cb.get("per_core_packets_per_s"):
-                cb["gpu_equals_reference_cores"] = round(value / cb["per_core_packets_per_s"], 1)
-            res["cpu_baseline"] = cb
+        if args.full:
+            res.update({
+                "parity_checked": parity,
+                "parity": {"what": "first step (freshly reset streams) hashed per block of 4096 streams: md5(nBytes || payload slots) and md5(decoded PCM), "
+                                   "compared with the compiled reference's hashes of the same streams (tests/golden/bench_blocks.json); block 0 also after "
+                                   "steps 2 and 3 run under the timed (pipelined) schedule: the third, state-continued step against the reference's third pass",
+                           "third_step_pipelined_checked": checked3,
+                           "ranks": [{"rank": r["rank"], "first_stream": r["first_stream"], "checked": r["parity_checked"], "blocks": r["blocks"]} for r in records]},
+                "shader_clock_mhz_under_vector_load": None if sclk_mhz is None else round(sclk_mhz, 1),
+                "clock_note": "effective shader clock of rank 0 right after the timed steps while every SIMD runs vector instructions (solo_debug_clock: shader-clock "
+                              "counter ticks per 100 MHz tick); boxes of a pool differ, compare lines at equal clock",
+                "roofline": {"kernel": kname[dom], "bound": "hbm", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 7), "traffic": tr_launch(dom),
+                             "traffic_is": "L2 memory-side (fabric) bytes per launch, rocprofv3 FETCH_SIZE x 2 + WRITE_SIZE: Infinity-Cache hits are included (no counter "
+                                           "behind the Infinity Cache is exposed), so an UPPER bound of the HBM bytes; the 32 MB quantiser ring lives in the 256 MiB Infinity Cache",
+                             "avg_launch_ms": round(kavg[dom] / nl[dom], 4), "launches_per_step": nl[dom],
+                             "packets_per_launch": packets_step // nl[dom],
+                             "algorithmic_bytes_per_packet": round(alg[dom], 2),
+                             "algorithmic_bytes_per_launch": int(alg_launch),
+                             "formula": "achieved = packets_per_launch x (1280 + mean_payload + 4) B / avg_launch_ms; frac = achieved / 8 TB/s "
+                                        "(SURVEY 8(d); hand-over records and stream state count as traffic, not as algorithmic bytes).  Every encoder "
+                                        "stage in `kernels` is priced with the full encode boundary bytes of its packets (the stages are one pass over "
+                                        "a packet): their achieved_GBps are per stage, not additive",
+                             "whole_step": {"algorithmic_bytes_per_packet": round(enc_alg + dec_alg, 2), "achieved": round(step_gbs, 4),
+                                            "frac": round(step_gbs / HBM_PEAK_GBS, 7)},
+                             "note": "serial fixed-point recursions: instruction-issue / latency bound, not HBM bound -- see valu_issue"},
+                "kernels": kernels,
+                "launches_per_step": {k: nl[n] for n, ks in stage_kernels.items() for k in ks},
+                "profile_matches_head": prof_ok,
+                "profile_source": {"files": prof_hash, "git_head_of_profile": traffic.get("git_head"), "summary": insts.get("source")},
+            })
+            if extra:
+                res["extra"] = extra
+            peak_issue = N_SIMD * CLOCK_HZ / CYCLES_PER_VALU
+            if insts.get("valu_per_packet_round_trip"):
+                v = insts["valu_per_packet_round_trip"] * (value / world)
+                # share of the time a SIMD's vector unit is executing: VALU wave-instructions of this run per SIMD and second (SQ_INSTS_VALU of the
+                # committed counter pass x this run's packet rate) x the measured cost of an instruction of this path's class mix (a third of them
+                # full rate at 1.15 ns, two thirds half rate at 1.85 ns per SIMD: profiles/r05_issue_model.txt, tools/debug/nsq_row_mix.py)
+                busy = v / N_SIMD * (1.15e-9 / 3.0 + 2.0 * 1.85e-9 / 3.0)
+                res["valu_issue"] = {"bound": "valu_issue", "achieved": round(v / 1e9, 2), "peak": round(peak_issue / 1e9, 1), "valu_busy_frac": round(busy, 3),
+                                     "unit": "G wave-instructions/s (VALU)", "frac": round(v / peak_issue, 4),
+                                     "valu_wave_instructions_per_packet": insts.get("valu_per_packet"),
+                                     "all_wave_instructions_per_packet": insts.get("all_per_packet"),
+                                     "valu_lane_utilisation": insts.get("valu_lane_utilisation"),
+                                     "lane_utilisation_is": "SQ_THREAD_CYCLES_VALU / (64 x SQ_ACTIVE_INST_VALU): lanes switched on (EXEC) while a vector instruction executes",
+                                     "source": insts.get("source"), "from_this_build": prof_ok,
+                                     "note": "SQ_INSTS_VALU per packet of each kernel (rocprofv3 --pmc pass) x packets/s of this run, per GPU; "
+                                             "peak = 1024 SIMD-32 x 2.4 GHz / 2 cycles per wave64 VALU instruction (nominal).  Measured on gfx950 "
+                                             "(tools/debug/mb_mix.hip, profiles/r05_issue_model.txt; round 4: mb_valu.hip, r04_valu_microbench.txt): a SIMD retires one "
+                                             "add / sub / logic / arithmetic-shift instruction with register operands per 1.1 - 1.2 ns and one multiply / left shift / "
+                                             "min / max / select / DPP / 3-operand / SGPR-operand instruction per 1.8 - 1.9 ns (a v_mul_hi + v_add pair 3.0, v_mad_i64_i32 2.1); "
+                                             "scalar and LDS instructions of OTHER waves overlap with them (a type mix costs ~ the maximum, not the sum); one wave issues "
+                                             "a dependent instruction every 3.6 - 4.0 ns, two waves interleave perfectly, four saturate the unit.  The encoder pipeline "
+                                             "holds 5 waves per SIMD (registers and LDS full) and keeps the vector unit ~65 % busy: time follows the instruction count"}
+            if world == 1 and not args.no_cpu_baseline:
+                cb = cpu_baseline(args.cpu_seconds, args.cpu_packets_per_stream)
+                if cb and cb.get("per_core_packets_per_s"):
+                    cb["gpu_equals_reference_cores"] = round(value / cb["per_core_packets_per_s"], 1)
+                res["cpu_baseline"] = cb
         print(json.dumps(compact_line(res), separators=(",", ":")), flush=True)
     if use_dist:
         dist.barrier()

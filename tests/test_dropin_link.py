@@ -9,6 +9,7 @@ the GPU box like the other prebuilt checkers; no reference source is copied).
   * GPU box: the binaries run the reference CLI's known-answer procedure on the GPU and reproduce its md5s."""
 import hashlib
 import os
+import shutil
 import subprocess
 
 import pytest
@@ -49,11 +50,13 @@ def _md5_file(path):
 def test_reference_cli_mains_on_the_gpu_reproduce_the_known_answers(tmp_path):
     """JC1Encoder / JC1Decoder of the reference, linked with this library: bitstream, decoded and `-loss 30` md5s of SURVEY 8(c)."""
     g = T.golden_json()
-    bit, dec, dec30 = str(tmp_path / "out.bit"), str(tmp_path / "dec.pcm"), str(tmp_path / "dec30.pcm")
-    pcm = os.path.join(T.GOLDEN, "Ch_f1_raw.pcm")
-    subprocess.run([ENC, pcm, bit, "-mode", "2", "-Fs_API", "16000", "-rate", "13600"], check=True, stdout=subprocess.DEVNULL, timeout=600)
-    assert _md5_file(bit) == g["ch_f1_bit_md5"]
-    subprocess.run([DEC, bit, dec, "-Fs_API", "16000"], check=True, stdout=subprocess.DEVNULL, timeout=600)
-    assert _md5_file(dec) == g["ch_f1_dec_loss0_md5"]
-    subprocess.run([DEC, bit, dec30, "-Fs_API", "16000", "-loss", "30"], check=True, stdout=subprocess.DEVNULL, timeout=600)
-    assert _md5_file(dec30) == g["ch_f1_dec_loss30_md5"]
+    # the mains copy their file-name arguments into char[100] (test/enc_main.c:88-111, dec_main.c:83-104): they run in tmp_path and
+    # get names relative to it, whatever the length of the absolute paths
+    shutil.copyfile(os.path.join(T.GOLDEN, "Ch_f1_raw.pcm"), str(tmp_path / "in.pcm"))
+    run = dict(cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL, timeout=600)
+    subprocess.run([ENC, "in.pcm", "out.bit", "-mode", "2", "-Fs_API", "16000", "-rate", "13600"], **run)
+    assert _md5_file(str(tmp_path / "out.bit")) == g["ch_f1_bit_md5"]
+    subprocess.run([DEC, "out.bit", "dec.pcm", "-Fs_API", "16000"], **run)
+    assert _md5_file(str(tmp_path / "dec.pcm")) == g["ch_f1_dec_loss0_md5"]
+    subprocess.run([DEC, "out.bit", "dec30.pcm", "-Fs_API", "16000", "-loss", "30"], **run)
+    assert _md5_file(str(tmp_path / "dec30.pcm")) == g["ch_f1_dec_loss30_md5"]

@@ -15,7 +15,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
-ARGS = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"]
+ARGS = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"]
 
 
 def _env(**kw):

@@ -1,7 +1,10 @@
 """the receiver front end (solo_batch_decode_split).  The descriptions of every packet arrive as separate
 network packets in two arrival slots -- missing, swapped or duplicated -- and the GPU assembles the decoder call itself.
 Checked against the ordinary batched decode with the equivalent arrival mask (which the other GPU tests pin to the compiled
-reference) and, for useMDIndex = 1, against the host emulation of the kernel source."""
+reference) and against the compiled reference's answers for the same scenarios (stored vectors; live where oracle/_ref exists)."""
+import os
+import zlib
+
 import numpy as np
 import pytest
 
@@ -66,9 +69,17 @@ def test_split_arrivals_vs_compiled_reference_and_masked_decode(torch_cuda, mdi,
     assert np.array_equal(got.cpu().numpy(), want.cpu().numpy())
     assert len({int(m) for m in recv.ravel()}) == 4
     # both against the COMPILED REFERENCE decoder fed the correctly ordered (ptr, nBytes, lostflag) call of test/dec_main.c:255-378
-    # (incl. the 32 kHz mode, which tests/test_pinned_corners.py does not cover)
-    assert R.have_ref("fix"), "oracle/_ref did not travel with the snapshot"
+    # (incl. the 32 kHz mode, which tests/test_pinned_corners.py does not cover): its answers for these scenarios are stored in
+    # tests/golden/receiver_split.npz (make_receiver_golden.py: lengths, payload CRCs, decoded-packet CRCs), and where oracle/_ref is
+    # present the reference decoder also runs live on the GPU's own bitstream
     w = got.cpu().numpy()
+    g = np.load(os.path.join(T.GOLDEN, "receiver_split.npz"))
+    key = "m%d_%d" % (mdi, fs)
+    assert np.array_equal(hn, g["nb_" + key])
+    assert np.array_equal(np.array([[zlib.crc32(hb[i, p, :hn[i, p, 0]].tobytes()) for p in range(P)] for i in range(N)], np.uint32), g["pcrc_" + key])
+    assert np.array_equal(np.array([[zlib.crc32(w[i, p].tobytes()) for p in range(P)] for i in range(N)], np.uint32), g["crc_" + key])
+    if not R.have_ref("fix"):
+        return
     for i in range(N):
         d = R.RefDecoder("fix", use_md_index=mdi, samplerate=fs)
         for p in range(P):

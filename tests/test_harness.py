@@ -53,6 +53,8 @@ def test_file_level_known_answers_32k():
 
 REF_ENC = os.path.join(T.ROOT, "oracle", "_ref", "JC1Encoder_ref")
 REF_DEC = os.path.join(T.ROOT, "oracle", "_ref", "JC1Decoder_ref")
+# (the CLI mains copy their file-name arguments into char[100], test/enc_main.c:88-111 / dec_main.c:83-104: they run in tmp_path
+# and get names relative to it, whatever the length of the absolute paths)
 
 
 @pytest.mark.gpu
@@ -71,14 +73,14 @@ def test_dtx_file_against_the_reference_cli(tmp_path):
     pcm[40:52] = (rng.standard_normal((12, 640)) * 2).astype(np.int16)
     src, bit = str(tmp_path / "in.pcm"), str(tmp_path / "ref.bit")
     pcm.tofile(src)
-    subprocess.run([REF_ENC, src, bit, "-Fs_API", "16000", "-rate", "13600", "-DTX", "1"], check=True, stdout=subprocess.DEVNULL, timeout=300)
+    subprocess.run([REF_ENC, os.path.basename(src), os.path.basename(bit), "-Fs_API", "16000", "-rate", "13600", "-DTX", "1"], cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL, timeout=300)
     raw = open(bit, "rb").read()
     recs = H.encode_pcm(pcm.reshape(-1), dtx=1)
     assert H.write_bit_container(recs) == raw
     assert sum(1 for r in recs if r[1] == 0) >= 12 and recs[0][1] > 0
     for loss in (0, 20):
         out = str(tmp_path / ("ref%d.pcm" % loss))
-        subprocess.run([REF_DEC, bit, out, "-Fs_API", "16000", "-loss", str(loss)], check=True, stdout=subprocess.DEVNULL, timeout=300)
+        subprocess.run([REF_DEC, os.path.basename(bit), os.path.basename(out), "-Fs_API", "16000", "-loss", str(loss)], cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL, timeout=300)
         want = np.fromfile(out, np.int16)
         got = H.decode_records(H.parse_bit_container(raw), loss_perc=loss)
         assert got.size == want.size and np.array_equal(got, want), loss
@@ -101,7 +103,7 @@ def test_dec_mode_against_the_reference_cli(tmp_path):
     outs = {}
     for mode in (1, 2):
         out = str(tmp_path / ("ref_m%d.pcm" % mode))
-        subprocess.run([REF_DEC, bit, out, "-Fs_API", "16000", "-dec_mode", str(mode)], check=True, stdout=subprocess.DEVNULL, timeout=300)
+        subprocess.run([REF_DEC, os.path.basename(bit), os.path.basename(out), "-Fs_API", "16000", "-dec_mode", str(mode)], cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL, timeout=300)
         want = np.fromfile(out, np.int16)
         got = H.decode_records(H.parse_bit_container(raw), dec_mode=mode)
         assert got.size == want.size and np.array_equal(got, want), mode
@@ -114,14 +116,14 @@ def test_dec_mode_against_the_reference_cli(tmp_path):
     pcm[8:30] = (rng.standard_normal((22, 640)) * 3).astype(np.int16)
     src, dbit = str(tmp_path / "dtx.pcm"), str(tmp_path / "dtx.bit")
     pcm.tofile(src)
-    subprocess.run([REF_ENC, src, dbit, "-Fs_API", "16000", "-rate", "13600", "-DTX", "1"], check=True, stdout=subprocess.DEVNULL, timeout=300)
+    subprocess.run([REF_ENC, os.path.basename(src), os.path.basename(dbit), "-Fs_API", "16000", "-rate", "13600", "-DTX", "1"], cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL, timeout=300)
     draw = open(dbit, "rb").read()
     assert sum(1 for r in H.parse_bit_container(draw) if r[1] == 0) >= 8
     for path, fs in ((dbit, 16000),):            # (the reference CLIs refuse -Fs_API 32000: "only support wideband")
         data = open(path, "rb").read()
         for mode in (1, 2):
             out = str(tmp_path / "o.pcm")
-            subprocess.run([REF_DEC, path, out, "-Fs_API", str(fs), "-dec_mode", str(mode)], check=True, stdout=subprocess.DEVNULL, timeout=300)
+            subprocess.run([REF_DEC, os.path.basename(path), os.path.basename(out), "-Fs_API", str(fs), "-dec_mode", str(mode)], cwd=str(tmp_path), check=True, stdout=subprocess.DEVNULL, timeout=300)
             want = np.fromfile(out, np.int16)
             got = H.decode_records(H.parse_bit_container(data), dec_mode=mode, samplerate=fs)
             assert got.size == want.size and np.array_equal(got, want), (path, mode)

@@ -5,7 +5,7 @@ ROOT=$(pwd); OUT=$ROOT/gpurun_out; mkdir -p "$OUT"; export TMPDIR=/tmp
 for round in 1 2; do
   for e in "NONE=0" "$@"; do
     echo "== $e" >> "$OUT/bench_env.log"
-    env $e timeout 300 python bench.py --steps 10 --warmup 2 --no-extra --no-cpu-baseline --no-hash 2>/dev/null | python -c "
+    env $e timeout 300 python bench.py --steps 10 --warmup 2 --full --no-extra --no-cpu-baseline --no-hash 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

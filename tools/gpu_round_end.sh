@@ -46,7 +46,7 @@ bash tools/profile_gpu.sh trace inst fetch write > "$OUT/profile1.log" 2>&1
 log "profile passes 1: $(tr '\n' ' ' < "$OUT/profile1.log" | cut -c1-200)"
 
 # ---- 4. the driver's bench command
-timeout 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 log "bench: rc=$? $(cut -c1-160 "$OUT/bench.json" | tail -1)"
 
 # ---- 5. profile, second half

@@ -7,4 +7,4 @@ timeout 900 python -m pytest tests -m gpu -x -q > "$OUT/gputest.log" 2>&1; echo 
 timeout 150 python tools/quick_bench.py 4096 10 2>&1 | grep -v amdgpu.ids | tee "$OUT/qb.log"
 timeout 150 python tools/quick_bench.py 8192 10 2>&1 | grep -v amdgpu.ids | tee -a "$OUT/qb.log"
 timeout 150 python tools/quick_bench.py 4096 10 32000 2>&1 | grep -v amdgpu.ids | tee -a "$OUT/qb.log"
-timeout 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cut -c1-400 "$OUT/bench.json" | tail -1
+timeout 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"; cut -c1-400 "$OUT/bench.json" | tail -1

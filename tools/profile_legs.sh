@@ -18,6 +18,6 @@ run() {   # leg, command...
   rm -rf "$OUT/$leg"
 }
 LOSS=0.3 run dec8192 python $ROOT/tools/quick_bench.py 8192 50
-run rt8192 python $ROOT/bench.py --streams 8192 --steps 3 --warmup 1 --no-cpu-baseline --no-extra
+run rt8192 python $ROOT/bench.py --streams 8192 --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra
 run wb32k python $ROOT/tools/quick_bench.py 4096 25 32000
 ls -la "$OUT"

@@ -21,7 +21,7 @@ try:
     git_dirty = bool(subprocess.check_output(["git", "-C", ROOT, "status", "--porcelain", "--", "solo_amd/csrc"], text=True).strip())
 except Exception:
     git_head, git_dirty = None, None
-out = {"source": "rocprofv3 --kernel-trace --stats / --pmc (separate passes) over `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra`",
+out = {"source": "rocprofv3 --kernel-trace --stats / --pmc (separate passes) over `python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra`",
        "packets_per_step": packets_step, "kernel_source_sha16": None, "git_head": git_head, "git_kernel_sources_modified_since_head": git_dirty, "kernels": {}}
 st = os.path.join(src, "trace", "r01_kernel_stats.csv")
 lines = []
