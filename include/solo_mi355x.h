@@ -113,6 +113,22 @@ void solo_batch_destroy(solo_batch_t *b);
 /* Re-initialises all stream states (same as destroy + create) -- EXCEPT the receiver staging ring: descriptions filed with
  * solo_recv_insert, play-out positions and statistics survive a reset; call solo_recv_create again to start the ring afresh. */
 int32_t solo_batch_reset(solo_batch_t *b, void *hip_stream);
+/* Re-initialises the listed streams, each as AGR_Sate_Encoder_Init / AGR_Sate_Decoder_Init would with its own control.
+ * which: 1 = encoder state, 2 = decoder state, 3 = both (only directions the handle has).  h_enc / h_dec: HOST arrays of n
+ * controls, h_enc[i] for stream h_streams[i]; NULL = the handle's create-time control for that direction.  Other streams untouched.
+ *   Per stream:  encoder targetRate_bps (<= 0 means 15600, AGR_BWE_SDK_API.c:35; the caller's array is not written back), dtx_enable,
+ *                useMDIndex (mode is ignored, as in the reference); decoder useMDIndex (packetLoss_perc is ignored, as in the reference).
+ *   Per handle:  samplerate, framesize_ms, joint_enable, joint_mode (they select the kernel build and the packet geometry): a listed
+ *                control that differs from the handle's in any of them is refused.
+ * Returns -1 and changes nothing (the checks run on the host before anything is enqueued) when n <= 0 or n > N, an index is out of
+ * range or listed twice, `which` names a direction the handle does not have, a control is given for a direction the call does not
+ * reset, or a control fails the checks of solo_batch_create (in the 32 kHz mode every stream's rate must leave SILK >= 14000 bps).
+ * Ordering as solo_batch_reset: the init kernels wait for this handle's encode / decode work still in flight on its internal streams
+ * (async joins included); work enqueued on hip_stream after the call sees the new states.  The host arrays are free when the call
+ * returns (the records travel as kernel arguments).  Reset streams play on with the receiver ring as it is: see solo_recv_reset_streams.
+ * A handle created with one control and given per-stream controls here is the way to run mixed rates / DTX / useMDIndex in one batch. */
+int32_t solo_batch_reset_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, int32_t which,
+                                 const USER_Ctrl_enc *h_enc, const USER_Ctrl_dec *h_dec, void *hip_stream);
 int32_t solo_batch_encode(solo_batch_t *b, const int16_t *d_pcm, int32_t n_packets, uint8_t *d_bits,
                           int16_t *d_nbytes, int32_t *d_status, void *hip_stream);
 int32_t solo_batch_decode(solo_batch_t *b, const uint8_t *d_bits, const int16_t *d_nbytes,
@@ -120,7 +136,7 @@ int32_t solo_batch_decode(solo_batch_t *b, const uint8_t *d_bits, const int16_t 
                           void *hip_stream);
 /* Receiver front end: the two descriptions of every packet arrive separately (MD1, and MD2 || HB(8)), possibly only one,
  * possibly in either arrival slot.  d_descA / d_descB: uint8 [N][P][slot_bytes]; d_lenA / d_lenB: int16 [N][P], 0 = nothing
- * arrived.  With useMDIndex = 1 in the decoder control the kernel identifies the descriptions by the index they carry
+ * arrived.  With useMDIndex = 1 in the stream's decoder control the kernel identifies the descriptions by the index they carry
  * (SKP_Silk_decode_parameters.c:55-57) and sorts them itself; with useMDIndex = 0 slot A is MD1 and slot B is MD2 || HB.
  * Builds the (ptr, nBytes, lostflag) call of test/dec_main.c:255-378 on the GPU and decodes.  Same outputs as
  * solo_batch_decode.  Packets above 252 bytes are rejected (status -11). */
@@ -144,6 +160,12 @@ int32_t solo_recv_insert(solo_batch_t *b, const solo_arrival_t *d_arrivals, int3
                          int64_t payload_bytes, void *hip_stream);
 int32_t solo_recv_decode(solo_batch_t *b, int32_t n_packets, int16_t *d_pcm, int32_t *d_status, void *hip_stream);
 int32_t solo_recv_stats(solo_batch_t *b, uint32_t *out8, void *hip_stream);
+/* Receiver ring: empties the queue of the listed streams and sets their play-out positions to h_first_seq[i] (>= 0).
+ * Statistics and all other streams are untouched.  h_streams / h_first_seq: HOST arrays of n; -1 (nothing changed) without a ring,
+ * for n <= 0 or n > N, an index out of range or listed twice, or a negative sequence number.  Whether an arrival with desc = -1 is
+ * accepted follows each stream's own decoder useMDIndex (solo_batch_reset_streams). */
+int32_t solo_recv_reset_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, const int32_t *h_first_seq,
+                                void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

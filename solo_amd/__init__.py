@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "solo_batch_last_kernel_ms", "solo_batch_last_encode_chunks", "solo_batch_decode_split", "solo_batch_set_async_join",
     "solo_batch_wait_encode", "solo_debug_l0", "solo_debug_sum_sqr_shift", "solo_debug_rowops", "solo_debug_clock", "solo_debug_nsq",
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
+    "solo_batch_reset_streams", "solo_recv_reset_streams",
 ]
 
 
@@ -83,6 +84,10 @@ def load_library():
     lib.solo_batch_destroy.argtypes = [C.c_void_p]
     lib.solo_batch_reset.argtypes = [C.c_void_p, C.c_void_p]
     lib.solo_batch_reset.restype = C.c_int32
+    lib.solo_batch_reset_streams.restype = C.c_int32
+    lib.solo_batch_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_recv_reset_streams.restype = C.c_int32
+    lib.solo_recv_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.solo_batch_encode.restype = C.c_int32
     lib.solo_batch_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_decode.restype = C.c_int32
@@ -188,6 +193,67 @@ class SoloBatch:
         r = self.lib.solo_batch_reset(self.h, self._stream())
         if r:
             raise RuntimeError("solo_batch_reset -> %d" % r)
+
+    _WHICH = {"enc": 1, "encoder": 1, "dec": 2, "decoder": 2, "both": 3, 1: 1, 2: 2, 3: 3}
+
+    def _stream_list(self, streams):
+        idx = [int(s) for s in (streams.tolist() if hasattr(streams, "tolist") else streams)]
+        if not 0 < len(idx) <= self.n_streams:
+            raise ValueError("between 1 and %d streams must be listed" % self.n_streams)
+        if any(s < 0 or s >= self.n_streams for s in idx):
+            raise ValueError("stream index out of range")
+        if len(set(idx)) != len(idx):
+            raise ValueError("a stream is listed twice")
+        return idx
+
+    @staticmethod
+    def _per_stream(v, n, name):
+        if v is None or isinstance(v, (int, bool)) or (hasattr(v, "ndim") and v.ndim == 0):
+            return [v] * n
+        v = list(v.tolist() if hasattr(v, "tolist") else v)
+        if len(v) != n:
+            raise ValueError("%s: one value per listed stream (%d), got %d" % (name, n, len(v)))
+        return v
+
+    def reset_streams(self, streams, rate=None, dtx=None, use_md_index=None, which="both"):
+        """Re-initialise the listed streams (solo_batch_reset_streams), each as a fresh encoder / decoder with its own control.  rate,
+        dtx and use_md_index take a scalar or one value per listed stream; None means the handle's create-time value.  rate and dtx
+        are encoder fields, use_md_index goes to both directions.  which: "enc" (1), "dec" (2) or "both" (3; on a handle of one
+        direction: that direction).  Other streams are untouched; work enqueued on the current stream afterwards sees the new states."""
+        idx = self._stream_list(streams)
+        n = len(idx)
+        if which not in self._WHICH:
+            raise ValueError("which must be 'enc', 'dec' or 'both'")
+        w = self._WHICH[which]
+        if which == "both":
+            w = (1 if self._enc is not None else 0) | (2 if self._dec is not None else 0)
+        if (w & 1 and self._enc is None) or (w & 2 and self._dec is None):
+            raise ValueError("the handle has no %s" % ("encoder" if (w & 1 and self._enc is None) else "decoder"))
+        rates, dtxs, mds = self._per_stream(rate, n, "rate"), self._per_stream(dtx, n, "dtx"), self._per_stream(use_md_index, n, "use_md_index")
+        enc_arr = dec_arr = None
+        if (rate is not None or dtx is not None) and not w & 1:
+            raise ValueError("rate / dtx are encoder controls: the call does not reset an encoder")
+        if w & 1 and (rate is not None or dtx is not None or use_md_index is not None):
+            h = self._enc
+            enc_arr = (USER_Ctrl_enc * n)()
+            for i in range(n):
+                r = h.targetRate_bps if rates[i] is None else int(rates[i])
+                if h.samplerate == 32000 and (15600 if r <= 0 else r) - (800 if h.joint_enable and h.joint_mode == 1 else 1600) < 14000:
+                    raise ValueError("the 32 kHz mode needs a rate that leaves SILK >= 14000 bps (stream %d: %d)" % (idx[i], r))
+                enc_arr[i] = USER_Ctrl_enc(mode=h.mode, targetRate_bps=r, samplerate=h.samplerate,
+                                           dtx_enable=h.dtx_enable if dtxs[i] is None else (1 if dtxs[i] else 0), framesize_ms=h.framesize_ms,
+                                           joint_enable=h.joint_enable, joint_mode=h.joint_mode,
+                                           useMDIndex=h.useMDIndex if mds[i] is None else int(mds[i]))
+        if w & 2 and use_md_index is not None:
+            h = self._dec
+            dec_arr = (USER_Ctrl_dec * n)()
+            for i in range(n):
+                dec_arr[i] = USER_Ctrl_dec(packetLoss_perc=h.packetLoss_perc, samplerate=h.samplerate, framesize_ms=h.framesize_ms,
+                                           joint_enable=h.joint_enable, joint_mode=h.joint_mode,
+                                           useMDIndex=h.useMDIndex if mds[i] is None else int(mds[i]))
+        r = self.lib.solo_batch_reset_streams(self.h, (C.c_int32 * n)(*idx), n, w, enc_arr, dec_arr, self._stream())
+        if r:
+            raise RuntimeError("solo_batch_reset_streams -> %d" % r)
 
     def encode(self, pcm, bits=None, nbytes=None, status=None):
         """pcm: int16 CUDA tensor [N, P, 640] -> (bits uint8 [N,P,slot], nbytes int16 [N,P,2], status int32 [N])"""
@@ -297,6 +363,18 @@ class SoloBatch:
         if r:
             raise RuntimeError("solo_recv_decode -> %d" % r)
         return pcm, status
+
+    def recv_reset_streams(self, streams, first_seq):
+        """Empty the staging queue of the listed streams and set their play-out positions (solo_recv_reset_streams); first_seq: a
+        scalar or one sequence number (>= 0) per listed stream.  Statistics and the other streams are untouched."""
+        idx = self._stream_list(streams)
+        seqs = [int(v) for v in self._per_stream(first_seq, len(idx), "first_seq")]
+        if any(v < 0 for v in seqs):
+            raise ValueError("first_seq must be >= 0")
+        n = len(idx)
+        r = self.lib.solo_recv_reset_streams(self.h, (C.c_int32 * n)(*idx), n, (C.c_int32 * n)(*seqs), self._stream())
+        if r:
+            raise RuntimeError("solo_recv_reset_streams -> %d" % r)
 
     def recv_stats(self):
         out = (C.c_uint32 * 8)()

@@ -45,20 +45,22 @@ __global__ void __launch_bounds__(64) solo_sum_sqr_probe_kernel(const i16* x, in
 // the same decoder compiled for the 32 kHz API rate (SILK wide band, 16 kHz bands): solo_api_wb.hip
 extern "C" {
 size_t solo_wb_dec_state_bytes();
-hipError_t solo_wb_dec_launch_init(void* states, int n_streams, int hb_joint, hipStream_t s);
+hipError_t solo_wb_dec_launch_init(void* states, int n_streams, int hb_joint, int useMDIndex, hipStream_t s);
+hipError_t solo_wb_dec_launch_init_list(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s);
 hipError_t solo_wb_dec_launch(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int slot,
-                              int useMDIndex, int16_t* pcm, int32_t* status, hipStream_t s);
+                              int16_t* pcm, int32_t* status, hipStream_t s);
 hipError_t solo_wb_dec_launch_extract(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets,
-                                      int p0, int pc, int slot, int useMDIndex, void* recs, hipStream_t s);
+                                      int p0, int pc, int slot, void* recs, hipStream_t s);
 hipError_t solo_wb_dec_launch_synth(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int p0,
-                                    int pc, int slot, int useMDIndex, const void* recs, int16_t* pcm, int32_t* status, hipStream_t s);
+                                    int pc, int slot, const void* recs, int16_t* pcm, int32_t* status, hipStream_t s);
 size_t solo_wb_dec_extracted_bytes();
 hipError_t solo_wb_dec_launch_split(void* states, const uint8_t* descA, const int16_t* lenA, const uint8_t* descB, const int16_t* lenB, int n_streams,
-                                    int n_packets, int slot, int useMDIndex, int16_t* pcm, int32_t* status, hipStream_t s);
-hipError_t solo_wb_dec_launch_raw(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int useMDIndex, int16_t* pcm, int32_t* status,
-                                  hipStream_t s);
+                                    int n_packets, int slot, int16_t* pcm, int32_t* status, hipStream_t s);
+hipError_t solo_wb_dec_launch_raw(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm, int32_t* status, hipStream_t s);
 hipError_t solo_wb_dec_launch_ring(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth, int slot,
-                                   int useMDIndex, int16_t* pcm, int32_t* status, hipStream_t s);
+                                   int16_t* pcm, int32_t* status, hipStream_t s);
+hipError_t solo_wb_recv_launch_insert(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth, int slot,
+                                      const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats, hipStream_t s);
 }
 
 #ifdef SOLO_WITH_ENCODER
@@ -247,9 +249,8 @@ int32_t solo_batch_wait_encode(solo_batch_t* b, void* hip_stream, int32_t which)
 }
 int32_t solo_batch_last_encode_chunks(const solo_batch_t* b) { return b ? b->last_chunks : 0; }
 
-int32_t solo_batch_reset(solo_batch_t* b, void* hip_stream) {
-    if (!b) return -1;
-    hipStream_t s = (hipStream_t)hip_stream;
+// Makes `s` wait for the handle's encode / decode work still in flight on its internal streams (before init kernels overwrite states).
+static int32_t solo_wait_in_flight(solo_batch_t* b, hipStream_t s) {
     if (b->pipe_ready && b->enc_seq > 0) {
         // kernels of the most recent encode calls may still run on the internal streams (always so with async joins, and when
         // reset is issued on another stream than the encode was): the init kernels must not overtake them
@@ -260,20 +261,92 @@ int32_t solo_batch_reset(solo_batch_t* b, void* hip_stream) {
             SOLO_CHECK(hipStreamWaitEvent(s, b->evJoinC[js], 0));
         }
     }
+    if (b->have_dec && b->dec_pipe_ready && b->dec_split && b->dec_calls > 0) {
+        // like the encoder above: a decode call issued on another stream may still run on the internal streams
+        SOLO_CHECK(hipStreamWaitEvent(s, b->evDJoin, 0));
+        SOLO_CHECK(hipStreamWaitEvent(s, b->evDJoin2, 0));
+    }
+    return 0;
+}
+// the decoder's hb_mode argument of sx_dec_state_init: bit 0 = joint_mode 1, bit 1 = one frame per packet
+static int ctrl_dec_hb_mode(const solo_batch* b) { return ctrl_hb_joint(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode) | (b->dec_ctrl.framesize_ms == 20 ? 2 : 0); }
+
+int32_t solo_batch_reset(solo_batch_t* b, void* hip_stream) {
+    if (!b) return -1;
+    hipStream_t s = (hipStream_t)hip_stream;
+    {
+        const int32_t r = solo_wait_in_flight(b, s);
+        if (r) return r;
+    }
     if (b->have_dec) {
-        if (b->dec_pipe_ready && b->dec_split && b->dec_calls > 0) {
-            // like the encoder above: a decode call issued on another stream may still run on the internal streams
-            SOLO_CHECK(hipStreamWaitEvent(s, b->evDJoin, 0));
-            SOLO_CHECK(hipStreamWaitEvent(s, b->evDJoin2, 0));
-        }
-        const int hbj = ctrl_hb_joint(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode) | (b->dec_ctrl.framesize_ms == 20 ? 2 : 0);      // (sx_dec_state_init: bit 1 = one frame per packet)
-        SOLO_CHECK(b->wb ? solo_wb_dec_launch_init(b->d_dec_state, b->n_streams, hbj, s) : solo_dec_launch_init(b->d_dec_state, b->n_streams, hbj, s));
+        const int hbj = ctrl_dec_hb_mode(b), md = b->dec_ctrl.useMDIndex;
+        SOLO_CHECK(b->wb ? solo_wb_dec_launch_init(b->d_dec_state, b->n_streams, hbj, md, s) : solo_dec_launch_init(b->d_dec_state, b->n_streams, hbj, md, s));
     }
 #ifdef SOLO_WITH_ENCODER
     if (b->have_enc) {
         int32_t r = solo_enc_reset(b, s);
         if (r) return r;
     }
+#endif
+    return 0;
+}
+
+// the listed stream indices: n in [1, N], every index in range and listed once
+static bool stream_list_ok(const solo_batch* b, const int32_t* h_streams, int32_t n) {
+    if (!h_streams || n <= 0 || n > b->n_streams) return false;
+    std::vector<char> seen((size_t)b->n_streams, 0);
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t s = h_streams[i];
+        if (s < 0 || s >= b->n_streams || seen[(size_t)s]) return false;
+        seen[(size_t)s] = 1;
+    }
+    return true;
+}
+
+// Per-stream re-initialisation: everything is validated and turned into records (solo_stream_ctl.h) before anything is enqueued, so a
+// refused call changes nothing.  Per stream: the encoder's rate, DTX and useMDIndex, the decoder's useMDIndex; samplerate, framesize_ms and
+// the joint mode select the kernel build and the packet geometry and must be the handle's.
+int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
+                                 const USER_Ctrl_dec* h_dec, void* hip_stream) {
+    if (!b || which < 1 || which > 3 || !stream_list_ok(b, h_streams, n)) return -1;
+    const bool do_enc = (which & 1) != 0, do_dec = (which & 2) != 0;
+    if ((do_enc && !b->have_enc) || (do_dec && !b->have_dec) || (h_enc && !do_enc) || (h_dec && !do_dec)) return -1;
+    std::vector<SxStreamCtl> er, dr;
+    if (do_enc) {
+        const USER_Ctrl_enc& he = b->enc_ctrl;
+        const int joint = ctrl_hb_joint(he.joint_enable, he.joint_mode);
+        er.resize((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            USER_Ctrl_enc c = h_enc ? h_enc[i] : he;
+            if (c.targetRate_bps <= 0) c.targetRate_bps = 15600;                    // AGR_BWE_SDK_API.c:35 (on a copy: the caller's array stays)
+            if (c.samplerate != he.samplerate || c.framesize_ms != he.framesize_ms || c.joint_enable != he.joint_enable || c.joint_mode != he.joint_mode ||
+                !ctrl_enc_supported(&c))
+                return -1;
+            er[(size_t)i] = SxStreamCtl{h_streams[i], c.targetRate_bps - (joint ? 800 : 1600), c.useMDIndex, c.dtx_enable ? 1 : 0};
+        }
+    }
+    if (do_dec) {
+        const USER_Ctrl_dec& hd = b->dec_ctrl;
+        dr.resize((size_t)n);
+        for (int32_t i = 0; i < n; i++) {
+            const USER_Ctrl_dec& c = h_dec ? h_dec[i] : hd;
+            if (c.samplerate != hd.samplerate || c.framesize_ms != hd.framesize_ms || c.joint_enable != hd.joint_enable || c.joint_mode != hd.joint_mode ||
+                !ctrl_dec_supported(&c))
+                return -1;
+            dr[(size_t)i] = SxStreamCtl{h_streams[i], c.useMDIndex, 0, 0};
+        }
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    {
+        const int32_t r = solo_wait_in_flight(b, s);
+        if (r) return r;
+    }
+    if (do_dec)
+        SOLO_CHECK((b->wb ? solo_wb_dec_launch_init_list : solo_dec_launch_init_list)(b->d_dec_state, dr.data(), n, ctrl_dec_hb_mode(b), s));
+#ifdef SOLO_WITH_ENCODER
+    if (do_enc)
+        SOLO_CHECK(b->eops->init_list(b->d_enc_state, er.data(), n, ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode),
+                                      b->enc_ctrl.framesize_ms == 20 ? 1 : 2, s));
 #endif
     return 0;
 }
@@ -392,7 +465,7 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
     if (!b->dec_split) {
         // single kernel: one wavefront per stream parses (two lanes) and synthesises
         const hipError_t e = (b->wb ? solo_wb_dec_launch : solo_dec_launch)(b->d_dec_state, d_bits, d_nbytes, d_recv, b->n_streams, n_packets, b->slot,
-                                                                             b->dec_ctrl.useMDIndex, d_pcm, d_status, st);
+                                                                             d_pcm, d_status, st);
         if (tm) { (void)hipEventRecord(b->ev[5], st); b->ev_dec = 1; }
         SOLO_CHECK(e);
         return 0;
@@ -442,12 +515,12 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
         // (every failure inside the loop goes through the join block below: nothing of this call stays forked)
         if (c >= 2 && (lerr = hipStreamWaitEvent(b->sP, b->evS[k], 0)) != hipSuccess) break;
         lerr = (b->wb ? solo_wb_dec_launch_extract : solo_dec_launch_extract)(b->d_dec_state, d_bits, d_nbytes, d_recv, b->n_streams, n_packets, p0, pc,
-                                                                              b->slot, b->dec_ctrl.useMDIndex, b->d_parsed[k], b->sP);
+                                                                              b->slot, b->d_parsed[k], b->sP);
         if (lerr != hipSuccess) break;
         if ((lerr = hipEventRecord(b->evP[k], b->sP)) != hipSuccess) break;
         if ((lerr = hipStreamWaitEvent(b->sS, b->evP[k], 0)) != hipSuccess) break;
         lerr = (b->wb ? solo_wb_dec_launch_synth : solo_dec_launch_synth)(b->d_dec_state, d_bits, d_nbytes, d_recv, b->n_streams, n_packets, p0, pc, b->slot,
-                                                                          b->dec_ctrl.useMDIndex, b->d_parsed[k], d_pcm, d_status, b->sS);
+                                                                          b->d_parsed[k], d_pcm, d_status, b->sS);
         if (lerr != hipSuccess) break;
         if ((lerr = hipEventRecord(b->evS[k], b->sS)) != hipSuccess) break;
     }
@@ -466,7 +539,7 @@ int32_t solo_batch_decode_split(solo_batch_t* b, const uint8_t* d_descA, const i
                                 void* hip_stream) {
     if (!b || !b->have_dec || !d_descA || !d_lenA || !d_descB || !d_lenB || !d_pcm || n_packets <= 0 || slot_bytes <= 0) return -1;
     SOLO_CHECK((b->wb ? solo_wb_dec_launch_split : solo_dec_launch_split)(b->d_dec_state, d_descA, d_lenA, d_descB, d_lenB, b->n_streams, n_packets,
-                                                                          slot_bytes, b->dec_ctrl.useMDIndex, d_pcm, d_status, (hipStream_t)hip_stream));
+                                                                          slot_bytes, d_pcm, d_status, (hipStream_t)hip_stream));
     return 0;
 }
 
@@ -496,18 +569,30 @@ int32_t solo_recv_create(solo_batch_t* b, int32_t depth, int32_t slot_bytes, int
     SOLO_CHECK(solo_recv_launch_reset(b->d_recv_lens, b->d_recv_play, b->d_recv_stats, b->n_streams, depth, first_seq, st));
     return 0;
 }
+int32_t solo_recv_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, const int32_t* h_first_seq, void* hip_stream) {
+    if (!b || !b->d_recv_ring || !h_first_seq || !stream_list_ok(b, h_streams, n)) return -1;
+    std::vector<SxStreamCtl> rr((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        if (h_first_seq[i] < 0) return -1;
+        rr[(size_t)i] = SxStreamCtl{h_streams[i], h_first_seq[i], 0, 0};
+    }
+    SOLO_CHECK(solo_recv_launch_reset_list(b->d_recv_lens, b->d_recv_play, rr.data(), n, b->recv_depth, (hipStream_t)hip_stream));
+    return 0;
+}
 int32_t solo_recv_insert(solo_batch_t* b, const solo_arrival_t* d_arrivals, int32_t n_arrivals, const uint8_t* d_payload, int64_t payload_bytes,
                          void* hip_stream) {
     if (!b || !b->d_recv_ring || n_arrivals < 0 || (n_arrivals > 0 && (!d_arrivals || !d_payload)) || payload_bytes < 0) return -1;
     if (n_arrivals == 0) return 0;
-    SOLO_CHECK(solo_recv_launch_insert(d_arrivals, n_arrivals, d_payload, (long long)payload_bytes, b->n_streams, b->recv_depth, b->recv_slot, b->dec_ctrl.useMDIndex,
-                                       b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->d_recv_stats, (hipStream_t)hip_stream));
+    // (desc = -1 is accepted for the streams whose decoder runs with useMDIndex = 1: the kernel reads each stream's own flag)
+    SOLO_CHECK((b->wb ? solo_wb_recv_launch_insert : solo_recv_launch_insert)(d_arrivals, n_arrivals, d_payload, (long long)payload_bytes, b->n_streams,
+                                                                              b->recv_depth, b->recv_slot, b->d_dec_state, b->d_recv_ring, b->d_recv_lens,
+                                                                              b->d_recv_play, b->d_recv_stats, (hipStream_t)hip_stream));
     return 0;
 }
 int32_t solo_recv_decode(solo_batch_t* b, int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
     if (!b || !b->d_recv_ring || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
     SOLO_CHECK((b->wb ? solo_wb_dec_launch_ring : solo_dec_launch_ring)(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->n_streams, n_packets,
-                                                                        b->recv_depth, b->recv_slot, b->dec_ctrl.useMDIndex, d_pcm, d_status,
+                                                                        b->recv_depth, b->recv_slot, d_pcm, d_status,
                                                                         (hipStream_t)hip_stream));
     return 0;
 }
@@ -921,7 +1006,7 @@ int32_t AGR_Sate_Decoder_Decode(void* st, int16_t* pcm, int16_t* nSamplesOut, co
         memcpy(h->h_blk + SOLO_SINGLE_BITS_OFF, bits, (size_t)n0);
         if (hipMemcpyAsync(h->d_bits, h->h_blk + SOLO_SINGLE_BITS_OFF, (size_t)n0, hipMemcpyHostToDevice, (hipStream_t)0) != hipSuccess) return -1;
     }
-    if ((h->b->wb ? solo_wb_dec_launch_raw : solo_dec_launch_raw)(h->b->d_dec_state, h->d_bits, n0, n1, lostflag, h->b->dec_ctrl.useMDIndex, h->d_pcm,
+    if ((h->b->wb ? solo_wb_dec_launch_raw : solo_dec_launch_raw)(h->b->d_dec_state, h->d_bits, n0, n1, lostflag, h->d_pcm,
                                                                   h->d_status, (hipStream_t)0) != hipSuccess) return -1;
     // status + decoded packet in one copy, one synchronisation
     if (hipMemcpyAsync(h->h_blk, h->d_blk, SOLO_SINGLE_PCM_OFF + (size_t)ns * 2, hipMemcpyDeviceToHost, (hipStream_t)0) != hipSuccess) return -1;

@@ -118,6 +118,9 @@ struct SxDecShadow {
 struct SxDecStream {             // one record per stream in HBM
     SxDecState st;
     SxDecShadow sh;
+    // the stream's USER_Ctrl_dec::useMDIndex (solo_batch_reset_streams gives every stream its own).  Kept out of SxDecState, which
+    // solo_dec_enter copies into LDS: the decoder kernels read it once per stream as a wave-uniform value
+    i32 useMDIndex;
 };
 
 // ---- per-packet working set (LDS) ----------------------------------------------------------------

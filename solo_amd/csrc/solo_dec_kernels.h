@@ -4,13 +4,24 @@
 #include <hip/hip_runtime.h>
 #include "solo_dec.h"
 #include "solo_recv.h"
+#include "solo_stream_ctl.h"
 
-__global__ void __launch_bounds__(64) SX_K(solo_dec_init_kernel)(SxDecStream* states, int n_streams, int hb_mode) {
+__device__ __forceinline__ void SX_K(sx_dec_stream_init)(SxDecStream* rec, int hb_mode, int useMDIndex) {
+    sx_dec_state_init(&rec->st, hb_mode);
+    u32* sh = (u32*)&rec->sh;
+    SX_PAR(i, (int)(sizeof(SxDecShadow) / 4)) sh[i] = 0;
+    if (SX_LANE == 0) rec->useMDIndex = useMDIndex;
+}
+__global__ void __launch_bounds__(64) SX_K(solo_dec_init_kernel)(SxDecStream* states, int n_streams, int hb_mode, int useMDIndex) {
     const int s = blockIdx.x;
     if (s >= n_streams) return;
-    sx_dec_state_init(&states[s].st, hb_mode);
-    u32* sh = (u32*)&states[s].sh;
-    SX_PAR(i, (int)(sizeof(SxDecShadow) / 4)) sh[i] = 0;
+    SX_K(sx_dec_stream_init)(&states[s], hb_mode, useMDIndex);
+}
+// solo_batch_reset_streams: the listed streams only, each with its own useMDIndex (record: stream, useMDIndex); one workgroup per record
+__global__ void __launch_bounds__(64) SX_K(solo_dec_init_list_kernel)(SxDecStream* states, const SxStreamCtlList list, int n, int hb_mode) {
+    if ((int)blockIdx.x >= n) return;
+    const SxStreamCtl r = list.r[blockIdx.x];
+    SX_K(sx_dec_stream_init)(&states[r.stream], hb_mode, r.a);
 }
 
 // Decoder: rows D0-D8.  blockIdx.x = stream.
@@ -67,11 +78,12 @@ SX_HD SxDecArgs sx_dec_map_record(i32 n0, i32 n1, int slot, int recv_mask, int h
 
 __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_kernel)(SxDecStream* states, const u8* __restrict__ bits,
                                                          const i16* __restrict__ nbytes, const u8* __restrict__ recv,
-                                                         int n_streams, int n_packets, int slot, int useMDIndex,
+                                                         int n_streams, int n_packets, int slot,
                                                          i16* __restrict__ pcm, i32* status) {
     SxDecWork& w = SX_K(g_sx_dec_work);
     const int s = blockIdx.x;
     if (s >= n_streams) return;
+    const int useMDIndex = SX_UNI(states[s].useMDIndex);        // (the stream's own flag, wave-uniform)
     SX_K(solo_dec_enter)(&w, &states[s]);
     i32 first_err = 0;
     for (int p = 0; p < n_packets; p++) {
@@ -114,15 +126,15 @@ struct SxExtractWork {
 // (The order of the list depends on the order the wavefronts' atomic adds arrive in; every entry is extracted into its own record
 // whatever lane takes it.)
 static __device__ __forceinline__ bool SX_K(sx_extract_slot)(const SxDecStream* states, const i16* __restrict__ nbytes, const u8* __restrict__ recv, size_t idx, int n_packets,
-                                                            int p0, int pc, int slot, size_t* pk_out, int* hb_joint_out, SxDecArgs* a_out, i32* off, i32* len, int* sel,
-                                                            i32* hb_off) {
+                                                            int p0, int pc, int slot, size_t* pk_out, int* hb_joint_out, int* md_out, SxDecArgs* a_out, i32* off,
+                                                            i32* len, int* sel, i32* hb_off) {
     const int md = (int)(idx & 1);
     const size_t sp = idx >> 1;
     const int s = (int)(sp / (size_t)pc), p = p0 + (int)(sp % (size_t)pc);
     const size_t pk = (size_t)s * n_packets + p;
     const int hb_joint = states[s].st.hb_joint | (states[s].st.fpp == 1);      // (what matters here: four high-band bytes instead of eight)
     const SxDecArgs a = sx_dec_map_record(nbytes[pk * 2 + 0], nbytes[pk * 2 + 1], slot, recv ? (int)recv[pk] : 3, hb_joint);
-    *pk_out = pk; *hb_joint_out = hb_joint; *a_out = a;
+    *pk_out = pk; *hb_joint_out = hb_joint; *md_out = states[s].useMDIndex; *a_out = a;
     *off = 0; *len = 0; *hb_off = -1; *sel = 0;
     return sx_desc_span(a.lostflag, a.a0, a.a1, hb_joint, md, off, len, sel, hb_off);
 }
@@ -133,8 +145,8 @@ __global__ void __launch_bounds__(64) SX_K(solo_dec_list_kernel)(const SxDecStre
     const size_t idx = (size_t)blockIdx.x * 64 + threadIdx.x;
     bool present = false;
     if (idx < (size_t)n_streams * (size_t)pc * 2) {
-        size_t pk; int hb_joint, sel; SxDecArgs a; i32 off, len, hb_off;
-        present = SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, &pk, &hb_joint, &a, &off, &len, &sel, &hb_off);
+        size_t pk; int hb_joint, md, sel; SxDecArgs a; i32 off, len, hb_off;
+        present = SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, &pk, &hb_joint, &md, &a, &off, &len, &sel, &hb_off);
         if (!present) recs[idx].usable = 0;
     }
     const unsigned long long m = __builtin_amdgcn_ballot_w64(present);
@@ -147,7 +159,7 @@ __global__ void __launch_bounds__(64) SX_K(solo_dec_list_kernel)(const SxDecStre
 __global__ void __launch_bounds__(SX_EXTRACT_LANES, SX_EXTRACT_WAVES) SX_K(solo_dec_extract_kernel)(const SxDecStream* states, const u8* __restrict__ bits,
                                                                                  const i16* __restrict__ nbytes, const u8* __restrict__ recv,
                                                                                  int n_streams, int n_packets, int p0, int pc, int slot,
-                                                                                 int useMDIndex, SxExtracted* __restrict__ recs, const u32* __restrict__ list,
+                                                                                 SxExtracted* __restrict__ recs, const u32* __restrict__ list,
                                                                                  const u32* __restrict__ count) {
     __shared__ SxExtractWork w;
     // (without a list -- the caller passed no reception flags, so nearly every slot carries bytes -- lane i takes slot i)
@@ -163,11 +175,11 @@ __global__ void __launch_bounds__(SX_EXTRACT_LANES, SX_EXTRACT_WAVES) SX_K(solo_
     const size_t li = (size_t)blockIdx.x * SX_EXTRACT_LANES + threadIdx.x;
     if (li >= n_listed) return;
     const size_t idx = list ? (size_t)list[li] : li;
-    size_t pk; int hb_joint, sel; SxDecArgs a; i32 off, len, hb_off;
+    size_t pk; int hb_joint, md, sel; SxDecArgs a; i32 off, len, hb_off;
     SxExtracted* rec = &recs[idx];
-    if (!SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, &pk, &hb_joint, &a, &off, &len, &sel, &hb_off)) { rec->usable = 0; return; }
+    if (!SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, &pk, &hb_joint, &md, &a, &off, &len, &sel, &hb_off)) { rec->usable = 0; return; }
     const u8* pkt = bits + pk * (size_t)slot + a.ptr_off;
-    sx_extract_desc(pkt + off, len, useMDIndex, (const SxCdf*)&w.cdf, &w.lane[threadIdx.x], rec, sel, hb_off >= 0 ? pkt + hb_off : 0, hb_joint);
+    sx_extract_desc(pkt + off, len, md, (const SxCdf*)&w.cdf, &w.lane[threadIdx.x], rec, sel, hb_off >= 0 ? pkt + hb_off : 0, hb_joint);
 }
 
 #if !defined(SX_DEC_NO_PREFETCH) && defined(__HIP_DEVICE_COMPILE__)
@@ -188,11 +200,12 @@ static __device__ __forceinline__ void sx_prefetch_records(const SxExtracted* ne
 
 __global__ void __launch_bounds__(64, 4) SX_K(solo_dec_synth_kernel)(SxDecStream* states, const u8* __restrict__ bits,
                                                             const i16* __restrict__ nbytes, const u8* __restrict__ recv,
-                                                            int n_streams, int n_packets, int p0, int pc, int slot, int useMDIndex,
+                                                            int n_streams, int n_packets, int p0, int pc, int slot,
                                                             const SxExtracted* __restrict__ recs, i16* __restrict__ pcm, i32* status) {
     SxDecWork& w = SX_K(g_sx_dec_work);
     const int s = blockIdx.x;
     if (s >= n_streams) return;
+    const int useMDIndex = SX_UNI(states[s].useMDIndex);
 #if defined(SX_STOPS) && defined(__HIP_DEVICE_COMPILE__)
     SX_STOPS_ENTER(0)
 #endif
@@ -256,10 +269,11 @@ __device__ __forceinline__ int SX_K(sx_decode_split_packet)(SxDecWork& w, const 
 
 __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_split_kernel)(SxDecStream* states, const u8* __restrict__ descA, const i16* __restrict__ lenA,
                                                                const u8* __restrict__ descB, const i16* __restrict__ lenB, int n_streams,
-                                                               int n_packets, int slot, int useMDIndex, i16* __restrict__ pcm, i32* status) {
+                                                               int n_packets, int slot, i16* __restrict__ pcm, i32* status) {
     SxDecWork& w = SX_K(g_sx_dec_work);
     const int s = blockIdx.x;
     if (s >= n_streams) return;
+    const int useMDIndex = SX_UNI(states[s].useMDIndex);
     SX_K(solo_dec_enter)(&w, &states[s]);
     i32 first_err = 0;
     for (int p = 0; p < n_packets; p++) {
@@ -276,11 +290,13 @@ __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_split_kernel)(SxDecStr
 // ---- receiver staging ring (solo_recv.h): arrivals filed by sequence number, decoded when their turn comes -----------------------
 // one wavefront files one arrival
 __global__ void __launch_bounds__(64) SX_K(solo_recv_insert_kernel)(const SxRecvArrival* __restrict__ arr, int n_arr, const u8* __restrict__ payload,
-                                                               long long payload_bytes, int n_streams, int depth, int slot, int useMDIndex, u8* ring,
-                                                               u32* lens, const i32* __restrict__ play, u32* stats) {
+                                                               long long payload_bytes, int n_streams, int depth, int slot, const SxDecStream* states,
+                                                               u8* ring, u32* lens, const i32* __restrict__ play, u32* stats) {
     const int a = blockIdx.x;
     if (a >= n_arr) return;
     const SxRecvArrival r = arr[a];
+    // desc = -1 is read off the payload only for a stream whose decoder runs with useMDIndex = 1 (a bad stream index is refused by sx_recv_file)
+    const int useMDIndex = (r.stream >= 0 && r.stream < n_streams) ? states[r.stream].useMDIndex : 0;
     int sl = -1;
     int verdict = sx_recv_file(&r, payload, payload_bytes, n_streams, depth, slot, useMDIndex, play, lens, SX_LANE == 0, &sl);
     if (verdict == SX_RECV_INSERTED) {
@@ -301,12 +317,22 @@ __global__ void __launch_bounds__(64) SX_K(solo_recv_reset_kernel)(u32* lens, i3
     if (i < (size_t)n_streams) play[i] = first_seq;
     if (i < SX_RECV_NSTATS) stats[i] = 0;
 }
+// solo_recv_reset_streams: empty the queue of each listed stream and set its play-out position (record: stream, first_seq); statistics
+// and the other streams are left alone.  One workgroup per record.
+__global__ void __launch_bounds__(64) SX_K(solo_recv_reset_list_kernel)(u32* lens, i32* play, const SxStreamCtlList list, int n, int depth) {
+    if ((int)blockIdx.x >= n) return;
+    const SxStreamCtl r = list.r[blockIdx.x];
+    u32* l = lens + (size_t)r.stream * (size_t)depth;
+    SX_PAR(i, depth) l[i] = 0;
+    if (SX_LANE == 0) play[r.stream] = r.a;
+}
 // the next n_packets sequence numbers of every stream: merge what has arrived (as the split kernel does), decode, free the entries
 __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_ring_kernel)(SxDecStream* states, const u8* ring, u32* lens, i32* play, int n_streams, int n_packets,
-                                                              int depth, int slot, int useMDIndex, i16* __restrict__ pcm, i32* status) {
+                                                              int depth, int slot, i16* __restrict__ pcm, i32* status) {
     SxDecWork& w = SX_K(g_sx_dec_work);
     const int s = blockIdx.x;
     if (s >= n_streams) return;
+    const int useMDIndex = SX_UNI(states[s].useMDIndex);
     SX_K(solo_dec_enter)(&w, &states[s]);
     i32 first_err = 0;
     const i32 play0 = play[s];
@@ -329,28 +355,42 @@ __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_ring_kernel)(SxDecStre
 
 // single-packet decode with the reference's raw (ptr, nBytes, lostflag) convention
 __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_raw_kernel)(SxDecStream* st, const u8* bits, int n0, int n1, int lostflag,
-                                                             int useMDIndex, i16* pcm, i32* status) {
+                                                             i16* pcm, i32* status) {
     SxDecWork& w = SX_K(g_sx_dec_work);
+    const int useMDIndex = SX_UNI(st->useMDIndex);
     SX_K(solo_dec_enter)(&w, st);
     int ret = sx_decode_packet(&w, bits, n0, n1, lostflag, useMDIndex, pcm);
     SX_K(solo_dec_leave)(&w, st);
     if (SX_LANE == 0) *status = ret;
 }
 
-// launchers (host): same signature for both rates
-static inline hipError_t SX_K(solo_dec_launch_init)(void* states, int n_streams, int hb_joint, hipStream_t s) {
-    hipLaunchKernelGGL(SX_K(solo_dec_init_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, n_streams, hb_joint);
+// launchers (host): same signature for both rates.  (The decoder's useMDIndex is per stream: SxDecStream::useMDIndex, written by the
+// init kernels; no decode launch takes it.)
+static inline hipError_t SX_K(solo_dec_launch_init)(void* states, int n_streams, int hb_joint, int useMDIndex, hipStream_t s) {
+    hipLaunchKernelGGL(SX_K(solo_dec_init_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, n_streams, hb_joint, useMDIndex);
     return hipGetLastError();
 }
+// recs: n records (stream, useMDIndex), validated by the caller; launches of SX_CTL_PER_LAUNCH records, the list passed by value
+static inline hipError_t SX_K(solo_dec_launch_init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
+        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
+        SxStreamCtlList l = {};
+        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
+        hipLaunchKernelGGL(SX_K(solo_dec_init_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k, hb_joint);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 static inline hipError_t SX_K(solo_dec_launch)(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
-                                               int n_packets, int slot, int useMDIndex, int16_t* pcm, int32_t* status, hipStream_t s) {
+                                               int n_packets, int slot, int16_t* pcm, int32_t* status, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_decode_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, bits, nbytes, recv, n_streams,
-                       n_packets, slot, useMDIndex, pcm, status);
+                       n_packets, slot, pcm, status);
     return hipGetLastError();
 }
 // recs: solo_dec_extracted_bytes() x n_streams x pc bytes + 256: the records, behind them the list of the slots that carry bytes and its count
 static inline hipError_t SX_K(solo_dec_launch_extract)(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
-                                                       int n_packets, int p0, int pc, int slot, int useMDIndex, void* recs, hipStream_t s) {
+                                                       int n_packets, int p0, int pc, int slot, void* recs, hipStream_t s) {
     const size_t lanes = (size_t)n_streams * (size_t)pc * 2;
     u32* list = recv ? (u32*)((SxExtracted*)recs + lanes) : (u32*)0;     // (reception flags given: descriptions may be missing)
     u32* count = list ? list + lanes : (u32*)0;
@@ -362,22 +402,22 @@ static inline hipError_t SX_K(solo_dec_launch_extract)(const void* states, const
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(SX_K(solo_dec_extract_kernel), dim3((unsigned)((lanes + SX_EXTRACT_LANES - 1) / SX_EXTRACT_LANES)), dim3(SX_EXTRACT_LANES), 0, s,
-                       (const SxDecStream*)states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, useMDIndex, (SxExtracted*)recs, list, count);
+                       (const SxDecStream*)states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, (SxExtracted*)recs, list, count);
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_dec_launch_synth)(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
-                                                     int n_packets, int p0, int pc, int slot, int useMDIndex, const void* recs,
+                                                     int n_packets, int p0, int pc, int slot, const void* recs,
                                                      int16_t* pcm, int32_t* status, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_dec_synth_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, bits, nbytes, recv, n_streams,
-                       n_packets, p0, pc, slot, useMDIndex, (const SxExtracted*)recs, pcm, status);
+                       n_packets, p0, pc, slot, (const SxExtracted*)recs, pcm, status);
     return hipGetLastError();
 }
 static inline size_t SX_K(solo_dec_extracted_bytes)() { return 2 * sizeof(SxExtracted) + 2 * sizeof(u32); }      // per packet: two records, two list entries
 static inline hipError_t SX_K(solo_dec_launch_split)(void* states, const uint8_t* descA, const int16_t* lenA, const uint8_t* descB,
-                                                     const int16_t* lenB, int n_streams, int n_packets, int slot, int useMDIndex,
+                                                     const int16_t* lenB, int n_streams, int n_packets, int slot,
                                                      int16_t* pcm, int32_t* status, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_decode_split_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, descA, lenA, descB, lenB,
-                       n_streams, n_packets, slot, useMDIndex, pcm, status);
+                       n_streams, n_packets, slot, pcm, status);
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_recv_launch_reset)(uint32_t* lens, int32_t* play, uint32_t* stats, int n_streams, int depth, int32_t first_seq, hipStream_t s) {
@@ -386,22 +426,34 @@ static inline hipError_t SX_K(solo_recv_launch_reset)(uint32_t* lens, int32_t* p
     hipLaunchKernelGGL(SX_K(solo_recv_reset_kernel), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, lens, play, stats, n_streams, depth, first_seq);
     return hipGetLastError();
 }
+// recs: n records (stream, first_seq), validated by the caller
+static inline hipError_t SX_K(solo_recv_launch_reset_list)(uint32_t* lens, int32_t* play, const SxStreamCtl* recs, int n, int depth, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
+        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
+        SxStreamCtlList l = {};
+        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
+        hipLaunchKernelGGL(SX_K(solo_recv_reset_list_kernel), dim3(k), dim3(64), 0, s, lens, play, l, k, depth);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 static inline hipError_t SX_K(solo_recv_launch_insert)(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth,
-                                                       int slot, int useMDIndex, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats,
+                                                       int slot, const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats,
                                                        hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_recv_insert_kernel), dim3(n_arr), dim3(64), 0, s, (const SxRecvArrival*)arrivals, n_arr, payload, payload_bytes, n_streams,
-                       depth, slot, useMDIndex, ring, lens, play, stats);
+                       depth, slot, (const SxDecStream*)states, ring, lens, play, stats);
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_dec_launch_ring)(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth,
-                                                    int slot, int useMDIndex, int16_t* pcm, int32_t* status, hipStream_t s) {
+                                                    int slot, int16_t* pcm, int32_t* status, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_decode_ring_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, ring, lens, play, n_streams, n_packets, depth,
-                       slot, useMDIndex, pcm, status);
+                       slot, pcm, status);
     return hipGetLastError();
 }
-static inline hipError_t SX_K(solo_dec_launch_raw)(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int useMDIndex, int16_t* pcm,
+static inline hipError_t SX_K(solo_dec_launch_raw)(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm,
                                                    int32_t* status, hipStream_t s) {
-    hipLaunchKernelGGL(SX_K(solo_decode_raw_kernel), dim3(1), dim3(64), 0, s, (SxDecStream*)state, bits, n0, n1, lostflag, useMDIndex, pcm, status);
+    hipLaunchKernelGGL(SX_K(solo_decode_raw_kernel), dim3(1), dim3(64), 0, s, (SxDecStream*)state, bits, n0, n1, lostflag, pcm, status);
     return hipGetLastError();
 }
 static inline size_t SX_K(solo_dec_state_bytes)() { return sizeof(SxDecStream); }

@@ -4,12 +4,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "solo_enc.h"
+#include "solo_stream_ctl.h"
 
 #ifndef SX_TU_FRONT       // (the front kernel lives in a translation unit of its own, solo_enc_front_k.hip: see there)
 __global__ void __launch_bounds__(64) SX_K(solo_enc_init_kernel)(SxEncStream* states, int n_streams, int silk_rate_bps, int useMDIndex, int hb_joint, int useDTX, int fpp) {
     const int s = blockIdx.x;
     if (s >= n_streams) return;
     sx_enc_state_init(&states[s], silk_rate_bps, useMDIndex, hb_joint, useDTX, fpp);
+}
+// solo_batch_reset_streams: the listed streams only, each with its own control (record: stream, SILK rate, useMDIndex, useDTX); the joint
+// mode and the packet size stay the handle's.  One workgroup per record.
+__global__ void __launch_bounds__(64) SX_K(solo_enc_init_list_kernel)(SxEncStream* states, const SxStreamCtlList list, int n, int hb_joint, int fpp) {
+    if ((int)blockIdx.x >= n) return;
+    const SxStreamCtl r = list.r[blockIdx.x];
+    sx_enc_state_init(&states[r.stream], r.a, r.b, hb_joint, r.c, fpp);
 }
 
 // Encoder, rows E0-E9, over HBM hand-over records.  Two schedules of the same stage functions (solo_api.hip picks one per call):
@@ -373,6 +381,17 @@ static hipError_t SX_K(solo_enc_launch_init)(void* states, int n_streams, int si
     hipLaunchKernelGGL(SX_K(solo_enc_init_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, n_streams, silk_rate_bps, useMDIndex, hb_joint, useDTX, fpp);
     return hipGetLastError();
 }
+static hipError_t SX_K(solo_enc_launch_init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, int fpp, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {           // (the records travel as the kernel argument: nothing to stage)
+        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
+        SxStreamCtlList l = {};
+        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
+        hipLaunchKernelGGL(SX_K(solo_enc_init_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k, hb_joint, fpp);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 static hipError_t SX_K(solo_enc_launch_analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in,
                                                  void* code_in, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_enc_analysis_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, pcm, n_streams, n_packets, p0, pc,
@@ -430,7 +449,7 @@ extern "C" hipError_t SX_K(solo_enc_launch_front)(void* states, const int16_t* p
                                                   unsigned int* started, hipStream_t s);
 static const solo_enc_ops SX_K(solo_enc_ops_table) = {
     sizeof(SxEncStream), sizeof(SxNsqIn), sizeof(SxNsqOut), sizeof(SxCodeIn), SX_PACKET,
-    SX_K(solo_enc_launch_init), SX_K(solo_enc_launch_analysis), SX_K(solo_launch_nsq), SX_K(solo_enc_launch_coding), SX_K(solo_enc_rc_scratch_bytes),
+    SX_K(solo_enc_launch_init), SX_K(solo_enc_launch_init_list), SX_K(solo_enc_launch_analysis), SX_K(solo_launch_nsq), SX_K(solo_enc_launch_coding), SX_K(solo_enc_rc_scratch_bytes),
     SX_K(solo_nsq_workgroups), SX_K(solo_nsq_ring_bytes), SX_K(solo_enc_launch_front), SX_K(solo_launch_nsq_persist), SX_K(solo_enc_front_scratch_bytes), SX_K(solo_nsq_persist_workgroups), SX_K(solo_nsq_stage_bytes),
     SX_FRONT_WAVES, SX_FRONT_PER_CU};
 

@@ -4,12 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "solo_stream_ctl.h"
 #ifndef SOLO_ENC_OPS_DEFINED
 #define SOLO_ENC_OPS_DEFINED
 struct solo_enc_ops {
     size_t state_bytes, nsq_in_bytes, nsq_out_bytes, code_in_bytes;      // sizeof SxEncStream / SxNsqIn / SxNsqOut / SxCodeIn
     int packet_samples;
     hipError_t (*init)(void* states, int n_streams, int silk_rate_bps, int useMDIndex, int hb_joint, int useDTX, int frames_per_packet, hipStream_t s);
+    // the listed streams only (solo_batch_reset_streams): records (stream, SILK rate, useMDIndex, useDTX), validated by the caller
+    hipError_t (*init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, int frames_per_packet, hipStream_t s);
     // ---- launch per chunk ----
     hipError_t (*analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in, void* code_in, hipStream_t s);
     int (*nsq)(void* states, const void* in, void* out, int n_streams, int n_packets, int p0, int pc, unsigned int* started, void* ring, void* hip_stream);
