@@ -152,6 +152,7 @@ int32_t solo_batch_decode_split(solo_batch_t *b, const uint8_t *d_descA, const i
  * more ahead, whose slot is taken (a second copy) or whose fields are out of range is dropped and counted.  solo_recv_decode decodes the
  * next n_packets (<= depth) sequence numbers of EVERY stream from what has arrived by then (the merge and the (ptr, nBytes, lostflag)
  * mapping of solo_batch_decode_split; nothing arrived = concealment), frees those entries and advances the play-out positions.
+ * Like solo_batch_decode_split it refuses a packet whose descriptions together exceed 252 bytes: not decoded, d_status -11.
  * d_pcm int16 [N][n_packets][packet samples], d_status int32 [N] or NULL.  Calls on one handle must be ordered (same stream, or
  * events).  solo_recv_stats copies {inserted, late, ahead, duplicate, bad, 0, 0, 0} to HOST memory (synchronises the stream). */
 typedef struct { int32_t stream, seq, desc, offset, len; } solo_arrival_t;

@@ -132,6 +132,12 @@ static void nsq_tap_before(SKP_Silk_encoder_state *psEncC, SKP_Silk_encoder_cont
     memcpy(t->Tilt_Q14, Tilt_Q14, sizeof(t->Tilt_Q14));
     memcpy(t->HarmShapeGain_Q14, HarmShapeGain_Q14, sizeof(t->HarmShapeGain_Q14));
     memcpy(t->PredCoef_Q12, PredCoef_Q12, sizeof(t->PredCoef_Q12));          /* SKP_int16 PredCoef_Q12[2][MAX_LPC_ORDER] */
+    {   /* the entries beyond the LPC order are never read and may hold whatever the caller's stack held: zeroed, so the record is
+         * a function of the input alone */
+        int k, o;
+        for (k = 0; k < 2; k++)
+            for (o = psEncC->predictLPCOrder; o < 16; o++) t->PredCoef_Q12[k][o] = 0;
+    }
     memcpy(t->LTPCoef_Q14, LTPCoef_Q14, sizeof(t->LTPCoef_Q14));
     memcpy(t->AR2_Q13, AR2_Q13, sizeof(t->AR2_Q13));
     memcpy(t->xfw, x, sizeof(t->xfw));

@@ -22,7 +22,8 @@ def test_parity_suite_through_the_alternate_build():
     env = dict(os.environ, SOLO_LIB_OVERRIDE=ALT)
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-m", "gpu", "-x", "-p", "no:cacheprovider",
                         os.path.join(T.ROOT, "tests", "test_gpu_decoder.py"), os.path.join(T.ROOT, "tests", "test_gpu_encoder.py"),
-                        os.path.join(T.ROOT, "tests", "test_pinned_corners.py"), os.path.join(T.ROOT, "tests", "test_gpu_receiver.py")],
+                        os.path.join(T.ROOT, "tests", "test_pinned_corners.py"), os.path.join(T.ROOT, "tests", "test_gpu_receiver.py"),
+                        os.path.join(T.ROOT, "tests", "test_gpu_rate_range.py")],
                        env=env, cwd=T.ROOT, capture_output=True, text=True, timeout=1500)
     tail = (r.stdout + r.stderr)[-1500:]
     assert r.returncode == 0, tail
