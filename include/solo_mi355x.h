@@ -167,6 +167,29 @@ int32_t solo_recv_stats(solo_batch_t *b, uint32_t *out8, void *hip_stream);
  * accepted follows each stream's own decoder useMDIndex (solo_batch_reset_streams). */
 int32_t solo_recv_reset_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, const int32_t *h_first_seq,
                                 void *hip_stream);
+/* Subset calls: encode, decode or play out only the n streams listed in d_streams, so that idle slots of a handle cost nothing.
+ *   d_streams  int32 [n]  DEVICE array, strictly increasing, every index in [0, N).  Being on the device, a per-tick list needs no
+ *                         host copy and the call can be captured in a graph.
+ *   I/O is COMPACT: row i of d_pcm, d_bits, d_nbytes, d_recv and d_status belongs to stream d_streams[i] (shapes as in the
+ *   calls above with n in place of N).  The codec state, the decoder state, the receiver queue and the play-out position are
+ *   those of stream d_streams[i].  A listed stream moves on exactly as if it had been called alone; an UNLISTED stream keeps its
+ *   encoder state, decoder state, receiver queue and play-out position bit for bit.
+ * The host checks only 0 < n <= N and the pointers (-1 otherwise, nothing enqueued).  The list itself is checked on the device, on
+ * hip_stream ahead of the call's kernels: a list that is not strictly increasing inside [0, N) is REFUSED -- no state, queue or
+ * play-out position changes, the outputs are left untouched, and every d_status[i] (if d_status is given) is set to -1.
+ * solo_batch_encode_streams always runs the launch-per-chunk schedule (SOLO_ENC_PERSIST does not apply to it); asynchronous joins and
+ * solo_batch_wait_encode work as for solo_batch_encode.  It returns -1 when N x (the size of one stream's encoder state) reaches
+ * 4 GiB (the quantiser addresses listed states with 32-bit offsets; ~249 000 streams at the 16 kHz API rate).
+ * solo_batch_decode_streams sizes its extraction records by n (the chunking of solo_batch_decode with n streams).
+ * solo_recv_decode_streams plays out the next n_packets sequence numbers of the listed streams only; the others keep their queue,
+ * which is decoded later at its own sequence numbers.  Arrivals are filed with solo_recv_insert as before. */
+int32_t solo_batch_encode_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, const int16_t *d_pcm, int32_t n_packets,
+                                  uint8_t *d_bits, int16_t *d_nbytes, int32_t *d_status, void *hip_stream);
+int32_t solo_batch_decode_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, const uint8_t *d_bits,
+                                  const int16_t *d_nbytes, const uint8_t *d_recv, int32_t n_packets, int16_t *d_pcm,
+                                  int32_t *d_status, void *hip_stream);
+int32_t solo_recv_decode_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, int32_t n_packets, int16_t *d_pcm,
+                                 int32_t *d_status, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

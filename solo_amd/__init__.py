@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "solo_batch_wait_encode", "solo_debug_l0", "solo_debug_sum_sqr_shift", "solo_debug_rowops", "solo_debug_clock", "solo_debug_nsq",
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams",
+    "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
 ]
 
 
@@ -90,6 +91,13 @@ def load_library():
     lib.solo_recv_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.solo_batch_encode.restype = C.c_int32
     lib.solo_batch_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_batch_encode_streams.restype = C.c_int32
+    lib.solo_batch_encode_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_batch_decode_streams.restype = C.c_int32
+    lib.solo_batch_decode_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+    lib.solo_recv_decode_streams.restype = C.c_int32
+    lib.solo_recv_decode_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_decode.restype = C.c_int32
     lib.solo_batch_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_n_streams.argtypes = [C.c_void_p]
@@ -206,6 +214,21 @@ class SoloBatch:
             raise ValueError("a stream is listed twice")
         return idx
 
+    def _subset(self, streams):
+        """streams= of encode / decode / recv_decode: a sequence or an int32 CUDA tensor of stream indices, strictly increasing ->
+        (int32 tensor on the device, n).  Checked here like _stream_list (the library checks the device list once more and refuses
+        a bad one with status -1, but by then the call is enqueued)."""
+        t = self.torch
+        on_dev = getattr(streams, "is_cuda", False)
+        if on_dev and (streams.dtype != t.int32 or streams.dim() != 1):
+            raise ValueError("streams: a sequence or a 1-D int32 CUDA tensor")
+        idx = self._stream_list(streams)
+        if any(a >= b for a, b in zip(idx, idx[1:])):
+            raise ValueError("streams must be listed in increasing order")
+        if on_dev:
+            return streams.contiguous(), len(idx)
+        return t.tensor(idx, dtype=t.int32, device=self.device), len(idx)
+
     @staticmethod
     def _per_stream(v, n, name):
         if v is None or isinstance(v, (int, bool)) or (hasattr(v, "ndim") and v.ndim == 0):
@@ -255,21 +278,34 @@ class SoloBatch:
         if r:
             raise RuntimeError("solo_batch_reset_streams -> %d" % r)
 
-    def encode(self, pcm, bits=None, nbytes=None, status=None):
-        """pcm: int16 CUDA tensor [N, P, 640] -> (bits uint8 [N,P,slot], nbytes int16 [N,P,2], status int32 [N])"""
+    def encode(self, pcm, bits=None, nbytes=None, status=None, streams=None):
+        """pcm: int16 CUDA tensor [N, P, 640] -> (bits uint8 [N,P,slot], nbytes int16 [N,P,2], status int32 [N]).
+        streams: encode only these streams (solo_batch_encode_streams); every shape then has n = len(streams) rows in place of N,
+        row i belonging to streams[i]; the other streams keep their state."""
         t = self.torch
         assert pcm.is_cuda and pcm.dtype == t.int16 and pcm.is_contiguous()
         N, P, L = pcm.shape
-        assert N == self.n_streams and L == self.packet_samples
+        smap = None
+        if streams is not None:
+            smap, n = self._subset(streams)
+            if N != n:
+                raise ValueError("pcm has %d rows for %d listed streams" % (N, n))
+        assert (smap is not None or N == self.n_streams) and L == self.packet_samples
         if bits is None:
             bits = t.zeros((N, P, self.slot), dtype=t.uint8, device=pcm.device)
         if nbytes is None:
             nbytes = t.zeros((N, P, 2), dtype=t.int16, device=pcm.device)
         if status is None:
             status = t.zeros((N,), dtype=t.int32, device=pcm.device)
-        r = self.lib.solo_batch_encode(self.h, pcm.data_ptr(), P, bits.data_ptr(), nbytes.data_ptr(), status.data_ptr(), self._stream())
+        if smap is not None:
+            r = self.lib.solo_batch_encode_streams(self.h, smap.data_ptr(), N, pcm.data_ptr(), P, bits.data_ptr(), nbytes.data_ptr(), status.data_ptr(),
+                                                   self._stream())
+            # (the handle's internal streams read the list: with asynchronous joins it must outlive the call, like its other inputs)
+            self._enc_lists = (getattr(self, "_enc_lists", (None,))[-1], smap)
+        else:
+            r = self.lib.solo_batch_encode(self.h, pcm.data_ptr(), P, bits.data_ptr(), nbytes.data_ptr(), status.data_ptr(), self._stream())
         if r:
-            raise RuntimeError("solo_batch_encode -> %d" % r)
+            raise RuntimeError("solo_batch_encode%s -> %d" % ("_streams" if smap is not None else "", r))
         return bits, nbytes, status
 
     def set_timing(self, on=True):
@@ -298,23 +334,33 @@ class SoloBatch:
         """launches per encoder kernel of the most recent encode call (the call's packets are pipelined in chunks)"""
         return int(self.lib.solo_batch_last_encode_chunks(self.h))
 
-    def decode(self, bits, nbytes, recv=None, pcm=None, status=None):
-        """bits uint8 [N,P,slot], nbytes int16 [N,P,2], recv uint8 [N,P] (bit0 MD1, bit1 MD2) -> pcm int16 [N,P,640] (1280 in the 32 kHz mode)"""
+    def decode(self, bits, nbytes, recv=None, pcm=None, status=None, streams=None):
+        """bits uint8 [N,P,slot], nbytes int16 [N,P,2], recv uint8 [N,P] (bit0 MD1, bit1 MD2) -> pcm int16 [N,P,640] (1280 in the 32 kHz mode).
+        streams: decode only these streams (solo_batch_decode_streams): n = len(streams) rows in place of N."""
         t = self.torch
         assert bits.is_cuda and bits.dtype == t.uint8 and bits.is_contiguous()
         assert nbytes.dtype == t.int16 and nbytes.is_contiguous()
         N, P, S = bits.shape
-        assert N == self.n_streams and S == self.slot
+        smap = None
+        if streams is not None:
+            smap, n = self._subset(streams)
+            if N != n:
+                raise ValueError("bits has %d rows for %d listed streams" % (N, n))
+        assert (smap is not None or N == self.n_streams) and S == self.slot
         if recv is not None:
             assert recv.dtype == t.uint8 and recv.is_contiguous() and tuple(recv.shape) == (N, P)
         if pcm is None:
             pcm = t.zeros((N, P, self.packet_samples), dtype=t.int16, device=bits.device)
         if status is None:
             status = t.zeros((N,), dtype=t.int32, device=bits.device)
-        r = self.lib.solo_batch_decode(self.h, bits.data_ptr(), nbytes.data_ptr(), recv.data_ptr() if recv is not None else None,
-                                       P, pcm.data_ptr(), status.data_ptr(), self._stream())
+        if smap is not None:
+            r = self.lib.solo_batch_decode_streams(self.h, smap.data_ptr(), N, bits.data_ptr(), nbytes.data_ptr(),
+                                                   recv.data_ptr() if recv is not None else None, P, pcm.data_ptr(), status.data_ptr(), self._stream())
+        else:
+            r = self.lib.solo_batch_decode(self.h, bits.data_ptr(), nbytes.data_ptr(), recv.data_ptr() if recv is not None else None,
+                                           P, pcm.data_ptr(), status.data_ptr(), self._stream())
         if r:
-            raise RuntimeError("solo_batch_decode -> %d" % r)
+            raise RuntimeError("solo_batch_decode%s -> %d" % ("_streams" if smap is not None else "", r))
         return pcm, status
 
     def decode_split(self, desc_a, len_a, desc_b, len_b, pcm=None, status=None):
@@ -352,16 +398,24 @@ class SoloBatch:
         if r:
             raise RuntimeError("solo_recv_insert -> %d" % r)
 
-    def recv_decode(self, n_packets=1, pcm=None, status=None):
-        """Decode the next n_packets sequence numbers of every stream from what has arrived -> pcm int16 [N,n_packets,samples]."""
+    def recv_decode(self, n_packets=1, pcm=None, status=None, streams=None):
+        """Decode the next n_packets sequence numbers of every stream from what has arrived -> pcm int16 [N,n_packets,samples].
+        streams: play out only these streams (solo_recv_decode_streams): pcm [n,n_packets,samples], status [n]; the others keep
+        their queue and play-out position."""
         t = self.torch
+        smap, N = None, self.n_streams
+        if streams is not None:
+            smap, N = self._subset(streams)
         if pcm is None:
-            pcm = t.zeros((self.n_streams, n_packets, self.packet_samples), dtype=t.int16, device=self.device)
+            pcm = t.zeros((N, n_packets, self.packet_samples), dtype=t.int16, device=self.device)
         if status is None:
-            status = t.zeros((self.n_streams,), dtype=t.int32, device=self.device)
-        r = self.lib.solo_recv_decode(self.h, n_packets, pcm.data_ptr(), status.data_ptr(), self._stream())
+            status = t.zeros((N,), dtype=t.int32, device=self.device)
+        if smap is not None:
+            r = self.lib.solo_recv_decode_streams(self.h, smap.data_ptr(), N, n_packets, pcm.data_ptr(), status.data_ptr(), self._stream())
+        else:
+            r = self.lib.solo_recv_decode(self.h, n_packets, pcm.data_ptr(), status.data_ptr(), self._stream())
         if r:
-            raise RuntimeError("solo_recv_decode -> %d" % r)
+            raise RuntimeError("solo_recv_decode%s -> %d" % ("_streams" if smap is not None else "", r))
         return pcm, status
 
     def recv_reset_streams(self, streams, first_seq):

@@ -42,23 +42,44 @@ __global__ void __launch_bounds__(64) solo_sum_sqr_probe_kernel(const i16* x, in
     if (SX_LANE == 0) { energy[blockIdx.x] = e; shift[blockIdx.x] = s; }
 }
 
+// Subset calls: is the caller's device list strictly increasing inside [0, n_streams)?  One workgroup; the verdict word (0 = accepted)
+// is the handle's (solo_batch::d_verdict), every kernel of the call reads it before it does anything (solo_stream_ctl.h).  A refused
+// list also writes -1 to every status word of the call.
+__global__ void __launch_bounds__(256) solo_stream_list_check_kernel(const i32* map, int n, int n_streams, u32* verdict, i32* status) {
+    __shared__ int bad;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const i32 v = map[i];
+        if (v < 0 || v >= n_streams || (i > 0 && map[i - 1] >= v)) mine = 1;
+    }
+    if (mine) atomicOr(&bad, 1);
+    __syncthreads();
+    const int verdict_bad = bad;
+    if (threadIdx.x == 0) *verdict = (u32)verdict_bad;
+    if (verdict_bad && status)
+        for (int i = threadIdx.x; i < n; i += 256) status[i] = -1;
+}
+
 // the same decoder compiled for the 32 kHz API rate (SILK wide band, 16 kHz bands): solo_api_wb.hip
 extern "C" {
 size_t solo_wb_dec_state_bytes();
 hipError_t solo_wb_dec_launch_init(void* states, int n_streams, int hb_joint, int useMDIndex, hipStream_t s);
 hipError_t solo_wb_dec_launch_init_list(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s);
 hipError_t solo_wb_dec_launch(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int slot,
-                              int16_t* pcm, int32_t* status, hipStream_t s);
+                              int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s);
 hipError_t solo_wb_dec_launch_extract(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets,
-                                      int p0, int pc, int slot, void* recs, hipStream_t s);
+                                      int p0, int pc, int slot, void* recs, const int32_t* map, const uint32_t* verdict, hipStream_t s);
 hipError_t solo_wb_dec_launch_synth(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int p0,
-                                    int pc, int slot, const void* recs, int16_t* pcm, int32_t* status, hipStream_t s);
+                                    int pc, int slot, const void* recs, int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict,
+                                    hipStream_t s);
 size_t solo_wb_dec_extracted_bytes();
 hipError_t solo_wb_dec_launch_split(void* states, const uint8_t* descA, const int16_t* lenA, const uint8_t* descB, const int16_t* lenB, int n_streams,
                                     int n_packets, int slot, int16_t* pcm, int32_t* status, hipStream_t s);
 hipError_t solo_wb_dec_launch_raw(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm, int32_t* status, hipStream_t s);
 hipError_t solo_wb_dec_launch_ring(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth, int slot,
-                                   int16_t* pcm, int32_t* status, hipStream_t s);
+                                   int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s);
 hipError_t solo_wb_recv_launch_insert(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth, int slot,
                                       const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats, hipStream_t s);
 }
@@ -131,6 +152,9 @@ struct solo_batch {
     int32_t* d_recv_play;
     uint32_t* d_recv_stats;
     int32_t recv_depth, recv_slot;
+    // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
+    // asynchronous joins), [2] decode, [3] receiver play-out
+    uint32_t* d_verdict;
     int wb;                          // decoder control asked for samplerate 32000: 1280-sample packets, SILK at 16 kHz
 };
 
@@ -303,6 +327,13 @@ static bool stream_list_ok(const solo_batch* b, const int32_t* h_streams, int32_
     return true;
 }
 
+// Subset calls: the host checks only the count and the pointers (the list itself lives on the device: it is checked there, on the
+// caller's stream, by solo_stream_list_check_kernel, whose verdict the call's kernels read)
+static hipError_t launch_list_check(const solo_batch* b, const int32_t* d_streams, int32_t n, uint32_t* verdict, int32_t* d_status, hipStream_t s) {
+    hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, s, d_streams, n, b->n_streams, verdict, d_status);
+    return hipGetLastError();
+}
+
 // Per-stream re-initialisation: everything is validated and turned into records (solo_stream_ctl.h) before anything is enqueued, so a
 // refused call changes nothing.  Per stream: the encoder's rate, DTX and useMDIndex, the decoder's useMDIndex; samplerate, framesize_ms and
 // the joint mode select the kernel build and the packet geometry and must be the handle's.
@@ -384,6 +415,10 @@ solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, con
         if (enc && enc->samplerate != dec->samplerate) { solo_batch_destroy(b); return NULL; }     // a handle has one rate
         if (hipMalloc(&b->d_dec_state, (b->wb ? solo_wb_dec_state_bytes() : solo_dec_state_bytes()) * (size_t)n_streams) != hipSuccess) { solo_batch_destroy(b); return NULL; }
     }
+    if (hipMalloc((void**)&b->d_verdict, 4 * sizeof(uint32_t)) != hipSuccess || hipMemset(b->d_verdict, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
+        solo_batch_destroy(b);
+        return NULL;
+    }
     if (solo_batch_reset(b, NULL) != 0 || hipDeviceSynchronize() != hipSuccess) { solo_batch_destroy(b); return NULL; }
     return b;
 }
@@ -403,6 +438,7 @@ void solo_batch_destroy(solo_batch_t* b) {
         b->d_parsed[i] = NULL;
     }
     if (b->d_dec_state) (void)hipFree(b->d_dec_state);
+    if (b->d_verdict) (void)hipFree(b->d_verdict);
     if (b->ev_ready) for (int i = 0; i < 6; i++) (void)hipEventDestroy(b->ev[i]);
     if (b->tev_ready) for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) (void)hipEventDestroy(b->tev[k][c][e]);
     if (b->pipe_ready) {
@@ -429,10 +465,11 @@ void solo_batch_destroy(solo_batch_t* b) {
 #define SOLO_DEC_FIRST_CHUNK 64
 #define SOLO_DEC_CHUNK_DEFAULT 64
 static_assert(2 * sizeof(SxExtracted) + 8 == 2216, "include/solo_mi355x.h documents 2216 bytes of extraction records (2 x 1104 B + two list entries) per packet (16 kHz API rate)");
-int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_recv,
-                          int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
-    if (!b || !b->have_dec || !d_bits || !d_nbytes || !d_pcm || n_packets <= 0) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
+// map = NULL: every stream (solo_batch_decode); else the n listed streams of solo_batch_decode_streams, their records / PCM / status compact
+static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_recv,
+                                int32_t n_packets, int16_t* d_pcm, int32_t* d_status, hipStream_t st) {
+    const int ns = map ? n : b->n_streams;
+    uint32_t* verdict = map ? b->d_verdict + 2 : NULL;
     const bool tm = b->timing && b->ev_ready;
     if (!b->dec_pipe_ready) {
         const char* e = getenv("SOLO_DEC_SPLIT");
@@ -464,8 +501,9 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
     if (tm) (void)hipEventRecord(b->ev[4], st);
     if (!b->dec_split) {
         // single kernel: one wavefront per stream parses (two lanes) and synthesises
-        const hipError_t e = (b->wb ? solo_wb_dec_launch : solo_dec_launch)(b->d_dec_state, d_bits, d_nbytes, d_recv, b->n_streams, n_packets, b->slot,
-                                                                             d_pcm, d_status, st);
+        if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));
+        const hipError_t e = (b->wb ? solo_wb_dec_launch : solo_dec_launch)(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, b->slot,
+                                                                             d_pcm, d_status, map, verdict, st);
         if (tm) { (void)hipEventRecord(b->ev[5], st); b->ev_dec = 1; }
         SOLO_CHECK(e);
         return 0;
@@ -480,12 +518,12 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
     const size_t rec_bytes = b->wb ? solo_wb_dec_extracted_bytes() : solo_dec_extracted_bytes();
     int cp = n_packets < b->dec_chunk ? n_packets : b->dec_chunk;
     {   // (floor: one packet per chunk -- a handle with more than cap / 2216 streams holds n_streams x 2216 B per buffer, see the header)
-        const size_t fit = b->dec_scratch_cap / ((size_t)b->n_streams * rec_bytes);
+        const size_t fit = b->dec_scratch_cap / ((size_t)ns * rec_bytes);
         if ((size_t)cp > fit) cp = fit < 1 ? 1 : (int)fit;
     }
     const int c0 = (n_packets > 2 * b->dec_first && cp > b->dec_first) ? b->dec_first : cp;      // (never larger than the buffers: c0 <= cp)
     const int nchunks = 1 + (n_packets - c0 + cp - 1) / cp;
-    const size_t need = (size_t)b->n_streams * (size_t)cp * rec_bytes + 256;      // (+ the count of the listed description slots)
+    const size_t need = (size_t)ns * (size_t)cp * rec_bytes + 256;      // (+ the count of the listed description slots)
     if (need > b->parsed_bytes || (nchunks > 1 && !b->parsed_two)) {
         SOLO_CHECK(hipStreamSynchronize(st));
         (void)hipStreamSynchronize(b->sP);
@@ -505,6 +543,7 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
         SOLO_CHECK(hipStreamWaitEvent(st, b->evDJoin, 0));
         SOLO_CHECK(hipStreamWaitEvent(st, b->evDJoin2, 0));
     }
+    if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));      // (the previous call's kernels, which read the verdict, are done)
     SOLO_CHECK(hipEventRecord(b->evDFork, st));
     SOLO_CHECK(hipStreamWaitEvent(b->sP, b->evDFork, 0));
     SOLO_CHECK(hipStreamWaitEvent(b->sS, b->evDFork, 0));
@@ -514,13 +553,13 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
         const int p0 = c == 0 ? 0 : c0 + (c - 1) * cp, pc = c == 0 ? c0 : ((p0 + cp <= n_packets) ? cp : n_packets - p0), k = c & 1;
         // (every failure inside the loop goes through the join block below: nothing of this call stays forked)
         if (c >= 2 && (lerr = hipStreamWaitEvent(b->sP, b->evS[k], 0)) != hipSuccess) break;
-        lerr = (b->wb ? solo_wb_dec_launch_extract : solo_dec_launch_extract)(b->d_dec_state, d_bits, d_nbytes, d_recv, b->n_streams, n_packets, p0, pc,
-                                                                              b->slot, b->d_parsed[k], b->sP);
+        lerr = (b->wb ? solo_wb_dec_launch_extract : solo_dec_launch_extract)(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc,
+                                                                              b->slot, b->d_parsed[k], map, verdict, b->sP);
         if (lerr != hipSuccess) break;
         if ((lerr = hipEventRecord(b->evP[k], b->sP)) != hipSuccess) break;
         if ((lerr = hipStreamWaitEvent(b->sS, b->evP[k], 0)) != hipSuccess) break;
-        lerr = (b->wb ? solo_wb_dec_launch_synth : solo_dec_launch_synth)(b->d_dec_state, d_bits, d_nbytes, d_recv, b->n_streams, n_packets, p0, pc, b->slot,
-                                                                          b->d_parsed[k], d_pcm, d_status, b->sS);
+        lerr = (b->wb ? solo_wb_dec_launch_synth : solo_dec_launch_synth)(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot,
+                                                                          b->d_parsed[k], d_pcm, d_status, map, verdict, b->sS);
         if (lerr != hipSuccess) break;
         if ((lerr = hipEventRecord(b->evS[k], b->sS)) != hipSuccess) break;
     }
@@ -532,6 +571,16 @@ int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t*
     if (tm) { (void)hipEventRecord(b->ev[5], st); b->ev_dec = 1; }
     SOLO_CHECK(lerr);
     return 0;
+}
+int32_t solo_batch_decode(solo_batch_t* b, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_recv,
+                          int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
+    if (!b || !b->have_dec || !d_bits || !d_nbytes || !d_pcm || n_packets <= 0) return -1;
+    return solo_decode_impl(b, NULL, 0, d_bits, d_nbytes, d_recv, n_packets, d_pcm, d_status, (hipStream_t)hip_stream);
+}
+int32_t solo_batch_decode_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, const uint8_t* d_bits, const int16_t* d_nbytes,
+                                  const uint8_t* d_recv, int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
+    if (!b || !b->have_dec || !d_streams || n <= 0 || n > b->n_streams || !d_bits || !d_nbytes || !d_pcm || n_packets <= 0) return -1;
+    return solo_decode_impl(b, d_streams, n, d_bits, d_nbytes, d_recv, n_packets, d_pcm, d_status, (hipStream_t)hip_stream);
 }
 
 int32_t solo_batch_decode_split(solo_batch_t* b, const uint8_t* d_descA, const int16_t* d_lenA, const uint8_t* d_descB,
@@ -592,8 +641,18 @@ int32_t solo_recv_insert(solo_batch_t* b, const solo_arrival_t* d_arrivals, int3
 int32_t solo_recv_decode(solo_batch_t* b, int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
     if (!b || !b->d_recv_ring || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
     SOLO_CHECK((b->wb ? solo_wb_dec_launch_ring : solo_dec_launch_ring)(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->n_streams, n_packets,
-                                                                        b->recv_depth, b->recv_slot, d_pcm, d_status,
+                                                                        b->recv_depth, b->recv_slot, d_pcm, d_status, NULL, NULL,
                                                                         (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_recv_decode_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, int32_t n_packets, int16_t* d_pcm, int32_t* d_status,
+                                 void* hip_stream) {
+    if (!b || !b->d_recv_ring || !d_streams || n <= 0 || n > b->n_streams || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    uint32_t* verdict = b->d_verdict + 3;
+    SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, d_status, st));
+    SOLO_CHECK((b->wb ? solo_wb_dec_launch_ring : solo_dec_launch_ring)(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, n, n_packets,
+                                                                        b->recv_depth, b->recv_slot, d_pcm, d_status, d_streams, verdict, st));
     return 0;
 }
 int32_t solo_recv_stats(solo_batch_t* b, uint32_t* out8, void* hip_stream) {
@@ -754,12 +813,14 @@ static int32_t solo_encode_persist(solo_batch* b, const int16_t* d_pcm, int32_t 
     return 0;
 }
 
-int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes,
-                          int32_t* d_status, void* hip_stream) {
-    if (!b || !b->have_enc || !d_pcm || !d_bits || !d_nbytes || n_packets <= 0) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
+// map = NULL: every stream (solo_batch_encode); else the n listed streams of solo_batch_encode_streams: PCM, payloads, status and the
+// hand-over records at the compact position, the stream state through the map (solo_stream_ctl.h)
+static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes,
+                                int32_t* d_status, hipStream_t st) {
     const size_t np = (size_t)b->n_streams * (size_t)n_packets;
     const solo_enc_ops* ops = b->eops;
+    // a subset call's quantiser addresses the states of its rows with 32-bit offsets from the handle's first state (solo_nsq_row.hip)
+    if (map && (unsigned long long)b->n_streams * (unsigned long long)ops->state_bytes >= (1ull << 32)) return -1;
     // the quantiser addresses the hand-over records of its wavefront's four streams with 32-bit offsets from a wave-uniform base
     // (solo_nsq_row.hip): the records of 3 streams x 2 n_packets, plus one more record for the offsets inside the last one, must stay
     // below 4 GiB (~700 k packets per call at the 16 kHz API rate)
@@ -782,8 +843,9 @@ int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packe
         const int32_t r = solo_enc_pipe_setup(b);
         if (r) return r;
     }
-    // SOLO_ENC_PERSIST=1: calls of two or more packets run the persistent schedule (a single packet has nothing to pipeline inside the call)
-    if (b->persist && n_packets >= 2) return solo_encode_persist(b, d_pcm, n_packets, d_bits, d_nbytes, d_status, st, nin, nout, cin);
+    // SOLO_ENC_PERSIST=1: calls of two or more packets run the persistent schedule (a single packet has nothing to pipeline inside the call);
+    // a subset call always runs the launch-per-chunk schedule
+    if (!map && b->persist && n_packets >= 2) return solo_encode_persist(b, d_pcm, n_packets, d_bits, d_nbytes, d_status, st, nin, nout, cin);
 
     // Launch per chunk: chunk c of the call's packets goes analysis (stream sA) -> quantiser (sB) -> high band, range coder (sC).  A_c
     // follows A_{c-1}, B_c follows A_c and B_{c-1}, C_c follows B_c and C_{c-1}; so the quantiser of chunk c (one wave per SIMD, latency
@@ -807,6 +869,18 @@ int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packe
         }
     }
     const bool tm_req = b->timing && b->tev_ready;
+    uint32_t* verdict = NULL;
+    if (map) {
+        // the layout of the hand-over records depends on the list: no chunk-wise reuse across a subset call, either side
+        b->evC_valid = 0;
+        // the verdict word of this call; the call two before used the same one: its kernels must be through
+        verdict = b->d_verdict + (b->enc_seq & 1u);
+        if (b->enc_seq >= 2) {
+            SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinA[b->enc_seq & 1u], 0));
+            SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinC[b->enc_seq & 1u], 0));
+        }
+        SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));
+    }
     if (b->enc_seq > 0 && (b->last_np != n_packets || b->last_cp != cp || b->evC_valid == 0)) {
         // the previous call laid its hand-over records out differently (or ran the persistent schedule): no chunk-wise reuse, wait for all of it
         SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evJoinC[(b->enc_seq - 1u) & 1u], 0));
@@ -821,16 +895,19 @@ int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packe
     SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evFork, 0));
     // Streams beyond the launch group (SOLO_ENC_GROUP) are processed group after group; all per-stream arrays are stream-major, so a
     // group is the same launch on offset pointers.
-    const int G = b->group_streams > 0 ? b->group_streams : b->n_streams;
-    const int ngroups = (b->n_streams + G - 1) / G;
+    // (a subset call: groups of compact positions, group g works on the streams map[s0 .. s0 + ns))
+    const int nall = map ? n : b->n_streams;
+    const int G = b->group_streams > 0 ? b->group_streams : nall;
+    const int ngroups = (nall + G - 1) / G;
     const bool tm = tm_req && (size_t)ngroups * (size_t)nchunks <= SOLO_MAX_CHUNKS;     // (per-launch timing brackets: one per event slot)
     const size_t frame_samples = (size_t)(b->enc_ctrl.framesize_ms == 20 ? ops->packet_samples / 2 : ops->packet_samples);
     int idx = 0;
     hipError_t lerr = hipSuccess;
     for (int g = 0; g < ngroups; g++) {
-        const int s0 = g * G, ns = (s0 + G <= b->n_streams) ? G : b->n_streams - s0;
+        const int s0 = g * G, ns = (s0 + G <= nall) ? G : nall - s0;
         const size_t pk0 = (size_t)s0 * (size_t)n_packets;                               // first packet record of the group
-        void* g_states = (char*)states + (size_t)s0 * ops->state_bytes;
+        void* g_states = map ? states : (char*)states + (size_t)s0 * ops->state_bytes;
+        const int32_t* g_map = map ? map + s0 : NULL;
         const int16_t* g_pcm = d_pcm + pk0 * frame_samples;
         void* g_nin = (char*)nin + pk0 * 2 * ops->nsq_in_bytes;
         void* g_nout = (char*)nout + pk0 * 2 * ops->nsq_out_bytes;
@@ -844,7 +921,7 @@ int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packe
             if (ngroups == 1 && cc < b->evC_valid) SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evC[c], 0));      // (previous call: its coding of this chunk's records is done)
             if (idx > 0 && b->gate > 0) (void)solo_launch_gate(&b->d_started[cprev], b->started_target[cprev], b->sA);
             if (tm) (void)hipEventRecord(b->tev[0][c][0], b->sA);
-            if ((lerr = ops->analysis(g_states, g_pcm, ns, n_packets, p0, pc, g_nin, g_cin, b->sA)) != hipSuccess) goto launch_failed;
+            if ((lerr = ops->analysis(g_states, g_pcm, ns, n_packets, p0, pc, g_nin, g_cin, g_map, verdict, b->sA)) != hipSuccess) goto launch_failed;
             if (tm) (void)hipEventRecord(b->tev[0][c][1], b->sA);
             SOLO_CHECK(hipEventRecord(b->evA[c], b->sA));
             SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evA[c], 0));
@@ -855,7 +932,7 @@ int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packe
             constexpr int exp_skip = 0;
 #endif
             if (!(exp_skip & 1)) {
-            if ((lerr = (hipError_t)ops->nsq(g_states, g_nin, g_nout, ns, n_packets, p0, pc, &b->d_started[c], b->d_nsq_ring, b->sB)) != hipSuccess) goto launch_failed;
+            if ((lerr = (hipError_t)ops->nsq(g_states, g_nin, g_nout, ns, n_packets, p0, pc, &b->d_started[c], b->d_nsq_ring, g_map, verdict, b->sB)) != hipSuccess) goto launch_failed;
             b->started_target[c] += (unsigned int)ops->nsq_workgroups(ns);     // workgroups of this launch, counted once it is enqueued
             }
             if (tm) (void)hipEventRecord(b->tev[1][c][1], b->sB);
@@ -863,7 +940,7 @@ int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packe
             SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[c], 0));
             if (tm) (void)hipEventRecord(b->tev[2][c][0], b->sC);
             if (!(exp_skip & 2))
-            if ((lerr = ops->coding(g_states, g_cin, g_nout, ns, n_packets, p0, pc, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, b->sC)) != hipSuccess) goto launch_failed;
+            if ((lerr = ops->coding(g_states, g_cin, g_nout, ns, n_packets, p0, pc, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) goto launch_failed;
             if (tm) (void)hipEventRecord(b->tev[2][c][1], b->sC);
             SOLO_CHECK(hipEventRecord(b->evC[c], b->sC));
         }
@@ -884,7 +961,7 @@ launch_failed:
         (void)hipStreamWaitEvent(st, b->evFork, 0);
         return -(int32_t)lerr;
     }
-    b->evC_valid = ngroups == 1 ? nchunks : 0;       // chunk-wise hand-over guards only for single-group calls
+    b->evC_valid = (ngroups == 1 && !map) ? nchunks : 0;       // chunk-wise hand-over guards only for single-group calls of every stream
     const int js = (int)(b->enc_seq & 1u);
     b->enc_seq++;
     SOLO_CHECK(hipEventRecord(b->evJoinA[js], b->sA));
@@ -898,8 +975,19 @@ launch_failed:
     SOLO_CHECK(hipGetLastError());
     return 0;
 }
+int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes,
+                          int32_t* d_status, void* hip_stream) {
+    if (!b || !b->have_enc || !d_pcm || !d_bits || !d_nbytes || n_packets <= 0) return -1;
+    return solo_encode_impl(b, NULL, 0, d_pcm, n_packets, d_bits, d_nbytes, d_status, (hipStream_t)hip_stream);
+}
+int32_t solo_batch_encode_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits,
+                                  int16_t* d_nbytes, int32_t* d_status, void* hip_stream) {
+    if (!b || !b->have_enc || !d_streams || n <= 0 || n > b->n_streams || !d_pcm || !d_bits || !d_nbytes || n_packets <= 0) return -1;
+    return solo_encode_impl(b, d_streams, n, d_pcm, n_packets, d_bits, d_nbytes, d_status, (hipStream_t)hip_stream);
+}
 #else
 int32_t solo_batch_encode(solo_batch_t*, const int16_t*, int32_t, uint8_t*, int16_t*, int32_t*, void*) { return -1; }
+int32_t solo_batch_encode_streams(solo_batch_t*, const int32_t*, int32_t, const int16_t*, int32_t, uint8_t*, int16_t*, int32_t*, void*) { return -1; }
 #endif
 
 // ---- the reference's six entry points: a batch of one stream, staged through device buffers ----------
@@ -1061,7 +1149,7 @@ int32_t solo_debug_nsq(int32_t n_streams, int32_t n_packets, const void* h_in, v
     if (hipMalloc(&st, ops->state_bytes * (size_t)n_streams) == hipSuccess && hipMalloc(&d_in, sz_in) == hipSuccess && hipMalloc(&d_out, sz_out) == hipSuccess &&
         hipMalloc(&ring, ops->nsq_ring_bytes(n_streams)) == hipSuccess && hipMemset(d_out, 0, sz_out) == hipSuccess &&
         ops->init(st, n_streams, 12000, 0, 0, 0, 2, (hipStream_t)0) == hipSuccess && hipMemcpy(d_in, h_in, sz_in, hipMemcpyHostToDevice) == hipSuccess &&
-        ops->nsq(st, d_in, d_out, n_streams, n_packets, 0, n_packets, NULL, ring, NULL) == 0 && hipDeviceSynchronize() == hipSuccess &&
+        ops->nsq(st, d_in, d_out, n_streams, n_packets, 0, n_packets, NULL, ring, NULL, NULL, NULL) == 0 && hipDeviceSynchronize() == hipSuccess &&
         hipMemcpy(h_out, d_out, sz_out, hipMemcpyDeviceToHost) == hipSuccess)
         rc = (int32_t)ops->nsq_out_bytes;                       // (the caller checks its idea of the record size)
     (void)hipFree(st); (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(ring);

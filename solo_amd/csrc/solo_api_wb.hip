@@ -14,16 +14,17 @@ hipError_t solo_wb_dec_launch_init_list(void* states, const SxStreamCtl* recs, i
     return solo_dec_launch_init_list_wb(states, recs, n, hb_joint, s);
 }
 hipError_t solo_wb_dec_launch(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int slot,
-                              int16_t* pcm, int32_t* status, hipStream_t s) {
-    return solo_dec_launch_wb(states, bits, nbytes, recv, n_streams, n_packets, slot, pcm, status, s);
+                              int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
+    return solo_dec_launch_wb(states, bits, nbytes, recv, n_streams, n_packets, slot, pcm, status, map, verdict, s);
 }
 hipError_t solo_wb_dec_launch_extract(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets,
-                                      int p0, int pc, int slot, void* recs, hipStream_t s) {
-    return solo_dec_launch_extract_wb(states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, recs, s);
+                                      int p0, int pc, int slot, void* recs, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
+    return solo_dec_launch_extract_wb(states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, recs, map, verdict, s);
 }
 hipError_t solo_wb_dec_launch_synth(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int p0,
-                                    int pc, int slot, const void* recs, int16_t* pcm, int32_t* status, hipStream_t s) {
-    return solo_dec_launch_synth_wb(states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, recs, pcm, status, s);
+                                    int pc, int slot, const void* recs, int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict,
+                                    hipStream_t s) {
+    return solo_dec_launch_synth_wb(states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, recs, pcm, status, map, verdict, s);
 }
 size_t solo_wb_dec_extracted_bytes() { return solo_dec_extracted_bytes_wb(); }
 hipError_t solo_wb_dec_launch_split(void* states, const uint8_t* descA, const int16_t* lenA, const uint8_t* descB, const int16_t* lenB, int n_streams,
@@ -31,8 +32,8 @@ hipError_t solo_wb_dec_launch_split(void* states, const uint8_t* descA, const in
     return solo_dec_launch_split_wb(states, descA, lenA, descB, lenB, n_streams, n_packets, slot, pcm, status, s);
 }
 hipError_t solo_wb_dec_launch_ring(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth, int slot,
-                                   int16_t* pcm, int32_t* status, hipStream_t s) {
-    return solo_dec_launch_ring_wb(states, ring, lens, play, n_streams, n_packets, depth, slot, pcm, status, s);
+                                   int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
+    return solo_dec_launch_ring_wb(states, ring, lens, play, n_streams, n_packets, depth, slot, pcm, status, map, verdict, s);
 }
 hipError_t solo_wb_dec_launch_raw(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm, int32_t* status, hipStream_t s) {
     return solo_dec_launch_raw_wb(state, bits, n0, n1, lostflag, pcm, status, s);

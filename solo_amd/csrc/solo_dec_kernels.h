@@ -79,12 +79,13 @@ SX_HD SxDecArgs sx_dec_map_record(i32 n0, i32 n1, int slot, int recv_mask, int h
 __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_kernel)(SxDecStream* states, const u8* __restrict__ bits,
                                                          const i16* __restrict__ nbytes, const u8* __restrict__ recv,
                                                          int n_streams, int n_packets, int slot,
-                                                         i16* __restrict__ pcm, i32* status) {
+                                                         i16* __restrict__ pcm, i32* status, const i32* __restrict__ map, const u32* verdict) {
     SxDecWork& w = SX_K(g_sx_dec_work);
-    const int s = blockIdx.x;
-    if (s >= n_streams) return;
-    const int useMDIndex = SX_UNI(states[s].useMDIndex);        // (the stream's own flag, wave-uniform)
-    SX_K(solo_dec_enter)(&w, &states[s]);
+    const int s = blockIdx.x;           // compact position: records, PCM, status; the state is that of stream map[s] (solo_stream_ctl.h)
+    if (s >= n_streams || sx_map_refused(map, verdict)) return;
+    SxDecStream* rec = &states[sx_map_stream(map, s)];
+    const int useMDIndex = SX_UNI(rec->useMDIndex);             // (the stream's own flag, wave-uniform)
+    SX_K(solo_dec_enter)(&w, rec);
     i32 first_err = 0;
     for (int p = 0; p < n_packets; p++) {
         const size_t pk = (size_t)s * n_packets + p;
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_kernel)(SxDecStream* s
         if (ret < 0 && first_err == 0) first_err = ret;
         wv_sync();
     }
-    SX_K(solo_dec_leave)(&w, &states[s]);
+    SX_K(solo_dec_leave)(&w, rec);
     if (status && SX_LANE == 0) status[s] = first_err;
 }
 
@@ -126,27 +127,29 @@ struct SxExtractWork {
 // (The order of the list depends on the order the wavefronts' atomic adds arrive in; every entry is extracted into its own record
 // whatever lane takes it.)
 static __device__ __forceinline__ bool SX_K(sx_extract_slot)(const SxDecStream* states, const i16* __restrict__ nbytes, const u8* __restrict__ recv, size_t idx, int n_packets,
-                                                            int p0, int pc, int slot, size_t* pk_out, int* hb_joint_out, int* md_out, SxDecArgs* a_out, i32* off,
-                                                            i32* len, int* sel, i32* hb_off) {
+                                                            int p0, int pc, int slot, const i32* __restrict__ map, size_t* pk_out, int* hb_joint_out, int* md_out,
+                                                            SxDecArgs* a_out, i32* off, i32* len, int* sel, i32* hb_off) {
     const int md = (int)(idx & 1);
     const size_t sp = idx >> 1;
-    const int s = (int)(sp / (size_t)pc), p = p0 + (int)(sp % (size_t)pc);
+    const int s = (int)(sp / (size_t)pc), p = p0 + (int)(sp % (size_t)pc);       // s: compact position (a lane's own: no wave-uniform map look-up)
     const size_t pk = (size_t)s * n_packets + p;
-    const int hb_joint = states[s].st.hb_joint | (states[s].st.fpp == 1);      // (what matters here: four high-band bytes instead of eight)
+    const SxDecStream* rec = &states[map ? map[s] : s];
+    const int hb_joint = rec->st.hb_joint | (rec->st.fpp == 1);      // (what matters here: four high-band bytes instead of eight)
     const SxDecArgs a = sx_dec_map_record(nbytes[pk * 2 + 0], nbytes[pk * 2 + 1], slot, recv ? (int)recv[pk] : 3, hb_joint);
-    *pk_out = pk; *hb_joint_out = hb_joint; *md_out = states[s].useMDIndex; *a_out = a;
+    *pk_out = pk; *hb_joint_out = hb_joint; *md_out = rec->useMDIndex; *a_out = a;
     *off = 0; *len = 0; *hb_off = -1; *sel = 0;
     return sx_desc_span(a.lostflag, a.a0, a.a1, hb_joint, md, off, len, sel, hb_off);
 }
 // list: n_streams * pc * 2 entries, count: one word behind them, zeroed before the launch
 __global__ void __launch_bounds__(64) SX_K(solo_dec_list_kernel)(const SxDecStream* states, const i16* __restrict__ nbytes, const u8* __restrict__ recv, int n_streams,
                                                                 int n_packets, int p0, int pc, int slot, SxExtracted* __restrict__ recs, u32* __restrict__ list,
-                                                                u32* __restrict__ count) {
+                                                                u32* __restrict__ count, const i32* __restrict__ map, const u32* verdict) {
+    if (sx_map_refused(map, verdict)) return;
     const size_t idx = (size_t)blockIdx.x * 64 + threadIdx.x;
     bool present = false;
     if (idx < (size_t)n_streams * (size_t)pc * 2) {
         size_t pk; int hb_joint, md, sel; SxDecArgs a; i32 off, len, hb_off;
-        present = SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, &pk, &hb_joint, &md, &a, &off, &len, &sel, &hb_off);
+        present = SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, map, &pk, &hb_joint, &md, &a, &off, &len, &sel, &hb_off);
         if (!present) recs[idx].usable = 0;
     }
     const unsigned long long m = __builtin_amdgcn_ballot_w64(present);
@@ -160,8 +163,9 @@ __global__ void __launch_bounds__(SX_EXTRACT_LANES, SX_EXTRACT_WAVES) SX_K(solo_
                                                                                  const i16* __restrict__ nbytes, const u8* __restrict__ recv,
                                                                                  int n_streams, int n_packets, int p0, int pc, int slot,
                                                                                  SxExtracted* __restrict__ recs, const u32* __restrict__ list,
-                                                                                 const u32* __restrict__ count) {
+                                                                                 const u32* __restrict__ count, const i32* __restrict__ map, const u32* verdict) {
     __shared__ SxExtractWork w;
+    if (sx_map_refused(map, verdict)) return;
     // (without a list -- the caller passed no reception flags, so nearly every slot carries bytes -- lane i takes slot i)
     const size_t n_listed = list ? (size_t)*count : (size_t)n_streams * (size_t)pc * 2;
     if ((size_t)blockIdx.x * SX_EXTRACT_LANES >= n_listed) return;                  // (the grid is sized for "every slot carries bytes")
@@ -177,7 +181,7 @@ __global__ void __launch_bounds__(SX_EXTRACT_LANES, SX_EXTRACT_WAVES) SX_K(solo_
     const size_t idx = list ? (size_t)list[li] : li;
     size_t pk; int hb_joint, md, sel; SxDecArgs a; i32 off, len, hb_off;
     SxExtracted* rec = &recs[idx];
-    if (!SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, &pk, &hb_joint, &md, &a, &off, &len, &sel, &hb_off)) { rec->usable = 0; return; }
+    if (!SX_K(sx_extract_slot)(states, nbytes, recv, idx, n_packets, p0, pc, slot, map, &pk, &hb_joint, &md, &a, &off, &len, &sel, &hb_off)) { rec->usable = 0; return; }
     const u8* pkt = bits + pk * (size_t)slot + a.ptr_off;
     sx_extract_desc(pkt + off, len, md, (const SxCdf*)&w.cdf, &w.lane[threadIdx.x], rec, sel, hb_off >= 0 ? pkt + hb_off : 0, hb_joint);
 }
@@ -201,15 +205,17 @@ static __device__ __forceinline__ void sx_prefetch_records(const SxExtracted* ne
 __global__ void __launch_bounds__(64, 4) SX_K(solo_dec_synth_kernel)(SxDecStream* states, const u8* __restrict__ bits,
                                                             const i16* __restrict__ nbytes, const u8* __restrict__ recv,
                                                             int n_streams, int n_packets, int p0, int pc, int slot,
-                                                            const SxExtracted* __restrict__ recs, i16* __restrict__ pcm, i32* status) {
+                                                            const SxExtracted* __restrict__ recs, i16* __restrict__ pcm, i32* status,
+                                                            const i32* __restrict__ map, const u32* verdict) {
     SxDecWork& w = SX_K(g_sx_dec_work);
-    const int s = blockIdx.x;
-    if (s >= n_streams) return;
-    const int useMDIndex = SX_UNI(states[s].useMDIndex);
+    const int s = blockIdx.x;           // compact position; the state is that of stream map[s]
+    if (s >= n_streams || sx_map_refused(map, verdict)) return;
+    SxDecStream* rec = &states[sx_map_stream(map, s)];
+    const int useMDIndex = SX_UNI(rec->useMDIndex);
 #if defined(SX_STOPS) && defined(__HIP_DEVICE_COMPILE__)
     SX_STOPS_ENTER(0)
 #endif
-    SX_K(solo_dec_enter)(&w, &states[s]);
+    SX_K(solo_dec_enter)(&w, rec);
     i32 first_err = 0;
     for (int p = p0; p < p0 + pc; p++) {
         const size_t pk = (size_t)s * n_packets + p;
@@ -223,7 +229,7 @@ __global__ void __launch_bounds__(64, 4) SX_K(solo_dec_synth_kernel)(SxDecStream
         if (ret < 0 && first_err == 0) first_err = ret;
         wv_sync();
     }
-    SX_K(solo_dec_leave)(&w, &states[s]);
+    SX_K(solo_dec_leave)(&w, rec);
     if (status && SX_LANE == 0) {
         if (p0 == 0) status[s] = first_err;
         else if (first_err != 0 && status[s] == 0) status[s] = first_err;
@@ -326,18 +332,21 @@ __global__ void __launch_bounds__(64) SX_K(solo_recv_reset_list_kernel)(u32* len
     SX_PAR(i, depth) l[i] = 0;
     if (SX_LANE == 0) play[r.stream] = r.a;
 }
-// the next n_packets sequence numbers of every stream: merge what has arrived (as the split kernel does), decode, free the entries
+// the next n_packets sequence numbers of every stream: merge what has arrived (as the split kernel does), decode, free the entries.
+// With a map (solo_recv_decode_streams) position s plays out stream map[s]: its state, queue and play-out position; PCM and status compact.
 __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_ring_kernel)(SxDecStream* states, const u8* ring, u32* lens, i32* play, int n_streams, int n_packets,
-                                                              int depth, int slot, i16* __restrict__ pcm, i32* status) {
+                                                              int depth, int slot, i16* __restrict__ pcm, i32* status, const i32* __restrict__ map,
+                                                              const u32* verdict) {
     SxDecWork& w = SX_K(g_sx_dec_work);
     const int s = blockIdx.x;
-    if (s >= n_streams) return;
-    const int useMDIndex = SX_UNI(states[s].useMDIndex);
-    SX_K(solo_dec_enter)(&w, &states[s]);
+    if (s >= n_streams || sx_map_refused(map, verdict)) return;
+    const int ss = sx_map_stream(map, s);
+    const int useMDIndex = SX_UNI(states[ss].useMDIndex);
+    SX_K(solo_dec_enter)(&w, &states[ss]);
     i32 first_err = 0;
-    const i32 play0 = play[s];
+    const i32 play0 = play[ss];
     for (int p = 0; p < n_packets; p++) {
-        const size_t e = sx_recv_entry(s, play0 + p, depth);
+        const size_t e = sx_recv_entry(ss, play0 + p, depth);
         const u32 lw = lens[e];
         const u8* pa = ring + e * 2 * (size_t)slot;
         const int ret = SX_K(sx_decode_split_packet)(w, pa, (i32)(lw & 0xFFFFu), pa + slot, (i32)(lw >> 16), slot, useMDIndex,
@@ -346,9 +355,9 @@ __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_ring_kernel)(SxDecStre
         wv_sync();
         if (SX_LANE == 0) lens[e] = 0;
     }
-    SX_K(solo_dec_leave)(&w, &states[s]);
+    SX_K(solo_dec_leave)(&w, &states[ss]);
     if (SX_LANE == 0) {
-        play[s] = play0 + n_packets;
+        play[ss] = play0 + n_packets;
         if (status) status[s] = first_err;
     }
 }
@@ -382,15 +391,18 @@ static inline hipError_t SX_K(solo_dec_launch_init_list)(void* states, const SxS
     }
     return hipSuccess;
 }
+// (map, verdict: a subset call's stream list and verdict word, solo_stream_ctl.h; NULL, NULL: every stream of the handle)
 static inline hipError_t SX_K(solo_dec_launch)(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
-                                               int n_packets, int slot, int16_t* pcm, int32_t* status, hipStream_t s) {
+                                               int n_packets, int slot, int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict,
+                                               hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_decode_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, bits, nbytes, recv, n_streams,
-                       n_packets, slot, pcm, status);
+                       n_packets, slot, pcm, status, map, verdict);
     return hipGetLastError();
 }
 // recs: solo_dec_extracted_bytes() x n_streams x pc bytes + 256: the records, behind them the list of the slots that carry bytes and its count
 static inline hipError_t SX_K(solo_dec_launch_extract)(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
-                                                       int n_packets, int p0, int pc, int slot, void* recs, hipStream_t s) {
+                                                       int n_packets, int p0, int pc, int slot, void* recs, const int32_t* map, const uint32_t* verdict,
+                                                       hipStream_t s) {
     const size_t lanes = (size_t)n_streams * (size_t)pc * 2;
     u32* list = recv ? (u32*)((SxExtracted*)recs + lanes) : (u32*)0;     // (reception flags given: descriptions may be missing)
     u32* count = list ? list + lanes : (u32*)0;
@@ -398,18 +410,18 @@ static inline hipError_t SX_K(solo_dec_launch_extract)(const void* states, const
         hipError_t e = hipMemsetAsync(count, 0, sizeof(u32), s);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(SX_K(solo_dec_list_kernel), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, s, (const SxDecStream*)states, nbytes, recv, n_streams,
-                           n_packets, p0, pc, slot, (SxExtracted*)recs, list, count);
+                           n_packets, p0, pc, slot, (SxExtracted*)recs, list, count, map, verdict);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(SX_K(solo_dec_extract_kernel), dim3((unsigned)((lanes + SX_EXTRACT_LANES - 1) / SX_EXTRACT_LANES)), dim3(SX_EXTRACT_LANES), 0, s,
-                       (const SxDecStream*)states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, (SxExtracted*)recs, list, count);
+                       (const SxDecStream*)states, bits, nbytes, recv, n_streams, n_packets, p0, pc, slot, (SxExtracted*)recs, list, count, map, verdict);
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_dec_launch_synth)(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
                                                      int n_packets, int p0, int pc, int slot, const void* recs,
-                                                     int16_t* pcm, int32_t* status, hipStream_t s) {
+                                                     int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_dec_synth_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, bits, nbytes, recv, n_streams,
-                       n_packets, p0, pc, slot, (const SxExtracted*)recs, pcm, status);
+                       n_packets, p0, pc, slot, (const SxExtracted*)recs, pcm, status, map, verdict);
     return hipGetLastError();
 }
 static inline size_t SX_K(solo_dec_extracted_bytes)() { return 2 * sizeof(SxExtracted) + 2 * sizeof(u32); }      // per packet: two records, two list entries
@@ -446,9 +458,9 @@ static inline hipError_t SX_K(solo_recv_launch_insert)(const void* arrivals, int
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_dec_launch_ring)(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth,
-                                                    int slot, int16_t* pcm, int32_t* status, hipStream_t s) {
+                                                    int slot, int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_decode_ring_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, ring, lens, play, n_streams, n_packets, depth,
-                       slot, pcm, status);
+                       slot, pcm, status, map, verdict);
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_dec_launch_raw)(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm,

@@ -63,14 +63,14 @@ SX_ENTER_FN void SX_K(solo_enc_leave)(SxEncWork* w, SxEncStream* rec) {
 #ifndef SX_TU_FRONT
 __global__ void __launch_bounds__(64, SX_ANALYSIS_WAVES) SX_K(solo_enc_analysis_kernel)(SxEncStream* states, const i16* __restrict__ pcm, int n_streams,
                                                                   int n_packets, int p0, int pc, SxNsqIn* __restrict__ nsq_in,
-                                                                  SxCodeIn* __restrict__ code_in) {
+                                                                  SxCodeIn* __restrict__ code_in, const i32* __restrict__ map, const u32* verdict) {
     __shared__ SxEncWork w;
-    const int s = blockIdx.x;
-    if (s >= n_streams) return;
+    const int s = blockIdx.x;           // compact position: inputs and hand-over records; the state is that of stream map[s] (solo_stream_ctl.h)
+    if (s >= n_streams || sx_map_refused(map, verdict)) return;
     // the same issue priority as the quantiser's wave (solo_nsq_row.hip): with the quantiser above the analysis waves the encoder is
     // 0.5 % slower, below them 18 % (the quantiser starves); the range coder / coding kernels of older chunks stay at 0
     __builtin_amdgcn_s_setprio(SX_ANALYSIS_PRIO);
-    SxEncStream* rec = &states[s];
+    SxEncStream* rec = &states[sx_map_stream(map, s)];
 #if defined(SX_PROF) && defined(__HIP_DEVICE_COMPILE__)
     const unsigned long long hist_t0_ = wall_clock64();
 #endif
@@ -149,13 +149,15 @@ __device__ __forceinline__ i32 SX_K(sx_rc_code_and_assemble)(const SxFrameIdx* i
 __global__ void __launch_bounds__(64) SX_K(solo_enc_rc_kernel)(const SxEncStream* states, const SxCodeIn* __restrict__ code_in,
                                                                const SxNsqOut* __restrict__ nsq_out, int n_streams, int n_packets, int p0, int pc,
                                                                u8* __restrict__ rcbuf, SxRcInfo* __restrict__ rcinfo, const u8* __restrict__ hbout,
-                                                               int slot_bytes, u8* __restrict__ bits, i16* __restrict__ nbytes, i32* status) {
+                                                               int slot_bytes, u8* __restrict__ bits, i16* __restrict__ nbytes, i32* status,
+                                                               const i32* __restrict__ map, const u32* verdict) {
     __shared__ SxRcWork w;
+    if (sx_map_refused(map, verdict)) return;
     SX_K(sx_cdf_stage)(&w.cdf);
     const int lane = threadIdx.x, md = lane & 1;
     const int s = blockIdx.x * (SX_RC_LANES / 2) + (lane >> 1);
     if (lane >= SX_RC_LANES || s >= n_streams) return;
-    const SxEncState* st = &states[s].core;
+    const SxEncState* st = &states[map ? map[s] : s].core;
     const int useDTX = st->useDTX, useMDIndex = st->useMDIndex, fpp = st->fpp;
     const int hb_bytes = st->hb_joint ? 4 : 4 * fpp;
     i32 first_err = 0;
@@ -178,11 +180,11 @@ __global__ void __launch_bounds__(64) SX_K(solo_enc_rc_kernel)(const SxEncStream
 // to find room between the analysis kernel's: they are in line as soon as the quantiser is through, DESIGN_NOTES.md section 10.)
 __global__ void __launch_bounds__(64, SX_ANALYSIS_WAVES) SX_K(solo_enc_coding_kernel)(SxEncStream* states, const SxCodeIn* __restrict__ code_in,
                                                                 const SxNsqOut* __restrict__ nsq_out, int n_streams, int n_packets, int p0,
-                                                                int pc, u8* __restrict__ hbout) {
+                                                                int pc, u8* __restrict__ hbout, const i32* __restrict__ map, const u32* verdict) {
     __shared__ SxEncWork w;
     const int s = blockIdx.x;
-    if (s >= n_streams) return;
-    SxEncStream* rec = &states[s];
+    if (s >= n_streams || sx_map_refused(map, verdict)) return;
+    SxEncStream* rec = &states[sx_map_stream(map, s)];
 #if defined(SX_STOPS) && defined(__HIP_DEVICE_COMPILE__)
     SX_STOPS_ENTER(1)
 #endif
@@ -366,7 +368,7 @@ __global__ void __launch_bounds__(64 * SX_FRONT_WAVES, SX_ANALYSIS_WAVES) SX_K(s
 
 #endif
 extern "C" int SX_K(solo_launch_nsq)(void* states, const void* in, void* out, int n_streams, int n_packets, int p0, int pc, unsigned int* started,
-                                     void* ring, void* hip_stream);   // solo_nsq_row.hip / solo_nsq_row_wb.hip
+                                     void* ring, const int32_t* map, const uint32_t* verdict, void* hip_stream);   // solo_nsq_row.hip / solo_nsq_row_wb.hip
 extern "C" int SX_K(solo_launch_nsq_persist)(void* states, const void* in, void* out, int n_streams, int n_packets, unsigned int* started, void* ring,
                                              const unsigned int* ana_flag, unsigned int* nsq_flag, unsigned int ticket0, unsigned int* err, void* stage,
                                              void* hip_stream);
@@ -393,9 +395,9 @@ static hipError_t SX_K(solo_enc_launch_init_list)(void* states, const SxStreamCt
     return hipSuccess;
 }
 static hipError_t SX_K(solo_enc_launch_analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in,
-                                                 void* code_in, hipStream_t s) {
+                                                 void* code_in, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_enc_analysis_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, pcm, n_streams, n_packets, p0, pc,
-                       (SxNsqIn*)nsq_in, (SxCodeIn*)code_in);
+                       (SxNsqIn*)nsq_in, (SxCodeIn*)code_in, map, verdict);
     return hipGetLastError();
 }
 // rc_scratch of a launch-per-chunk coding stage: [n_streams * pc * 2] byte buffers of SX_RC_BUF_STRIDE, then as many SxRcInfo, then 8
@@ -411,15 +413,16 @@ static u8* SX_K(solo_enc_hbout_of)(u8* rcbuf, int n_streams, int pc) {
 }
 // third stage of a chunk: high band, then range coder + payload assembly
 static hipError_t SX_K(solo_enc_launch_coding)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int p0, int pc,
-                                               int slot, uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, hipStream_t s) {
+                                               int slot, uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, const int32_t* map,
+                                               const uint32_t* verdict, hipStream_t s) {
     u8* rcbuf = (u8*)rc_scratch;
     hipLaunchKernelGGL(SX_K(solo_enc_coding_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, (const SxCodeIn*)code_in,
-                       (const SxNsqOut*)nsq_out, n_streams, n_packets, p0, pc, SX_K(solo_enc_hbout_of)(rcbuf, n_streams, pc));
+                       (const SxNsqOut*)nsq_out, n_streams, n_packets, p0, pc, SX_K(solo_enc_hbout_of)(rcbuf, n_streams, pc), map, verdict);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(SX_K(solo_enc_rc_kernel), dim3((n_streams + SX_RC_LANES / 2 - 1) / (SX_RC_LANES / 2)), dim3(64), 0, s, (const SxEncStream*)states, (const SxCodeIn*)code_in,
                        (const SxNsqOut*)nsq_out, n_streams, n_packets, p0, pc, rcbuf, SX_K(solo_enc_rcinfo_of)(rcbuf, n_streams, pc),
-                       (const u8*)SX_K(solo_enc_hbout_of)(rcbuf, n_streams, pc), slot, bits, nbytes, status);
+                       (const u8*)SX_K(solo_enc_hbout_of)(rcbuf, n_streams, pc), slot, bits, nbytes, status, map, verdict);
     return hipGetLastError();
 }
 #endif

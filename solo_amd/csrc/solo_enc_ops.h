@@ -13,12 +13,14 @@ struct solo_enc_ops {
     hipError_t (*init)(void* states, int n_streams, int silk_rate_bps, int useMDIndex, int hb_joint, int useDTX, int frames_per_packet, hipStream_t s);
     // the listed streams only (solo_batch_reset_streams): records (stream, SILK rate, useMDIndex, useDTX), validated by the caller
     hipError_t (*init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, int frames_per_packet, hipStream_t s);
-    // ---- launch per chunk ----
-    hipError_t (*analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in, void* code_in, hipStream_t s);
-    int (*nsq)(void* states, const void* in, void* out, int n_streams, int n_packets, int p0, int pc, unsigned int* started, void* ring, void* hip_stream);
+    // ---- launch per chunk ----  (map, verdict: a subset call's stream list and verdict word, solo_stream_ctl.h; NULL, NULL: all streams)
+    hipError_t (*analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in, void* code_in, const int32_t* map,
+                           const uint32_t* verdict, hipStream_t s);
+    int (*nsq)(void* states, const void* in, void* out, int n_streams, int n_packets, int p0, int pc, unsigned int* started, void* ring, const int32_t* map,
+               const uint32_t* verdict, void* hip_stream);
     // third stage of a chunk: high band (one wavefront per stream), then range coder + payload assembly (one lane per description)
     hipError_t (*coding)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int p0, int pc, int slot,
-                         uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, hipStream_t s);
+                         uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, const int32_t* map, const uint32_t* verdict, hipStream_t s);
     size_t (*rc_scratch_bytes)(int n_streams, int pc);                   // scratch of one coding launch (pc packets per stream)
     int (*nsq_workgroups)(int n_streams);                                // workgroups of one quantiser launch (they count into the residency gate)
     size_t (*nsq_ring_bytes)(int n_streams);                             // emission-ring scratch of one quantiser launch

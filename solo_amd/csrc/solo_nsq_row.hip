@@ -39,22 +39,28 @@
 #endif
 // ring: SX_DD_DELAY rows of 64 cells per workgroup and track-per-lane (the emission ring of its streams, rows of 64 lanes = 1 KB)
 #define SX_NSQ_RING_CELLS (SX_DD_DELAY * 64)
-extern "C" __global__ void SX_NSQ_CAP_ATTR __launch_bounds__(64) SX_K(solo_nsq_kernel)(SxEncStream* states, const SxNsqIn* __restrict__ in,
-                                                                 SxNsqOut* __restrict__ out, int n_streams, int n_packets, int p0, int pc,
-                                                                 unsigned int* started, SxRowCell* __restrict__ ring) {
-    __shared__ SxRowWork w[SX_PER_WAVE];
+// One launch per chunk.  MAPPED (subset calls, solo_stream_ctl.h): the rows of a wavefront work on the states of streams map[s], which may
+// lie anywhere in the handle, so the wave-uniform base is the handle's first state and each row's 32-bit offset points at its own stream
+// (solo_api.hip refuses a subset call when the handle's states reach 4 GiB); the hand-over records and the ring stay compact.  The
+// identity instance keeps the base of its four consecutive states.
+template <bool MAPPED>
+__device__ __forceinline__ void SX_K(sx_nsq_chunk)(SxEncStream* states, const SxNsqIn* __restrict__ in, SxNsqOut* __restrict__ out, int n_streams, int n_packets,
+                                                   int p0, int pc, unsigned int* started, SxRowCell* __restrict__ ring, const i32* __restrict__ map,
+                                                   const u32* verdict, SxRowWork* w) {
     const int g = threadIdx.x / SX_GROUP;
     const int s = blockIdx.x * SX_PER_WAVE + g;
     if (started && threadIdx.x == 0) atomicAdd(started, 1u);     // lets the host-side pipeline start the next analysis chunk once this kernel is resident
+    if (MAPPED && __builtin_amdgcn_readfirstlane((int)*verdict) != 0) return;
     if (s >= n_streams) return;
     // a latency-bound wave that shares its SIMD with the analysis / coding kernels of neighbouring chunks: issue first
     __builtin_amdgcn_s_setprio(SX_NSQ_PRIO);
     // wave-uniform bases + 32-bit lane offsets (solo_enc_nsq_row.h): the states / records of the wavefront's four streams
-    char* Pu = (char*)&states[(size_t)blockIdx.x * SX_PER_WAVE];
-    const u32 pOff = (u32)g * (u32)sizeof(SxEncStream) + (u32)offsetof(SxEncStream, nsq);
+    char* Pu = MAPPED ? (char*)states : (char*)&states[(size_t)blockIdx.x * SX_PER_WAVE];
+    const u32 pOff = (MAPPED ? (u32)map[s] : (u32)g) * (u32)sizeof(SxEncStream) + (u32)offsetof(SxEncStream, nsq);
     const u32 rec_stride = (u32)n_packets * 2u;                     // hand-over records between consecutive streams
     SxRowCell* rgu = ring + (size_t)blockIdx.x * SX_NSQ_RING_CELLS;
-    const int fpp = __builtin_amdgcn_readfirstlane(states[(size_t)blockIdx.x * SX_PER_WAVE].core.fpp);      // frames per packet: the same for every stream of a handle
+    const size_t s_first = MAPPED ? (size_t)(u32)__builtin_amdgcn_readfirstlane(map[(size_t)blockIdx.x * SX_PER_WAVE]) : (size_t)blockIdx.x * SX_PER_WAVE;
+    const int fpp = __builtin_amdgcn_readfirstlane(states[s_first].core.fpp);      // frames per packet: the same for every stream of a handle
     for (int p = p0; p < p0 + pc; p++) {          // packets [p0, p0 + pc) of a launch of n_packets (row stride of the records)
         for (int f = 0; f < fpp; f++) {
             const size_t r0 = ((size_t)blockIdx.x * SX_PER_WAVE * n_packets + p) * 2 + f;       // record of the wavefront's first stream
@@ -63,6 +69,19 @@ extern "C" __global__ void SX_NSQ_CAP_ATTR __launch_bounds__(64) SX_K(solo_nsq_k
             wv_sync();
         }
     }
+}
+extern "C" __global__ void SX_NSQ_CAP_ATTR __launch_bounds__(64) SX_K(solo_nsq_kernel)(SxEncStream* states, const SxNsqIn* __restrict__ in,
+                                                                 SxNsqOut* __restrict__ out, int n_streams, int n_packets, int p0, int pc,
+                                                                 unsigned int* started, SxRowCell* __restrict__ ring) {
+    __shared__ SxRowWork w[SX_PER_WAVE];
+    SX_K(sx_nsq_chunk)<false>(states, in, out, n_streams, n_packets, p0, pc, started, ring, nullptr, nullptr, w);
+}
+extern "C" __global__ void SX_NSQ_CAP_ATTR __launch_bounds__(64) SX_K(solo_nsq_kernel_mapped)(SxEncStream* states, const SxNsqIn* __restrict__ in,
+                                                                        SxNsqOut* __restrict__ out, int n_streams, int n_packets, int p0, int pc,
+                                                                        unsigned int* started, SxRowCell* __restrict__ ring,
+                                                                        const i32* __restrict__ map, const u32* verdict) {
+    __shared__ SxRowWork w[SX_PER_WAVE];
+    SX_K(sx_nsq_chunk)<true>(states, in, out, n_streams, n_packets, p0, pc, started, ring, map, verdict, w);
 }
 
 // The quantiser of the PERSISTENT pipeline (solo_api.hip, solo_enc_kernels.h: solo_enc_front_kernel): one launch per call and launch group.
@@ -251,8 +270,12 @@ extern "C" size_t SX_K(solo_nsq_ring_bytes)(int n_streams) {
     return (size_t)((n_streams + SX_PER_WAVE - 1) / SX_PER_WAVE) * SX_NSQ_RING_CELLS * sizeof(SxRowCell);
 }
 extern "C" int SX_K(solo_launch_nsq)(void* states, const void* in, void* out, int n_streams, int n_packets, int p0, int pc, unsigned int* started,
-                               void* ring, void* hip_stream) {
-    hipLaunchKernelGGL(SX_K(solo_nsq_kernel), dim3((n_streams + SX_PER_WAVE - 1) / SX_PER_WAVE), dim3(64), 0, (hipStream_t)hip_stream, (SxEncStream*)states,
-                       (const SxNsqIn*)in, (SxNsqOut*)out, n_streams, n_packets, p0, pc, started, (SxRowCell*)ring);
+                               void* ring, const int32_t* map, const uint32_t* verdict, void* hip_stream) {
+    if (map)
+        hipLaunchKernelGGL(SX_K(solo_nsq_kernel_mapped), dim3((n_streams + SX_PER_WAVE - 1) / SX_PER_WAVE), dim3(64), 0, (hipStream_t)hip_stream, (SxEncStream*)states,
+                           (const SxNsqIn*)in, (SxNsqOut*)out, n_streams, n_packets, p0, pc, started, (SxRowCell*)ring, map, verdict);
+    else
+        hipLaunchKernelGGL(SX_K(solo_nsq_kernel), dim3((n_streams + SX_PER_WAVE - 1) / SX_PER_WAVE), dim3(64), 0, (hipStream_t)hip_stream, (SxEncStream*)states,
+                           (const SxNsqIn*)in, (SxNsqOut*)out, n_streams, n_packets, p0, pc, started, (SxRowCell*)ring);
     return (int)hipGetLastError();
 }

@@ -14,3 +14,15 @@ struct SxStreamCtl {
 struct SxStreamCtlList {
     SxStreamCtl r[SX_CTL_PER_LAUNCH];
 };
+
+// Subset calls (solo_batch_encode_streams, solo_batch_decode_streams, solo_recv_decode_streams): compact position i of a launch works
+// on the state of stream map[i]; its inputs and outputs stay at position i.  A NULL map is the identity (every other entry point), and
+// the kernels branch on it once, wave-uniformly.  The call's verdict word (solo_api.hip: solo_stream_list_check_kernel) is non-zero when
+// the list is not strictly increasing inside [0, N): every kernel of such a call leaves before it touches anything.
+#if defined(__HIPCC__)
+__device__ __forceinline__ bool sx_map_refused(const int32_t* map, const uint32_t* verdict) {
+    return map != nullptr && __builtin_amdgcn_readfirstlane((int)*verdict) != 0;
+}
+// (s wave-uniform: the stream of a one-wavefront-per-stream kernel)
+__device__ __forceinline__ int sx_map_stream(const int32_t* map, int s) { return map ? __builtin_amdgcn_readfirstlane(map[s]) : s; }
+#endif
