@@ -129,6 +129,20 @@ int32_t solo_batch_reset(solo_batch_t *b, void *hip_stream);
  * A handle created with one control and given per-stream controls here is the way to run mixed rates / DTX / useMDIndex in one batch. */
 int32_t solo_batch_reset_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, int32_t which,
                                  const USER_Ctrl_enc *h_enc, const USER_Ctrl_dec *h_dec, void *hip_stream);
+/* Changes the control of the listed RUNNING streams without re-initialising them: what SKP_Silk_SDK_Encode / _Decode take from their
+ * control on every call (SKP_Silk_enc_API.c:165-176, SKP_Silk_dec_API.c:107).  Arguments, checks and refusals are exactly those of
+ * solo_batch_reset_streams (-1 and nothing enqueued).
+ *   Encoder, per stream:  the SILK rate (targetRate_bps, <= 0 meaning 15600, minus 1600 -- 800 with joint_mode 1 --, clamped to
+ *                         [5000, 100000]) sets the two SNR targets as SKP_Silk_setup_rate_FIX does; dtx_enable and useMDIndex are set.
+ *   Decoder, per stream:  useMDIndex is set.
+ * Every other byte of the states stays bit for bit (first_frame_after_reset, VAD, noSpeechCounter / inDTX, all histories), and so do
+ * the receiver ring and the play-out positions.  The new control applies from the first packet encoded / decoded after the call on
+ * hip_stream; the update waits for this handle's encode / decode work still in flight (async joins included), so packets of earlier
+ * calls keep the old control.  Side effects, as in the reference: DTX switched on during a silence of more than 5 frames drops the very
+ * next packet (noSpeechCounter kept counting); sender and receiver must switch useMDIndex at the same packet; whether the receiver ring
+ * files a desc = -1 arrival follows the stream's decoder useMDIndex when solo_recv_insert runs. */
+int32_t solo_batch_update_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, int32_t which,
+                                  const USER_Ctrl_enc *h_enc, const USER_Ctrl_dec *h_dec, void *hip_stream);
 int32_t solo_batch_encode(solo_batch_t *b, const int16_t *d_pcm, int32_t n_packets, uint8_t *d_bits,
                           int16_t *d_nbytes, int32_t *d_status, void *hip_stream);
 int32_t solo_batch_decode(solo_batch_t *b, const uint8_t *d_bits, const int16_t *d_nbytes,

@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "solo_batch_last_kernel_ms", "solo_batch_last_encode_chunks", "solo_batch_decode_split", "solo_batch_set_async_join",
     "solo_batch_wait_encode", "solo_debug_l0", "solo_debug_sum_sqr_shift", "solo_debug_rowops", "solo_debug_clock", "solo_debug_nsq",
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
-    "solo_batch_reset_streams", "solo_recv_reset_streams",
+    "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
 ]
 
@@ -87,6 +87,8 @@ def load_library():
     lib.solo_batch_reset.restype = C.c_int32
     lib.solo_batch_reset_streams.restype = C.c_int32
     lib.solo_batch_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_batch_update_streams.restype = C.c_int32
+    lib.solo_batch_update_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_recv_reset_streams.restype = C.c_int32
     lib.solo_recv_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.solo_batch_encode.restype = C.c_int32
@@ -238,11 +240,9 @@ class SoloBatch:
             raise ValueError("%s: one value per listed stream (%d), got %d" % (name, n, len(v)))
         return v
 
-    def reset_streams(self, streams, rate=None, dtx=None, use_md_index=None, which="both"):
-        """Re-initialise the listed streams (solo_batch_reset_streams), each as a fresh encoder / decoder with its own control.  rate,
-        dtx and use_md_index take a scalar or one value per listed stream; None means the handle's create-time value.  rate and dtx
-        are encoder fields, use_md_index goes to both directions.  which: "enc" (1), "dec" (2) or "both" (3; on a handle of one
-        direction: that direction).  Other streams are untouched; work enqueued on the current stream afterwards sees the new states."""
+    def _ctl_arrays(self, streams, rate, dtx, use_md_index, which):
+        """the arguments of solo_batch_reset_streams / solo_batch_update_streams: (stream indices, which, encoder controls or None,
+        decoder controls or None); None controls mean the handle's create-time control"""
         idx = self._stream_list(streams)
         n = len(idx)
         if which not in self._WHICH:
@@ -255,7 +255,7 @@ class SoloBatch:
         rates, dtxs, mds = self._per_stream(rate, n, "rate"), self._per_stream(dtx, n, "dtx"), self._per_stream(use_md_index, n, "use_md_index")
         enc_arr = dec_arr = None
         if (rate is not None or dtx is not None) and not w & 1:
-            raise ValueError("rate / dtx are encoder controls: the call does not reset an encoder")
+            raise ValueError("rate / dtx are encoder controls: the call does not reach an encoder")
         if w & 1 and (rate is not None or dtx is not None or use_md_index is not None):
             h = self._enc
             enc_arr = (USER_Ctrl_enc * n)()
@@ -274,9 +274,29 @@ class SoloBatch:
                 dec_arr[i] = USER_Ctrl_dec(packetLoss_perc=h.packetLoss_perc, samplerate=h.samplerate, framesize_ms=h.framesize_ms,
                                            joint_enable=h.joint_enable, joint_mode=h.joint_mode,
                                            useMDIndex=h.useMDIndex if mds[i] is None else int(mds[i]))
+        return idx, w, enc_arr, dec_arr
+
+    def reset_streams(self, streams, rate=None, dtx=None, use_md_index=None, which="both"):
+        """Re-initialise the listed streams (solo_batch_reset_streams), each as a fresh encoder / decoder with its own control.  rate,
+        dtx and use_md_index take a scalar or one value per listed stream; None means the handle's create-time value.  rate and dtx
+        are encoder fields, use_md_index goes to both directions.  which: "enc" (1), "dec" (2) or "both" (3; on a handle of one
+        direction: that direction).  Other streams are untouched; work enqueued on the current stream afterwards sees the new states."""
+        idx, w, enc_arr, dec_arr = self._ctl_arrays(streams, rate, dtx, use_md_index, which)
+        n = len(idx)
         r = self.lib.solo_batch_reset_streams(self.h, (C.c_int32 * n)(*idx), n, w, enc_arr, dec_arr, self._stream())
         if r:
             raise RuntimeError("solo_batch_reset_streams -> %d" % r)
+
+    def update_streams(self, streams, rate=None, dtx=None, use_md_index=None, which="both"):
+        """Change the control of the listed RUNNING streams (solo_batch_update_streams): the encoder's rate, DTX and useMDIndex, the
+        decoder's useMDIndex; nothing else of their state, queue or play-out position changes.  Arguments as reset_streams (None: the
+        handle's create-time value).  The new control applies from the next packet encoded / decoded on the current stream; packets
+        of earlier calls keep the old one."""
+        idx, w, enc_arr, dec_arr = self._ctl_arrays(streams, rate, dtx, use_md_index, which)
+        n = len(idx)
+        r = self.lib.solo_batch_update_streams(self.h, (C.c_int32 * n)(*idx), n, w, enc_arr, dec_arr, self._stream())
+        if r:
+            raise RuntimeError("solo_batch_update_streams -> %d" % r)
 
     def encode(self, pcm, bits=None, nbytes=None, status=None, streams=None):
         """pcm: int16 CUDA tensor [N, P, 640] -> (bits uint8 [N,P,slot], nbytes int16 [N,P,2], status int32 [N]).

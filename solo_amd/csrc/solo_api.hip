@@ -67,6 +67,7 @@ extern "C" {
 size_t solo_wb_dec_state_bytes();
 hipError_t solo_wb_dec_launch_init(void* states, int n_streams, int hb_joint, int useMDIndex, hipStream_t s);
 hipError_t solo_wb_dec_launch_init_list(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s);
+hipError_t solo_wb_dec_launch_ctl_list(void* states, const SxStreamCtl* recs, int n, hipStream_t s);
 hipError_t solo_wb_dec_launch(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int slot,
                               int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s);
 hipError_t solo_wb_dec_launch_extract(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets,
@@ -334,15 +335,15 @@ static hipError_t launch_list_check(const solo_batch* b, const int32_t* d_stream
     return hipGetLastError();
 }
 
-// Per-stream re-initialisation: everything is validated and turned into records (solo_stream_ctl.h) before anything is enqueued, so a
-// refused call changes nothing.  Per stream: the encoder's rate, DTX and useMDIndex, the decoder's useMDIndex; samplerate, framesize_ms and
-// the joint mode select the kernel build and the packet geometry and must be the handle's.
-int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
-                                 const USER_Ctrl_dec* h_dec, void* hip_stream) {
-    if (!b || which < 1 || which > 3 || !stream_list_ok(b, h_streams, n)) return -1;
+// Per-stream controls of solo_batch_reset_streams and solo_batch_update_streams: everything is validated and turned into records
+// (solo_stream_ctl.h) before anything is enqueued, so a refused call changes nothing.  Per stream: the encoder's rate, DTX and
+// useMDIndex, the decoder's useMDIndex; samplerate, framesize_ms and the joint mode select the kernel build and the packet geometry
+// and must be the handle's.  false: the call is refused.
+static bool stream_ctl_records(const solo_batch* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
+                               const USER_Ctrl_dec* h_dec, std::vector<SxStreamCtl>& er, std::vector<SxStreamCtl>& dr) {
+    if (!b || which < 1 || which > 3 || !stream_list_ok(b, h_streams, n)) return false;
     const bool do_enc = (which & 1) != 0, do_dec = (which & 2) != 0;
-    if ((do_enc && !b->have_enc) || (do_dec && !b->have_dec) || (h_enc && !do_enc) || (h_dec && !do_dec)) return -1;
-    std::vector<SxStreamCtl> er, dr;
+    if ((do_enc && !b->have_enc) || (do_dec && !b->have_dec) || (h_enc && !do_enc) || (h_dec && !do_dec)) return false;
     if (do_enc) {
         const USER_Ctrl_enc& he = b->enc_ctrl;
         const int joint = ctrl_hb_joint(he.joint_enable, he.joint_mode);
@@ -352,7 +353,7 @@ int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int3
             if (c.targetRate_bps <= 0) c.targetRate_bps = 15600;                    // AGR_BWE_SDK_API.c:35 (on a copy: the caller's array stays)
             if (c.samplerate != he.samplerate || c.framesize_ms != he.framesize_ms || c.joint_enable != he.joint_enable || c.joint_mode != he.joint_mode ||
                 !ctrl_enc_supported(&c))
-                return -1;
+                return false;
             er[(size_t)i] = SxStreamCtl{h_streams[i], c.targetRate_bps - (joint ? 800 : 1600), c.useMDIndex, c.dtx_enable ? 1 : 0};
         }
     }
@@ -363,21 +364,49 @@ int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int3
             const USER_Ctrl_dec& c = h_dec ? h_dec[i] : hd;
             if (c.samplerate != hd.samplerate || c.framesize_ms != hd.framesize_ms || c.joint_enable != hd.joint_enable || c.joint_mode != hd.joint_mode ||
                 !ctrl_dec_supported(&c))
-                return -1;
+                return false;
             dr[(size_t)i] = SxStreamCtl{h_streams[i], c.useMDIndex, 0, 0};
         }
     }
+    return true;
+}
+
+// Per-stream re-initialisation (records: stream_ctl_records).
+int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
+                                 const USER_Ctrl_dec* h_dec, void* hip_stream) {
+    std::vector<SxStreamCtl> er, dr;
+    if (!stream_ctl_records(b, h_streams, n, which, h_enc, h_dec, er, dr)) return -1;
     hipStream_t s = (hipStream_t)hip_stream;
     {
         const int32_t r = solo_wait_in_flight(b, s);
         if (r) return r;
     }
-    if (do_dec)
+    if (!dr.empty())
         SOLO_CHECK((b->wb ? solo_wb_dec_launch_init_list : solo_dec_launch_init_list)(b->d_dec_state, dr.data(), n, ctrl_dec_hb_mode(b), s));
 #ifdef SOLO_WITH_ENCODER
-    if (do_enc)
+    if (!er.empty())
         SOLO_CHECK(b->eops->init_list(b->d_enc_state, er.data(), n, ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode),
                                       b->enc_ctrl.framesize_ms == 20 ? 1 : 2, s));
+#endif
+    return 0;
+}
+
+// A running stream's control (records: stream_ctl_records): the encoder's rate (setup_rate: the two SNR targets), DTX and useMDIndex,
+// the decoder's useMDIndex; every other word of the states, the receiver ring and the play-out positions stay.  The wait matters even
+// more than for a reset: the analysis / front kernels write a stream's whole SxEncState back when they end (an update that overtook
+// them would be undone), and the coder reads useDTX / useMDIndex of the packets it codes.
+int32_t solo_batch_update_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
+                                  const USER_Ctrl_dec* h_dec, void* hip_stream) {
+    std::vector<SxStreamCtl> er, dr;
+    if (!stream_ctl_records(b, h_streams, n, which, h_enc, h_dec, er, dr)) return -1;
+    hipStream_t s = (hipStream_t)hip_stream;
+    {
+        const int32_t r = solo_wait_in_flight(b, s);
+        if (r) return r;
+    }
+    if (!dr.empty()) SOLO_CHECK((b->wb ? solo_wb_dec_launch_ctl_list : solo_dec_launch_ctl_list)(b->d_dec_state, dr.data(), n, s));
+#ifdef SOLO_WITH_ENCODER
+    if (!er.empty()) SOLO_CHECK(b->eops->ctl_list(b->d_enc_state, er.data(), n, s));
 #endif
     return 0;
 }

@@ -13,6 +13,9 @@ hipError_t solo_wb_dec_launch_init(void* states, int n_streams, int hb_joint, in
 hipError_t solo_wb_dec_launch_init_list(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s) {
     return solo_dec_launch_init_list_wb(states, recs, n, hb_joint, s);
 }
+hipError_t solo_wb_dec_launch_ctl_list(void* states, const SxStreamCtl* recs, int n, hipStream_t s) {
+    return solo_dec_launch_ctl_list_wb(states, recs, n, s);
+}
 hipError_t solo_wb_dec_launch(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int slot,
                               int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
     return solo_dec_launch_wb(states, bits, nbytes, recv, n_streams, n_packets, slot, pcm, status, map, verdict, s);

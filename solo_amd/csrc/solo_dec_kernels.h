@@ -23,6 +23,13 @@ __global__ void __launch_bounds__(64) SX_K(solo_dec_init_list_kernel)(SxDecStrea
     const SxStreamCtl r = list.r[blockIdx.x];
     SX_K(sx_dec_stream_init)(&states[r.stream], hb_mode, r.a);
 }
+// solo_batch_update_streams: a RUNNING stream's useMDIndex (record: stream, useMDIndex), taken by the reference on every call
+// (dec_API.c:107); the decoder state itself stays.  One workgroup per record.
+__global__ void __launch_bounds__(64) SX_K(solo_dec_ctl_list_kernel)(SxDecStream* states, const SxStreamCtlList list, int n) {
+    if ((int)blockIdx.x >= n || SX_LANE != 0) return;
+    const SxStreamCtl r = list.r[blockIdx.x];
+    states[r.stream].useMDIndex = r.a;
+}
 
 // Decoder: rows D0-D8.  blockIdx.x = stream.
 // state record HBM <-> LDS (whole launch) and the entropy tables
@@ -386,6 +393,17 @@ static inline hipError_t SX_K(solo_dec_launch_init_list)(void* states, const SxS
         SxStreamCtlList l = {};
         for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
         hipLaunchKernelGGL(SX_K(solo_dec_init_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k, hb_joint);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+static inline hipError_t SX_K(solo_dec_launch_ctl_list)(void* states, const SxStreamCtl* recs, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
+        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
+        SxStreamCtlList l = {};
+        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
+        hipLaunchKernelGGL(SX_K(solo_dec_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

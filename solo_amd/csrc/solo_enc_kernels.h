@@ -19,6 +19,16 @@ __global__ void __launch_bounds__(64) SX_K(solo_enc_init_list_kernel)(SxEncStrea
     const SxStreamCtl r = list.r[blockIdx.x];
     sx_enc_state_init(&states[r.stream], r.a, r.b, hb_joint, r.c, fpp);
 }
+// solo_batch_update_streams: a RUNNING stream's control (record: stream, SILK rate, useMDIndex, useDTX), as SKP_Silk_SDK_Encode takes it at
+// the start of a packet (enc_API.c:165-176: setup_rate, useDTX, writeMDIndex); every other word of the state stays.  One workgroup per record.
+__global__ void __launch_bounds__(64) SX_K(solo_enc_ctl_list_kernel)(SxEncStream* states, const SxStreamCtlList list, int n) {
+    if ((int)blockIdx.x >= n || SX_LANE != 0) return;
+    const SxStreamCtl r = list.r[blockIdx.x];
+    SxEncState* st = &states[r.stream].core;
+    sx_enc_setup_rate(st, r.a);
+    st->useMDIndex = r.b;
+    st->useDTX = r.c;
+}
 
 // Encoder, rows E0-E9, over HBM hand-over records.  Two schedules of the same stage functions (solo_api.hip picks one per call):
 //  * launch per chunk (the default):
@@ -394,6 +404,17 @@ static hipError_t SX_K(solo_enc_launch_init_list)(void* states, const SxStreamCt
     }
     return hipSuccess;
 }
+static hipError_t SX_K(solo_enc_launch_ctl_list)(void* states, const SxStreamCtl* recs, int n, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
+        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
+        SxStreamCtlList l = {};
+        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
+        hipLaunchKernelGGL(SX_K(solo_enc_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 static hipError_t SX_K(solo_enc_launch_analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in,
                                                  void* code_in, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_enc_analysis_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, pcm, n_streams, n_packets, p0, pc,
@@ -452,7 +473,7 @@ extern "C" hipError_t SX_K(solo_enc_launch_front)(void* states, const int16_t* p
                                                   unsigned int* started, hipStream_t s);
 static const solo_enc_ops SX_K(solo_enc_ops_table) = {
     sizeof(SxEncStream), sizeof(SxNsqIn), sizeof(SxNsqOut), sizeof(SxCodeIn), SX_PACKET,
-    SX_K(solo_enc_launch_init), SX_K(solo_enc_launch_init_list), SX_K(solo_enc_launch_analysis), SX_K(solo_launch_nsq), SX_K(solo_enc_launch_coding), SX_K(solo_enc_rc_scratch_bytes),
+    SX_K(solo_enc_launch_init), SX_K(solo_enc_launch_init_list), SX_K(solo_enc_launch_ctl_list), SX_K(solo_enc_launch_analysis), SX_K(solo_launch_nsq), SX_K(solo_enc_launch_coding), SX_K(solo_enc_rc_scratch_bytes),
     SX_K(solo_nsq_workgroups), SX_K(solo_nsq_ring_bytes), SX_K(solo_enc_launch_front), SX_K(solo_launch_nsq_persist), SX_K(solo_enc_front_scratch_bytes), SX_K(solo_nsq_persist_workgroups), SX_K(solo_nsq_stage_bytes),
     SX_FRONT_WAVES, SX_FRONT_PER_CU};
 

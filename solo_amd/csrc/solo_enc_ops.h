@@ -13,6 +13,8 @@ struct solo_enc_ops {
     hipError_t (*init)(void* states, int n_streams, int silk_rate_bps, int useMDIndex, int hb_joint, int useDTX, int frames_per_packet, hipStream_t s);
     // the listed streams only (solo_batch_reset_streams): records (stream, SILK rate, useMDIndex, useDTX), validated by the caller
     hipError_t (*init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, int frames_per_packet, hipStream_t s);
+    // the listed RUNNING streams (solo_batch_update_streams): same records; rate, useMDIndex and useDTX change, nothing else of the state
+    hipError_t (*ctl_list)(void* states, const SxStreamCtl* recs, int n, hipStream_t s);
     // ---- launch per chunk ----  (map, verdict: a subset call's stream list and verdict word, solo_stream_ctl.h; NULL, NULL: all streams)
     hipError_t (*analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in, void* code_in, const int32_t* map,
                            const uint32_t* verdict, hipStream_t s);

@@ -153,6 +153,28 @@ struct SxEncCtrl {
     i32 vadFlag;                     // copy of state->vadFlag for this frame (coded per frame)
 };
 
+// SKP_Silk_setup_rate_FIX (control_codec_FIX.c:319): bitrate -> SNR tables, per description and total.  A field is assigned only where
+// the rate falls into an interval of its table; the reference keeps the old value otherwise.  Called by sx_enc_state_init and by
+// solo_batch_update_streams (solo_enc_ctl_list_kernel), on a running stream whose other state stays as it is.
+SX_HD void sx_enc_setup_rate(SxEncState* st, i32 silk_rate_bps) {
+    silk_rate_bps = sx_limit(silk_rate_bps, 5000, 100000);           // enc_API.c:187
+    i32 md_rate = silk_rate_bps / 2;
+    for (int k = 1; k < 8; k++) {
+        if (md_rate < T_target_rate[k]) {
+            i32 frac_Q6 = sx_shl(md_rate - T_target_rate[k - 1], 6) / (T_target_rate[k] - T_target_rate[k - 1]);
+            st->SNRPerMD_dB_Q7 = sx_shl(T_snr_table_Q1[k - 1], 6) + sx_mul(frac_Q6, T_snr_table_Q1[k] - T_snr_table_Q1[k - 1]);
+            break;
+        }
+    }
+    for (int k = 1; k < 8; k++) {
+        if (silk_rate_bps <= T_target_rate[k]) {
+            i32 frac_Q6 = sx_shl(silk_rate_bps - T_target_rate[k - 1], 6) / (T_target_rate[k] - T_target_rate[k - 1]);
+            st->SNR_dB_Q7 = sx_shl(T_snr_table_Q1[k - 1], 6) + sx_mul(frac_Q6, T_snr_table_Q1[k] - T_snr_table_Q1[k - 1]);
+            break;
+        }
+    }
+}
+
 // SKP_Silk_init_encoder_FIX (SKP_Silk_init_encoder_FIX.c:33) + the first SKP_Silk_control_encoder_FIX
 // pass (control_codec_FIX.c:56-130: setup_fs(8), setup_rate, ...) + AGR_Sate_Encoder_Init
 // (libBWE/AGR_BWE_SDK_API.c:11-126).  `silk_rate_bps` = targetRate_bps - 1600.
@@ -186,22 +208,6 @@ SX_FN void sx_enc_state_init(SxEncStream* rec, i32 silk_rate_bps, i32 useMDIndex
     st->pf_lagPrev = 100;
     st->LastGainIndex = 1;
     rec->nsq.trk[0].s.lagPrev = 100;
-    // setup_rate_FIX (control_codec_FIX.c:319): bitrate -> SNR tables, per description and total
-    silk_rate_bps = sx_limit(silk_rate_bps, 5000, 100000);           // enc_API.c:187
-    i32 md_rate = silk_rate_bps / 2;
-    for (int k = 1; k < 8; k++) {
-        if (md_rate < T_target_rate[k]) {
-            i32 frac_Q6 = sx_shl(md_rate - T_target_rate[k - 1], 6) / (T_target_rate[k] - T_target_rate[k - 1]);
-            st->SNRPerMD_dB_Q7 = sx_shl(T_snr_table_Q1[k - 1], 6) + sx_mul(frac_Q6, T_snr_table_Q1[k] - T_snr_table_Q1[k - 1]);
-            break;
-        }
-    }
-    for (int k = 1; k < 8; k++) {
-        if (silk_rate_bps <= T_target_rate[k]) {
-            i32 frac_Q6 = sx_shl(silk_rate_bps - T_target_rate[k - 1], 6) / (T_target_rate[k] - T_target_rate[k - 1]);
-            st->SNR_dB_Q7 = sx_shl(T_snr_table_Q1[k - 1], 6) + sx_mul(frac_Q6, T_snr_table_Q1[k] - T_snr_table_Q1[k - 1]);
-            break;
-        }
-    }
+    sx_enc_setup_rate(st, silk_rate_bps);
     wv_sync();
 }
