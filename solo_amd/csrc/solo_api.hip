@@ -1,4 +1,6 @@
-// solo_api.hip -- gfx950 kernels + the C ABI of libsolo_mi355x.so (include/solo_mi355x.h).
+// solo_api.hip -- the C ABI of libsolo_mi355x.so (include/solo_mi355x.h), the host-side pipelines behind it, and the decoder kernels of
+// the 16 kHz API rate (solo_dec_kernels.h).  The encoder kernels and the 32 kHz decoder are reached through one launch table per build
+// (solo_enc_ops.h, solo_dec_ops.h).
 //
 // Execution model: one 64-lane wavefront (= one workgroup) owns one stream and walks its packets in
 // order; thousands of streams run concurrently.  Persistent codec state is an array of per-stream
@@ -62,28 +64,8 @@ __global__ void __launch_bounds__(256) solo_stream_list_check_kernel(const i32* 
         for (int i = threadIdx.x; i < n; i += 256) status[i] = -1;
 }
 
-// the same decoder compiled for the 32 kHz API rate (SILK wide band, 16 kHz bands): solo_api_wb.hip
-extern "C" {
-size_t solo_wb_dec_state_bytes();
-hipError_t solo_wb_dec_launch_init(void* states, int n_streams, int hb_joint, int useMDIndex, hipStream_t s);
-hipError_t solo_wb_dec_launch_init_list(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s);
-hipError_t solo_wb_dec_launch_ctl_list(void* states, const SxStreamCtl* recs, int n, hipStream_t s);
-hipError_t solo_wb_dec_launch(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int slot,
-                              int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s);
-hipError_t solo_wb_dec_launch_extract(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets,
-                                      int p0, int pc, int slot, void* recs, const int32_t* map, const uint32_t* verdict, hipStream_t s);
-hipError_t solo_wb_dec_launch_synth(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams, int n_packets, int p0,
-                                    int pc, int slot, const void* recs, int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict,
-                                    hipStream_t s);
-size_t solo_wb_dec_extracted_bytes();
-hipError_t solo_wb_dec_launch_split(void* states, const uint8_t* descA, const int16_t* lenA, const uint8_t* descB, const int16_t* lenB, int n_streams,
-                                    int n_packets, int slot, int16_t* pcm, int32_t* status, hipStream_t s);
-hipError_t solo_wb_dec_launch_raw(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm, int32_t* status, hipStream_t s);
-hipError_t solo_wb_dec_launch_ring(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth, int slot,
-                                   int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s);
-hipError_t solo_wb_recv_launch_insert(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth, int slot,
-                                      const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats, hipStream_t s);
-}
+extern "C" const solo_dec_ops* solo_nb_dec_ops() { return &solo_dec_ops_table; }
+extern "C" const solo_dec_ops* solo_wb_dec_ops();          // the same decoder compiled for the 32 kHz API rate (SILK wide band, 16 kHz bands): solo_api_wb.hip
 
 #ifdef SOLO_WITH_ENCODER
 #include "solo_enc_ops.h"
@@ -121,7 +103,7 @@ struct solo_batch {
     void* d_enc_work;                // hand-over records of one launch: SxNsqIn[N][P][2] | SxNsqOut[N][P][2] | SxCodeIn[N][P]
     int32_t enc_work_packets;        // P the hand-over area is sized for
     int timing;                      // solo_batch_set_timing: bracket every kernel with HIP events on its launch stream
-    hipEvent_t ev[6];                // decode: 4|D|5  (0..3: unused since the encoder is pipelined)
+    hipEvent_t evDec[2];             // brackets of a decode call on the caller's stream (the encoder's: tev)
     int ev_ready, ev_enc, ev_dec;
     // encoder: three internal streams (analysis / front kernel: sA, quantiser: sB, third stage of the launch-per-chunk schedule: sC)
     int pipe_ready, chunk_packets;   // chunk_packets: packets per chunk of the launch-per-chunk schedule (env SOLO_ENC_CHUNK, default 1; 0 = one chunk)
@@ -146,7 +128,8 @@ struct solo_batch {
     int front_defer;                 // SOLO_ENC_FINAL_WAIT_US=-1
     void* d_nsq_stage;               // the persistent quantiser's staging records (one launch group)
     void* d_front_scratch;           // byte buffers of the front kernel's in-wave range coder (one launch group)
-    void* d_dec_state;               // SxDecState[n_streams] of the build that matches `wb`
+    const solo_dec_ops* dops;        // launch table of the build that matches the decoder's rate (solo_dec_kernels.h)
+    void* d_dec_state;               // SxDecStream[n_streams] of that build
     // receiver staging ring (solo_recv.h): payload [N][D][2][slot] | length words [N][D] | play-out positions [N] | statistics
     uint8_t* d_recv_ring;
     uint32_t* d_recv_lens;
@@ -156,9 +139,11 @@ struct solo_batch {
     // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
     // asynchronous joins), [2] decode, [3] receiver play-out
     uint32_t* d_verdict;
-    int wb;                          // decoder control asked for samplerate 32000: 1280-sample packets, SILK at 16 kHz
 };
 
+static int ctrl_hb_joint(int joint_enable, int joint_mode) { return joint_enable != 0 && joint_mode == 1; }
+// AGR_BWE_SDK_API.c:119: the SILK core gets the target rate minus the high-band share, 1600 * 20 / bwe_framesize_ms
+static int ctrl_silk_rate(const USER_Ctrl_enc* c) { return c->targetRate_bps - (ctrl_hb_joint(c->joint_enable, c->joint_mode) ? 800 : 1600); }
 // joint_enable = 0, or joint_mode 1 (one 40 ms high-band frame per packet, AGR_BWE_SDK_API.c:64-67); the other joint modes are
 // "reserved" in the reference as well
 static bool ctrl_enc_supported(const USER_Ctrl_enc* c) {
@@ -169,46 +154,52 @@ static bool ctrl_enc_supported(const USER_Ctrl_enc* c) {
     // 32 kHz input: SILK runs wide band.  Below WB2MB_BITRATE_BPS (14 kbps for SILK = 15.6 kbps total, 14.8 kbps with the 40 ms
     // high-band frame) the reference starts at, or switches down to, 12 / 8 kHz internally (SKP_Silk_control_audio_bandwidth.c:44-76):
     // those rates and the switching are not built, so such a configuration is refused instead of coded differently
-    const int hb_bps = (c->joint_enable != 0 && c->joint_mode == 1) ? 800 : 1600;
-    const int rate = c->targetRate_bps <= 0 ? 15600 : c->targetRate_bps;
-    return c->samplerate == 32000 && rate - hb_bps >= 14000;
+    USER_Ctrl_enc d = *c;
+    if (d.targetRate_bps <= 0) d.targetRate_bps = 15600;
+    return c->samplerate == 32000 && ctrl_silk_rate(&d) >= 14000;
 }
 static bool ctrl_dec_supported(const USER_Ctrl_dec* c) {
     // 32000: the wide-band decoder (solo_api_wb.hip); a stream whose internal rate is not 16 kHz is rejected packet by packet
     return (c->samplerate == 16000 || c->samplerate == 32000) && (c->framesize_ms == 40 || (c->framesize_ms == 20 && c->joint_enable == 0)) &&
            (c->joint_enable == 0 || c->joint_mode == 1);
 }
-static int ctrl_hb_joint(int joint_enable, int joint_mode) { return joint_enable != 0 && joint_mode == 1; }
 // bytes of high band per packet: (QMF_HB_FrameSize / BWE_FrameSize) * HB_BYTE
 static int ctrl_hb_bytes(int joint_enable, int joint_mode, int framesize_ms) { return (ctrl_hb_joint(joint_enable, joint_mode) || framesize_ms == 20) ? SX_HB_BYTES / 2 : SX_HB_BYTES; }
+// SILK frames per packet, and the samples of a packet (JC1_FrameSize) given those of a 40 ms packet at the build's rate
+static int ctrl_frames_per_packet(int framesize_ms) { return framesize_ms == 20 ? 1 : 2; }
+static int ctrl_packet_samples(int samples_40ms, int framesize_ms) { return framesize_ms == 20 ? samples_40ms / 2 : samples_40ms; }
+static int dec_packet_samples(const solo_batch* b) { return ctrl_packet_samples(b->dops->packet_samples, b->dec_ctrl.framesize_ms); }
+// the decoder's hb_mode argument of sx_dec_state_init: bit 0 = joint_mode 1, bit 1 = one frame per packet
+static int dec_hb_mode(const solo_batch* b) { return ctrl_hb_joint(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode) | (ctrl_frames_per_packet(b->dec_ctrl.framesize_ms) == 1 ? 2 : 0); }
+
+// an environment knob that is a number
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+template <typename T>
+static void dev_free(T*& p) {
+    if (p) (void)hipFree(p);
+    p = NULL;
+}
 
 #ifdef SOLO_WITH_ENCODER
-static int32_t solo_enc_alloc(solo_batch* b) {
-    SOLO_CHECK(hipMalloc(&b->d_enc_state, b->eops->state_bytes * (size_t)b->n_streams));
-    return 0;
-}
+static int enc_hb_joint(const solo_batch* b) { return ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode); }
+static int enc_frames_per_packet(const solo_batch* b) { return ctrl_frames_per_packet(b->enc_ctrl.framesize_ms); }
+static int enc_packet_samples(const solo_batch* b) { return ctrl_packet_samples(b->eops->packet_samples, b->enc_ctrl.framesize_ms); }
 static int32_t solo_enc_reset(solo_batch* b, hipStream_t s) {
-    // AGR_BWE_SDK_API.c:119: the SILK core gets the target rate minus the high-band share, 1600 * 20 / bwe_framesize_ms
-    const int joint = ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode);
-    SOLO_CHECK(b->eops->init(b->d_enc_state, b->n_streams, b->enc_ctrl.targetRate_bps - (joint ? 800 : 1600), b->enc_ctrl.useMDIndex, joint,
-                             b->enc_ctrl.dtx_enable ? 1 : 0, b->enc_ctrl.framesize_ms == 20 ? 1 : 2, s));
+    SOLO_CHECK(b->eops->init(b->d_enc_state, b->n_streams, ctrl_silk_rate(&b->enc_ctrl), b->enc_ctrl.useMDIndex, enc_hb_joint(b),
+                             b->enc_ctrl.dtx_enable ? 1 : 0, enc_frames_per_packet(b), s));
     return 0;
 }
 static void solo_enc_free(solo_batch* b) {
-    if (b->d_enc_state) (void)hipFree(b->d_enc_state);
-    if (b->d_enc_work) (void)hipFree(b->d_enc_work);
-    if (b->d_nsq_ring) (void)hipFree(b->d_nsq_ring);
-    b->d_nsq_ring = NULL;
-    if (b->d_rc_scratch) (void)hipFree(b->d_rc_scratch);
-    b->d_rc_scratch = NULL;
-    if (b->d_flags) (void)hipFree(b->d_flags);
-    b->d_flags = NULL;
-    if (b->d_front_scratch) (void)hipFree(b->d_front_scratch);
-    b->d_front_scratch = NULL;
-    if (b->d_nsq_stage) (void)hipFree(b->d_nsq_stage);
-    b->d_nsq_stage = NULL;
-    b->d_enc_state = NULL;
-    b->d_enc_work = NULL;
+    dev_free(b->d_enc_state);
+    dev_free(b->d_enc_work);
+    dev_free(b->d_nsq_ring);
+    dev_free(b->d_rc_scratch);
+    dev_free(b->d_flags);
+    dev_free(b->d_front_scratch);
+    dev_free(b->d_nsq_stage);
 }
 #endif
 
@@ -226,7 +217,7 @@ int32_t solo_batch_n_streams(const solo_batch_t* b) { return b ? b->n_streams : 
 int32_t solo_batch_set_timing(solo_batch_t* b, int32_t on) {
     if (!b) return -1;
     if (on && !b->ev_ready) {
-        for (int i = 0; i < 6; i++) SOLO_CHECK(hipEventCreate(&b->ev[i]));
+        for (int i = 0; i < 2; i++) SOLO_CHECK(hipEventCreate(&b->evDec[i]));
         b->ev_ready = 1;
         for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) SOLO_CHECK(hipEventCreate(&b->tev[k][c][e]));
         b->tev_ready = 1;
@@ -250,8 +241,8 @@ int32_t solo_batch_last_kernel_ms(solo_batch_t* b, float* ms4) {
         }
     }
     if (b->ev_dec) {
-        SOLO_CHECK(hipEventSynchronize(b->ev[5]));
-        SOLO_CHECK(hipEventElapsedTime(&ms4[3], b->ev[4], b->ev[5]));
+        SOLO_CHECK(hipEventSynchronize(b->evDec[1]));
+        SOLO_CHECK(hipEventElapsedTime(&ms4[3], b->evDec[0], b->evDec[1]));
     }
     return 0;
 }
@@ -293,8 +284,6 @@ static int32_t solo_wait_in_flight(solo_batch_t* b, hipStream_t s) {
     }
     return 0;
 }
-// the decoder's hb_mode argument of sx_dec_state_init: bit 0 = joint_mode 1, bit 1 = one frame per packet
-static int ctrl_dec_hb_mode(const solo_batch* b) { return ctrl_hb_joint(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode) | (b->dec_ctrl.framesize_ms == 20 ? 2 : 0); }
 
 int32_t solo_batch_reset(solo_batch_t* b, void* hip_stream) {
     if (!b) return -1;
@@ -303,10 +292,7 @@ int32_t solo_batch_reset(solo_batch_t* b, void* hip_stream) {
         const int32_t r = solo_wait_in_flight(b, s);
         if (r) return r;
     }
-    if (b->have_dec) {
-        const int hbj = ctrl_dec_hb_mode(b), md = b->dec_ctrl.useMDIndex;
-        SOLO_CHECK(b->wb ? solo_wb_dec_launch_init(b->d_dec_state, b->n_streams, hbj, md, s) : solo_dec_launch_init(b->d_dec_state, b->n_streams, hbj, md, s));
-    }
+    if (b->have_dec) SOLO_CHECK(b->dops->init(b->d_dec_state, b->n_streams, dec_hb_mode(b), b->dec_ctrl.useMDIndex, s));
 #ifdef SOLO_WITH_ENCODER
     if (b->have_enc) {
         int32_t r = solo_enc_reset(b, s);
@@ -346,7 +332,6 @@ static bool stream_ctl_records(const solo_batch* b, const int32_t* h_streams, in
     if ((do_enc && !b->have_enc) || (do_dec && !b->have_dec) || (h_enc && !do_enc) || (h_dec && !do_dec)) return false;
     if (do_enc) {
         const USER_Ctrl_enc& he = b->enc_ctrl;
-        const int joint = ctrl_hb_joint(he.joint_enable, he.joint_mode);
         er.resize((size_t)n);
         for (int32_t i = 0; i < n; i++) {
             USER_Ctrl_enc c = h_enc ? h_enc[i] : he;
@@ -354,7 +339,7 @@ static bool stream_ctl_records(const solo_batch* b, const int32_t* h_streams, in
             if (c.samplerate != he.samplerate || c.framesize_ms != he.framesize_ms || c.joint_enable != he.joint_enable || c.joint_mode != he.joint_mode ||
                 !ctrl_enc_supported(&c))
                 return false;
-            er[(size_t)i] = SxStreamCtl{h_streams[i], c.targetRate_bps - (joint ? 800 : 1600), c.useMDIndex, c.dtx_enable ? 1 : 0};
+            er[(size_t)i] = SxStreamCtl{h_streams[i], ctrl_silk_rate(&c), c.useMDIndex, c.dtx_enable ? 1 : 0};      // (c's joint mode is the handle's)
         }
     }
     if (do_dec) {
@@ -371,44 +356,34 @@ static bool stream_ctl_records(const solo_batch* b, const int32_t* h_streams, in
     return true;
 }
 
-// Per-stream re-initialisation (records: stream_ctl_records).
-int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
-                                 const USER_Ctrl_dec* h_dec, void* hip_stream) {
+// solo_batch_reset_streams (reinit: the listed streams start afresh) and solo_batch_update_streams (a running stream's control: the
+// encoder's rate (setup_rate: the two SNR targets), DTX and useMDIndex, the decoder's useMDIndex; every other word of the states, the
+// receiver ring and the play-out positions stay).  Records: stream_ctl_records.  The wait matters even more for an update than for a
+// reset: the analysis / front kernels write a stream's whole SxEncState back when they end (an update that overtook them would be
+// undone), and the coder reads useDTX / useMDIndex of the packets it codes.
+static int32_t stream_ctl_apply(solo_batch_t* b, bool reinit, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
+                                const USER_Ctrl_dec* h_dec, hipStream_t s) {
     std::vector<SxStreamCtl> er, dr;
     if (!stream_ctl_records(b, h_streams, n, which, h_enc, h_dec, er, dr)) return -1;
-    hipStream_t s = (hipStream_t)hip_stream;
     {
         const int32_t r = solo_wait_in_flight(b, s);
         if (r) return r;
     }
-    if (!dr.empty())
-        SOLO_CHECK((b->wb ? solo_wb_dec_launch_init_list : solo_dec_launch_init_list)(b->d_dec_state, dr.data(), n, ctrl_dec_hb_mode(b), s));
+    if (!dr.empty()) SOLO_CHECK(reinit ? b->dops->init_list(b->d_dec_state, dr.data(), n, dec_hb_mode(b), s) : b->dops->ctl_list(b->d_dec_state, dr.data(), n, s));
 #ifdef SOLO_WITH_ENCODER
     if (!er.empty())
-        SOLO_CHECK(b->eops->init_list(b->d_enc_state, er.data(), n, ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode),
-                                      b->enc_ctrl.framesize_ms == 20 ? 1 : 2, s));
+        SOLO_CHECK(reinit ? b->eops->init_list(b->d_enc_state, er.data(), n, enc_hb_joint(b), enc_frames_per_packet(b), s)
+                          : b->eops->ctl_list(b->d_enc_state, er.data(), n, s));
 #endif
     return 0;
 }
-
-// A running stream's control (records: stream_ctl_records): the encoder's rate (setup_rate: the two SNR targets), DTX and useMDIndex,
-// the decoder's useMDIndex; every other word of the states, the receiver ring and the play-out positions stay.  The wait matters even
-// more than for a reset: the analysis / front kernels write a stream's whole SxEncState back when they end (an update that overtook
-// them would be undone), and the coder reads useDTX / useMDIndex of the packets it codes.
+int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
+                                 const USER_Ctrl_dec* h_dec, void* hip_stream) {
+    return stream_ctl_apply(b, true, h_streams, n, which, h_enc, h_dec, (hipStream_t)hip_stream);
+}
 int32_t solo_batch_update_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
                                   const USER_Ctrl_dec* h_dec, void* hip_stream) {
-    std::vector<SxStreamCtl> er, dr;
-    if (!stream_ctl_records(b, h_streams, n, which, h_enc, h_dec, er, dr)) return -1;
-    hipStream_t s = (hipStream_t)hip_stream;
-    {
-        const int32_t r = solo_wait_in_flight(b, s);
-        if (r) return r;
-    }
-    if (!dr.empty()) SOLO_CHECK((b->wb ? solo_wb_dec_launch_ctl_list : solo_dec_launch_ctl_list)(b->d_dec_state, dr.data(), n, s));
-#ifdef SOLO_WITH_ENCODER
-    if (!er.empty()) SOLO_CHECK(b->eops->ctl_list(b->d_enc_state, er.data(), n, s));
-#endif
-    return 0;
+    return stream_ctl_apply(b, false, h_streams, n, which, h_enc, h_dec, (hipStream_t)hip_stream);
 }
 
 solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, const USER_Ctrl_dec* dec, int32_t slot_bytes) {
@@ -431,7 +406,7 @@ solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, con
         b->enc_ctrl = *enc;
         if (b->enc_ctrl.targetRate_bps <= 0) b->enc_ctrl.targetRate_bps = 15600;  // AGR_BWE_SDK_API.c:35
         b->eops = enc->samplerate == 32000 ? solo_wb_enc_ops() : solo_nb_enc_ops();
-        if (solo_enc_alloc(b) != 0) { solo_batch_destroy(b); return NULL; }
+        if (hipMalloc(&b->d_enc_state, b->eops->state_bytes * (size_t)n_streams) != hipSuccess) { solo_batch_destroy(b); return NULL; }
 #else
         delete b;
         return NULL;
@@ -440,9 +415,9 @@ solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, con
     if (dec) {
         b->have_dec = 1;
         b->dec_ctrl = *dec;
-        b->wb = dec->samplerate == 32000;
+        b->dops = dec->samplerate == 32000 ? solo_wb_dec_ops() : solo_nb_dec_ops();
         if (enc && enc->samplerate != dec->samplerate) { solo_batch_destroy(b); return NULL; }     // a handle has one rate
-        if (hipMalloc(&b->d_dec_state, (b->wb ? solo_wb_dec_state_bytes() : solo_dec_state_bytes()) * (size_t)n_streams) != hipSuccess) { solo_batch_destroy(b); return NULL; }
+        if (hipMalloc(&b->d_dec_state, b->dops->state_bytes * (size_t)n_streams) != hipSuccess) { solo_batch_destroy(b); return NULL; }
     }
     if (hipMalloc((void**)&b->d_verdict, 4 * sizeof(uint32_t)) != hipSuccess || hipMemset(b->d_verdict, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
         solo_batch_destroy(b);
@@ -462,18 +437,15 @@ void solo_batch_destroy(solo_batch_t* b) {
         (void)hipEventDestroy(b->evDFork); (void)hipEventDestroy(b->evDJoin); (void)hipEventDestroy(b->evDJoin2);
         for (int i = 0; i < 2; i++) { (void)hipEventDestroy(b->evP[i]); (void)hipEventDestroy(b->evS[i]); }
     }
-    for (int i = 0; i < 2; i++) {
-        if (b->d_parsed[i]) (void)hipFree(b->d_parsed[i]);
-        b->d_parsed[i] = NULL;
-    }
-    if (b->d_dec_state) (void)hipFree(b->d_dec_state);
-    if (b->d_verdict) (void)hipFree(b->d_verdict);
-    if (b->ev_ready) for (int i = 0; i < 6; i++) (void)hipEventDestroy(b->ev[i]);
+    for (int i = 0; i < 2; i++) dev_free(b->d_parsed[i]);
+    dev_free(b->d_dec_state);
+    dev_free(b->d_verdict);
+    if (b->ev_ready) for (int i = 0; i < 2; i++) (void)hipEventDestroy(b->evDec[i]);
     if (b->tev_ready) for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) (void)hipEventDestroy(b->tev[k][c][e]);
     if (b->pipe_ready) {
         (void)hipStreamSynchronize(b->sA); (void)hipStreamSynchronize(b->sB); (void)hipStreamSynchronize(b->sC);
         (void)hipStreamDestroy(b->sA); (void)hipStreamDestroy(b->sB); (void)hipStreamDestroy(b->sC);
-        if (b->d_started) (void)hipFree(b->d_started);
+        dev_free(b->d_started);
         (void)hipEventDestroy(b->evFork);
         for (int i = 0; i < 2; i++) { (void)hipEventDestroy(b->evJoinA[i]); (void)hipEventDestroy(b->evJoinC[i]); }
         for (int c = 0; c < SOLO_MAX_CHUNKS; c++) (void)hipEventDestroy(b->evC[c]);
@@ -501,17 +473,14 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     uint32_t* verdict = map ? b->d_verdict + 2 : NULL;
     const bool tm = b->timing && b->ev_ready;
     if (!b->dec_pipe_ready) {
-        const char* e = getenv("SOLO_DEC_SPLIT");
-        b->dec_split = e ? atoi(e) : 1;
-        if (b->dec_ctrl.framesize_ms == 20) b->dec_split = 0;      // (the read-ahead records describe two-frame packets)
-        e = getenv("SOLO_DEC_CHUNK");
-        b->dec_chunk = e ? atoi(e) : SOLO_DEC_CHUNK_DEFAULT;
+        b->dec_split = env_int("SOLO_DEC_SPLIT", 1);
+        if (ctrl_frames_per_packet(b->dec_ctrl.framesize_ms) == 1) b->dec_split = 0;      // (the read-ahead records describe two-frame packets)
+        b->dec_chunk = env_int("SOLO_DEC_CHUNK", SOLO_DEC_CHUNK_DEFAULT);
         if (b->dec_chunk <= 0) b->dec_chunk = 1 << 30;
-        e = getenv("SOLO_DEC_FIRST_CHUNK");
-        b->dec_first = e ? atoi(e) : SOLO_DEC_FIRST_CHUNK;
+        b->dec_first = env_int("SOLO_DEC_FIRST_CHUNK", SOLO_DEC_FIRST_CHUNK);
         if (b->dec_first <= 0) b->dec_first = SOLO_DEC_FIRST_CHUNK;
         // (read per handle like the other SOLO_DEC_* knobs; a value that does not parse to a positive number means the default)
-        e = getenv("SOLO_DEC_SCRATCH_CAP");
+        const char* e = getenv("SOLO_DEC_SCRATCH_CAP");
         b->dec_scratch_cap = e ? (size_t)strtoull(e, NULL, 10) : 0;
         if (b->dec_scratch_cap == 0) b->dec_scratch_cap = (size_t)1 << 30;
         if (b->dec_split) {
@@ -527,13 +496,12 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         }
         b->dec_pipe_ready = 1;
     }
-    if (tm) (void)hipEventRecord(b->ev[4], st);
+    if (tm) (void)hipEventRecord(b->evDec[0], st);
     if (!b->dec_split) {
         // single kernel: one wavefront per stream parses (two lanes) and synthesises
         if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));
-        const hipError_t e = (b->wb ? solo_wb_dec_launch : solo_dec_launch)(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, b->slot,
-                                                                             d_pcm, d_status, map, verdict, st);
-        if (tm) { (void)hipEventRecord(b->ev[5], st); b->ev_dec = 1; }
+        const hipError_t e = b->dops->decode(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, b->slot, d_pcm, d_status, map, verdict, st);
+        if (tm) { (void)hipEventRecord(b->evDec[1], st); b->ev_dec = 1; }
         SOLO_CHECK(e);
         return 0;
     }
@@ -544,7 +512,7 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     // packets per chunk: the knob, capped so that ONE buffer of extraction records stays below SOLO_DEC_SCRATCH_CAP bytes (default 1 GiB;
     // the records are 2216 B per packet at the 16 kHz API rate: 4096 streams x 64 packets = 581 MB, 65536 streams -> 7 packets per chunk).
     // A handle holds at most two such buffers (calls longer than one chunk); include/solo_mi355x.h states the footprint.
-    const size_t rec_bytes = b->wb ? solo_wb_dec_extracted_bytes() : solo_dec_extracted_bytes();
+    const size_t rec_bytes = b->dops->extracted_bytes;
     int cp = n_packets < b->dec_chunk ? n_packets : b->dec_chunk;
     {   // (floor: one packet per chunk -- a handle with more than cap / 2216 streams holds n_streams x 2216 B per buffer, see the header)
         const size_t fit = b->dec_scratch_cap / ((size_t)ns * rec_bytes);
@@ -557,10 +525,7 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         SOLO_CHECK(hipStreamSynchronize(st));
         (void)hipStreamSynchronize(b->sP);
         (void)hipStreamSynchronize(b->sS);
-        for (int i = 0; i < 2; i++) {
-            if (b->d_parsed[i]) (void)hipFree(b->d_parsed[i]);
-            b->d_parsed[i] = NULL;
-        }
+        for (int i = 0; i < 2; i++) dev_free(b->d_parsed[i]);
         b->parsed_bytes = 0;
         for (int i = 0; i < 2; i++) SOLO_CHECK(hipMalloc(&b->d_parsed[i], i == 0 || nchunks > 1 ? need : 256));     // (one chunk: one buffer)
         b->parsed_bytes = need;
@@ -582,13 +547,11 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         const int p0 = c == 0 ? 0 : c0 + (c - 1) * cp, pc = c == 0 ? c0 : ((p0 + cp <= n_packets) ? cp : n_packets - p0), k = c & 1;
         // (every failure inside the loop goes through the join block below: nothing of this call stays forked)
         if (c >= 2 && (lerr = hipStreamWaitEvent(b->sP, b->evS[k], 0)) != hipSuccess) break;
-        lerr = (b->wb ? solo_wb_dec_launch_extract : solo_dec_launch_extract)(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc,
-                                                                              b->slot, b->d_parsed[k], map, verdict, b->sP);
+        lerr = b->dops->extract(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot, b->d_parsed[k], map, verdict, b->sP);
         if (lerr != hipSuccess) break;
         if ((lerr = hipEventRecord(b->evP[k], b->sP)) != hipSuccess) break;
         if ((lerr = hipStreamWaitEvent(b->sS, b->evP[k], 0)) != hipSuccess) break;
-        lerr = (b->wb ? solo_wb_dec_launch_synth : solo_dec_launch_synth)(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot,
-                                                                          b->d_parsed[k], d_pcm, d_status, map, verdict, b->sS);
+        lerr = b->dops->synth(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot, b->d_parsed[k], d_pcm, d_status, map, verdict, b->sS);
         if (lerr != hipSuccess) break;
         if ((lerr = hipEventRecord(b->evS[k], b->sS)) != hipSuccess) break;
     }
@@ -597,7 +560,7 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     (void)hipStreamWaitEvent(st, b->evDJoin, 0);
     (void)hipEventRecord(b->evDJoin2, b->sS);
     (void)hipStreamWaitEvent(st, b->evDJoin2, 0);
-    if (tm) { (void)hipEventRecord(b->ev[5], st); b->ev_dec = 1; }
+    if (tm) { (void)hipEventRecord(b->evDec[1], st); b->ev_dec = 1; }
     SOLO_CHECK(lerr);
     return 0;
 }
@@ -616,18 +579,16 @@ int32_t solo_batch_decode_split(solo_batch_t* b, const uint8_t* d_descA, const i
                                 const int16_t* d_lenB, int32_t slot_bytes, int32_t n_packets, int16_t* d_pcm, int32_t* d_status,
                                 void* hip_stream) {
     if (!b || !b->have_dec || !d_descA || !d_lenA || !d_descB || !d_lenB || !d_pcm || n_packets <= 0 || slot_bytes <= 0) return -1;
-    SOLO_CHECK((b->wb ? solo_wb_dec_launch_split : solo_dec_launch_split)(b->d_dec_state, d_descA, d_lenA, d_descB, d_lenB, b->n_streams, n_packets,
-                                                                          slot_bytes, d_pcm, d_status, (hipStream_t)hip_stream));
+    SOLO_CHECK(b->dops->split(b->d_dec_state, d_descA, d_lenA, d_descB, d_lenB, b->n_streams, n_packets, slot_bytes, d_pcm, d_status, (hipStream_t)hip_stream));
     return 0;
 }
 
 // ---- receiver staging ring (solo_recv.h) ---------------------------------------------------------------------------------------
 static void solo_recv_free(solo_batch_t* b) {
-    if (b->d_recv_ring) (void)hipFree(b->d_recv_ring);
-    if (b->d_recv_lens) (void)hipFree(b->d_recv_lens);
-    if (b->d_recv_play) (void)hipFree(b->d_recv_play);
-    if (b->d_recv_stats) (void)hipFree(b->d_recv_stats);
-    b->d_recv_ring = NULL; b->d_recv_lens = NULL; b->d_recv_play = NULL; b->d_recv_stats = NULL;
+    dev_free(b->d_recv_ring);
+    dev_free(b->d_recv_lens);
+    dev_free(b->d_recv_play);
+    dev_free(b->d_recv_stats);
     b->recv_depth = b->recv_slot = 0;
 }
 int32_t solo_recv_create(solo_batch_t* b, int32_t depth, int32_t slot_bytes, int32_t first_seq, void* hip_stream) {
@@ -662,16 +623,14 @@ int32_t solo_recv_insert(solo_batch_t* b, const solo_arrival_t* d_arrivals, int3
     if (!b || !b->d_recv_ring || n_arrivals < 0 || (n_arrivals > 0 && (!d_arrivals || !d_payload)) || payload_bytes < 0) return -1;
     if (n_arrivals == 0) return 0;
     // (desc = -1 is accepted for the streams whose decoder runs with useMDIndex = 1: the kernel reads each stream's own flag)
-    SOLO_CHECK((b->wb ? solo_wb_recv_launch_insert : solo_recv_launch_insert)(d_arrivals, n_arrivals, d_payload, (long long)payload_bytes, b->n_streams,
-                                                                              b->recv_depth, b->recv_slot, b->d_dec_state, b->d_recv_ring, b->d_recv_lens,
-                                                                              b->d_recv_play, b->d_recv_stats, (hipStream_t)hip_stream));
+    SOLO_CHECK(b->dops->recv_insert(d_arrivals, n_arrivals, d_payload, (long long)payload_bytes, b->n_streams, b->recv_depth, b->recv_slot, b->d_dec_state,
+                                    b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->d_recv_stats, (hipStream_t)hip_stream));
     return 0;
 }
 int32_t solo_recv_decode(solo_batch_t* b, int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
     if (!b || !b->d_recv_ring || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
-    SOLO_CHECK((b->wb ? solo_wb_dec_launch_ring : solo_dec_launch_ring)(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->n_streams, n_packets,
-                                                                        b->recv_depth, b->recv_slot, d_pcm, d_status, NULL, NULL,
-                                                                        (hipStream_t)hip_stream));
+    SOLO_CHECK(b->dops->ring(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->n_streams, n_packets, b->recv_depth, b->recv_slot, d_pcm,
+                             d_status, NULL, NULL, (hipStream_t)hip_stream));
     return 0;
 }
 int32_t solo_recv_decode_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, int32_t n_packets, int16_t* d_pcm, int32_t* d_status,
@@ -680,8 +639,8 @@ int32_t solo_recv_decode_streams(solo_batch_t* b, const int32_t* d_streams, int3
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t* verdict = b->d_verdict + 3;
     SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, d_status, st));
-    SOLO_CHECK((b->wb ? solo_wb_dec_launch_ring : solo_dec_launch_ring)(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, n, n_packets,
-                                                                        b->recv_depth, b->recv_slot, d_pcm, d_status, d_streams, verdict, st));
+    SOLO_CHECK(b->dops->ring(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, n, n_packets, b->recv_depth, b->recv_slot, d_pcm, d_status,
+                             d_streams, verdict, st));
     return 0;
 }
 int32_t solo_recv_stats(solo_batch_t* b, uint32_t* out8, void* hip_stream) {
@@ -717,29 +676,24 @@ static int32_t solo_enc_pipe_setup(solo_batch* b) {
     // chunk and stage.  Bit-exact and deadlock-free by construction, but measured SLOWER (54 - 60 against 50.5 ms per 4096 x 50 packets:
     // DESIGN.md section 9 has the trace): it removes the launch tails, but it also fixes the SIMD's population at five dependent
     // chains, where the launch-per-chunk schedule reaches nine.  Off unless asked for.
-    const char* e = getenv("SOLO_ENC_PERSIST");
-    b->persist = e ? (atoi(e) != 0) : 0;
-    e = getenv("SOLO_ENC_CHUNK");
-    b->chunk_packets = e ? atoi(e) : 1;
+    b->persist = env_int("SOLO_ENC_PERSIST", 0) != 0;
+    b->chunk_packets = env_int("SOLO_ENC_CHUNK", 1);
     if (b->chunk_packets < 0) b->chunk_packets = 1;
     // launch per chunk: the residency gate (hold analysis chunk c + 1 until the quantiser launch of chunk c is resident) costs 3 % with 256
     // quantiser workgroups per chunk: off unless asked for.  Persistent: ONE gate per launch group, in front of the front kernel -- the
     // quantiser's wavefronts have to be resident before 4096 front workgroups take every register of the device: on unless turned off.
-    e = getenv("SOLO_ENC_GATE");
-    b->gate = e ? (atoi(e) != 0) : -1;                          // (-1: the schedule's default)
+    b->gate = getenv("SOLO_ENC_GATE") ? (env_int("SOLO_ENC_GATE", 0) != 0) : -1;      // (-1: the schedule's default)
     // streams per launch group.  Launch per chunk: 8192 (one group of 8192 takes 120 ms per 50 packets, two of 4096 take 134).  Persistent:
     // what is resident at once -- front workgroups per compute unit (LDS-bound: 16 at the 16 kHz rate, 9 at 32 kHz) x compute units, a
     // multiple of the quantiser's four streams per wavefront: a larger group's last workgroups would only start when the first ones have
     // finished ALL their packets, while their quantiser wavefronts held registers from the start
-    e = getenv("SOLO_ENC_GROUP");
-    const int g_env = e ? atoi(e) : -1;
+    const int g_env = env_int("SOLO_ENC_GROUP", -1);
     b->group_streams = g_env >= 0 ? g_env : 8192;
     b->persist_group = g_env > 0 ? ((g_env + 3) & ~3) : ((ops->front_per_cu * (ncu > 0 ? ncu : 256)) & ~3);
     if (b->persist_group < 4) b->persist_group = 4;
-    e = getenv("SOLO_ENC_FINAL_WAIT_US");
     {
         // (-1, tests: the front launch codes nothing -- no look at the quantiser's flags at all --, the second launch every packet)
-        const long us = e ? atol(e) : 20000;
+        const long us = env_int("SOLO_ENC_FINAL_WAIT_US", 20000);
         b->front_defer = us < 0;
         b->final_wait_ticks = (unsigned int)((us < 0 ? 0 : (us > 10000000 ? 10000000 : us)) * 100);
     }
@@ -778,7 +732,7 @@ static int32_t solo_encode_persist(solo_batch* b, const int16_t* d_pcm, int32_t 
     unsigned int* err = prog + b->n_streams;
     const unsigned int ticket0 = b->ticket;
     b->ticket += (unsigned int)n_packets;
-    const size_t frame_samples = (size_t)(b->enc_ctrl.framesize_ms == 20 ? ops->packet_samples / 2 : ops->packet_samples);
+    const size_t frame_samples = (size_t)enc_packet_samples(b);
     SOLO_CHECK(hipEventRecord(b->evFork, st));
     SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evFork, 0));
     SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evFork, 0));
@@ -859,8 +813,7 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     if (n_packets > b->enc_work_packets) {          // grow the hand-over area (synchronises; steady-state launches do not)
         SOLO_CHECK(hipStreamSynchronize(st));
         if (b->pipe_ready) { (void)hipStreamSynchronize(b->sA); (void)hipStreamSynchronize(b->sB); (void)hipStreamSynchronize(b->sC); }
-        if (b->d_enc_work) (void)hipFree(b->d_enc_work);
-        b->d_enc_work = NULL;
+        dev_free(b->d_enc_work);
         SOLO_CHECK(hipMalloc(&b->d_enc_work, sz_in + sz_out + sz_code + 256));
         b->enc_work_packets = n_packets;
     }
@@ -889,8 +842,7 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         if (need > b->rc_scratch_bytes) {
             if (b->d_rc_scratch) {
                 SOLO_CHECK(hipStreamSynchronize(b->sC));             // (a coding launch of the previous call may still read the old one)
-                (void)hipFree(b->d_rc_scratch);
-                b->d_rc_scratch = NULL;
+                dev_free(b->d_rc_scratch);
                 b->rc_scratch_bytes = 0;
             }
             SOLO_CHECK(hipMalloc(&b->d_rc_scratch, need));
@@ -929,10 +881,10 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     const int G = b->group_streams > 0 ? b->group_streams : nall;
     const int ngroups = (nall + G - 1) / G;
     const bool tm = tm_req && (size_t)ngroups * (size_t)nchunks <= SOLO_MAX_CHUNKS;     // (per-launch timing brackets: one per event slot)
-    const size_t frame_samples = (size_t)(b->enc_ctrl.framesize_ms == 20 ? ops->packet_samples / 2 : ops->packet_samples);
+    const size_t frame_samples = (size_t)enc_packet_samples(b);
     int idx = 0;
     hipError_t lerr = hipSuccess;
-    for (int g = 0; g < ngroups; g++) {
+    for (int g = 0; g < ngroups && lerr == hipSuccess; g++) {
         const int s0 = g * G, ns = (s0 + G <= nall) ? G : nall - s0;
         const size_t pk0 = (size_t)s0 * (size_t)n_packets;                               // first packet record of the group
         void* g_states = map ? states : (char*)states + (size_t)s0 * ops->state_bytes;
@@ -950,18 +902,19 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
             if (ngroups == 1 && cc < b->evC_valid) SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evC[c], 0));      // (previous call: its coding of this chunk's records is done)
             if (idx > 0 && b->gate > 0) (void)solo_launch_gate(&b->d_started[cprev], b->started_target[cprev], b->sA);
             if (tm) (void)hipEventRecord(b->tev[0][c][0], b->sA);
-            if ((lerr = ops->analysis(g_states, g_pcm, ns, n_packets, p0, pc, g_nin, g_cin, g_map, verdict, b->sA)) != hipSuccess) goto launch_failed;
+            // (a refused launch leaves both loops for the join block below)
+            if ((lerr = ops->analysis(g_states, g_pcm, ns, n_packets, p0, pc, g_nin, g_cin, g_map, verdict, b->sA)) != hipSuccess) break;
             if (tm) (void)hipEventRecord(b->tev[0][c][1], b->sA);
             SOLO_CHECK(hipEventRecord(b->evA[c], b->sA));
             SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evA[c], 0));
             if (tm) (void)hipEventRecord(b->tev[1][c][0], b->sB);
 #ifdef SX_EXPERIMENTS     // builds for the section tools only (tools/build_stops.sh): SOLO_EXP_SKIP bit 0 = no quantiser, bit 1 = no third stage -- wrong output
-            static const int exp_skip = getenv("SOLO_EXP_SKIP") ? atoi(getenv("SOLO_EXP_SKIP")) : 0;
+            static const int exp_skip = env_int("SOLO_EXP_SKIP", 0);
 #else
             constexpr int exp_skip = 0;
 #endif
             if (!(exp_skip & 1)) {
-            if ((lerr = (hipError_t)ops->nsq(g_states, g_nin, g_nout, ns, n_packets, p0, pc, &b->d_started[c], b->d_nsq_ring, g_map, verdict, b->sB)) != hipSuccess) goto launch_failed;
+            if ((lerr = (hipError_t)ops->nsq(g_states, g_nin, g_nout, ns, n_packets, p0, pc, &b->d_started[c], b->d_nsq_ring, g_map, verdict, b->sB)) != hipSuccess) break;
             b->started_target[c] += (unsigned int)ops->nsq_workgroups(ns);     // workgroups of this launch, counted once it is enqueued
             }
             if (tm) (void)hipEventRecord(b->tev[1][c][1], b->sB);
@@ -969,38 +922,30 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
             SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[c], 0));
             if (tm) (void)hipEventRecord(b->tev[2][c][0], b->sC);
             if (!(exp_skip & 2))
-            if ((lerr = ops->coding(g_states, g_cin, g_nout, ns, n_packets, p0, pc, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) goto launch_failed;
+            if ((lerr = ops->coding(g_states, g_cin, g_nout, ns, n_packets, p0, pc, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) break;
             if (tm) (void)hipEventRecord(b->tev[2][c][1], b->sC);
             SOLO_CHECK(hipEventRecord(b->evC[c], b->sC));
         }
     }
-    if (0) {
-launch_failed:
-        // a kernel launch was refused: whatever was enqueued so far still runs; join the internal streams back into the
-        // caller's stream so that nothing of this call is left forked, drop the chunk-wise guards, report the HIP error
-        const int jf = (int)(b->enc_seq & 1u);
-        b->enc_seq++;
-        b->evC_valid = 0;
-        b->last_chunks = 0;
-        (void)hipEventRecord(b->evJoinA[jf], b->sA);
-        (void)hipEventRecord(b->evJoinC[jf], b->sC);
-        (void)hipStreamWaitEvent(st, b->evJoinA[jf], 0);
-        (void)hipStreamWaitEvent(st, b->evJoinC[jf], 0);
-        (void)hipEventRecord(b->evFork, b->sB);
-        (void)hipStreamWaitEvent(st, b->evFork, 0);
-        return -(int32_t)lerr;
-    }
-    b->evC_valid = (ngroups == 1 && !map) ? nchunks : 0;       // chunk-wise hand-over guards only for single-group calls of every stream
+    // join the internal streams back into the caller's.  After a refused launch too: whatever was enqueued so far still runs, nothing of
+    // this call is left forked (sB as well, which sC's last launch may not have waited for), the chunk-wise guards are dropped
+    const bool ok = lerr == hipSuccess;
+    b->evC_valid = (ok && ngroups == 1 && !map) ? nchunks : 0;       // chunk-wise hand-over guards only for single-group calls of every stream
     const int js = (int)(b->enc_seq & 1u);
     b->enc_seq++;
-    SOLO_CHECK(hipEventRecord(b->evJoinA[js], b->sA));
-    SOLO_CHECK(hipEventRecord(b->evJoinC[js], b->sC));      // (sC's last launch waits for sB's)
-    if (!b->async_join) {
-        SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinA[js], 0));
-        SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinC[js], 0));
+    (void)hipEventRecord(b->evJoinA[js], b->sA);
+    (void)hipEventRecord(b->evJoinC[js], b->sC);      // (sC's last launch waits for sB's)
+    if (!b->async_join || !ok) {
+        (void)hipStreamWaitEvent(st, b->evJoinA[js], 0);
+        (void)hipStreamWaitEvent(st, b->evJoinC[js], 0);
     }
-    b->last_chunks = tm ? ngroups * nchunks : (ngroups == 1 ? nchunks : 0);
-    if (tm) b->ev_enc = 1;
+    if (!ok) {
+        (void)hipEventRecord(b->evFork, b->sB);
+        (void)hipStreamWaitEvent(st, b->evFork, 0);
+    }
+    b->last_chunks = !ok ? 0 : (tm ? ngroups * nchunks : (ngroups == 1 ? nchunks : 0));
+    if (tm && ok) b->ev_enc = 1;
+    SOLO_CHECK(lerr);
     SOLO_CHECK(hipGetLastError());
     return 0;
 }
@@ -1076,7 +1021,7 @@ void* AGR_Sate_Encoder_Init(USER_Ctrl_enc* enc_Ctrl) {
 int32_t AGR_Sate_Encoder_Encode(void* st, const int16_t* pcm, uint8_t* bits, int32_t bufSize, int16_t* nBytesOut) {
     solo_single* h = (solo_single*)st;
     if (!h || !h->is_enc) return -1;
-    const size_t pcm_bytes = (size_t)(h->b->enc_ctrl.framesize_ms == 20 ? h->b->eops->packet_samples / 2 : h->b->eops->packet_samples) * 2;      // JC1_FrameSize samples
+    const size_t pcm_bytes = (size_t)enc_packet_samples(h->b) * 2;      // JC1_FrameSize samples
     memcpy(h->h_blk + SOLO_SINGLE_PCM_OFF, pcm, pcm_bytes);
     if (hipMemcpyAsync(h->d_pcm, h->h_blk + SOLO_SINGLE_PCM_OFF, pcm_bytes, hipMemcpyHostToDevice, (hipStream_t)0) != hipSuccess) return -1;
     if (solo_batch_encode(h->b, h->d_pcm, 1, h->d_bits, h->d_nbytes, h->d_status, NULL) != 0) return -1;
@@ -1112,7 +1057,7 @@ int32_t AGR_Sate_Decoder_Decode(void* st, int16_t* pcm, int16_t* nSamplesOut, co
     if (!h || h->is_enc) return -1;
     if (nBytes[0] <= 0) return -1;                                           // AGR_BWE_SDK_API.c:266 (state untouched, outputs unwritten)
     if (lostflag < 1 || lostflag > 4) return -1;
-    const int ns = (h->b->wb ? 2 * SX_PACKET : SX_PACKET) / (h->b->dec_ctrl.framesize_ms == 20 ? 2 : 1);                      // JC1_FrameSize (AGR_BWE_SDK_API.c:277)
+    const int ns = dec_packet_samples(h->b);                                 // JC1_FrameSize (AGR_BWE_SDK_API.c:277)
     const int32_t hbb = ctrl_hb_bytes(h->b->dec_ctrl.joint_enable, h->b->dec_ctrl.joint_mode, h->b->dec_ctrl.framesize_ms);
     int32_t n0 = nBytes[0], n1 = nBytes[1];
     if (lostflag != 1) {
@@ -1123,8 +1068,7 @@ int32_t AGR_Sate_Decoder_Decode(void* st, int16_t* pcm, int16_t* nSamplesOut, co
         memcpy(h->h_blk + SOLO_SINGLE_BITS_OFF, bits, (size_t)n0);
         if (hipMemcpyAsync(h->d_bits, h->h_blk + SOLO_SINGLE_BITS_OFF, (size_t)n0, hipMemcpyHostToDevice, (hipStream_t)0) != hipSuccess) return -1;
     }
-    if ((h->b->wb ? solo_wb_dec_launch_raw : solo_dec_launch_raw)(h->b->d_dec_state, h->d_bits, n0, n1, lostflag, h->d_pcm,
-                                                                  h->d_status, (hipStream_t)0) != hipSuccess) return -1;
+    if (h->b->dops->raw(h->b->d_dec_state, h->d_bits, n0, n1, lostflag, h->d_pcm, h->d_status, (hipStream_t)0) != hipSuccess) return -1;
     // status + decoded packet in one copy, one synchronisation
     if (hipMemcpyAsync(h->h_blk, h->d_blk, SOLO_SINGLE_PCM_OFF + (size_t)ns * 2, hipMemcpyDeviceToHost, (hipStream_t)0) != hipSuccess) return -1;
     if (hipStreamSynchronize((hipStream_t)0) != hipSuccess) return -1;

@@ -386,28 +386,12 @@ static inline hipError_t SX_K(solo_dec_launch_init)(void* states, int n_streams,
     hipLaunchKernelGGL(SX_K(solo_dec_init_kernel), dim3(n_streams), dim3(64), 0, s, (SxDecStream*)states, n_streams, hb_joint, useMDIndex);
     return hipGetLastError();
 }
-// recs: n records (stream, useMDIndex), validated by the caller; launches of SX_CTL_PER_LAUNCH records, the list passed by value
+// recs: n records (stream, useMDIndex), validated by the caller; the list travels by value (sx_launch_ctl_batches, solo_stream_ctl.h)
 static inline hipError_t SX_K(solo_dec_launch_init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
-        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
-        SxStreamCtlList l = {};
-        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
-        hipLaunchKernelGGL(SX_K(solo_dec_init_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k, hb_joint);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return sx_launch_ctl_batches(recs, n, [&](const SxStreamCtlList& l, int k) { hipLaunchKernelGGL(SX_K(solo_dec_init_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k, hb_joint); });
 }
 static inline hipError_t SX_K(solo_dec_launch_ctl_list)(void* states, const SxStreamCtl* recs, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
-        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
-        SxStreamCtlList l = {};
-        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
-        hipLaunchKernelGGL(SX_K(solo_dec_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return sx_launch_ctl_batches(recs, n, [&](const SxStreamCtlList& l, int k) { hipLaunchKernelGGL(SX_K(solo_dec_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxDecStream*)states, l, k); });
 }
 // (map, verdict: a subset call's stream list and verdict word, solo_stream_ctl.h; NULL, NULL: every stream of the handle)
 static inline hipError_t SX_K(solo_dec_launch)(void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
@@ -417,7 +401,7 @@ static inline hipError_t SX_K(solo_dec_launch)(void* states, const uint8_t* bits
                        n_packets, slot, pcm, status, map, verdict);
     return hipGetLastError();
 }
-// recs: solo_dec_extracted_bytes() x n_streams x pc bytes + 256: the records, behind them the list of the slots that carry bytes and its count
+// recs: solo_dec_ops::extracted_bytes x n_streams x pc bytes + 256: the records, behind them the list of the slots that carry bytes and its count
 static inline hipError_t SX_K(solo_dec_launch_extract)(const void* states, const uint8_t* bits, const int16_t* nbytes, const uint8_t* recv, int n_streams,
                                                        int n_packets, int p0, int pc, int slot, void* recs, const int32_t* map, const uint32_t* verdict,
                                                        hipStream_t s) {
@@ -442,7 +426,6 @@ static inline hipError_t SX_K(solo_dec_launch_synth)(void* states, const uint8_t
                        n_packets, p0, pc, slot, (const SxExtracted*)recs, pcm, status, map, verdict);
     return hipGetLastError();
 }
-static inline size_t SX_K(solo_dec_extracted_bytes)() { return 2 * sizeof(SxExtracted) + 2 * sizeof(u32); }      // per packet: two records, two list entries
 static inline hipError_t SX_K(solo_dec_launch_split)(void* states, const uint8_t* descA, const int16_t* lenA, const uint8_t* descB,
                                                      const int16_t* lenB, int n_streams, int n_packets, int slot,
                                                      int16_t* pcm, int32_t* status, hipStream_t s) {
@@ -458,15 +441,7 @@ static inline hipError_t SX_K(solo_recv_launch_reset)(uint32_t* lens, int32_t* p
 }
 // recs: n records (stream, first_seq), validated by the caller
 static inline hipError_t SX_K(solo_recv_launch_reset_list)(uint32_t* lens, int32_t* play, const SxStreamCtl* recs, int n, int depth, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
-        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
-        SxStreamCtlList l = {};
-        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
-        hipLaunchKernelGGL(SX_K(solo_recv_reset_list_kernel), dim3(k), dim3(64), 0, s, lens, play, l, k, depth);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return sx_launch_ctl_batches(recs, n, [&](const SxStreamCtlList& l, int k) { hipLaunchKernelGGL(SX_K(solo_recv_reset_list_kernel), dim3(k), dim3(64), 0, s, lens, play, l, k, depth); });
 }
 static inline hipError_t SX_K(solo_recv_launch_insert)(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth,
                                                        int slot, const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats,
@@ -486,4 +461,10 @@ static inline hipError_t SX_K(solo_dec_launch_raw)(void* state, const uint8_t* b
     hipLaunchKernelGGL(SX_K(solo_decode_raw_kernel), dim3(1), dim3(64), 0, s, (SxDecStream*)state, bits, n0, n1, lostflag, pcm, status);
     return hipGetLastError();
 }
-static inline size_t SX_K(solo_dec_state_bytes)() { return sizeof(SxDecStream); }
+
+// the launch table of this build (solo_dec_ops.h): solo_api.hip (solo_nb_dec_ops) / solo_api_wb.hip (solo_wb_dec_ops) hand it out
+#include "solo_dec_ops.h"
+static const solo_dec_ops SX_K(solo_dec_ops_table) = {
+    sizeof(SxDecStream), 2 * sizeof(SxExtracted) + 2 * sizeof(u32), SX_PACKET,
+    SX_K(solo_dec_launch_init), SX_K(solo_dec_launch_init_list), SX_K(solo_dec_launch_ctl_list), SX_K(solo_dec_launch), SX_K(solo_dec_launch_extract),
+    SX_K(solo_dec_launch_synth), SX_K(solo_dec_launch_split), SX_K(solo_dec_launch_ring), SX_K(solo_dec_launch_raw), SX_K(solo_recv_launch_insert)};

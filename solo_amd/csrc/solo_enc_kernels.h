@@ -1,6 +1,6 @@
 // solo_enc_kernels.h -- the encoder's analysis / coding kernels and the launch table of one build (the quantiser kernel lives in
-// solo_nsq_row.hip).  Compiled once per internal rate like solo_dec_kernels.h: solo_api.hip (SX_FS_KHZ = 8, 16 kHz API rate) and
-// solo_api_wb.hip (SX_FS_KHZ = 16, 32 kHz API rate).
+// solo_nsq_row.hip).  Compiled once per internal rate, in translation units of their own: solo_enc_k.hip / solo_enc_front_k.hip
+// (SX_FS_KHZ = 8, 16 kHz API rate) and solo_enc_k_wb.hip / solo_enc_front_k_wb.hip (SX_FS_KHZ = 16, 32 kHz API rate).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "solo_enc.h"
@@ -394,26 +394,10 @@ static hipError_t SX_K(solo_enc_launch_init)(void* states, int n_streams, int si
     return hipGetLastError();
 }
 static hipError_t SX_K(solo_enc_launch_init_list)(void* states, const SxStreamCtl* recs, int n, int hb_joint, int fpp, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {           // (the records travel as the kernel argument: nothing to stage)
-        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
-        SxStreamCtlList l = {};
-        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
-        hipLaunchKernelGGL(SX_K(solo_enc_init_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k, hb_joint, fpp);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return sx_launch_ctl_batches(recs, n, [&](const SxStreamCtlList& l, int k) { hipLaunchKernelGGL(SX_K(solo_enc_init_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k, hb_joint, fpp); });
 }
 static hipError_t SX_K(solo_enc_launch_ctl_list)(void* states, const SxStreamCtl* recs, int n, hipStream_t s) {
-    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
-        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
-        SxStreamCtlList l = {};
-        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
-        hipLaunchKernelGGL(SX_K(solo_enc_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return sx_launch_ctl_batches(recs, n, [&](const SxStreamCtlList& l, int k) { hipLaunchKernelGGL(SX_K(solo_enc_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k); });
 }
 static hipError_t SX_K(solo_enc_launch_analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in,
                                                  void* code_in, const int32_t* map, const uint32_t* verdict, hipStream_t s) {

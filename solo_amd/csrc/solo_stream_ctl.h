@@ -5,6 +5,9 @@
 // device memory, so the caller's arrays are free as soon as the call returns and two calls in flight cannot overwrite each other.
 #pragma once
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 struct SxStreamCtl {
     int32_t stream;              // index in the handle
@@ -14,6 +17,24 @@ struct SxStreamCtl {
 struct SxStreamCtlList {
     SxStreamCtl r[SX_CTL_PER_LAUNCH];
 };
+
+#if defined(__HIPCC__)
+// The one loop behind every list launcher (solo_dec_kernels.h, solo_enc_kernels.h): n records, validated by the caller, go out
+// SX_CTL_PER_LAUNCH at a time; launch(l, k) enqueues one launch of k workgroups, one per record of l.  (A callable, not the kernel and
+// its arguments: the kernels do not agree on how many arguments stand in front of the list.)
+template <typename Launch>
+static inline hipError_t sx_launch_ctl_batches(const SxStreamCtl* recs, int n, Launch launch) {
+    for (int i0 = 0; i0 < n; i0 += SX_CTL_PER_LAUNCH) {
+        const int k = n - i0 < SX_CTL_PER_LAUNCH ? n - i0 : SX_CTL_PER_LAUNCH;
+        SxStreamCtlList l = {};
+        for (int i = 0; i < k; i++) l.r[i] = recs[i0 + i];
+        launch(l, k);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+#endif
 
 // Subset calls (solo_batch_encode_streams, solo_batch_decode_streams, solo_recv_decode_streams): compact position i of a launch works
 // on the state of stream map[i]; its inputs and outputs stay at position i.  A NULL map is the identity (every other entry point), and
