@@ -204,6 +204,51 @@ int32_t solo_batch_decode_streams(solo_batch_t *b, const int32_t *d_streams, int
                                   int32_t *d_status, void *hip_stream);
 int32_t solo_recv_decode_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, int32_t n_packets, int16_t *d_pcm,
                                  int32_t *d_status, void *hip_stream);
+/* Sender back end: turns what an encode call wrote into the datagrams that go on the wire -- per packet up to two, MD1 and
+ * MD2 || HB -- as one solo_arrival_t per datagram plus a dense payload pool: exactly what solo_recv_insert of the receiving handle
+ * takes, so encode -> pack -> (network, or another handle's ring) -> play-out never brings codec data to the host, and a
+ * device-to-host copy of the result moves the bytes that are sent instead of whole slots.
+ *   d_bits, d_nbytes  what solo_batch_encode / solo_batch_encode_streams wrote ([n][P][slot], [n][P][2]; compact rows in the _streams form)
+ *   d_send            uint8 [n][P] in the format of d_recv: bit 0 sends MD1, bit 1 sends MD2 || HB; NULL = both.  Loss, single-description
+ *                     and FEC policies are expressed through this mask.
+ *   sequence number   of packet p of row i: first_seq + (d_seq_base ? d_seq_base[i] : 0) + p (d_seq_base: int32 [n] or NULL).  A packet
+ *                     that is not sent still consumes its number: the ring counts packets, not datagrams.
+ *   d_records         solo_arrival_t [max_records]: stream (i, or d_streams[i]), seq, desc (0 / 1), offset, len -- compacted, no holes
+ *   d_payload         uint8 [payload_capacity]: the datagrams back to back, each offset the sum of the earlier lengths, no padding
+ *   d_count           one solo_send_count_t (8-byte aligned): what was written and what the call needed, so that a caller whose buffers
+ *                     were too small can size them and repeat the call
+ * Order: PACKET-MAJOR (p outer), then row i, then description 0 before 1 -- a tick's datagrams are contiguous and the output is a pure
+ * function of the inputs.  Which datagrams a packet yields, with hbb = 8, or 4 with framesize_ms 20 or joint_mode 1 (the geometry of the
+ * handle: of its encoder, or of its decoder when it has no encoder), total = nbytes[0], n1 = nbytes[1]:
+ *   total <= 0 (a DTX packet): none, counted `empty` -- whatever else the record says;
+ *   a sequence number that is negative or does not fit int32, total > slot, n1 < 0, n1 > total or 0 < n1 < hbb: none, counted `refused`;
+ *                     such a record is never dereferenced;
+ *   otherwise         MD1 = the first total - n1 bytes if that is > 0 and bit 0 is set; MD2 || HB = the last n1 bytes if n1 > hbb and bit 1
+ *                     is set.  Bytes of a slot beyond its payload are never read.
+ * Record k is written iff k < max_records and offset_k + len_k <= min(payload_capacity, 2^31 - 1); both grow along the order, so what is
+ * written is a prefix, and nothing is written at or beyond either cap (max_records = 0 / payload_capacity = 0 only count).  Sizes that
+ * never overflow: 2 x n x n_packets records, n x n_packets x slot bytes.
+ * Returns -1 with nothing enqueued for a NULL handle, d_bits, d_nbytes, d_records, d_payload or d_count, n_packets <= 0, a negative
+ * cap, n x n_packets x 2 >= 2^31, and (_streams form) a NULL list or n outside (0, N].  The list itself is checked on the device like
+ * that of the other subset calls: a list that is not strictly increasing inside [0, N) writes d_count->records = -1 and nothing else.
+ * Any handle will do (only N, slot_bytes and the packet geometry are used; no codec state is read).  Three short kernels on hip_stream
+ * only, no host synchronisation, so the call can be captured in a graph -- except that the handle's scratch for the scan (32 bytes per
+ * 256 packets) grows, with a stream synchronisation, when a call is larger than every one before it.  The call does NOT wait for the
+ * handle's internal streams: after an encode with asynchronous joins call solo_batch_wait_encode(b, hip_stream, 0) first.  Calls on
+ * one handle must be ordered (same stream, or events). */
+typedef struct {
+    int32_t records, records_needed;   /* written / what the call would have written without the caps */
+    int64_t bytes, bytes_needed;       /* the same for payload bytes */
+    int32_t empty, refused;            /* packets skipped: total <= 0 (DTX) / sequence number or length record invalid */
+} solo_send_count_t;                   /* 32 bytes */
+int32_t solo_send_pack(solo_batch_t *b, const uint8_t *d_bits, const int16_t *d_nbytes, const uint8_t *d_send,
+                       int32_t n_packets, const int32_t *d_seq_base, int32_t first_seq,
+                       solo_arrival_t *d_records, int32_t max_records, uint8_t *d_payload, int64_t payload_capacity,
+                       solo_send_count_t *d_count, void *hip_stream);
+int32_t solo_send_pack_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, const uint8_t *d_bits, const int16_t *d_nbytes,
+                               const uint8_t *d_send, int32_t n_packets, const int32_t *d_seq_base, int32_t first_seq,
+                               solo_arrival_t *d_records, int32_t max_records, uint8_t *d_payload, int64_t payload_capacity,
+                               solo_send_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

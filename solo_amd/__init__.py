@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
+    "solo_send_pack", "solo_send_pack_streams",
 ]
 
 
@@ -39,6 +40,12 @@ class USER_Ctrl_enc(C.Structure):
 class USER_Ctrl_dec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "packetLoss_perc", "samplerate", "framesize_ms", "joint_enable", "joint_mode", "useMDIndex")]
+
+
+class solo_send_count_t(C.Structure):
+    """what a solo_send_pack call wrote and what it needed (include/solo_mi355x.h); 32 bytes"""
+    _fields_ = [("records", C.c_int32), ("records_needed", C.c_int32), ("bytes", C.c_int64), ("bytes_needed", C.c_int64),
+                ("empty", C.c_int32), ("refused", C.c_int32)]
 
 
 _lib = None
@@ -119,6 +126,11 @@ def load_library():
     lib.solo_recv_decode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_recv_stats.restype = C.c_int32
     lib.solo_recv_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    _send = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.solo_send_pack.restype = C.c_int32
+    lib.solo_send_pack.argtypes = [C.c_void_p] + _send
+    lib.solo_send_pack_streams.restype = C.c_int32
+    lib.solo_send_pack_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + _send
     lib.solo_batch_set_async_join.restype = C.c_int32
     lib.solo_batch_set_async_join.argtypes = [C.c_void_p, C.c_int32]
     lib.solo_batch_wait_encode.restype = C.c_int32
@@ -456,6 +468,72 @@ class SoloBatch:
         if r:
             raise RuntimeError("solo_recv_stats -> %d" % r)
         return dict(zip(self.RECV_STATS, list(out)[:5]))
+
+    # ---- sender back end (solo_send_pack): slots + length records -> datagram records + a dense payload pool ----
+    SEND_COUNT = ("records", "records_needed", "bytes", "bytes_needed", "empty", "refused")
+
+    def send_pack(self, bits, nbytes, send=None, first_seq=0, seq_base=None, records=None, payload=None, streams=None):
+        """What encode() wrote -> the datagrams to send: bits uint8 [n,P,slot], nbytes int16 [n,P,2], send uint8 [n,P] (bit 0: MD1, bit 1:
+        MD2 || HB; None = both), seq_base int32 [n] or None -> (records int32 [max,5] = (stream, seq, desc, offset, len) per datagram,
+        payload uint8 [cap], count int32 [8] on the device: read it with send_count()).  Packet p of row i has the sequence number
+        first_seq + seq_base[i] + p; the order is packet-major, then row, then description.  records / payload: the caller's buffers
+        (their sizes are the caps; what does not fit is counted, not written); the defaults, 2*n*P records and n*P*slot bytes, never
+        overflow.  streams: the rows are these streams (solo_send_pack_streams), as in encode().  The records and the pool are what
+        recv_insert() of the receiving handle takes.  Enqueued on the current stream, no synchronisation; with asynchronous joins call
+        wait_encode() first."""
+        t = self.torch
+        if not (getattr(bits, "is_cuda", False) and bits.dtype == t.uint8 and bits.is_contiguous() and len(bits.shape) == 3):
+            raise ValueError("bits: a contiguous uint8 CUDA tensor [n, P, slot]")
+        n, P, S = bits.shape
+        if S != self.slot or P <= 0:
+            raise ValueError("bits: slots of %d bytes and at least one packet" % self.slot)
+        if not (getattr(nbytes, "is_cuda", False) and nbytes.dtype == t.int16 and nbytes.is_contiguous() and tuple(nbytes.shape) == (n, P, 2)):
+            raise ValueError("nbytes: a contiguous int16 CUDA tensor [%d, %d, 2]" % (n, P))
+        smap = None
+        if streams is not None:
+            smap, k = self._subset(streams)
+            if n != k:
+                raise ValueError("bits has %d rows for %d listed streams" % (n, k))
+        elif n != self.n_streams:
+            raise ValueError("bits has %d rows, the handle %d streams" % (n, self.n_streams))
+        if send is not None and not (getattr(send, "is_cuda", False) and send.dtype == t.uint8 and send.is_contiguous() and tuple(send.shape) == (n, P)):
+            raise ValueError("send: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
+        if seq_base is not None and not (getattr(seq_base, "is_cuda", False) and seq_base.dtype == t.int32 and seq_base.is_contiguous()
+                                         and tuple(seq_base.shape) == (n,)):
+            raise ValueError("seq_base: a contiguous int32 CUDA tensor [%d]" % n)
+        first_seq = int(first_seq)
+        if not -2 ** 31 <= first_seq < 2 ** 31:
+            raise ValueError("first_seq must fit int32")
+        if 2 * n * P >= 2 ** 31:
+            raise ValueError("n * P * 2 must stay below 2^31")
+        if records is not None and not (getattr(records, "is_cuda", False) and records.dtype == t.int32 and records.is_contiguous()
+                                        and len(records.shape) == 2 and records.shape[1] == 5):
+            raise ValueError("records: a contiguous int32 CUDA tensor [max, 5]")
+        if payload is not None and not (getattr(payload, "is_cuda", False) and payload.dtype == t.uint8 and payload.is_contiguous()
+                                        and len(payload.shape) == 1):
+            raise ValueError("payload: a contiguous 1-D uint8 CUDA tensor")
+        if records is None:
+            records = t.zeros((2 * n * P, 5), dtype=t.int32, device=bits.device)
+        if payload is None:
+            payload = t.zeros((n * P * S,), dtype=t.uint8, device=bits.device)
+        count = t.zeros((8,), dtype=t.int32, device=bits.device)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
+        tail = (bits.data_ptr(), nbytes.data_ptr(), ptr(send), P, ptr(seq_base), first_seq, records.data_ptr() or count.data_ptr(), records.shape[0],
+                payload.data_ptr() or count.data_ptr(), payload.shape[0], count.data_ptr(), self._stream())
+        if smap is not None:
+            r = self.lib.solo_send_pack_streams(self.h, smap.data_ptr(), n, *tail)
+        else:
+            r = self.lib.solo_send_pack(self.h, *tail)
+        if r:
+            raise RuntimeError("solo_send_pack%s -> %d" % ("_streams" if smap is not None else "", r))
+        return records, payload, count
+
+    def send_count(self, count):
+        """the count tensor of send_pack() as a dict (synchronises): records / bytes written, records_needed / bytes_needed without the
+        caps, empty (DTX) and refused packets; records == -1: the stream list was refused on the device"""
+        c = solo_send_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.SEND_COUNT}
 
     def close(self):
         if getattr(self, "h", None):

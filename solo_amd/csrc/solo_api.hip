@@ -27,6 +27,7 @@
 // ---------------------------------------------------------------------------------------------------
 #include "solo_dec_kernels.h"
 #include "solo_l0_probe.h"
+#include "solo_send.h"          // the sender back end (solo_send_pack): rate-independent, compiled once, not a member of the launch tables
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -78,6 +79,7 @@ extern "C" const solo_enc_ops* solo_wb_enc_ops();                               
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
 #define SOLO_MAX_CHUNKS 64
+#define SOLO_N_VERDICTS 5
 struct solo_batch {
     int32_t n_streams;
     int32_t slot;
@@ -137,8 +139,10 @@ struct solo_batch {
     uint32_t* d_recv_stats;
     int32_t recv_depth, recv_slot;
     // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
-    // asynchronous joins), [2] decode, [3] receiver play-out
+    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams
     uint32_t* d_verdict;
+    void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack call (solo_send.h), grown on demand
+    size_t send_scratch_bytes;
 };
 
 static int ctrl_hb_joint(int joint_enable, int joint_mode) { return joint_enable != 0 && joint_mode == 1; }
@@ -419,7 +423,7 @@ solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, con
         if (enc && enc->samplerate != dec->samplerate) { solo_batch_destroy(b); return NULL; }     // a handle has one rate
         if (hipMalloc(&b->d_dec_state, b->dops->state_bytes * (size_t)n_streams) != hipSuccess) { solo_batch_destroy(b); return NULL; }
     }
-    if (hipMalloc((void**)&b->d_verdict, 4 * sizeof(uint32_t)) != hipSuccess || hipMemset(b->d_verdict, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
+    if (hipMalloc((void**)&b->d_verdict, SOLO_N_VERDICTS * sizeof(uint32_t)) != hipSuccess || hipMemset(b->d_verdict, 0, SOLO_N_VERDICTS * sizeof(uint32_t)) != hipSuccess) {
         solo_batch_destroy(b);
         return NULL;
     }
@@ -440,6 +444,7 @@ void solo_batch_destroy(solo_batch_t* b) {
     for (int i = 0; i < 2; i++) dev_free(b->d_parsed[i]);
     dev_free(b->d_dec_state);
     dev_free(b->d_verdict);
+    dev_free(b->d_send_scratch);
     if (b->ev_ready) for (int i = 0; i < 2; i++) (void)hipEventDestroy(b->evDec[i]);
     if (b->tev_ready) for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) (void)hipEventDestroy(b->tev[k][c][e]);
     if (b->pipe_ready) {
@@ -648,6 +653,51 @@ int32_t solo_recv_stats(solo_batch_t* b, uint32_t* out8, void* hip_stream) {
     SOLO_CHECK(hipMemcpyAsync(out8, b->d_recv_stats, SX_RECV_NSTATS * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
     SOLO_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
     return 0;
+}
+
+// ---- sender back end (solo_send.h): slots + length records -> datagram records + a dense payload pool ----------------------------
+static_assert(sizeof(solo_send_count_t) == sizeof(SxSendCount) && sizeof(solo_arrival_t) == sizeof(SxSendRecord), "include/solo_mi355x.h and solo_send.h agree");
+// map = NULL: the rows are the handle's streams 0 .. n - 1; else row i is stream map[i] (checked on the device, ahead of the passes)
+static int32_t solo_send_impl(solo_batch_t* b, const int32_t* map, int32_t n, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_send,
+                              int32_t n_packets, const int32_t* d_seq_base, int32_t first_seq, solo_arrival_t* d_records, int32_t max_records,
+                              uint8_t* d_payload, int64_t payload_capacity, solo_send_count_t* d_count, hipStream_t st) {
+    if (!d_bits || !d_nbytes || !d_records || !d_payload || !d_count || n_packets <= 0 || max_records < 0 || payload_capacity < 0) return -1;
+    if ((int64_t)n * (int64_t)n_packets * 2 >= ((int64_t)1 << 31)) return -1;
+    const size_t need = solo_send_scratch_bytes(n * n_packets);
+    if (need > b->send_scratch_bytes) {                    // grow the scan's scratch (synchronises; steady-state calls do not)
+        if (b->d_send_scratch) {
+            SOLO_CHECK(hipStreamSynchronize(st));
+            dev_free(b->d_send_scratch);
+            b->send_scratch_bytes = 0;
+        }
+        SOLO_CHECK(hipMalloc(&b->d_send_scratch, need));
+        b->send_scratch_bytes = need;
+    }
+    // the packet geometry is the handle's: that of its encoder, or of its decoder when it has none
+    const int hbb = b->have_enc ? ctrl_hb_bytes(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode, b->enc_ctrl.framesize_ms)
+                                : ctrl_hb_bytes(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode, b->dec_ctrl.framesize_ms);
+    uint32_t* verdict = b->d_verdict + 4;
+    if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, NULL, st));
+    SxSendArgs a;
+    a.bits = d_bits; a.nbytes = d_nbytes; a.send = d_send; a.seq_base = d_seq_base; a.map = map;
+    a.n = n; a.n_packets = n_packets; a.slot = b->slot; a.hbb = hbb; a.first_seq = first_seq;
+    SOLO_CHECK(solo_send_launch(a, b->d_send_scratch, (SxSendRecord*)d_records, max_records, d_payload, (long long)payload_capacity, (SxSendCount*)d_count,
+                                verdict, st));
+    return 0;
+}
+int32_t solo_send_pack(solo_batch_t* b, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_send, int32_t n_packets,
+                       const int32_t* d_seq_base, int32_t first_seq, solo_arrival_t* d_records, int32_t max_records, uint8_t* d_payload,
+                       int64_t payload_capacity, solo_send_count_t* d_count, void* hip_stream) {
+    if (!b) return -1;
+    return solo_send_impl(b, NULL, b->n_streams, d_bits, d_nbytes, d_send, n_packets, d_seq_base, first_seq, d_records, max_records, d_payload,
+                          payload_capacity, d_count, (hipStream_t)hip_stream);
+}
+int32_t solo_send_pack_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, const uint8_t* d_bits, const int16_t* d_nbytes,
+                               const uint8_t* d_send, int32_t n_packets, const int32_t* d_seq_base, int32_t first_seq, solo_arrival_t* d_records,
+                               int32_t max_records, uint8_t* d_payload, int64_t payload_capacity, solo_send_count_t* d_count, void* hip_stream) {
+    if (!b || !d_streams || n <= 0 || n > b->n_streams) return -1;
+    return solo_send_impl(b, d_streams, n, d_bits, d_nbytes, d_send, n_packets, d_seq_base, first_seq, d_records, max_records, d_payload,
+                          payload_capacity, d_count, (hipStream_t)hip_stream);
 }
 
 #ifdef SOLO_WITH_ENCODER

@@ -125,6 +125,33 @@ SX_HD i64 wv_sum64(i64 v) { SX_XOR_REDUCE(v, v + t_) return v; }
 SX_HD i32 wv_max(i32 v) { SX_XOR_REDUCE(v, (t_ > v ? t_ : v)) return v; }
 SX_HD i32 wv_min(i32 v) { SX_XOR_REDUCE(v, (t_ < v ? t_ : v)) return v; }
 #endif
+// Inclusive scan over the 64 lanes (lane l gets v[0] + ... + v[l], wrapping adds): four DPP row shifts (row_shr:1, 2, 4, 8; a lane whose
+// source lies outside its 16-lane row adds 0) scan every row, then the two row broadcasts of gfx9 carry the row totals on: row_bcast:15
+// adds lane 15 of rows 0 and 2 to rows 1 and 3, row_bcast:31 adds lane 31 -- by then the total of rows 0 and 1 -- to rows 2 and 3.  No LDS,
+// six DPP moves + six adds.  Every lane of the wave must be active.  The host form runs the same six steps on an array of 64 values
+// (wv_scan_incl_steps: what tests/test_send_pack_model.py checks against a running sum); the 1-lane emulation is the identity.
+SX_HD void wv_scan_incl_steps(i32 v[64]) {
+    for (int sh = 1; sh < 16; sh <<= 1) {                   // row_shr:sh, reading the values of before the step
+        i32 t[64];
+        for (int l = 0; l < 64; l++) t[l] = (l & 15) >= sh ? v[l - sh] : 0;
+        for (int l = 0; l < 64; l++) v[l] = sx_add(v[l], t[l]);
+    }
+    const i32 b15[2] = {v[15], v[47]};                      // row_bcast:15 row_mask:0xa
+    for (int l = 0; l < 64; l++) if ((l >> 4) & 1) v[l] = sx_add(v[l], b15[l >> 5]);
+    const i32 b31 = v[31];                                  // row_bcast:31 row_mask:0xc
+    for (int l = 32; l < 64; l++) v[l] = sx_add(v[l], b31);
+}
+SX_HD i32 wv_scan_incl(i32 v) {
+#if defined(__HIP_DEVICE_COMPILE__) && SX_NLANES == 64
+    v = sx_add(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true));
+    v = sx_add(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true));
+    v = sx_add(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true));
+    v = sx_add(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true));
+    v = sx_add(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));
+    v = sx_add(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));
+#endif
+    return v;
+}
 SX_HD i32 wv_bcast(i32 v, int src) {   // broadcast lane `src`'s value
 #if defined(__HIP_DEVICE_COMPILE__)
     return __shfl(v, src, SX_NLANES);
