@@ -249,6 +249,39 @@ int32_t solo_send_pack_streams(solo_batch_t *b, const int32_t *d_streams, int32_
                                const uint8_t *d_send, int32_t n_packets, const int32_t *d_seq_base, int32_t first_seq,
                                solo_arrival_t *d_records, int32_t max_records, uint8_t *d_payload, int64_t payload_capacity,
                                solo_send_count_t *d_count, void *hip_stream);
+/* Mixing bridge: the step between the receiving and the sending half -- every participant of a conference room hears the sum of the
+ * others ("mix-minus"), on the device.  d_pcm_in / d_pcm_out: int16 [n][n_packets][L], L = the handle's packet samples: the layout the
+ * decode calls write and the encode calls read, compact rows of the subset calls included (the mixer works on ROWS and never looks at
+ * slot numbers).  d_room: int32 [n], the room of row i in [0, n_rooms), or -1 = in no room.  d_gain_q12: int16 [n] or NULL (= 4096
+ * everywhere); a negative gain counts as 0.  Per packet p, statelessly, for a room with member set M:
+ *   c_j[s]   = (x_j[s] * g_j + 2048) >> 12            (arithmetic shift; g = 4096 passes the samples through)
+ *   e_j      = sum_s c_j[s]^2                          (64 bits, exact)
+ *   sel      = M when max_speakers <= 0 or >= |M|, else the max_speakers members that come first in the order
+ *              (larger e_j first, then smaller row index)
+ *   S[s]     = sum_{j in sel} c_j[s]
+ *   out_i[s] = sat16(S[s] - (i in sel ? c_i[s] : 0))   for every i in M -- a room of one hears silence.
+ * d_energy (int64 [n][n_packets] or NULL): e_j; d_mixed (uint8 [n][n_packets] or NULL): 1 if the row was in sel.  Rows with room -1:
+ * nothing of d_pcm_out, d_energy, d_mixed is written.  d_count (may be NULL): rows that got an output, rooms with at least one member,
+ * output samples that saturated.
+ * Returns -1 with nothing enqueued for a NULL handle, d_pcm_in, d_room or d_pcm_out; n <= 0, n_packets <= 0, n_rooms <= 0 or > n;
+ * n x n_packets >= 2^31; max_speakers > 64; max_speakers <= 0 together with n > 8191 (only then could more than 8191 contributions of
+ * |c| < 2^18 meet in one 32-bit sum; a caller with more rows passes max_speakers 64, which still mixes every member of any room of up
+ * to 64); PCM pointers that are not 16-byte aligned; input and output ranges that overlap (mix-minus cannot run in place).
+ * A room id outside [-1, n_rooms) is found on the device, ahead of the other kernels, and refuses the whole call: nothing is written
+ * except d_count->rows = -1.
+ * Any handle will do (only L and the handle's scratch are used).  Five short kernels on hip_stream only, no host synchronisation, so
+ * the call can be captured in a graph -- except that the handle's scratch for the room plan (9 bytes per row and packet + 16 per row)
+ * grows, with a stream synchronisation, when a call is larger than every one before it.  Like solo_send_pack the call does NOT wait
+ * for the handle's internal streams, and calls on one handle must be ordered.  One wavefront walks a (room, packet): a room of
+ * thousands is mixed correctly but not in parallel (INTEGRATION.md section 2 has the measured costs). */
+typedef struct {
+    int32_t rows, rooms;   /* rows that got an output / rooms with at least one member; rows = -1: call refused on the device */
+    int64_t clipped;       /* output samples that saturated */
+} solo_mix_count_t;        /* 16 bytes */
+int32_t solo_mix(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t n_packets,
+                 const int32_t *d_room, int32_t n_rooms, const int16_t *d_gain_q12, int32_t max_speakers,
+                 int16_t *d_pcm_out, int64_t *d_energy, uint8_t *d_mixed,
+                 solo_mix_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

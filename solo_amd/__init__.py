@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
-    "solo_send_pack", "solo_send_pack_streams",
+    "solo_send_pack", "solo_send_pack_streams", "solo_mix",
 ]
 
 
@@ -46,6 +46,11 @@ class solo_send_count_t(C.Structure):
     """what a solo_send_pack call wrote and what it needed (include/solo_mi355x.h); 32 bytes"""
     _fields_ = [("records", C.c_int32), ("records_needed", C.c_int32), ("bytes", C.c_int64), ("bytes_needed", C.c_int64),
                 ("empty", C.c_int32), ("refused", C.c_int32)]
+
+
+class solo_mix_count_t(C.Structure):
+    """what a solo_mix call did (include/solo_mi355x.h); 16 bytes"""
+    _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("clipped", C.c_int64)]
 
 
 _lib = None
@@ -131,6 +136,9 @@ def load_library():
     lib.solo_send_pack.argtypes = [C.c_void_p] + _send
     lib.solo_send_pack_streams.restype = C.c_int32
     lib.solo_send_pack_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int32] + _send
+    lib.solo_mix.restype = C.c_int32
+    lib.solo_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
     lib.solo_batch_set_async_join.argtypes = [C.c_void_p, C.c_int32]
     lib.solo_batch_wait_encode.restype = C.c_int32
@@ -534,6 +542,59 @@ class SoloBatch:
         caps, empty (DTX) and refused packets; records == -1: the stream list was refused on the device"""
         c = solo_send_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
         return {k: int(getattr(c, k)) for k in self.SEND_COUNT}
+
+    # ---- mixing bridge (solo_mix): decoded rows -> what every participant of a room hears ----
+    MIX_COUNT = ("rows", "rooms", "clipped")
+
+    def mix(self, pcm, room, gain=None, max_speakers=0, out=None, energy=None, mixed=None):
+        """Mix-minus on the device: pcm int16 [n,P,samples] (what decode() / recv_decode() wrote, compact rows included), room int32 [n]
+        (the room of row i, -1 = in none), gain int16 [n] in Q12 or None (= 4096; negative = muted) -> (out int16 [n,P,samples] = what
+        encode() takes, count int32 [4] on the device: read it with mix_count()).  Every member of a room hears the sum of the others;
+        with 0 < max_speakers (<= 64) < the room only the max_speakers loudest rows of each packet are mixed (larger energy first,
+        then smaller row index).  Rows in no room keep their `out` (zeros when `out` is allocated here).  energy int64 [n,P] /
+        mixed uint8 [n,P]: optional outputs, the energy of every member's contribution and whether it was mixed.  Room ids run up to
+        n - 1 (a row is in one room, so n rooms are enough); an id outside [-1, n) refuses the call on the device: rows == -1 in
+        the count, nothing else written.  Without a selection (max_speakers <= 0) at most 8191 rows.  Enqueued on the current stream,
+        no synchronisation."""
+        t = self.torch
+        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
+        if not dev(pcm, t.int16, 3):
+            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
+        n, P, L = pcm.shape
+        if L != self.packet_samples or n <= 0 or P <= 0:
+            raise ValueError("pcm: packets of %d samples, at least one row and one packet" % self.packet_samples)
+        if n * P >= 2 ** 31:
+            raise ValueError("n * P must stay below 2^31")
+        if not (dev(room, t.int32, 1) and room.shape[0] == n):
+            raise ValueError("room: a contiguous int32 CUDA tensor [%d]" % n)
+        if gain is not None and not (dev(gain, t.int16, 1) and gain.shape[0] == n):
+            raise ValueError("gain: a contiguous int16 CUDA tensor [%d]" % n)
+        max_speakers = int(max_speakers)
+        if max_speakers > 64:
+            raise ValueError("max_speakers: at most 64")
+        if max_speakers <= 0 and n > 8191:
+            raise ValueError("more than 8191 rows need 0 < max_speakers <= 64")
+        if out is not None and not (dev(out, t.int16, 3) and tuple(out.shape) == (n, P, L)):
+            raise ValueError("out: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, L))
+        if energy is not None and not (dev(energy, t.int64, 2) and tuple(energy.shape) == (n, P)):
+            raise ValueError("energy: a contiguous int64 CUDA tensor [%d, %d]" % (n, P))
+        if mixed is not None and not (dev(mixed, t.uint8, 2) and tuple(mixed.shape) == (n, P)):
+            raise ValueError("mixed: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
+        if out is None:
+            out = t.zeros((n, P, L), dtype=t.int16, device=pcm.device)
+        count = t.zeros((4,), dtype=t.int32, device=pcm.device)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        r = self.lib.solo_mix(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n, ptr(gain), max_speakers, out.data_ptr(), ptr(energy), ptr(mixed),
+                              count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_mix -> %d" % r)
+        return out, count
+
+    def mix_count(self, count):
+        """the count tensor of mix() as a dict (synchronises): rows that got an output, rooms with a member, saturated output samples;
+        rows == -1: a room id was refused on the device"""
+        c = solo_mix_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.MIX_COUNT}
 
     def close(self):
         if getattr(self, "h", None):

@@ -28,6 +28,7 @@
 #include "solo_dec_kernels.h"
 #include "solo_l0_probe.h"
 #include "solo_send.h"          // the sender back end (solo_send_pack): rate-independent, compiled once, not a member of the launch tables
+#include "solo_mix.h"           // the mixing bridge (solo_mix): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -79,7 +80,7 @@ extern "C" const solo_enc_ops* solo_wb_enc_ops();                               
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
 #define SOLO_MAX_CHUNKS 64
-#define SOLO_N_VERDICTS 5
+#define SOLO_N_VERDICTS 6
 struct solo_batch {
     int32_t n_streams;
     int32_t slot;
@@ -139,10 +140,12 @@ struct solo_batch {
     uint32_t* d_recv_stats;
     int32_t recv_depth, recv_slot;
     // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
-    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams
+    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams, [5] solo_mix (its room ids)
     uint32_t* d_verdict;
     void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack call (solo_send.h), grown on demand
     size_t send_scratch_bytes;
+    void* d_mix_scratch;             // room plan, energies and flags of a solo_mix call (solo_mix.h), grown on demand
+    size_t mix_scratch_bytes;
 };
 
 static int ctrl_hb_joint(int joint_enable, int joint_mode) { return joint_enable != 0 && joint_mode == 1; }
@@ -445,6 +448,7 @@ void solo_batch_destroy(solo_batch_t* b) {
     dev_free(b->d_dec_state);
     dev_free(b->d_verdict);
     dev_free(b->d_send_scratch);
+    dev_free(b->d_mix_scratch);
     if (b->ev_ready) for (int i = 0; i < 2; i++) (void)hipEventDestroy(b->evDec[i]);
     if (b->tev_ready) for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) (void)hipEventDestroy(b->tev[k][c][e]);
     if (b->pipe_ready) {
@@ -698,6 +702,43 @@ int32_t solo_send_pack_streams(solo_batch_t* b, const int32_t* d_streams, int32_
     if (!b || !d_streams || n <= 0 || n > b->n_streams) return -1;
     return solo_send_impl(b, d_streams, n, d_bits, d_nbytes, d_send, n_packets, d_seq_base, first_seq, d_records, max_records, d_payload,
                           payload_capacity, d_count, (hipStream_t)hip_stream);
+}
+
+// ---- mixing bridge (solo_mix.h): decoded rows -> mix-minus rows, room by room ------------------------------------------------------
+static_assert(sizeof(solo_mix_count_t) == sizeof(SxMixCount), "include/solo_mi355x.h and solo_mix.h agree");
+int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
+                 const int16_t* d_gain_q12, int32_t max_speakers, int16_t* d_pcm_out, int64_t* d_energy, uint8_t* d_mixed, solo_mix_count_t* d_count,
+                 void* hip_stream) {
+    if (!b || !d_pcm_in || !d_room || !d_pcm_out || n <= 0 || n_packets <= 0 || n_rooms <= 0 || n_rooms > n) return -1;
+    if ((int64_t)n * (int64_t)n_packets >= ((int64_t)1 << 31)) return -1;
+    if (max_speakers > SX_MIX_MAX_SPEAKERS || (max_speakers <= 0 && n > SX_MIX_MAX_ALL_ROWS)) return -1;
+    // the packet geometry is the handle's: that of its decoder, or of its encoder when it has none
+    int L = 0;
+    if (b->have_dec) L = dec_packet_samples(b);
+#ifdef SOLO_WITH_ENCODER
+    else if (b->have_enc) L = enc_packet_samples(b);
+#endif
+    if (L <= 0 || L > SX_MIX_MAX_L || (L & 7)) return -1;
+    const uintptr_t in0 = (uintptr_t)d_pcm_in, out0 = (uintptr_t)d_pcm_out;
+    const uintptr_t bytes = (uintptr_t)n * (uintptr_t)n_packets * (uintptr_t)L * sizeof(int16_t);
+    if ((in0 & 15) || (out0 & 15) || (in0 < out0 + bytes && out0 < in0 + bytes)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const size_t need = solo_mix_scratch_bytes(n, n_packets);
+    if (need > b->mix_scratch_bytes) {                     // grow the scratch (synchronises; steady-state calls do not)
+        if (b->d_mix_scratch) {
+            SOLO_CHECK(hipStreamSynchronize(st));
+            dev_free(b->d_mix_scratch);
+            b->mix_scratch_bytes = 0;
+        }
+        SOLO_CHECK(hipMalloc(&b->d_mix_scratch, need));
+        b->mix_scratch_bytes = need;
+    }
+    SxMixArgs a;
+    a.pcm_in = d_pcm_in; a.gain = d_gain_q12; a.pcm_out = d_pcm_out; a.energy = d_energy; a.mixed = d_mixed;
+    a.counts = NULL; a.starts = NULL; a.members = NULL;
+    a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
+    SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + 5, st));
+    return 0;
 }
 
 #ifdef SOLO_WITH_ENCODER
