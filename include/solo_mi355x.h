@@ -204,6 +204,58 @@ int32_t solo_batch_decode_streams(solo_batch_t *b, const int32_t *d_streams, int
                                   int32_t *d_status, void *hip_stream);
 int32_t solo_recv_decode_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, int32_t n_packets, int16_t *d_pcm,
                                  int32_t *d_status, void *hip_stream);
+/* Read side of the receiver ring: what is queued for a stream, what became of its arrivals and of its played packets, and -- from the
+ * same pass -- the compacted list of the streams that are ready to play, in the form solo_recv_decode_streams takes.  The ring still
+ * decides nothing (no play-out adaptation, no time stretching); it states the facts a jitter policy and a receiver report need.
+ *   Queue fields (always): for stream s with play-out position p and ring depth D, from the D length words of the stream alone (a second
+ *   description of <= hbb bytes, or a packet above 252 bytes that play-out will answer with -11, counts as queued like any other):
+ *   play = p; queued / complete = sequence numbers of [p, p + D) that hold at least one / both descriptions; ready = length of the run
+ *   of non-empty entries that starts AT p; span = 1 + (highest queued sequence number - p), 0 for an empty queue; head = entry p in
+ *   d_recv format (bit 0 MD1 queued, bit 1 MD2 || HB queued).
+ *   Counters (uint32, wrapping, cumulative; counted only while solo_recv_track is on): inserted / late / ahead / duplicate / bad = the
+ *   verdict solo_recv_insert gave each arrival of the stream (an arrival whose stream index is out of range appears in solo_recv_stats
+ *   only; solo_recv_stats itself is unchanged); played_both / played_md1 / played_md2 / played_none = one per packet that solo_recv_decode /
+ *   solo_recv_decode_streams played for the stream, by its entry's length word at play-out (a refused list plays and counts nothing);
+ *   margin_min = the smallest (seq - play) of an INSERTED arrival at filing time, D when there was none.  A handle that never tracked
+ *   reports 0 everywhere and margin_min = D.
+ * solo_recv_track(b, 1, st) allocates the counters on first use (40 bytes per stream) and ZEROES them on every call; (b, 0, st) stops
+ * the counting and keeps the values (reports go on showing them).  -1 without a ring.  solo_recv_create zeroes the counters of all
+ * streams and leaves the switch as it is; solo_recv_reset_streams zeroes those of the listed streams (a new call joins the slot).
+ * Default: off -- solo_recv_insert and solo_recv_decode* then enqueue exactly the kernels they always did; on costs one more short
+ * kernel per play-out call, ahead of the decoder.
+ * solo_recv_report: row i is stream d_streams[i] (DEVICE list as in the subset calls), or stream i with d_streams = NULL and n = N.
+ *   Row i is SELECTED iff ready_i >= m_i, m_i = d_min_ready ? d_min_ready[i] : min_ready (d_min_ready: DEVICE int32 [n] or NULL;
+ *   m_i <= 0 selects always), or max_span > 0 and span_i >= max_span (the queue is about to overflow).
+ *   d_reports   solo_recv_report_t [n], 16-byte aligned; d_play_list / d_play_rows int32 [n]: the stream index / the row index of the k-th
+ *   selected row in row order, compacted, no holes; entries at and beyond `selected` are not written.  The input list is strictly
+ *   increasing, so d_play_list is too: a valid d_streams of solo_recv_decode_streams.  d_count = {selected, n}; the caller reads these
+ *   8 bytes to get the n of the play-out call.  Any of the three outputs may be NULL (not wanted).
+ *   flags: SOLO_RECV_REPORT_CLEAR_MARGIN sets margin_min of the listed streams back to D after it was read.
+ * Returns -1 with nothing enqueued for a NULL handle, no ring, n <= 0, n > N, d_streams = NULL with n != N, all three outputs NULL, a
+ * list output without d_count, a d_reports that is not 16-byte aligned, unknown flag bits.  The list is checked on the device like that
+ * of the other subset calls: one that is not strictly increasing inside [0, N) writes d_count->selected = -1 (when given) and nothing
+ * else, and clears no margin.  At most three short kernels on hip_stream only, no host synchronisation, no allocation: the call can be
+ * captured.  Calls on one handle must be ordered (same stream, or events), as for the rest of the ring. */
+typedef struct {                 /* 64 bytes, one per listed stream */
+    int32_t  play;               /* sequence number the stream decodes next                                             */
+    int32_t  queued;             /* sequence numbers in [play, play + depth) that hold at least one description          */
+    int32_t  complete;           /* of those, how many hold both                                                         */
+    int32_t  ready;              /* length of the run of non-empty entries that starts AT play (0 .. depth)              */
+    int32_t  span;               /* 1 + (highest queued sequence number - play); 0 when nothing is queued                */
+    int32_t  head;               /* entry `play` in d_recv format: bit 0 MD1 queued, bit 1 MD2 || HB queued              */
+    uint32_t inserted, late, ahead, duplicate, bad;           /* what became of this stream's arrivals (tracking on)     */
+    uint32_t played_both, played_md1, played_md2, played_none;/* what its played packets were made of (tracking on)      */
+    int32_t  margin_min;         /* smallest (seq - play) of an INSERTED arrival since the last clear; depth = none      */
+} solo_recv_report_t;
+typedef struct { int32_t selected, listed; } solo_recv_report_count_t;   /* 8 bytes; selected = -1: list refused on the device */
+
+#define SOLO_RECV_REPORT_CLEAR_MARGIN 1
+
+int32_t solo_recv_track(solo_batch_t *b, int32_t on, void *hip_stream);
+int32_t solo_recv_report(solo_batch_t *b, const int32_t *d_streams, int32_t n,
+                         const int32_t *d_min_ready, int32_t min_ready, int32_t max_span, int32_t flags,
+                         solo_recv_report_t *d_reports, int32_t *d_play_list, int32_t *d_play_rows,
+                         solo_recv_report_count_t *d_count, void *hip_stream);
 /* Sender back end: turns what an encode call wrote into the datagrams that go on the wire -- per packet up to two, MD1 and
  * MD2 || HB -- as one solo_arrival_t per datagram plus a dense payload pool: exactly what solo_recv_insert of the receiving handle
  * takes, so encode -> pack -> (network, or another handle's ring) -> play-out never brings codec data to the host, and a

@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
-    "solo_send_pack", "solo_send_pack_streams", "solo_mix",
+    "solo_send_pack", "solo_send_pack_streams", "solo_mix", "solo_recv_track", "solo_recv_report",
 ]
 
 
@@ -52,6 +52,20 @@ class solo_mix_count_t(C.Structure):
     """what a solo_mix call did (include/solo_mi355x.h); 16 bytes"""
     _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("clipped", C.c_int64)]
 
+
+class solo_recv_report_t(C.Structure):
+    """one stream's queue and counters as solo_recv_report writes them (include/solo_mi355x.h); 64 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("play", "queued", "complete", "ready", "span", "head")] + \
+               [(n, C.c_uint32) for n in ("inserted", "late", "ahead", "duplicate", "bad", "played_both", "played_md1", "played_md2", "played_none")] + \
+               [("margin_min", C.c_int32)]
+
+
+class solo_recv_report_count_t(C.Structure):
+    """how many rows a solo_recv_report call selected, of how many listed; 8 bytes; selected = -1: list refused on the device"""
+    _fields_ = [("selected", C.c_int32), ("listed", C.c_int32)]
+
+
+RECV_REPORT_CLEAR_MARGIN = 1
 
 _lib = None
 
@@ -131,6 +145,11 @@ def load_library():
     lib.solo_recv_decode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_recv_stats.restype = C.c_int32
     lib.solo_recv_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_recv_track.restype = C.c_int32
+    lib.solo_recv_track.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_recv_report.restype = C.c_int32
+    lib.solo_recv_report.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
     _send = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.solo_send_pack.restype = C.c_int32
     lib.solo_send_pack.argtypes = [C.c_void_p] + _send
@@ -476,6 +495,69 @@ class SoloBatch:
         if r:
             raise RuntimeError("solo_recv_stats -> %d" % r)
         return dict(zip(self.RECV_STATS, list(out)[:5]))
+
+    # ---- read side of the ring (solo_recv_track, solo_recv_report): per-stream queue report, counters, play-out list ----
+    RECV_REPORT = tuple(f[0] for f in solo_recv_report_t._fields_)
+
+    def recv_track(self, on=True):
+        """Per-stream counting of arrivals and played packets (solo_recv_track): on zeroes the counters and starts, off stops and keeps
+        the values.  Off by default; while off insert and play-out enqueue exactly what they always did."""
+        r = self.lib.solo_recv_track(self.h, 1 if on else 0, self._stream())
+        if r:
+            raise RuntimeError("solo_recv_track -> %d" % r)
+
+    def recv_report(self, streams=None, min_ready=0, max_span=0, clear_margin=False, reports=None, play_list=None, play_rows=None):
+        """What is queued per stream, its counters, and the streams that are ready to play (solo_recv_report) -> (reports int32 [n,16] with
+        the columns RECV_REPORT, play_list int32 [n], play_rows int32 [n], count int32 [2] on the device: read it with
+        recv_report_count()).  streams: None = all, a strictly increasing sequence, or a 1-D int32 CUDA tensor (taken as it is and
+        checked on the device: a bad one gives selected = -1).  Row i is selected when ready >= min_ready (an int, or an int32 CUDA
+        tensor [n] with one threshold per row; <= 0 selects always) or when max_span > 0 and span >= max_span.  play_list[:selected] is
+        what recv_decode(streams=...) takes.  clear_margin: margin_min of the listed streams starts afresh after this report.
+        Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        dev = lambda x, nd: getattr(x, "is_cuda", False) and x.dtype == t.int32 and x.is_contiguous() and len(x.shape) == nd
+        smap, n = None, self.n_streams
+        if streams is not None:
+            if getattr(streams, "is_cuda", False):
+                if not dev(streams, 1) or not 0 < streams.shape[0] <= self.n_streams:
+                    raise ValueError("streams: a sequence or a contiguous 1-D int32 CUDA tensor of 1 .. %d indices" % self.n_streams)
+                smap, n = streams, int(streams.shape[0])
+            else:
+                smap, n = self._subset(streams)
+        mr_v, mr = None, 0
+        if isinstance(min_ready, int) and not isinstance(min_ready, bool):
+            mr = min_ready
+        elif dev(min_ready, 1) and min_ready.shape[0] == n:
+            mr_v = min_ready
+        else:
+            raise ValueError("min_ready: an int or a contiguous int32 CUDA tensor [%d]" % n)
+        max_span = int(max_span)
+        if not (-2 ** 31 <= mr < 2 ** 31 and -2 ** 31 <= max_span < 2 ** 31):
+            raise ValueError("min_ready / max_span must fit int32")
+        if reports is not None and not (dev(reports, 2) and tuple(reports.shape) == (n, 16)):
+            raise ValueError("reports: a contiguous int32 CUDA tensor [%d, 16]" % n)
+        for x, name in ((play_list, "play_list"), (play_rows, "play_rows")):
+            if x is not None and not (dev(x, 1) and x.shape[0] == n):
+                raise ValueError("%s: a contiguous int32 CUDA tensor [%d]" % (name, n))
+        if reports is None:
+            reports = t.zeros((n, 16), dtype=t.int32, device=self.device)
+        if play_list is None:
+            play_list = t.zeros((n,), dtype=t.int32, device=self.device)
+        if play_rows is None:
+            play_rows = t.zeros((n,), dtype=t.int32, device=self.device)
+        count = t.zeros((2,), dtype=t.int32, device=self.device)
+        r = self.lib.solo_recv_report(self.h, smap.data_ptr() if smap is not None else None, n, mr_v.data_ptr() if mr_v is not None else None, mr,
+                                      max_span, RECV_REPORT_CLEAR_MARGIN if clear_margin else 0, reports.data_ptr(), play_list.data_ptr(),
+                                      play_rows.data_ptr(), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_recv_report -> %d" % r)
+        return reports, play_list, play_rows, count
+
+    def recv_report_count(self, count):
+        """the count tensor of recv_report() as a dict (synchronises): selected rows, listed rows; selected == -1: the stream list was
+        refused on the device"""
+        c = solo_recv_report_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {"selected": int(c.selected), "listed": int(c.listed)}
 
     # ---- sender back end (solo_send_pack): slots + length records -> datagram records + a dense payload pool ----
     SEND_COUNT = ("records", "records_needed", "bytes", "bytes_needed", "empty", "refused")

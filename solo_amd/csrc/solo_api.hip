@@ -29,6 +29,7 @@
 #include "solo_l0_probe.h"
 #include "solo_send.h"          // the sender back end (solo_send_pack): rate-independent, compiled once, not a member of the launch tables
 #include "solo_mix.h"           // the mixing bridge (solo_mix): likewise
+#include "solo_recv_report.h"   // the read side of the receiver ring (solo_recv_report, solo_recv_track): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -80,7 +81,7 @@ extern "C" const solo_enc_ops* solo_wb_enc_ops();                               
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
 #define SOLO_MAX_CHUNKS 64
-#define SOLO_N_VERDICTS 6
+#define SOLO_N_VERDICTS 7
 struct solo_batch {
     int32_t n_streams;
     int32_t slot;
@@ -139,8 +140,13 @@ struct solo_batch {
     int32_t* d_recv_play;
     uint32_t* d_recv_stats;
     int32_t recv_depth, recv_slot;
+    // read side of the ring (solo_recv_report.h): per-stream counters [N][SX_RECV_TRK_WORDS] (allocated by the first solo_recv_track(1),
+    // kept until the handle goes), the switch (counting happens only while it is on), and the selection flags [N] of a report call
+    uint32_t* d_recv_trk;
+    int recv_track;
+    int32_t* d_recv_sel;
     // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
-    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams, [5] solo_mix (its room ids)
+    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams, [5] solo_mix (its room ids), [6] solo_recv_report
     uint32_t* d_verdict;
     void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack call (solo_send.h), grown on demand
     size_t send_scratch_bytes;
@@ -438,6 +444,7 @@ static void solo_recv_free(solo_batch_t* b);
 void solo_batch_destroy(solo_batch_t* b) {
     if (!b) return;
     solo_recv_free(b);
+    dev_free(b->d_recv_trk);
     if (b->dec_pipe_ready && b->dec_split) {
         (void)hipStreamSynchronize(b->sP); (void)hipStreamSynchronize(b->sS);
         (void)hipStreamDestroy(b->sP); (void)hipStreamDestroy(b->sS);
@@ -598,6 +605,7 @@ static void solo_recv_free(solo_batch_t* b) {
     dev_free(b->d_recv_lens);
     dev_free(b->d_recv_play);
     dev_free(b->d_recv_stats);
+    dev_free(b->d_recv_sel);
     b->recv_depth = b->recv_slot = 0;
 }
 int32_t solo_recv_create(solo_batch_t* b, int32_t depth, int32_t slot_bytes, int32_t first_seq, void* hip_stream) {
@@ -611,10 +619,12 @@ int32_t solo_recv_create(solo_batch_t* b, int32_t depth, int32_t slot_bytes, int
         if (e == hipSuccess) e = hipMalloc((void**)&b->d_recv_lens, ne * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&b->d_recv_play, (size_t)b->n_streams * sizeof(int32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&b->d_recv_stats, SX_RECV_NSTATS * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->d_recv_sel, (size_t)b->n_streams * sizeof(int32_t));      // (so that solo_recv_report allocates nothing)
         if (e != hipSuccess) { solo_recv_free(b); return -(int32_t)e; }
         b->recv_depth = depth; b->recv_slot = slot_bytes;
     }
     SOLO_CHECK(solo_recv_launch_reset(b->d_recv_lens, b->d_recv_play, b->d_recv_stats, b->n_streams, depth, first_seq, st));
+    if (b->d_recv_trk) SOLO_CHECK(solo_recv_trk_reset_launch(b->d_recv_trk, b->n_streams, depth, st));
     return 0;
 }
 int32_t solo_recv_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, const int32_t* h_first_seq, void* hip_stream) {
@@ -625,6 +635,7 @@ int32_t solo_recv_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32
         rr[(size_t)i] = SxStreamCtl{h_streams[i], h_first_seq[i], 0, 0};
     }
     SOLO_CHECK(solo_recv_launch_reset_list(b->d_recv_lens, b->d_recv_play, rr.data(), n, b->recv_depth, (hipStream_t)hip_stream));
+    if (b->d_recv_trk) SOLO_CHECK(solo_recv_trk_reset_list_launch(b->d_recv_trk, rr.data(), n, b->recv_depth, (hipStream_t)hip_stream));   // (a new call joins the slot)
     return 0;
 }
 int32_t solo_recv_insert(solo_batch_t* b, const solo_arrival_t* d_arrivals, int32_t n_arrivals, const uint8_t* d_payload, int64_t payload_bytes,
@@ -633,11 +644,14 @@ int32_t solo_recv_insert(solo_batch_t* b, const solo_arrival_t* d_arrivals, int3
     if (n_arrivals == 0) return 0;
     // (desc = -1 is accepted for the streams whose decoder runs with useMDIndex = 1: the kernel reads each stream's own flag)
     SOLO_CHECK(b->dops->recv_insert(d_arrivals, n_arrivals, d_payload, (long long)payload_bytes, b->n_streams, b->recv_depth, b->recv_slot, b->d_dec_state,
-                                    b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->d_recv_stats, (hipStream_t)hip_stream));
+                                    b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->d_recv_stats, b->recv_track ? b->d_recv_trk : NULL,
+                                    (hipStream_t)hip_stream));
     return 0;
 }
 int32_t solo_recv_decode(solo_batch_t* b, int32_t n_packets, int16_t* d_pcm, int32_t* d_status, void* hip_stream) {
     if (!b || !b->d_recv_ring || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
+    if (b->recv_track)            // what the packets about to be played are made of (solo_recv_report.h), ahead of the kernel that clears them
+        SOLO_CHECK(solo_recv_account_launch(b->d_recv_lens, b->d_recv_play, b->d_recv_trk, b->n_streams, n_packets, b->recv_depth, NULL, NULL, (hipStream_t)hip_stream));
     SOLO_CHECK(b->dops->ring(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, b->n_streams, n_packets, b->recv_depth, b->recv_slot, d_pcm,
                              d_status, NULL, NULL, (hipStream_t)hip_stream));
     return 0;
@@ -648,6 +662,7 @@ int32_t solo_recv_decode_streams(solo_batch_t* b, const int32_t* d_streams, int3
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t* verdict = b->d_verdict + 3;
     SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, d_status, st));
+    if (b->recv_track) SOLO_CHECK(solo_recv_account_launch(b->d_recv_lens, b->d_recv_play, b->d_recv_trk, n, n_packets, b->recv_depth, d_streams, verdict, st));
     SOLO_CHECK(b->dops->ring(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, n, n_packets, b->recv_depth, b->recv_slot, d_pcm, d_status,
                              d_streams, verdict, st));
     return 0;
@@ -656,6 +671,37 @@ int32_t solo_recv_stats(solo_batch_t* b, uint32_t* out8, void* hip_stream) {
     if (!b || !b->d_recv_ring || !out8) return -1;
     SOLO_CHECK(hipMemcpyAsync(out8, b->d_recv_stats, SX_RECV_NSTATS * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
     SOLO_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
+    return 0;
+}
+
+// ---- read side of the ring (solo_recv_report.h): per-stream counters, queue report, play-out list ----------------------------------
+static_assert(sizeof(solo_recv_report_t) == sizeof(SxRecvReport) && sizeof(solo_recv_report_count_t) == sizeof(SxRecvReportCount) &&
+              SOLO_RECV_REPORT_CLEAR_MARGIN == SX_RECV_REPORT_CLEAR_MARGIN, "include/solo_mi355x.h and solo_recv_report.h agree");
+int32_t solo_recv_track(solo_batch_t* b, int32_t on, void* hip_stream) {
+    if (!b || !b->d_recv_ring) return -1;
+    if (!on) { b->recv_track = 0; return 0; }               // (the values stay; solo_recv_report goes on showing them)
+    if (!b->d_recv_trk) {
+        const hipError_t e = hipMalloc((void**)&b->d_recv_trk, (size_t)b->n_streams * SX_RECV_TRK_WORDS * sizeof(uint32_t));
+        if (e != hipSuccess) { b->d_recv_trk = NULL; return -(int32_t)e; }
+    }
+    SOLO_CHECK(solo_recv_trk_reset_launch(b->d_recv_trk, b->n_streams, b->recv_depth, (hipStream_t)hip_stream));
+    b->recv_track = 1;
+    return 0;
+}
+int32_t solo_recv_report(solo_batch_t* b, const int32_t* d_streams, int32_t n, const int32_t* d_min_ready, int32_t min_ready, int32_t max_span,
+                         int32_t flags, solo_recv_report_t* d_reports, int32_t* d_play_list, int32_t* d_play_rows, solo_recv_report_count_t* d_count,
+                         void* hip_stream) {
+    if (!b || !b->d_recv_ring || n <= 0 || n > b->n_streams || (!d_streams && n != b->n_streams)) return -1;
+    if ((!d_reports && !d_play_list && !d_play_rows) || ((d_play_list || d_play_rows) && !d_count) || (flags & ~SOLO_RECV_REPORT_CLEAR_MARGIN)) return -1;
+    if ((uintptr_t)d_reports & 15) return -1;               // (the records are stored 16 bytes at a time)
+    hipStream_t st = (hipStream_t)hip_stream;
+    uint32_t* verdict = b->d_verdict + 6;
+    if (d_streams) SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
+    SxRecvReportArgs a;
+    a.lens = b->d_recv_lens; a.play = b->d_recv_play; a.trk = b->d_recv_trk; a.map = d_streams; a.min_ready_v = d_min_ready;
+    a.reports = (uint32_t*)d_reports; a.sel = b->d_recv_sel;
+    a.n = n; a.depth = b->recv_depth; a.min_ready = min_ready; a.max_span = max_span; a.clear_margin = (flags & SOLO_RECV_REPORT_CLEAR_MARGIN) != 0;
+    SOLO_CHECK(solo_recv_report_launch(a, d_play_list, d_play_rows, (SxRecvReportCount*)d_count, verdict, st));
     return 0;
 }
 

@@ -304,7 +304,7 @@ __global__ void __launch_bounds__(64, 4) SX_K(solo_decode_split_kernel)(SxDecStr
 // one wavefront files one arrival
 __global__ void __launch_bounds__(64) SX_K(solo_recv_insert_kernel)(const SxRecvArrival* __restrict__ arr, int n_arr, const u8* __restrict__ payload,
                                                                long long payload_bytes, int n_streams, int depth, int slot, const SxDecStream* states,
-                                                               u8* ring, u32* lens, const i32* __restrict__ play, u32* stats) {
+                                                               u8* ring, u32* lens, const i32* __restrict__ play, u32* stats, u32* trk) {
     const int a = blockIdx.x;
     if (a >= n_arr) return;
     const SxRecvArrival r = arr[a];
@@ -317,7 +317,14 @@ __global__ void __launch_bounds__(64) SX_K(solo_recv_insert_kernel)(const SxRecv
         if (sl < 0) verdict = SX_RECV_DUP;
     }
     const size_t e = sl >= 0 ? sx_recv_entry(r.stream, r.seq, depth) : 0;
-    if (SX_LANE == 0) atomicAdd(&stats[verdict], 1u);
+    if (SX_LANE == 0) {
+        atomicAdd(&stats[verdict], 1u);
+        if (trk && r.stream >= 0 && r.stream < n_streams) {     // per-stream counters (solo_recv_track; a stream out of range has none)
+            u32* t = trk + (size_t)r.stream * SX_RECV_TRK_WORDS;
+            atomicAdd(&t[verdict], 1u);
+            if (verdict == SX_RECV_INSERTED) atomicMin((i32*)&t[SX_RECV_TRK_MARGIN], r.seq - play[r.stream]);
+        }
+    }
     if (sl >= 0) {
         u8* dst = ring + (e * 2 + (size_t)sl) * (size_t)slot;
         const u8* src = payload + r.offset;
@@ -445,9 +452,9 @@ static inline hipError_t SX_K(solo_recv_launch_reset_list)(uint32_t* lens, int32
 }
 static inline hipError_t SX_K(solo_recv_launch_insert)(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth,
                                                        int slot, const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats,
-                                                       hipStream_t s) {
+                                                       uint32_t* trk, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_recv_insert_kernel), dim3(n_arr), dim3(64), 0, s, (const SxRecvArrival*)arrivals, n_arr, payload, payload_bytes, n_streams,
-                       depth, slot, (const SxDecStream*)states, ring, lens, play, stats);
+                       depth, slot, (const SxDecStream*)states, ring, lens, play, stats, trk);
     return hipGetLastError();
 }
 static inline hipError_t SX_K(solo_dec_launch_ring)(void* states, const uint8_t* ring, uint32_t* lens, int32_t* play, int n_streams, int n_packets, int depth,

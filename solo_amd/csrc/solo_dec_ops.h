@@ -38,8 +38,9 @@ struct solo_dec_ops {
                        int16_t* pcm, int32_t* status, const int32_t* map, const uint32_t* verdict, hipStream_t s);
     // one packet with the reference's raw (ptr, nBytes, lostflag) convention (AGR_Sate_Decoder_Decode)
     hipError_t (*raw)(void* state, const uint8_t* bits, int n0, int n1, int lostflag, int16_t* pcm, int32_t* status, hipStream_t s);
-    // arrivals into the staging ring (reads each stream's useMDIndex from its decoder state)
+    // arrivals into the staging ring (reads each stream's useMDIndex from its decoder state); trk: the per-stream counters of
+    // solo_recv_track (solo_recv.h), NULL = not counted
     hipError_t (*recv_insert)(const void* arrivals, int n_arr, const uint8_t* payload, long long payload_bytes, int n_streams, int depth, int slot,
-                              const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats, hipStream_t s);
+                              const void* states, uint8_t* ring, uint32_t* lens, const int32_t* play, uint32_t* stats, uint32_t* trk, hipStream_t s);
 };
 #endif

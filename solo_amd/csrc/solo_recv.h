@@ -18,7 +18,10 @@
 // length word (a second copy of a description loses and is dropped) and copies the payload.  Decoding n packets walks entries play .. play + n - 1 of every stream through the same merge
 // as solo_batch_decode_split (what has arrived BY THEN is decoded, the rest is concealed), clears them and advances `play`.
 // A description that arrives after its partner but before its packet's turn is therefore merged on the GPU; one that arrives
-// after the packet was played is counted as late.  This is the staging only -- no play-out adaptation, no time stretching.
+// after the packet was played is counted as late.  This is the staging only -- no play-out adaptation, no time stretching: WHEN a
+// packet is played stays the caller's decision.  The facts for that decision -- how many packets of a stream are queued in a row, how
+// early its arrivals come, how many come late, and the list of the streams that are ready to play -- are the ring's read side:
+// solo_recv_report (solo_recv_report.h).
 #pragma once
 #include "solo_rc.h"
 
@@ -32,6 +35,11 @@ static_assert(sizeof(SxRecvArrival) == 20, "solo_arrival_t layout");
 #define SX_RECV_DUP 3           // its slot already holds an arrival (a second copy of the description)
 #define SX_RECV_BAD 4           // stream / description / length / payload range outside the handle's; desc = -1 without useMDIndex, or unreadable
 #define SX_RECV_NSTATS 8
+// per-stream counters (solo_recv_track; NULL = not tracked): the five verdicts above, what the played packets were made of (both
+// descriptions / MD1 only / MD2 || HB only / neither), and the smallest seq - play of an inserted arrival (depth = none yet)
+#define SX_RECV_TRK_WORDS 10
+#define SX_RECV_TRK_PLAYED 5
+#define SX_RECV_TRK_MARGIN 9
 
 SX_HD size_t sx_recv_entry(int stream, i32 seq, int depth) { return (size_t)stream * (size_t)depth + (size_t)((u32)seq % (u32)depth); }
 
