@@ -366,6 +366,16 @@ int32_t solo_batch_last_encode_chunks(const solo_batch_t *b);
 int32_t solo_debug_l0(int32_t op, int32_t n, const int32_t *d_a, const int32_t *d_b, const int32_t *d_c, int32_t *d_out);
 int32_t solo_debug_sum_sqr_shift(const int16_t *d_x, int32_t rows, int32_t len, int32_t stride, int32_t odd_start,
                                  int32_t *d_energy, int32_t *d_shift);
+/* solo_debug_waveops: the wave-level vocabulary of solo_amd/csrc/solo_wave.h in its 64-lane form (wv_sum, wv_max, wv_min, wv_row_sum,
+ * wv_col_sum, wv_sum64, wv_scan_incl, wv_argmin, wv_argmax, wv_bcast, SX_UNI, SX_RDLANE / SX_WRLANE, sx_lcg_first / sx_lcg_next) as the
+ * codec kernels get it.  d_v, d_aux: n_vec vectors of 64 words each (aux: the index operand of the arg functions, the high word of
+ * wv_sum64, the source lane of wv_bcast; its word 0 the LCG seed, the rotation and the trip count); one wavefront per vector,
+ * waves_per_block = 1 or 4 wavefronts per workgroup.  mode 0: every primitive on the raw input; mode 1: the primitives chained on each
+ * other's results, straight and in a loop of (aux[0] & 7) + 1 rounds.  d_out: int32 [n_vec][rows][64], every lane's own copy of
+ * every result; returns rows (27 / 18; also for n_vec == 0, which launches nothing) or a negative error.  The rows are listed in
+ * tests/wave_model.py, which defines what each must hold (tests/test_gpu_wave_ops.py). */
+int32_t solo_debug_waveops(int32_t mode, int32_t n_vec, int32_t waves_per_block, const int32_t *d_v, const int32_t *d_aux,
+                           int32_t *d_out);
 /* solo_debug_rowops: the lane exchanges of the quantiser kernel (solo_amd/csrc/solo_enc_nsq_row.h: bank-masked DPP row shifts, row
  * rotations, quad permutes) applied to 64 input words, 14 rows of 64 results (tests/test_gpu_nsq_row.py).
  * solo_debug_clock: the effective shader clock in MHz while every SIMD runs vector instructions (~1 ms): lets benchmark lines from

@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "solo_batch_n_streams", "solo_batch_slot_bytes", "solo_kernel_name", "solo_version", "solo_batch_set_timing",
     "solo_batch_last_kernel_ms", "solo_batch_last_encode_chunks", "solo_batch_decode_split", "solo_batch_set_async_join",
     "solo_batch_wait_encode", "solo_debug_l0", "solo_debug_sum_sqr_shift", "solo_debug_rowops", "solo_debug_clock", "solo_debug_nsq",
+    "solo_debug_waveops",
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
@@ -166,6 +167,8 @@ def load_library():
     lib.solo_batch_last_encode_chunks.argtypes = [C.c_void_p]
     lib.solo_debug_rowops.restype = C.c_int32
     lib.solo_debug_rowops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_debug_waveops.restype = C.c_int32
+    lib.solo_debug_waveops.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_debug_nsq.restype = C.c_int32
     lib.solo_debug_nsq.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     lib.solo_debug_clock.restype = C.c_int32

@@ -47,6 +47,94 @@ __global__ void __launch_bounds__(64) solo_sum_sqr_probe_kernel(const i16* x, in
     if (SX_LANE == 0) { energy[blockIdx.x] = e; shift[blockIdx.x] = s; }
 }
 
+// conformance probe of the lane-crossing vocabulary of solo_wave.h in its 64-lane form, as this translation unit's kernels get it
+// (solo_debug_waveops below): ONE wavefront per input vector of 64 words (v) and 64 second words (aux); a workgroup holds `wpb`
+// wavefronts (1, or 4: the geometry of the front kernel), each with a vector of its own.  One output row of 64 words per result,
+// EVERY lane stores its own copy: out[vector][row][lane].  No input reaches an address except the source lanes of wv_bcast and of
+// the lane-register round trip, masked to 0 .. 63 (0 .. 127 samples) here.  The row numbers are restated by tests/wave_model.py.
+#define SOLO_WAVEOPS_ROWS0 27
+#define SOLO_WAVEOPS_ROWS1 18
+// the chain of mode 1: every primitive consumes the result of the one before it, nothing else in between
+#define SOLO_WAVEOPS_CHAIN(v)                                                                     \
+    a = wv_sum(v);                                                                                \
+    b = wv_max(sx_add(v, a));                                                                     \
+    c = wv_min(v ^ b);                                                                            \
+    d = wv_sum(sx_add(c, v));                                                                     \
+    e = wv_scan_incl(sx_add(v, d));                                                               \
+    f = e ^ v; g = lane; wv_argmin(&f, &g);                                                       \
+    h = wv_sum64((i64)sx_mul(v, g));
+__global__ void __launch_bounds__(256) solo_waveops_probe_kernel(int mode, int n_vec, int wpb, const i32* vin, const i32* auxin, i32* out) {
+#if defined(__HIP_DEVICE_COMPILE__)                         // (the host pass has the 1-lane vocabulary: no lane registers, no column sum)
+    const int vec = (int)blockIdx.x * wpb + (int)(threadIdx.x >> 6);
+    if (vec >= n_vec) return;                               // (whole wavefronts leave: every lane of a working wave stays active)
+    const int lane = SX_LANE;
+    const i32 v = vin[(size_t)vec * 64 + lane], aux = auxin[(size_t)vec * 64 + lane];
+    const i32 aux0 = auxin[(size_t)vec * 64];               // lane 0's second word: source lane, rotation, seed, trip count
+    i32* o = out + (size_t)vec * (mode == 0 ? SOLO_WAVEOPS_ROWS0 : SOLO_WAVEOPS_ROWS1) * 64 + lane;
+#define ROW(r, x) o[(r) * 64] = (i32)(x)
+    if (mode == 0) {
+        ROW(0, wv_sum(v));
+        ROW(1, wv_max(v));
+        ROW(2, wv_min(v));
+        ROW(3, wv_row_sum(v));
+        ROW(4, wv_col_sum(v));
+        const i64 s64 = wv_sum64((i64)(((u64)(u32)aux << 32) | (u32)v));
+        ROW(5, (u32)s64);
+        ROW(6, (u32)((u64)s64 >> 32));
+        ROW(7, wv_scan_incl(v));
+        i32 bv, bi;
+        bv = v; bi = lane; wv_argmin(&bv, &bi); ROW(8, bv); ROW(9, bi);
+        bv = v; bi = aux; wv_argmin(&bv, &bi); ROW(10, bv); ROW(11, bi);
+        bv = v; bi = lane; wv_argmax(&bv, &bi); ROW(12, bv); ROW(13, bi);
+        bv = v; bi = aux; wv_argmax(&bv, &bi); ROW(14, bv); ROW(15, bi);
+        ROW(16, wv_bcast(v, aux0 & 63));
+        ROW(17, wv_bcast(v, aux & 63));
+        ROW(18, SX_UNI(wv_max(v)));
+        {   // 128 samples in two lane registers (sample i: lane i & 63 of register i >> 6), deposited one by one, then fetched one by
+            // one rotated by aux0 & 63 samples and deposited again
+            const i32 rot = SX_UNI(aux0 & 63), key = SX_UNI(aux0);
+            i32 w0 = 0, w1 = 0, r0 = 0, r1 = 0;
+            for (int i = 0; i < 64; i++) {
+                SX_WRLANE(w0, i, sx_mul(i + 1, (i32)0x9E3779B1u) ^ key);
+                SX_WRLANE(w1, i, sx_mul(i + 65, (i32)0x9E3779B1u) ^ key);
+            }
+            for (int i = 0; i < 64; i++) {
+                const int j0 = (i + rot) & 127, j1 = (i + 64 + rot) & 127;
+                const i32 s0 = j0 < 64 ? SX_RDLANE(w0, j0 & 63) : SX_RDLANE(w1, j0 & 63);
+                const i32 s1 = j1 < 64 ? SX_RDLANE(w0, j1 & 63) : SX_RDLANE(w1, j1 & 63);
+                SX_WRLANE(r0, i, s0);
+                SX_WRLANE(r1, i, s1);
+            }
+            ROW(19, r0);
+            ROW(20, r1);
+        }
+        i32 z = sx_lcg_first(aux0);
+        ROW(21, z);
+        z = sx_lcg_next(z); ROW(22, z);
+        z = sx_lcg_next(z); ROW(23, z);
+        z = sx_lcg_next(z); ROW(24, z);
+        // value, then index among the lanes that hold it (the selection rounds of solo_enc_analysis.h)
+        const i32 vmin = wv_min(v);
+        ROW(25, vmin);
+        ROW(26, wv_min(v == vmin ? lane : SX_I32_MAX));
+    } else {
+        i32 a, b, c, d, e, f, g;
+        i64 h;
+        SOLO_WAVEOPS_CHAIN(v)
+        ROW(0, a); ROW(1, b); ROW(2, c); ROW(3, d); ROW(4, e); ROW(5, f); ROW(6, g); ROW(7, (u32)h); ROW(8, (u32)((u64)h >> 32));
+        // the same in a loop whose trip count only the input knows, every result fed back into the next round's vector
+        const int trips = (aux0 & 7) + 1;
+        i32 x = v;
+        for (int t = 0; t < trips; t++) {
+            if (t) x = sx_add(sx_add(x, a), sx_add(f, sx_add(g, (i32)(u32)h)));
+            SOLO_WAVEOPS_CHAIN(x)
+        }
+        ROW(9, a); ROW(10, b); ROW(11, c); ROW(12, d); ROW(13, e); ROW(14, f); ROW(15, g); ROW(16, (u32)h); ROW(17, (u32)((u64)h >> 32));
+    }
+#undef ROW
+#endif
+}
+
 // Subset calls: is the caller's device list strictly increasing inside [0, n_streams)?  One workgroup; the verdict word (0 = accepted)
 // is the handle's (solo_batch::d_verdict), every kernel of the call reads it before it does anything (solo_stream_ctl.h).  A refused
 // list also writes -1 to every status word of the call.
@@ -1245,6 +1333,21 @@ int32_t solo_debug_sum_sqr_shift(const int16_t* d_x, int32_t rows, int32_t len, 
     SOLO_CHECK(hipGetLastError());
     SOLO_CHECK(hipDeviceSynchronize());
     return 0;
+}
+
+// The lane-crossing vocabulary of solo_wave.h (solo_waveops_probe_kernel above): n_vec vectors of 64 words in d_v and in d_aux, one
+// wavefront each, waves_per_block (1 or 4) of them per workgroup; d_out = int32 [n_vec][rows][64].  Returns `rows` of the mode (also
+// for n_vec == 0, which launches nothing: how a caller sizes d_out).
+int32_t solo_debug_waveops(int32_t mode, int32_t n_vec, int32_t waves_per_block, const int32_t* d_v, const int32_t* d_aux, int32_t* d_out) {
+    if ((mode != 0 && mode != 1) || n_vec < 0 || (waves_per_block != 1 && waves_per_block != 4)) return -1;
+    const int32_t rows = mode == 0 ? SOLO_WAVEOPS_ROWS0 : SOLO_WAVEOPS_ROWS1;
+    if (n_vec == 0) return rows;
+    if (!d_v || !d_aux || !d_out) return -1;
+    hipLaunchKernelGGL(solo_waveops_probe_kernel, dim3((n_vec + waves_per_block - 1) / waves_per_block), dim3(64 * waves_per_block), 0, (hipStream_t)0,
+                       mode, n_vec, waves_per_block, d_v, d_aux, d_out);
+    SOLO_CHECK(hipGetLastError());
+    SOLO_CHECK(hipDeviceSynchronize());
+    return rows;
 }
 
 #ifdef SOLO_WITH_ENCODER

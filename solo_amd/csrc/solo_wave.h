@@ -12,7 +12,10 @@
 // barrier + LDS/global fence (hipcc drops the s_barrier for single-wave groups).
 //
 // Host build (SOLO_HOST_EMU): SX_NLANES == 1, the same source runs serially -- used only by the
-// CPU-side tests to check the kernel source against the reference without a GPU.
+// CPU-side tests to check the kernel source against the reference without a GPU.  In that build every lane-crossing function of this
+// file (wv_sum / wv_max / wv_min / wv_row_sum / wv_sum64 / wv_scan_incl / wv_argmin / wv_argmax / wv_bcast, SX_UNI, sx_lcg_first /
+// sx_lcg_next) is the identity or a 1-lane special case, so the host emulation CANNOT test them: their 64-lane forms are checked
+// on the GPU, lane by lane against plain integer definitions, by tests/test_gpu_wave_ops.py (probe: solo_debug_waveops, solo_api.hip).
 #pragma once
 #include "solo_fix.h"
 
