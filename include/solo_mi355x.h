@@ -385,6 +385,24 @@ int32_t solo_debug_rowops(const int32_t *d_in, const int32_t *d_idx, int32_t *d_
  * SKP_Silk_NSQ_del_dec calls (SKP_Silk_NSQ_del_dec.c:925) as hand-over records [n_streams][n_packets][2] of 660 bytes (16 kHz API rate),
  * h_out: the kernel's output records {int32 Seed; int32 r[160]; int8 q[2][164]}; HOST pointers; returns the output record size. */
 int32_t solo_debug_nsq(int32_t n_streams, int32_t n_packets, const void *h_in, void *h_out);
+/* Stage probes of the encoder (tests/test_enc_stages.py): ONE stage of the launch-per-chunk pipeline alone, through the launch table of the
+ * rate's build (samplerate 16000 / 32000), on streams freshly initialised with (silk_rate_bps, useMDIndex, joint, dtx, frames_per_packet); HOST
+ * pointers, default stream, synchronous.  `chunk` > 0 walks the n_packets in launches of `chunk` packets, 0 is one launch.
+ * solo_debug_nsq_ex: solo_debug_nsq with the rate and the init arguments (solo_debug_nsq = 16000, 12000, 0, 0, 0, 2).
+ * solo_debug_analysis: h_pcm int16 [n_streams][n_packets][packet samples] -> h_nsq_in SxNsqIn[n_streams][n_packets][2], h_code_in
+ *   SxCodeIn[n_streams][n_packets] (solo_amd/csrc/solo_enc_state.h, solo_enc.h); returns the SxNsqIn record size.  h_sizes (may be NULL):
+ *   {SxNsqIn, SxNsqOut, SxCodeIn bytes, samples of a 40 ms packet, streams per front workgroup}; n_streams == 0 launches
+ *   nothing and only fills it.
+ * solo_debug_coding: h_code_in SxCodeIn[n_streams][n_packets], h_nsq_out SxNsqOut[n_streams][n_packets][2] -> h_bits
+ *   [n_streams][n_packets][slot_bytes], h_nbytes int16 [n_streams][n_packets][2], h_status int32 [n_streams]; returns the SxCodeIn record size. */
+int32_t solo_debug_nsq_ex(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
+                          int32_t n_streams, int32_t n_packets, const void *h_in, void *h_out);
+int32_t solo_debug_analysis(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
+                            int32_t n_streams, int32_t n_packets, int32_t chunk, const int16_t *h_pcm, void *h_nsq_in, void *h_code_in,
+                            int32_t *h_sizes);
+int32_t solo_debug_coding(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
+                          int32_t n_streams, int32_t n_packets, int32_t chunk, int32_t slot_bytes, const void *h_code_in, const void *h_nsq_out,
+                          uint8_t *h_bits, int16_t *h_nbytes, int32_t *h_status);
 int32_t solo_debug_clock(double *mhz_out);
 /* Library version string. */
 const char *solo_version(void);

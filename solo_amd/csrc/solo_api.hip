@@ -1351,21 +1351,98 @@ int32_t solo_debug_waveops(int32_t mode, int32_t n_vec, int32_t waves_per_block,
 }
 
 #ifdef SOLO_WITH_ENCODER
-// The quantiser kernel ALONE (tests/test_nsq_taps.py): h_in = SxNsqIn[n_streams][n_packets][2] as recorded from the reference's
-// SKP_Silk_NSQ_del_dec calls, h_out = SxNsqOut[n_streams][n_packets][2]; host pointers; freshly initialised streams; synchronous.
-int32_t solo_debug_nsq(int32_t n_streams, int32_t n_packets, const void* h_in, void* h_out) {
-    if (n_streams <= 0 || n_packets <= 0 || !h_in || !h_out) return -1;
-    const solo_enc_ops* ops = solo_nb_enc_ops();
+// Stage probes of the encoder (tests/test_nsq_taps.py, tests/test_enc_stages.py): each runs ONE of the three stages of the launch-per-chunk schedule
+// alone, through the launch table of the rate's build, on freshly initialised streams; HOST pointers; default stream; synchronous.  `samplerate`
+// 16000 / 32000 picks the table; silk_rate_bps, useMDIndex, joint, dtx, frames_per_packet are the arguments of its `init`.
+static const solo_enc_ops* debug_enc_ops(int32_t samplerate) { return samplerate == 16000 ? solo_nb_enc_ops() : (samplerate == 32000 ? solo_wb_enc_ops() : NULL); }
+static bool debug_enc_args(const solo_enc_ops* ops, int32_t fpp, int32_t n_streams, int32_t n_packets) {
+    return ops && (fpp == 1 || fpp == 2) && n_streams > 0 && n_packets > 0 && (long long)n_streams * n_packets <= (1 << 20);
+}
+// The quantiser kernel ALONE: h_in = SxNsqIn[n_streams][n_packets][2] as recorded from the reference's SKP_Silk_NSQ_del_dec calls (or as the
+// analysis probe left them), h_out = SxNsqOut[n_streams][n_packets][2].  Returns the output record size.
+int32_t solo_debug_nsq_ex(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
+                          int32_t n_streams, int32_t n_packets, const void* h_in, void* h_out) {
+    const solo_enc_ops* ops = debug_enc_ops(samplerate);
+    if (!debug_enc_args(ops, frames_per_packet, n_streams, n_packets) || !h_in || !h_out) return -1;
     const size_t sz_in = (size_t)n_streams * n_packets * 2 * ops->nsq_in_bytes, sz_out = (size_t)n_streams * n_packets * 2 * ops->nsq_out_bytes;
     void *st = NULL, *d_in = NULL, *d_out = NULL, *ring = NULL;
     int32_t rc = -1;
     if (hipMalloc(&st, ops->state_bytes * (size_t)n_streams) == hipSuccess && hipMalloc(&d_in, sz_in) == hipSuccess && hipMalloc(&d_out, sz_out) == hipSuccess &&
         hipMalloc(&ring, ops->nsq_ring_bytes(n_streams)) == hipSuccess && hipMemset(d_out, 0, sz_out) == hipSuccess &&
-        ops->init(st, n_streams, 12000, 0, 0, 0, 2, (hipStream_t)0) == hipSuccess && hipMemcpy(d_in, h_in, sz_in, hipMemcpyHostToDevice) == hipSuccess &&
+        ops->init(st, n_streams, silk_rate_bps, useMDIndex, joint, dtx, frames_per_packet, (hipStream_t)0) == hipSuccess &&
+        hipMemcpy(d_in, h_in, sz_in, hipMemcpyHostToDevice) == hipSuccess &&
         ops->nsq(st, d_in, d_out, n_streams, n_packets, 0, n_packets, NULL, ring, NULL, NULL, NULL) == 0 && hipDeviceSynchronize() == hipSuccess &&
         hipMemcpy(h_out, d_out, sz_out, hipMemcpyDeviceToHost) == hipSuccess)
         rc = (int32_t)ops->nsq_out_bytes;                       // (the caller checks its idea of the record size)
     (void)hipFree(st); (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(ring);
+    return rc;
+}
+int32_t solo_debug_nsq(int32_t n_streams, int32_t n_packets, const void* h_in, void* h_out) {
+    return solo_debug_nsq_ex(16000, 12000, 0, 0, 0, 2, n_streams, n_packets, h_in, h_out);
+}
+// The analysis kernel ALONE: h_pcm = int16 [n_streams][n_packets][packet samples] -> h_nsq_in = SxNsqIn[n_streams][n_packets][2], h_code_in =
+// SxCodeIn[n_streams][n_packets], by ops->analysis with the pipeline's p0 / pc addressing: chunk > 0 walks the packets in launches of `chunk`
+// packets (the compact state goes through the stream record between two launches), 0 is one launch.  h_sizes (may be NULL) receives
+// {nsq_in_bytes, nsq_out_bytes, code_in_bytes, samples of a 40 ms packet, front_waves} of the table; n_streams == 0 launches nothing
+// and only fills it.  Returns the size of an SxNsqIn record.
+int32_t solo_debug_analysis(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
+                            int32_t n_streams, int32_t n_packets, int32_t chunk, const int16_t* h_pcm, void* h_nsq_in, void* h_code_in, int32_t* h_sizes) {
+    const solo_enc_ops* ops = debug_enc_ops(samplerate);
+    if (!ops) return -1;
+    if (h_sizes) {
+        h_sizes[0] = (int32_t)ops->nsq_in_bytes; h_sizes[1] = (int32_t)ops->nsq_out_bytes; h_sizes[2] = (int32_t)ops->code_in_bytes;
+        h_sizes[3] = ops->packet_samples; h_sizes[4] = ops->front_waves;
+    }
+    if (n_streams == 0) return (int32_t)ops->nsq_in_bytes;
+    if (!debug_enc_args(ops, frames_per_packet, n_streams, n_packets) || chunk < 0 || !h_pcm || !h_nsq_in || !h_code_in) return -1;
+    const size_t np = (size_t)n_streams * n_packets;
+    const size_t sz_pcm = np * (size_t)(ops->packet_samples / 2 * frames_per_packet) * 2, sz_in = np * 2 * ops->nsq_in_bytes, sz_code = np * ops->code_in_bytes;
+    void *st = NULL, *d_pcm = NULL, *d_in = NULL, *d_code = NULL;
+    int32_t rc = -1;
+    const int cp = chunk > 0 ? chunk : n_packets;
+    bool ok = hipMalloc(&st, ops->state_bytes * (size_t)n_streams) == hipSuccess && hipMalloc(&d_pcm, sz_pcm) == hipSuccess && hipMalloc(&d_in, sz_in) == hipSuccess &&
+              hipMalloc(&d_code, sz_code) == hipSuccess && hipMemset(d_in, 0, sz_in) == hipSuccess && hipMemset(d_code, 0, sz_code) == hipSuccess &&
+              ops->init(st, n_streams, silk_rate_bps, useMDIndex, joint, dtx, frames_per_packet, (hipStream_t)0) == hipSuccess &&
+              hipMemcpy(d_pcm, h_pcm, sz_pcm, hipMemcpyHostToDevice) == hipSuccess;
+    for (int p0 = 0; ok && p0 < n_packets; p0 += cp)
+        ok = ops->analysis(st, (const int16_t*)d_pcm, n_streams, n_packets, p0, p0 + cp <= n_packets ? cp : n_packets - p0, d_in, d_code, NULL, NULL, (hipStream_t)0) == hipSuccess;
+    if (ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h_nsq_in, d_in, sz_in, hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(h_code_in, d_code, sz_code, hipMemcpyDeviceToHost) == hipSuccess)
+        rc = (int32_t)ops->nsq_in_bytes;
+    (void)hipFree(st); (void)hipFree(d_pcm); (void)hipFree(d_in); (void)hipFree(d_code);
+    return rc;
+}
+// The coding stage ALONE (high band, range coder, payload assembly): h_code_in = SxCodeIn[n_streams][n_packets], h_nsq_out =
+// SxNsqOut[n_streams][n_packets][2] -> h_bits [n_streams][n_packets][slot_bytes], h_nbytes int16 [n_streams][n_packets][2], h_status int32
+// [n_streams], by ops->coding on a scratch of ops->rc_scratch_bytes, in launches of `chunk` packets (0: one).  Of the stream record the stage
+// reads what `init` sets (useMDIndex, useDTX, hb_joint, fpp) and owns the high-band history, which it alone writes: nothing that the analysis
+// stage leaves per packet, so freshly initialised streams are all it needs.  Returns the size of an SxCodeIn record.
+int32_t solo_debug_coding(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
+                          int32_t n_streams, int32_t n_packets, int32_t chunk, int32_t slot_bytes, const void* h_code_in, const void* h_nsq_out,
+                          uint8_t* h_bits, int16_t* h_nbytes, int32_t* h_status) {
+    const solo_enc_ops* ops = debug_enc_ops(samplerate);
+    if (!debug_enc_args(ops, frames_per_packet, n_streams, n_packets) || chunk < 0 || slot_bytes <= 0 || slot_bytes > 4096 || !h_code_in || !h_nsq_out || !h_bits ||
+        !h_nbytes || !h_status)
+        return -1;
+    const size_t np = (size_t)n_streams * n_packets;
+    const size_t sz_code = np * ops->code_in_bytes, sz_out = np * 2 * ops->nsq_out_bytes, sz_bits = np * (size_t)slot_bytes, sz_nb = np * 2 * sizeof(int16_t),
+                 sz_st = (size_t)n_streams * sizeof(int32_t);
+    const int cp = chunk > 0 && chunk < n_packets ? chunk : n_packets;
+    void *st = NULL, *d_code = NULL, *d_out = NULL, *d_bits = NULL, *d_nb = NULL, *d_status = NULL, *scratch = NULL;
+    int32_t rc = -1;
+    bool ok = hipMalloc(&st, ops->state_bytes * (size_t)n_streams) == hipSuccess && hipMalloc(&d_code, sz_code) == hipSuccess && hipMalloc(&d_out, sz_out) == hipSuccess &&
+              hipMalloc(&d_bits, sz_bits) == hipSuccess && hipMalloc(&d_nb, sz_nb) == hipSuccess && hipMalloc(&d_status, sz_st) == hipSuccess &&
+              hipMalloc(&scratch, ops->rc_scratch_bytes(n_streams, cp)) == hipSuccess && hipMemset(d_bits, 0, sz_bits) == hipSuccess &&
+              hipMemset(d_nb, 0xFF, sz_nb) == hipSuccess && hipMemset(d_status, 0xFF, sz_st) == hipSuccess &&
+              ops->init(st, n_streams, silk_rate_bps, useMDIndex, joint, dtx, frames_per_packet, (hipStream_t)0) == hipSuccess &&
+              hipMemcpy(d_code, h_code_in, sz_code, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_out, h_nsq_out, sz_out, hipMemcpyHostToDevice) == hipSuccess;
+    for (int p0 = 0; ok && p0 < n_packets; p0 += cp)
+        ok = ops->coding(st, d_code, d_out, n_streams, n_packets, p0, p0 + cp <= n_packets ? cp : n_packets - p0, slot_bytes, (uint8_t*)d_bits, (int16_t*)d_nb,
+                         (int32_t*)d_status, scratch, NULL, NULL, (hipStream_t)0) == hipSuccess;
+    if (ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(h_bits, d_bits, sz_bits, hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(h_nbytes, d_nb, sz_nb, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(h_status, d_status, sz_st, hipMemcpyDeviceToHost) == hipSuccess)
+        rc = (int32_t)ops->code_in_bytes;
+    (void)hipFree(st); (void)hipFree(d_code); (void)hipFree(d_out); (void)hipFree(d_bits); (void)hipFree(d_nb); (void)hipFree(d_status); (void)hipFree(scratch);
     return rc;
 }
 #endif

@@ -533,7 +533,8 @@ SX_FNW void sx_enc_analyse_frame(SxEncStream* rec, SxEncWork* w, const i16* pIn,
             sx_pub_st(&in->pitchL[i], c->pitchL[i]); sx_pub_st(&in->Gains_Q16[i], c->Gains_Q16[i]); sx_pub_st(&in->LF_shp_Q14[i], c->LF_shp_Q14[i]);
             sx_pub_st(&in->Tilt_Q14[i], c->Tilt_Q14[i]); sx_pub_st(&in->HarmShapeGain_Q14[i], c->HarmShapeGain_Q14[i]);
         }
-        SX_PAR(i, 2 * SX_MAX_LPC) sx_pub_st(&(&in->PredCoef_Q12[0][0])[i], (&c->PredCoef_Q12[0][0])[i]);
+        // (the entries beyond the LPC order are never assigned in the control block, which is not kept across launches: zero in the record)
+        SX_PAR(i, 2 * SX_MAX_LPC) sx_pub_st(&(&in->PredCoef_Q12[0][0])[i], (i & (SX_MAX_LPC - 1)) < SX_LPC ? (&c->PredCoef_Q12[0][0])[i] : (i16)0);
         SX_PAR(i, SX_LTP_ORDER * SX_NB_SUBFR) sx_pub_st(&in->LTPCoef_Q14[i], c->LTPCoef_Q14[i]);
         SX_PAR(i, SX_NB_SUBFR * SX_SHAPE_ORDER) sx_pub_st(&in->AR2_Q13[i], c->AR2_Q13[i]);
         SX_PAR(i, SX_FRAME) sx_pub_st(&in->xfw[i], w->xfw[i]);

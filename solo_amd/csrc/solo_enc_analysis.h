@@ -2430,6 +2430,11 @@ SX_FN1 void sx_find_pred_coefs(SxEncState* st, SxEncCtrl* c, const i16* x_buf, i
         wv_sync();
         for (int i = 0; i < 20; i++) c->LTPCoef_Q14[i] = 0;
         c->LTPredCodGain_Q7 = 0;
+        // The reference assigns the long-term indices and the LTP scale in the voiced branch alone and hands on what its stack held
+        // (SKP_Silk_find_pred_coefs_FIX.c:93-109).  The control block lives in LDS and is not kept across launches: zeroed, so that the
+        // hand-over records (SxNsqIn::LTP_scale_Q14, SxFrameIdx) are a function of the input and not of how a call is cut into launches
+        c->PERIndex = 0; c->LTP_scaleIndex = 0; c->LTP_scale_Q14 = 0;
+        for (int i = 0; i < SX_NB_SUBFR; i++) c->LTPIndex[i] = 0;
     }
     SX_T(16)
     sx_find_LPC(NLSF_Q15, &c->NLSFInterpCoef_Q2, st->prev_NLSFq_Q15, 1 - st->first_frame_after_reset, SX_LPC, w->LPC_in_pre,

@@ -109,6 +109,40 @@ int emu_nsq_frames(const void* in, int n, void* out) {
     emu_enc_destroy(e);
     return (int)sizeof(SxNsqOut);
 }
+// the analysis stage alone (tests/test_enc_stages.py): n_packets of ONE freshly initialised stream (arguments as emu_enc_create's) through
+// sx_enc_stage_a -> in2 = SxNsqIn[n_packets][2], cin = SxCodeIn[n_packets].  chunk > 0: the compact state goes back to the stream record and
+// is loaded again every `chunk` packets, as between two launches of solo_enc_analysis_kernel
+int emu_analysis_packets(int rate_bps, int useMDIndex, const int16_t* pcm, int n_packets, int chunk, void* in2, void* cin) {
+    EmuEnc* e = (EmuEnc*)emu_enc_create(rate_bps, useMDIndex);
+    const int cp = chunk > 0 ? chunk : n_packets;
+    for (int p0 = 0; p0 < n_packets; p0 += cp) {
+        e->w.st = e->rec.core;
+        for (int p = p0; p < p0 + cp && p < n_packets; p++)
+            sx_enc_stage_a(&e->rec, &e->w, pcm + (size_t)p * (SX_FRAME * 2 * e->w.st.fpp), (SxNsqIn*)in2 + 2 * p, (SxCodeIn*)cin + p);
+        e->rec.core = e->w.st;
+    }
+    emu_enc_destroy(e);
+    return (int)sizeof(SxNsqIn);
+}
+// the coding stage alone: cin = SxCodeIn[n_packets], out2 = SxNsqOut[n_packets][2] -> bits[n_packets][slot_bytes], nbytes[n_packets][2]; returns the
+// first negative status (0: none).  Like solo_enc_coding_kernel / solo_enc_rc_kernel it loads the compact state at the start of every chunk and
+// never writes it back: of the stream record the stage owns the high-band history only
+int emu_coding_packets(int rate_bps, int useMDIndex, const void* cin, const void* out2, int n_packets, int chunk, int slot_bytes, uint8_t* bits, int16_t* nbytes) {
+    EmuEnc* e = (EmuEnc*)emu_enc_create(rate_bps, useMDIndex);
+    const int cp = chunk > 0 ? chunk : n_packets;
+    int status = 0;
+    for (int p0 = 0; p0 < n_packets; p0 += cp) {
+        e->w.st = e->rec.core;
+        for (int p = p0; p < p0 + cp && p < n_packets; p++) {
+            const int r = sx_enc_stage_c(&e->rec, &e->w, (const SxCodeIn*)cin + p, (const SxNsqOut*)out2 + 2 * p, bits + (size_t)p * slot_bytes, slot_bytes, nbytes + 2 * p);
+            if (r < 0 && status == 0) status = r;
+        }
+    }
+    emu_enc_destroy(e);
+    return status;
+}
+int emu_sizeof_code_in() { return (int)sizeof(SxCodeIn); }
+int emu_sizeof_nsq_out() { return (int)sizeof(SxNsqOut); }
 // the pulse coder alone (tests/test_pulse_coder.py): one frame of pulses through a fresh range coder -> its bytes (SKP_Silk_encode_pulses.c:55)
 int emu_encode_pulses(int sigtype, int QuantOffsetType, const int8_t* q, uint8_t* out, int* error) {
     static SxCdf cdf;
