@@ -403,6 +403,24 @@ int32_t solo_debug_analysis(int32_t samplerate, int32_t silk_rate_bps, int32_t u
 int32_t solo_debug_coding(int32_t samplerate, int32_t silk_rate_bps, int32_t useMDIndex, int32_t joint, int32_t dtx, int32_t frames_per_packet,
                           int32_t n_streams, int32_t n_packets, int32_t chunk, int32_t slot_bytes, const void *h_code_in, const void *h_nsq_out,
                           uint8_t *h_bits, int16_t *h_nbytes, int32_t *h_status);
+/* Stage probes of the decoder (tests/test_dec_stages.py): ONE of the two kernels of the batch path alone, through the launch table of the rate's
+ * build (samplerate 16000 / 32000), on streams freshly initialised with (useMDIndex, joint, frames_per_packet); HOST pointers, default stream,
+ * synchronous.  h_bits [n_streams][n_packets][slot_bytes], h_nbytes int16 [n_streams][n_packets][2], h_recv uint8 [n_streams][n_packets] (NULL:
+ * everything arrived) as solo_batch_decode takes them; `chunk` > 0 walks the packets in launches of `chunk` packets, 0 is one launch.
+ * solo_debug_dec_extract: the extraction step alone -> h_recs SxExtracted[n_streams][n_packets][2] (solo_amd/csrc/solo_dec.h; a record that is
+ *   not usable says why in pad_[0]: 1 length, 2 sampling-rate symbol, 3 coder error, 4 pulses too large for the lane's storage, 5 symbols that
+ *   depend on the bytes behind the description), h_counts (may be NULL) int32 [launches]: the description slots that carry bytes as the list
+ *   kernel counted them (-1 without h_recv).  Returns the SxExtracted record size; n_streams == 0 launches nothing and only returns it.
+ * solo_debug_dec_synth: the decoder proper alone, from h_recs (the extract probe's records or the caller's own), or with h_recs == NULL the
+ *   single kernel that reads the symbols itself.  After every launch: h_pcm int16 [n_streams][n_packets][packet samples], h_status int32
+ *   [launches][n_streams], h_state [launches][n_streams][state_bytes] = the head of every stream record, its SxDecState (NULL with
+ *   state_bytes 0: not wanted).  Returns the SxExtracted record size. */
+int32_t solo_debug_dec_extract(int32_t samplerate, int32_t useMDIndex, int32_t joint, int32_t frames_per_packet, int32_t n_streams,
+                               int32_t n_packets, int32_t chunk, int32_t slot_bytes, const uint8_t *h_bits, const int16_t *h_nbytes,
+                               const uint8_t *h_recv, void *h_recs, int32_t *h_counts);
+int32_t solo_debug_dec_synth(int32_t samplerate, int32_t useMDIndex, int32_t joint, int32_t frames_per_packet, int32_t n_streams,
+                             int32_t n_packets, int32_t chunk, int32_t slot_bytes, const uint8_t *h_bits, const int16_t *h_nbytes,
+                             const uint8_t *h_recv, const void *h_recs, int16_t *h_pcm, int32_t *h_status, void *h_state, int32_t state_bytes);
 int32_t solo_debug_clock(double *mhz_out);
 /* Library version string. */
 const char *solo_version(void);

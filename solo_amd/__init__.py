@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "solo_batch_n_streams", "solo_batch_slot_bytes", "solo_kernel_name", "solo_version", "solo_batch_set_timing",
     "solo_batch_last_kernel_ms", "solo_batch_last_encode_chunks", "solo_batch_decode_split", "solo_batch_set_async_join",
     "solo_batch_wait_encode", "solo_debug_l0", "solo_debug_sum_sqr_shift", "solo_debug_rowops", "solo_debug_clock", "solo_debug_nsq",
-    "solo_debug_waveops", "solo_debug_nsq_ex", "solo_debug_analysis", "solo_debug_coding",
+    "solo_debug_waveops", "solo_debug_nsq_ex", "solo_debug_analysis", "solo_debug_coding", "solo_debug_dec_extract", "solo_debug_dec_synth",
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
@@ -178,6 +178,10 @@ def load_library():
     lib.solo_debug_analysis.argtypes = [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_debug_coding.restype = C.c_int32
     lib.solo_debug_coding.argtypes = [C.c_int32] * 10 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_debug_dec_extract.restype = C.c_int32
+    lib.solo_debug_dec_extract.argtypes = [C.c_int32] * 8 + [C.c_void_p] * 5
+    lib.solo_debug_dec_synth.restype = C.c_int32
+    lib.solo_debug_dec_synth.argtypes = [C.c_int32] * 8 + [C.c_void_p] * 7 + [C.c_int32]
     lib.solo_debug_clock.restype = C.c_int32
     lib.solo_debug_clock.argtypes = [C.c_void_p]
     lib.solo_kernel_name.restype = C.c_char_p

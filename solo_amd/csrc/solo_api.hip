@@ -1350,6 +1350,118 @@ int32_t solo_debug_waveops(int32_t mode, int32_t n_vec, int32_t waves_per_block,
     return rows;
 }
 
+// Stage probes of the decoder (tests/test_dec_stages.py): ONE of the two kernels of the batch path alone, through the launch table of the rate's
+// build (samplerate 16000 / 32000), on streams freshly initialised with (useMDIndex, joint, frames_per_packet); HOST pointers, default stream,
+// synchronous.  h_bits [n_streams][n_packets][slot_bytes], h_nbytes int16 [n_streams][n_packets][2], h_recv uint8 [n_streams][n_packets] (may be
+// NULL: both descriptions of every packet arrived) as solo_batch_decode takes them; `chunk` > 0 walks the packets in launches of `chunk`
+// packets with the pipeline's p0 / pc addressing, 0 is one launch.
+static const solo_dec_ops* debug_dec_ops(int32_t samplerate) { return samplerate == 16000 ? solo_nb_dec_ops() : (samplerate == 32000 ? solo_wb_dec_ops() : NULL); }
+static bool debug_dec_args(const solo_dec_ops* ops, int32_t fpp, int32_t n_streams, int32_t n_packets, int32_t chunk, int32_t slot_bytes) {
+    return ops && (fpp == 1 || fpp == 2) && n_streams > 0 && n_packets > 0 && (long long)n_streams * n_packets <= (1 << 16) && chunk >= 0 && slot_bytes > 0 &&
+           slot_bytes <= 4096;
+}
+// The extraction step ALONE (ops->extract: the list kernel, when h_recv is given, and solo_dec_extract_kernel): h_recs =
+// SxExtracted[n_streams][n_packets][2], every record of a launch zeroed before it; h_counts (may be NULL) int32 [launches]: the number of
+// description slots that carry bytes as the list kernel counted them (-1 without h_recv: no list).  Returns the size of an SxExtracted record;
+// n_streams == 0 launches nothing and only returns it.
+int32_t solo_debug_dec_extract(int32_t samplerate, int32_t useMDIndex, int32_t joint, int32_t frames_per_packet, int32_t n_streams, int32_t n_packets,
+                               int32_t chunk, int32_t slot_bytes, const uint8_t* h_bits, const int16_t* h_nbytes, const uint8_t* h_recv, void* h_recs,
+                               int32_t* h_counts) {
+    const solo_dec_ops* ops = debug_dec_ops(samplerate);
+    if (!ops) return -1;
+    const size_t rec = (ops->extracted_bytes - 2 * sizeof(uint32_t)) / 2;
+    if (n_streams == 0) return (int32_t)rec;
+    if (!debug_dec_args(ops, frames_per_packet, n_streams, n_packets, chunk, slot_bytes) || !h_bits || !h_nbytes || !h_recs) return -1;
+    const size_t np = (size_t)n_streams * n_packets, sz_bits = np * (size_t)slot_bytes, sz_nb = np * 2 * sizeof(int16_t);
+    const int cp = chunk > 0 && chunk < n_packets ? chunk : n_packets;
+    const size_t lanes = (size_t)n_streams * cp * 2, sz_recs = (size_t)n_streams * cp * ops->extracted_bytes + 256;
+    void *st = NULL, *d_bits = NULL, *d_nb = NULL, *d_recv = NULL, *d_recs = NULL;
+    int32_t rc = -1;
+    bool ok = hipMalloc(&st, ops->state_bytes * (size_t)n_streams) == hipSuccess && hipMalloc(&d_bits, sz_bits) == hipSuccess && hipMalloc(&d_nb, sz_nb) == hipSuccess &&
+              hipMalloc(&d_recs, sz_recs) == hipSuccess && (!h_recv || hipMalloc(&d_recv, np) == hipSuccess) &&
+              ops->init(st, n_streams, (joint ? 1 : 0) | (frames_per_packet == 1 ? 2 : 0), useMDIndex, (hipStream_t)0) == hipSuccess &&
+              hipMemcpy(d_bits, h_bits, sz_bits, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_nb, h_nbytes, sz_nb, hipMemcpyHostToDevice) == hipSuccess &&
+              (!h_recv || hipMemcpy(d_recv, h_recv, np, hipMemcpyHostToDevice) == hipSuccess);
+    int launch = 0;
+    for (int p0 = 0; ok && p0 < n_packets; p0 += cp, launch++) {
+        const int pc = p0 + cp <= n_packets ? cp : n_packets - p0;
+        ok = hipMemset(d_recs, 0, sz_recs) == hipSuccess &&
+             ops->extract(st, (const uint8_t*)d_bits, (const int16_t*)d_nb, (const uint8_t*)d_recv, n_streams, n_packets, p0, pc, slot_bytes, d_recs, NULL, NULL,
+                          (hipStream_t)0) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             // device rows [stream][pc][2] -> host rows [stream][n_packets][2]
+             hipMemcpy2D((char*)h_recs + (size_t)p0 * 2 * rec, (size_t)n_packets * 2 * rec, d_recs, (size_t)pc * 2 * rec, (size_t)pc * 2 * rec, (size_t)n_streams,
+                         hipMemcpyDeviceToHost) == hipSuccess;
+        if (ok && h_counts) {
+            h_counts[launch] = -1;
+            // (the list and its count lie behind the records of THIS launch: solo_dec_launch_extract)
+            if (h_recv) ok = hipMemcpy(&h_counts[launch], (char*)d_recs + (size_t)n_streams * pc * 2 * rec + (size_t)n_streams * pc * 2 * sizeof(uint32_t), sizeof(int32_t),
+                                       hipMemcpyDeviceToHost) == hipSuccess;
+        }
+    }
+    (void)lanes;
+    if (ok) rc = (int32_t)rec;
+    (void)hipFree(st); (void)hipFree(d_bits); (void)hipFree(d_nb); (void)hipFree(d_recv); (void)hipFree(d_recs);
+    return rc;
+}
+// The decoder proper ALONE: with h_recs (SxExtracted[n_streams][n_packets][2]: the extract probe's, or packed by the caller from the reference's
+// symbols) ops->synth consumes them; with h_recs == NULL the single kernel ops->decode reads the symbols itself.  After EVERY launch the PCM of
+// its packets goes to h_pcm int16 [n_streams][n_packets][samples of a packet], the status word to h_status int32 [launches][n_streams] and the
+// first state_bytes bytes of every stream record -- its SxDecState -- to h_state [launches][n_streams][state_bytes] (may be NULL).  Returns the
+// size of an SxExtracted record.
+int32_t solo_debug_dec_synth(int32_t samplerate, int32_t useMDIndex, int32_t joint, int32_t frames_per_packet, int32_t n_streams, int32_t n_packets,
+                             int32_t chunk, int32_t slot_bytes, const uint8_t* h_bits, const int16_t* h_nbytes, const uint8_t* h_recv, const void* h_recs,
+                             int16_t* h_pcm, int32_t* h_status, void* h_state, int32_t state_bytes) {
+    const solo_dec_ops* ops = debug_dec_ops(samplerate);
+    if (!debug_dec_args(ops, frames_per_packet, n_streams, n_packets, chunk, slot_bytes) || !h_bits || !h_nbytes || !h_pcm || !h_status || state_bytes < 0 ||
+        (size_t)state_bytes > ops->state_bytes || (h_state == NULL) != (state_bytes == 0))
+        return -1;
+    const size_t rec = (ops->extracted_bytes - 2 * sizeof(uint32_t)) / 2;
+    const size_t np = (size_t)n_streams * n_packets, sz_bits = np * (size_t)slot_bytes, sz_nb = np * 2 * sizeof(int16_t);
+    const size_t samples = (size_t)(ops->packet_samples / 2 * frames_per_packet), sz_pcm = np * samples * sizeof(int16_t), sz_st = (size_t)n_streams * sizeof(int32_t);
+    const int cp = chunk > 0 && chunk < n_packets ? chunk : n_packets;
+    const size_t sz_recs = (size_t)n_streams * cp * ops->extracted_bytes + 256;
+    void *st = NULL, *d_bits = NULL, *d_nb = NULL, *d_recv = NULL, *d_recs = NULL, *d_pcm = NULL, *d_status = NULL;
+    int32_t rc = -1;
+    bool ok = hipMalloc(&st, ops->state_bytes * (size_t)n_streams) == hipSuccess && hipMalloc(&d_bits, sz_bits) == hipSuccess && hipMalloc(&d_nb, sz_nb) == hipSuccess &&
+              hipMalloc(&d_pcm, sz_pcm) == hipSuccess && hipMalloc(&d_status, sz_st) == hipSuccess && hipMalloc(&d_recv, np) == hipSuccess &&
+              (!h_recs || hipMalloc(&d_recs, sz_recs) == hipSuccess) && hipMemset(d_pcm, 0, sz_pcm) == hipSuccess && hipMemset(d_status, 0xFF, sz_st) == hipSuccess &&
+              ops->init(st, n_streams, (joint ? 1 : 0) | (frames_per_packet == 1 ? 2 : 0), useMDIndex, (hipStream_t)0) == hipSuccess;
+    if (ok && h_recs) {
+        ok = hipMemcpy(d_bits, h_bits, sz_bits, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_nb, h_nbytes, sz_nb, hipMemcpyHostToDevice) == hipSuccess &&
+             (h_recv ? hipMemcpy(d_recv, h_recv, np, hipMemcpyHostToDevice) : hipMemset(d_recv, 3, np)) == hipSuccess;
+    }
+    int launch = 0;
+    for (int p0 = 0; ok && p0 < n_packets; p0 += cp, launch++) {
+        const int pc = p0 + cp <= n_packets ? cp : n_packets - p0;
+        if (h_recs) {
+            // host rows [stream][n_packets][2] -> device rows [stream][pc][2]
+            ok = hipMemcpy2D(d_recs, (size_t)pc * 2 * rec, (const char*)h_recs + (size_t)p0 * 2 * rec, (size_t)n_packets * 2 * rec, (size_t)pc * 2 * rec, (size_t)n_streams,
+                             hipMemcpyHostToDevice) == hipSuccess &&
+                 ops->synth(st, (const uint8_t*)d_bits, (const int16_t*)d_nb, (const uint8_t*)d_recv, n_streams, n_packets, p0, pc, slot_bytes, d_recs, (int16_t*)d_pcm,
+                            (int32_t*)d_status, NULL, NULL, (hipStream_t)0) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                 hipMemcpy2D(h_pcm + (size_t)p0 * samples, (size_t)n_packets * samples * 2, (const int16_t*)d_pcm + (size_t)p0 * samples, (size_t)n_packets * samples * 2,
+                             (size_t)pc * samples * 2, (size_t)n_streams, hipMemcpyDeviceToHost) == hipSuccess;
+        } else {
+            // the single kernel has no p0: the launch's packets are handed to it as a call of their own, rows [stream][pc]
+            ok = hipMemcpy2D(d_bits, (size_t)pc * slot_bytes, h_bits + (size_t)p0 * slot_bytes, (size_t)n_packets * slot_bytes, (size_t)pc * slot_bytes, (size_t)n_streams,
+                             hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy2D(d_nb, (size_t)pc * 4, h_nbytes + (size_t)p0 * 2, (size_t)n_packets * 4, (size_t)pc * 4, (size_t)n_streams, hipMemcpyHostToDevice) == hipSuccess &&
+                 (h_recv ? hipMemcpy2D(d_recv, (size_t)pc, h_recv + p0, (size_t)n_packets, (size_t)pc, (size_t)n_streams, hipMemcpyHostToDevice) : hipMemset(d_recv, 3, np)) ==
+                     hipSuccess &&
+                 ops->decode(st, (const uint8_t*)d_bits, (const int16_t*)d_nb, (const uint8_t*)d_recv, n_streams, pc, slot_bytes, (int16_t*)d_pcm, (int32_t*)d_status, NULL,
+                             NULL, (hipStream_t)0) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                 hipMemcpy2D(h_pcm + (size_t)p0 * samples, (size_t)n_packets * samples * 2, d_pcm, (size_t)pc * samples * 2, (size_t)pc * samples * 2, (size_t)n_streams,
+                             hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        ok = ok && hipMemcpy(h_status + (size_t)launch * n_streams, d_status, sz_st, hipMemcpyDeviceToHost) == hipSuccess &&
+             (!h_state || hipMemcpy2D((char*)h_state + (size_t)launch * n_streams * state_bytes, (size_t)state_bytes, st, ops->state_bytes, (size_t)state_bytes,
+                                      (size_t)n_streams, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    if (ok) rc = (int32_t)rec;
+    (void)hipFree(st); (void)hipFree(d_bits); (void)hipFree(d_nb); (void)hipFree(d_recv); (void)hipFree(d_recs); (void)hipFree(d_pcm); (void)hipFree(d_status);
+    return rc;
+}
+
 #ifdef SOLO_WITH_ENCODER
 // Stage probes of the encoder (tests/test_nsq_taps.py, tests/test_enc_stages.py): each runs ONE of the three stages of the launch-per-chunk schedule
 // alone, through the launch table of the rate's build, on freshly initialised streams; HOST pointers; default stream; synchronous.  `samplerate`

@@ -147,7 +147,8 @@ struct SxFrameSyms {
 // what the batch path's extraction kernel leaves for ONE description slot of one packet (HBM): see sx_extract_desc
 struct alignas(16) SxExtracted {
     i32 usable;                      // both frames were read without a coder error and the symbols do not depend on the stream's history
-    i32 pad_[3];
+    i32 pad_[3];                     // pad_[0]: why the record is not usable (SX_UNUSABLE_*; 0 with usable = 1) -- read by no kernel, only by
+                                     // solo_debug_dec_extract's caller (tests/test_dec_stages.py)
     SxFrameSyms y[2];
     i8 pulses[2][SX_FRAME];
     // What needs nothing but this packet's bits, for the slot the decoder takes its coefficients from (the last description slot in
@@ -168,6 +169,12 @@ struct alignas(16) SxExtracted {
     SxDecCtrl ctl[2];
     i32 lastGain[2];
 };
+// SxExtracted::pad_[0] of a record sx_extract_desc gave up on, in the order it checks
+#define SX_UNUSABLE_LENGTH 1         // no bytes, or more than a range-coder buffer holds
+#define SX_UNUSABLE_FS_BAD 2         // the sampling-rate symbol of frame 0 names another internal rate
+#define SX_UNUSABLE_ERROR 3          // the range coder reported an error in one of the two frames
+#define SX_UNUSABLE_NARROW 4         // a pulse above 127 or more than 7 LSB planes: does not fit the lane's byte storage
+#define SX_UNUSABLE_AMBIGUOUS 5      // a symbol depends on the bytes behind the description (SxRangeDec2)
 #define SX_DEC_PAYLOAD_LDS 252      // packets up to this size are staged in LDS (13.6 kbps packets are ~80 B; larger ones are read from HBM)
 // High band of a packet, decoded up front (side information) and synthesised next to the low band: see sx_hb_decode_side
 struct SxHbParams {
@@ -405,6 +412,8 @@ SX_HD void sx_extract_parameters(int nFramesDecoded, i32* typeOffsetPrev, i32* d
         Ix = sx_rc_dec(rc, cdf->cdf_fs, T_CDF_MID_FS);
         if (Ix != (SX_FS_KHZ == 8 ? 0 : 2)) {  // index into {8, 12, 16, 24} kHz: this build decodes ONE internal rate (reference: decoder_set_fs)
             if (!rc->error) rc->error = SX_RC_ILLEGAL_SAMPLING_RATE;
+            // (nothing after it is read: the rest of the record is zero, not what the caller's copy held -- the extraction publishes it)
+            { const i32 mdi = y->MDIndex; i32* z = (i32*)y; for (int i = 0; i < (int)(sizeof(SxFrameSyms) / 4); i++) z[i] = 0; y->MDIndex = mdi; }
             y->fs_bad = 1;
             y->error = rc->error;
             y->bufferLength = rc->bufferLength;
@@ -1308,7 +1317,25 @@ SX_HD int sx_silk_decode_frame(SxDecState* st, SxDecWork* w, SxRangeDec* rc, int
             st->prev_sigtype = c->sigtype;
         }
     }
-    if (ret < 0) return ret;   // corrupt payload: the reference returns before producing output
+    if (ret < 0) {
+        // Corrupt payload.  The reference marks the frame for concealment (ret = 1, decode_frame.c:138) but overwrites that with the error code
+        // (:150-154), so the concealment of :357 never runs and the rest of SKP_Silk_decode_frame works on the caller's UNINITIALISED output
+        // buffer (OutLow, AGR_BWE_decode_frame_FIX.c:137): outBuf[0, L), the concealed energy and -- past a packet's second frame -- the
+        // high-pass state take whatever the stack held.  What it leaves that IS a function of the stream is restated here: the loss flag of
+        // SKP_Silk_PLC_glue_frames (PLC.c:377-413), the comfort-noise estimate / generator (SKP_Silk_CNG works from the state and the control
+        // block, its output goes into the discarded signal) and the lag (decode_frame.c:391).  first_frame_after_reset stays (:277).
+        // Not where the last description's sampling-rate symbol stopped the parse: its control block was never de-quantised here (this LDS
+        // holds whatever the union held before), and the reference either left its own uninitialised (decode_parameters.c:64-67) or
+        // switched to a rate this build does not decode.
+        const int dequantised = action >= 2 && SX_UNI(sx_dec_syms(w, action == 4 ? 1 : 0)->fs_bad) == 0;
+        if (dequantised) {
+            st->plc.last_frame_lost = st->lossCnt ? 1 : 0;
+            wv_sync();
+            sx_cng(st, w, pOut, SX_FRAME);
+            st->lagPrev = c->pitchL[SX_NB_SUBFR - 1];
+        }
+        return ret;
+    }
     SX_T_RESET
     SX_PAR(i, SX_FRAME) st->outBuf[i] = pOut[i];
     wv_sync();
@@ -1656,7 +1683,7 @@ SX_HD void sx_extract_desc(const u8* src, i32 len, int useMDIndex, const SxCdf* 
     rec->usable = 0;
     rec->have_A = 0;
     rec->have_hb = 0;
-    if (len <= 0 || len > SX_MAX_ARITHM_BYTES) return;           // (the serial decoder reports what is wrong with it)
+    if (len <= 0 || len > SX_MAX_ARITHM_BYTES) { rec->pad_[0] = SX_UNUSABLE_LENGTH; return; }   // (the serial decoder reports what is wrong with it)
     SxRangeDec2 r;
     sx_rc_dec_init(&r, src, len);
     i32 top = 0, narrow = 0;
@@ -1665,10 +1692,10 @@ SX_HD void sx_extract_desc(const u8* src, i32 len, int useMDIndex, const SxCdf* 
         SxFrameSyms y;
         sx_extract_parameters(f, &top, dbg, &r, (i8*)&L->b[SX_EXTRACT_TMP], 0, useMDIndex, cdf, &y, &L->b[0], &narrow);
         { const i32* sy = (const i32*)&y; i32* dy = (i32*)&rec->y[f]; for (int i = 0; i < (int)(sizeof(SxFrameSyms) / 4); i++) dy[i] = sy[i]; }
-        if (y.fs_bad || y.error || narrow) return;
+        if (y.fs_bad || y.error || narrow) { rec->pad_[0] = y.fs_bad ? SX_UNUSABLE_FS_BAD : (y.error ? SX_UNUSABLE_ERROR : SX_UNUSABLE_NARROW); return; }
         { const i32* sq = (const i32*)&L->b[SX_EXTRACT_TMP]; i32* dq = (i32*)&rec->pulses[f][0]; for (int i = 0; i < SX_FRAME / 4; i++) dq[i] = sq[i]; }
     }
-    if (r.ambiguous) return;
+    if (r.ambiguous) { rec->pad_[0] = SX_UNUSABLE_AMBIGUOUS; return; }
     {   // the frames' side information de-quantised (see SxExtracted::ctl): blank description state, no first-frame override
         SxDecDesc m;
         SxDecCtrl c;
@@ -1714,5 +1741,6 @@ SX_HD void sx_extract_desc(const u8* src, i32 len, int useMDIndex, const SxCdf* 
             rec->have_hb = 1;
         }
     }
+    rec->pad_[0] = 0;
     rec->usable = 1;
 }

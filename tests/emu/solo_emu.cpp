@@ -36,27 +36,44 @@ void emu_dec_destroy(void* h) { free(h); }
 void emu_dec_set_split(void* h, int on) { ((EmuDec*)h)->two_step = on; }
 static int emu_usable_count = 0, emu_fallback_count = 0;
 int emu_dec_two_step_stats(int which) { return which ? emu_fallback_count : emu_usable_count; }
-int emu_dec_packet(void* h, const uint8_t* bits, int nBytes0, int nBytes1, int lostflag, int16_t* pcm) {
+// the extraction step alone (tests/test_dec_stages.py): the records solo_dec_extract_kernel leaves for the two description slots of ONE packet
+// handed over as (bits, nBytes0, nBytes1, lostflag); a slot without a description gets usable = 0 and nothing else (solo_dec_list_kernel).
+// fill: what the records hold before (0: like solo_debug_dec_extract; 0xA5: whatever the decoder takes from a record must have been written)
+void emu_dec_extract(void* h, const uint8_t* bits, int nBytes0, int nBytes1, int lostflag, void* recs2, int fill) {
     EmuDec* d = (EmuDec*)h;
+    SxExtracted* ext2 = (SxExtracted*)recs2;
     sx_cdf_load_dec(&d->w.cdf);
-    SxExtracted ext2[2];
-    if (d->two_step) {
-        memset(ext2, 0xA5, sizeof(ext2));                 // (whatever the decoder takes from a record must have been written by the extraction)
-        for (int md = 0; md < 2; md++) {                  // solo_dec_extract_kernel, one lane per description slot
-            ext2[md].usable = 0;
-            i32 off = 0, len = 0, hb_off = -1;
-            int sel = 0;
-            if (sx_desc_span(lostflag, nBytes0, nBytes1, d->st.hb_joint, md, &off, &len, &sel, &hb_off))
-                sx_extract_desc(bits + off, len, d->useMDIndex, (const SxCdf*)&d->w.cdf, &d->L, &ext2[md], sel, hb_off >= 0 ? bits + hb_off : 0, d->st.hb_joint);
-        }
-        if (lostflag >= 2) { if (sx_extracted_usable(&d->st, ext2, lostflag)) emu_usable_count++; else emu_fallback_count++; }
+    memset(ext2, fill, 2 * sizeof(SxExtracted));
+    const int hb_joint = d->st.hb_joint | (d->st.fpp == 1);   // (solo_dec_extract_kernel: four high-band bytes instead of eight)
+    for (int md = 0; md < 2; md++) {                      // one lane per description slot
+        ext2[md].usable = 0;
+        i32 off = 0, len = 0, hb_off = -1;
+        int sel = 0;
+        if (sx_desc_span(lostflag, nBytes0, nBytes1, hb_joint, md, &off, &len, &sel, &hb_off))
+            sx_extract_desc(bits + off, len, d->useMDIndex, (const SxCdf*)&d->w.cdf, &d->L, &ext2[md], sel, hb_off >= 0 ? bits + hb_off : 0, hb_joint);
     }
+}
+// the decoder proper alone: recs2 = the packet's two records (emu_dec_extract's or the caller's own) or NULL (the decoder reads its symbols itself)
+int emu_dec_packet_recs(void* h, const uint8_t* bits, int nBytes0, int nBytes1, int lostflag, const void* recs2, int16_t* pcm) {
+    EmuDec* d = (EmuDec*)h;
+    const SxExtracted* ext2 = (const SxExtracted*)recs2;
+    sx_cdf_load_dec(&d->w.cdf);
+    if (ext2 && lostflag >= 2) { if (sx_extracted_usable(&d->st, ext2, lostflag)) emu_usable_count++; else emu_fallback_count++; }
     d->w.st = d->st;                                      // the kernel keeps state + tables in LDS for a launch
     d->w.shadow = &d->sh;
-    int r = sx_decode_packet(&d->w, bits, nBytes0, nBytes1, lostflag, d->useMDIndex, pcm, d->two_step ? ext2 : 0);
+    int r = sx_decode_packet(&d->w, bits, nBytes0, nBytes1, lostflag, d->useMDIndex, pcm, ext2);
     d->st = d->w.st;
     return r;
 }
+int emu_dec_packet(void* h, const uint8_t* bits, int nBytes0, int nBytes1, int lostflag, int16_t* pcm) {
+    EmuDec* d = (EmuDec*)h;
+    SxExtracted ext2[2];
+    if (d->two_step) emu_dec_extract(h, bits, nBytes0, nBytes1, lostflag, ext2, 0xA5);
+    return emu_dec_packet_recs(h, bits, nBytes0, nBytes1, lostflag, d->two_step ? ext2 : 0, pcm);
+}
+int emu_sizeof_extracted() { return (int)sizeof(SxExtracted); }
+int emu_sizeof_frame_syms() { return (int)sizeof(SxFrameSyms); }
+int emu_sizeof_dec_ctrl() { return (int)sizeof(SxDecCtrl); }
 // L0 vocabulary, operand by operand (tests/test_l0_primitives.py)
 void emu_l0(int op, int n, const int32_t* a, const int32_t* b, const int32_t* c, int32_t* out) {
     for (int i = 0; i < n; i++) out[i] = sx_l0_probe(op, a[i], b[i], c[i]);
