@@ -334,6 +334,48 @@ int32_t solo_mix(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t n_
                  const int32_t *d_room, int32_t n_rooms, const int16_t *d_gain_q12, int32_t max_speakers,
                  int16_t *d_pcm_out, int64_t *d_energy, uint8_t *d_mixed,
                  solo_mix_count_t *d_count, void *hip_stream);
+/* Stream migration: the state of a running call leaves a handle as a DEVICE blob and enters any slot of any handle of the same
+ * geometry -- on this GPU, or on another one after the caller has moved the bytes (the blob is plain device memory: a torch.distributed
+ * send, a hipMemcpyPeer).  The call goes on where it stood: no first-frame logic, no cold-start concealment, VAD / DTX / CNG / PLC and
+ * gain histories intact.  For draining a GPU, rebalancing ranks, gathering a room's participants in one handle (solo_mix), standby copies.
+ *   which      1 = encoder state, 2 = decoder state, 4 = receive queue (payload, length words, play-out position, the per-stream
+ *              counters of solo_recv_track), or a sum of them
+ *   d_streams  int32 [n], DEVICE list as in the subset calls: strictly increasing inside [0, N), checked on the device
+ *   d_blob     uint8 [n][blob_stride]: row i belongs to d_streams[i]; 16-byte aligned, blob_stride a multiple of 16 and
+ *              >= solo_batch_state_bytes(b, which)
+ *   d_count    one solo_migrate_count_t on the device
+ * Record: a 64-byte header (magic, version, the sections present, the geometry of each -- samplerate, frames per packet, joint mode,
+ * the size of the stream record; ring depth and slot_bytes --, the origin stream, the body length, two checksums over the body's
+ * 32-bit words: sum w_i and sum (i + 1) w_i mod 2^32), then the sections in bit order, each padded to 16 bytes.  Sections 1 and 2 are the
+ * stream's records byte for byte, rate / DTX / useMDIndex included.  Section 4 is written in play-relative order (entry k = sequence
+ * number play + k) and only the bytes its length words declare, the rest zero: equal queues give equal blobs wherever the ring's
+ * storage wraps.  solo_amd/csrc/solo_migrate.h has the layout word by word.
+ * A BLOB IS VALID ONLY FOR THE LIBRARY BUILD THAT WROTE IT (the size words enforce it): a migration and standby format, not an archive.
+ * solo_batch_state_bytes: bytes of one record, header included, a multiple of 16; -1 when which is 0, has unknown bits or names a
+ *   direction or a ring the handle lacks.
+ * Both calls return -1 with nothing enqueued for a NULL pointer, n outside (0, N], such a `which`, a stride below
+ *   solo_batch_state_bytes(b, which), a stride or a base that is not 16-byte aligned.
+ * solo_batch_export_streams reads only: every state, queue and play-out position stays bit for bit.  d_count = {n, 0, bytes written};
+ *   a refused list writes d_count->streams = -1 and nothing else.
+ * solo_batch_import_streams checks EVERY record before it copies anything; the call is refused as a whole, d_count = {-1, index of the
+ *   first bad record + 1, 0}, when the list is invalid (the bad position counts as the record), or a record has a wrong magic or
+ *   version, lacks a section of `which`, differs from the handle in samplerate, frames per packet, joint mode, record size or (section 4)
+ *   ring depth / slot_bytes, has a wrong body length, a wrong checksum, or queue words no ring could hold.  After a refused import every
+ *   state of the handle is bit for bit what it was.  Otherwise the listed streams hold exactly the imported state -- their own rate, DTX and
+ *   useMDIndex included, whatever control the handle was created with (as after solo_batch_reset_streams) --, unlisted streams are
+ *   untouched and d_count = {n, 0, bytes taken}.  A blob may hold more sections than the call takes.  With section 4 the queue of a listed
+ *   stream is replaced entirely; the handle-wide solo_recv_stats words do not change; the per-stream counters are written only if the
+ *   handle has allocated them (solo_recv_track(b, 1) at any time before).
+ * Ordering as solo_batch_reset_streams: the kernels wait for this handle's encode / decode work still in flight on its internal streams
+ * (async joins included); work enqueued on hip_stream after the call sees the result.  No host synchronisation, no allocation.  The words
+ * of the persistent encoder schedule (flags, tickets) belong to the handle and do not travel: an imported stream encodes under the
+ * default schedule like any other.  The legacy AGR_Sate_* handles are not covered. */
+typedef struct { int32_t streams, refused; int64_t bytes; } solo_migrate_count_t;   /* 16 bytes */
+int64_t solo_batch_state_bytes(const solo_batch_t *b, int32_t which);
+int32_t solo_batch_export_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, int32_t which,
+                                  uint8_t *d_blob, int64_t blob_stride, solo_migrate_count_t *d_count, void *hip_stream);
+int32_t solo_batch_import_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, int32_t which,
+                                  const uint8_t *d_blob, int64_t blob_stride, solo_migrate_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

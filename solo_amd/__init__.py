@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
     "solo_send_pack", "solo_send_pack_streams", "solo_mix", "solo_recv_track", "solo_recv_report",
+    "solo_batch_state_bytes", "solo_batch_export_streams", "solo_batch_import_streams",
 ]
 
 
@@ -52,6 +53,11 @@ class solo_send_count_t(C.Structure):
 class solo_mix_count_t(C.Structure):
     """what a solo_mix call did (include/solo_mi355x.h); 16 bytes"""
     _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("clipped", C.c_int64)]
+
+
+class solo_migrate_count_t(C.Structure):
+    """what a solo_batch_export_streams / solo_batch_import_streams call did (include/solo_mi355x.h); 16 bytes"""
+    _fields_ = [("streams", C.c_int32), ("refused", C.c_int32), ("bytes", C.c_int64)]
 
 
 class solo_recv_report_t(C.Structure):
@@ -159,6 +165,11 @@ def load_library():
     lib.solo_mix.restype = C.c_int32
     lib.solo_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p]
+    lib.solo_batch_state_bytes.restype = C.c_int64
+    lib.solo_batch_state_bytes.argtypes = [C.c_void_p, C.c_int32]
+    for f in (lib.solo_batch_export_streams, lib.solo_batch_import_streams):
+        f.restype = C.c_int32
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
     lib.solo_batch_set_async_join.argtypes = [C.c_void_p, C.c_int32]
     lib.solo_batch_wait_encode.restype = C.c_int32
@@ -691,6 +702,87 @@ class SoloBatch:
         rows == -1: a room id was refused on the device"""
         c = solo_mix_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
         return {k: int(getattr(c, k)) for k in self.MIX_COUNT}
+
+    # ---- stream migration (solo_batch_export_streams / solo_batch_import_streams): a running call moves between handles ----
+    MIGRATE_COUNT = ("streams", "refused", "bytes")
+    _MIGRATE = {"enc": 1, "encoder": 1, "dec": 2, "decoder": 2, "recv": 4, "ring": 4}
+
+    def _migrate_which(self, which):
+        """"enc", "dec", "both" (the directions the handle has), "recv", a combination ("dec+recv", ("enc", "recv")), or the bits 1 | 2 | 4"""
+        if isinstance(which, int) and not isinstance(which, bool):
+            w = which
+        else:
+            w = 0
+            for name in (which.split("+") if isinstance(which, str) else which):
+                name = name.strip()
+                if name == "both":
+                    w |= (1 if self._enc is not None else 0) | (2 if self._dec is not None else 0)
+                elif name in self._MIGRATE:
+                    w |= self._MIGRATE[name]
+                else:
+                    raise ValueError("which: 'enc', 'dec', 'both', 'recv' or a combination such as 'dec+recv'")
+        if not 0 < w <= 7:
+            raise ValueError("which names no section")
+        return w
+
+    def state_bytes(self, which="both"):
+        """bytes of one exported record, header included (solo_batch_state_bytes): the smallest row stride of a blob"""
+        r = int(self.lib.solo_batch_state_bytes(self.h, self._migrate_which(which)))
+        if r < 0:
+            raise ValueError("the handle lacks a direction or the receiver ring that `which` names")
+        return r
+
+    def _migrate_list(self, streams):
+        t = self.torch
+        if getattr(streams, "is_cuda", False):               # (taken as it is and checked on the device: a bad one is refused there)
+            if streams.dtype != t.int32 or streams.dim() != 1 or not streams.is_contiguous() or not 0 < streams.shape[0] <= self.n_streams:
+                raise ValueError("streams: a sequence or a contiguous 1-D int32 CUDA tensor of 1 .. %d indices" % self.n_streams)
+            return streams, int(streams.shape[0])
+        return self._subset(streams)
+
+    def export_streams(self, streams, which="both", blob=None):
+        """The state of the listed streams as a device blob (solo_batch_export_streams) -> (blob uint8 [n, stride], count int32 [4] on the
+        device: read it with migrate_count()).  which: "enc", "dec", "both", "recv" (the receive queue) or a combination ("dec+recv").
+        Row i belongs to streams[i] (strictly increasing).  blob: the caller's buffer, contiguous, 16-byte aligned, stride >= state_bytes(which)
+        and a multiple of 16.  The handle is only read.  The blob is valid for this library build only; sending it to another rank is a
+        plain torch.distributed send of the tensor.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        w = self._migrate_which(which)
+        smap, n = self._migrate_list(streams)
+        need = self.state_bytes(w)
+        if blob is None:
+            blob = t.zeros((n, need), dtype=t.uint8, device=self.device)
+        elif not (getattr(blob, "is_cuda", False) and blob.dtype == t.uint8 and blob.is_contiguous() and blob.dim() == 2 and blob.shape[0] == n):
+            raise ValueError("blob: a contiguous uint8 CUDA tensor [%d, stride]" % n)
+        count = t.zeros((4,), dtype=t.int32, device=self.device)
+        r = self.lib.solo_batch_export_streams(self.h, smap.data_ptr(), n, w, blob.data_ptr(), blob.shape[1], count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_batch_export_streams -> %d" % r)
+        return blob, count
+
+    def import_streams(self, streams, blob, which="both"):
+        """Row i of an exported blob becomes the state of streams[i] (solo_batch_import_streams) -> count int32 [4] on the device: read it with
+        migrate_count().  Every record is checked on the device first (build, geometry, length, checksums); one bad record refuses the
+        whole call -- streams == -1, refused = its index + 1 -- and the handle stays bit for bit as it was.  The imported streams keep
+        their own rate, DTX and useMDIndex.  The blob may hold more sections than `which` takes."""
+        t = self.torch
+        w = self._migrate_which(which)
+        smap, n = self._migrate_list(streams)
+        if not (getattr(blob, "is_cuda", False) and blob.dtype == t.uint8 and blob.is_contiguous() and blob.dim() == 2 and blob.shape[0] == n):
+            raise ValueError("blob: a contiguous uint8 CUDA tensor [%d, stride]" % n)
+        count = t.zeros((4,), dtype=t.int32, device=self.device)
+        r = self.lib.solo_batch_import_streams(self.h, smap.data_ptr(), n, w, blob.data_ptr(), blob.shape[1], count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_batch_import_streams -> %d" % r)
+        return count
+
+    def migrate_count(self, count):
+        """the count tensor of export_streams() / import_streams() as a dict (synchronises): streams done, refused (import: index of the
+        first bad record + 1), bytes written / taken; streams == -1: the call was refused on the device.  A refused EXPORT writes that word
+        and nothing else: `refused` and `bytes` are then not defined by the library (0 here only because export_streams() hands it a
+        zeroed count)"""
+        c = solo_migrate_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.MIGRATE_COUNT}
 
     def close(self):
         if getattr(self, "h", None):

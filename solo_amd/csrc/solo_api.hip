@@ -30,6 +30,7 @@
 #include "solo_send.h"          // the sender back end (solo_send_pack): rate-independent, compiled once, not a member of the launch tables
 #include "solo_mix.h"           // the mixing bridge (solo_mix): likewise
 #include "solo_recv_report.h"   // the read side of the receiver ring (solo_recv_report, solo_recv_track): likewise
+#include "solo_migrate.h"       // stream states out of a handle and into another (solo_batch_export_streams / _import_streams): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -169,7 +170,7 @@ extern "C" const solo_enc_ops* solo_wb_enc_ops();                               
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
 #define SOLO_MAX_CHUNKS 64
-#define SOLO_N_VERDICTS 7
+#define SOLO_N_VERDICTS 10
 struct solo_batch {
     int32_t n_streams;
     int32_t slot;
@@ -234,7 +235,8 @@ struct solo_batch {
     int recv_track;
     int32_t* d_recv_sel;
     // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
-    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams, [5] solo_mix (its room ids), [6] solo_recv_report
+    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams, [5] solo_mix (its room ids), [6] solo_recv_report,
+    // [7] solo_batch_export_streams, [8, 9] solo_batch_import_streams (its list, its records)
     uint32_t* d_verdict;
     void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack call (solo_send.h), grown on demand
     size_t send_scratch_bytes;
@@ -872,6 +874,72 @@ int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_
     a.counts = NULL; a.starts = NULL; a.members = NULL;
     a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
     SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + 5, st));
+    return 0;
+}
+
+// ---- stream migration (solo_migrate.h): encoder state, decoder state and receive queue of listed streams <-> a device blob ---------
+static_assert(sizeof(solo_migrate_count_t) == sizeof(SxMigCount), "include/solo_mi355x.h and solo_migrate.h agree");
+// which: a non-empty subset of {1 encoder, 2 decoder, 4 receive queue} that the handle has
+static bool migrate_which_ok(const solo_batch* b, int32_t which) {
+    return b && which > 0 && which <= SX_MIG_ALL && !((which & SX_MIG_ENC) && !b->have_enc) && !((which & SX_MIG_DEC) && !b->have_dec) &&
+           !((which & SX_MIG_RECV) && !b->d_recv_ring);
+}
+static SxMigHandle migrate_handle(const solo_batch* b) {
+    SxMigHandle h;
+    memset(&h, 0, sizeof(h));
+    h.n_streams = b->n_streams;
+#ifdef SOLO_WITH_ENCODER
+    if (b->have_enc) {
+        h.enc = (uint8_t*)b->d_enc_state;
+        h.g.enc_rate = b->enc_ctrl.samplerate; h.g.enc_mode = sx_mig_mode(enc_frames_per_packet(b), enc_hb_joint(b)); h.g.enc_bytes = (int32_t)b->eops->state_bytes;
+    }
+#endif
+    if (b->have_dec) {
+        h.dec = (uint8_t*)b->d_dec_state;
+        h.g.dec_rate = b->dec_ctrl.samplerate;
+        h.g.dec_mode = sx_mig_mode(ctrl_frames_per_packet(b->dec_ctrl.framesize_ms), ctrl_hb_joint(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode));
+        h.g.dec_bytes = (int32_t)b->dops->state_bytes;
+    }
+    if (b->d_recv_ring) {
+        h.ring = b->d_recv_ring; h.lens = b->d_recv_lens; h.play = b->d_recv_play; h.trk = b->d_recv_trk;
+        h.g.depth = b->recv_depth; h.g.slot = b->recv_slot;
+    }
+    return h;
+}
+int64_t solo_batch_state_bytes(const solo_batch_t* b, int32_t which) {
+    if (!migrate_which_ok(b, which)) return -1;
+    const SxMigHandle h = migrate_handle(b);
+    return SX_MIG_HDR_BYTES + sx_mig_body_bytes(sx_mig_geom_of(h.g, which), which);
+}
+static bool migrate_args_ok(const solo_batch* b, const int32_t* d_streams, int32_t n, int32_t which, const uint8_t* d_blob, int64_t blob_stride,
+                            const solo_migrate_count_t* d_count) {
+    if (!migrate_which_ok(b, which) || !d_streams || !d_blob || !d_count || n <= 0 || n > b->n_streams) return false;
+    return blob_stride >= solo_batch_state_bytes(b, which) && !(blob_stride & 15) && !((uintptr_t)d_blob & 15);
+}
+int32_t solo_batch_export_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, int32_t which, uint8_t* d_blob, int64_t blob_stride,
+                                  solo_migrate_count_t* d_count, void* hip_stream) {
+    if (!migrate_args_ok(b, d_streams, n, which, d_blob, blob_stride, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    {   // (the states must be those the work in flight leaves behind)
+        const int32_t r = solo_wait_in_flight(b, st);
+        if (r) return r;
+    }
+    uint32_t* verdict = b->d_verdict + 7;
+    SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
+    SOLO_CHECK(solo_migrate_export_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
+    return 0;
+}
+int32_t solo_batch_import_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, int32_t which, const uint8_t* d_blob, int64_t blob_stride,
+                                  solo_migrate_count_t* d_count, void* hip_stream) {
+    if (!migrate_args_ok(b, d_streams, n, which, d_blob, blob_stride, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    {   // (as solo_batch_reset_streams: the kernels in flight write whole states back when they end)
+        const int32_t r = solo_wait_in_flight(b, st);
+        if (r) return r;
+    }
+    uint32_t* verdict = b->d_verdict + 8;
+    SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
+    SOLO_CHECK(solo_migrate_import_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
     return 0;
 }
 
