@@ -334,6 +334,41 @@ int32_t solo_mix(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t n_
                  const int32_t *d_room, int32_t n_rooms, const int16_t *d_gain_q12, int32_t max_speakers,
                  int16_t *d_pcm_out, int64_t *d_energy, uint8_t *d_mixed,
                  solo_mix_count_t *d_count, void *hip_stream);
+/* PCM rate conversion on the device: the reference SDK's own fixed-point resampler (SKP_Silk_resampler_init / SKP_Silk_resampler), bit for
+ * bit and with its stream state, so that callers on handles of different rates meet in one mix and 8 / 48 kHz endpoints need no host
+ * round trip.  A resampler is an object of its own -- it sits BETWEEN two handles -- with n_rows independent rows of filter memory.
+ *   pairs      fs_in -> fs_out with both rates in {8000, 16000, 32000, 48000} and fs_out : fs_in one of 1:2, 2:1, 1:3, 3:1, 2:3, 3:2:
+ *              48->16, 48->32, 32->16, 16->8 (second-order AR filter + 12-tap FIR), 16->32, 8->16 (all-pass 2x up-sampler with notch),
+ *              16->48, 32->48 (2x up-sampler + 6-tap fractional interpolation).  Every other pair -- equal rates, 1:4 (32->8), 1:6
+ *              (48->8) and their inverses, 12 / 24 / 44.1 kHz, rates above 48 kHz -- makes the create call return NULL.
+ *   d_in       int16 [n][n_packets][in_samples], d_out int16 [n][n_packets][out_samples]: the layouts the decode calls write and that
+ *              the mixer and the encode calls read, compact rows of the subset calls included.  Both 16-byte aligned, not overlapping.
+ *   in_samples any positive multiple of 10 ms of input (fs_in / 100 samples): a 20 ms or 40 ms packet at any of the four rates.  The
+ *              output has exactly in_samples * fs_out / fs_in samples per packet (see the out_samples call, -1 off that grid).
+ * The conversion works in batches of 10 ms as the reference does, so P packets in one call give what P calls of one packet give, and a
+ * row's 96 bytes of filter memory (the reference's sIIR[6], sFIR[16], sDown2[2]; about 1 ms of signal) live in device memory inside the
+ * object and carry from call to call.  The create call zeroes them (= the reference's init), and so do the two reset calls: every row,
+ * or a HOST list of rows (1 .. n_rows indices inside [0, n_rows), none twice, else -1), as the per-stream reset of a batch handle.
+ * The rows variant converts only the listed rows: d_rows is a DEVICE list, strictly increasing inside [0, n_rows), checked on the
+ * device ahead of the work like the lists of the other subset calls; row i of d_in / d_out belongs to d_rows[i] (compact I/O); unlisted
+ * rows keep their state bit for bit.  A refused list changes no state and writes nothing except d_count->rows = -1.
+ * Return -1 with nothing enqueued: NULL pointers (d_count included, in the rows variant); n outside (0, n_rows]; n_packets <= 0;
+ * in_samples not a positive multiple of fs_in / 100; n x n_packets x in_samples or x out_samples >= 2^31; buffers that are not 16-byte
+ * aligned or that overlap.  One kernel (two with a list) on hip_stream only, no host synchronisation and no allocation: the calls can
+ * be captured in a graph.  Calls on one resampler must be ordered (same stream, or events).
+ * Not offered: the other ratios; sample formats other than int16; resampler state in a migration blob -- a row that moves to another
+ * object starts from a reset there (its memory is about 1 ms of signal).  INTEGRATION.md section 2 has the recipes. */
+typedef struct solo_resampler solo_resampler_t;
+typedef struct { int32_t rows, listed; } solo_resample_count_t;   /* rows converted / rows listed; rows = -1: list refused on the device */
+solo_resampler_t *solo_resample_create(int32_t n_rows, int32_t fs_in, int32_t fs_out);
+void solo_resample_destroy(solo_resampler_t *r);
+int32_t solo_resample_out_samples(const solo_resampler_t *r, int32_t in_samples);
+int32_t solo_resample_reset(solo_resampler_t *r, void *hip_stream);
+int32_t solo_resample_reset_rows(solo_resampler_t *r, const int32_t *h_rows, int32_t n, void *hip_stream);
+int32_t solo_resample(solo_resampler_t *r, const int16_t *d_in, int32_t n_packets, int32_t in_samples,
+                      int16_t *d_out, void *hip_stream);
+int32_t solo_resample_rows(solo_resampler_t *r, const int32_t *d_rows, int32_t n, const int16_t *d_in, int32_t n_packets,
+                           int32_t in_samples, int16_t *d_out, solo_resample_count_t *d_count, void *hip_stream);
 /* Stream migration: the state of a running call leaves a handle as a DEVICE blob and enters any slot of any handle of the same
  * geometry -- on this GPU, or on another one after the caller has moved the bytes (the blob is plain device memory: a torch.distributed
  * send, a hipMemcpyPeer).  The call goes on where it stood: no first-frame logic, no cold-start concealment, VAD / DTX / CNG / PLC and

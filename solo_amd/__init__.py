@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
     "solo_send_pack", "solo_send_pack_streams", "solo_mix", "solo_recv_track", "solo_recv_report",
     "solo_batch_state_bytes", "solo_batch_export_streams", "solo_batch_import_streams",
+    "solo_resample_create", "solo_resample_destroy", "solo_resample_out_samples", "solo_resample_reset", "solo_resample_reset_rows",
+    "solo_resample", "solo_resample_rows",
 ]
 
 
@@ -53,6 +55,11 @@ class solo_send_count_t(C.Structure):
 class solo_mix_count_t(C.Structure):
     """what a solo_mix call did (include/solo_mi355x.h); 16 bytes"""
     _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("clipped", C.c_int64)]
+
+
+class solo_resample_count_t(C.Structure):
+    """what a solo_resample_rows call did (include/solo_mi355x.h); 8 bytes"""
+    _fields_ = [("rows", C.c_int32), ("listed", C.c_int32)]
 
 
 class solo_migrate_count_t(C.Structure):
@@ -170,6 +177,20 @@ def load_library():
     for f in (lib.solo_batch_export_streams, lib.solo_batch_import_streams):
         f.restype = C.c_int32
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.solo_resample_create.restype = C.c_void_p
+    lib.solo_resample_create.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.solo_resample_destroy.restype = None
+    lib.solo_resample_destroy.argtypes = [C.c_void_p]
+    lib.solo_resample_out_samples.restype = C.c_int32
+    lib.solo_resample_out_samples.argtypes = [C.c_void_p, C.c_int32]
+    lib.solo_resample_reset.restype = C.c_int32
+    lib.solo_resample_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.solo_resample_reset_rows.restype = C.c_int32
+    lib.solo_resample_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_resample.restype = C.c_int32
+    lib.solo_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_resample_rows.restype = C.c_int32
+    lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
     lib.solo_batch_set_async_join.argtypes = [C.c_void_p, C.c_int32]
     lib.solo_batch_wait_encode.restype = C.c_int32
@@ -794,3 +815,112 @@ class SoloBatch:
             self.close()
         except Exception:
             pass
+
+
+RESAMPLE_PAIRS = ((48000, 16000), (48000, 32000), (32000, 16000), (16000, 8000), (16000, 32000), (8000, 16000), (16000, 48000), (32000, 48000))
+
+
+class Resampler:
+    """n_rows independent PCM rate converters on the current HIP device (solo_resample, include/solo_mi355x.h): the reference's
+    fixed-point resampler bit for bit, its filter memory carried from call to call.  It sits between two handles of different rates,
+    or between a handle and an 8 / 48 kHz endpoint; the pairs are RESAMPLE_PAIRS."""
+
+    COUNT = ("rows", "listed")
+
+    def __init__(self, n_rows, fs_in, fs_out):
+        import torch
+        self.n_rows, self.fs_in, self.fs_out = int(n_rows), int(fs_in), int(fs_out)
+        if self.n_rows <= 0:
+            raise ValueError("n_rows must be positive")
+        if (self.fs_in, self.fs_out) not in RESAMPLE_PAIRS:
+            raise ValueError("fs_in -> fs_out must be one of %s" % ", ".join("%d->%d" % p for p in RESAMPLE_PAIRS))
+        self.h = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
+        self.torch = torch
+        self.lib = load_library()
+        self.h = self.lib.solo_resample_create(self.n_rows, self.fs_in, self.fs_out)
+        if not self.h:
+            raise RuntimeError("solo_resample_create failed (no GPU, or out of memory)")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.solo_resample_destroy(self.h)
+            self.h = None
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def out_samples(self, in_samples):
+        """samples per output packet of in_samples per input packet: in_samples * fs_out / fs_in; in_samples must be a positive multiple
+        of 10 ms (fs_in / 100 samples)"""
+        in_samples = int(in_samples)
+        if in_samples <= 0 or in_samples % (self.fs_in // 100):
+            raise ValueError("in_samples: a positive multiple of %d (10 ms at %d Hz)" % (self.fs_in // 100, self.fs_in))
+        return in_samples // (self.fs_in // 100) * (self.fs_out // 100)
+
+    def check(self, pcm, rows=None, out=None):
+        """the argument checks of run() -> (n, P, in_samples, out_samples); rows: None or an int32 CUDA tensor"""
+        t = self.torch
+        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
+        if not dev(pcm, t.int16, 3):
+            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
+        n, P, L = pcm.shape
+        if n <= 0 or P <= 0:
+            raise ValueError("pcm: at least one row and one packet")
+        outs = self.out_samples(L)
+        if rows is None:
+            if n != self.n_rows:
+                raise ValueError("pcm: %d rows (or pass rows=)" % self.n_rows)
+        elif not (dev(rows, t.int32, 1) and rows.shape[0] == n and n <= self.n_rows):
+            raise ValueError("rows: a contiguous int32 CUDA tensor [%d] of at most %d indices" % (n, self.n_rows))
+        if n * P * max(L, outs) >= 2 ** 31:
+            raise ValueError("n * P * samples must stay below 2^31")
+        if out is not None and not (dev(out, t.int16, 3) and tuple(out.shape) == (n, P, outs)):
+            raise ValueError("out: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, outs))
+        return n, P, L, outs
+
+    def run(self, pcm, rows=None, out=None):
+        """pcm int16 [n,P,in_samples] at fs_in (what decode() / mix() wrote, compact rows included) -> out int16 [n,P,out_samples] at fs_out
+        (what mix() / encode() take).  rows=None: n == n_rows, row i of the object converts row i.  rows = a sequence or an int32 CUDA tensor,
+        strictly increasing: only those rows are converted, row i of pcm / out belongs to rows[i], the others keep their state; returns
+        (out, count) with count int32 [2] on the device, read with count().  A bad list is refused on the device: rows == -1 in the
+        count, nothing else written.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        if rows is not None and not getattr(rows, "is_cuda", False):
+            idx = [int(v) for v in rows]
+            if not idx or any(b <= a for a, b in zip(idx, idx[1:])) or idx[0] < 0 or idx[-1] >= self.n_rows:
+                raise ValueError("rows: strictly increasing indices inside [0, %d)" % self.n_rows)
+            rows = t.tensor(idx, dtype=t.int32, device=self.device)
+        n, P, L, outs = self.check(pcm, rows, out)
+        if out is None:
+            out = t.empty((n, P, outs), dtype=t.int16, device=pcm.device)
+        if rows is None:
+            r = self.lib.solo_resample(self.h, pcm.data_ptr(), P, L, out.data_ptr(), self._stream())
+            if r:
+                raise RuntimeError("solo_resample -> %d" % r)
+            return out
+        count = t.zeros((2,), dtype=t.int32, device=pcm.device)
+        r = self.lib.solo_resample_rows(self.h, rows.data_ptr(), n, pcm.data_ptr(), P, L, out.data_ptr(), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_resample_rows -> %d" % r)
+        return out, count
+
+    def count(self, count):
+        """the count tensor of run(rows=) as a dict (synchronises): rows converted, rows listed; rows == -1: the list was refused"""
+        c = solo_resample_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.COUNT}
+
+    def reset(self, rows=None):
+        """zero the filter memory of every row, or of the listed rows (a host sequence: inside [0, n_rows), none twice)"""
+        if rows is None:
+            r = self.lib.solo_resample_reset(self.h, self._stream())
+        else:
+            idx = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+            if not 0 < len(idx) <= self.n_rows or any(v < 0 or v >= self.n_rows for v in idx) or len(set(idx)) != len(idx):
+                raise ValueError("rows: 1 .. %d indices inside [0, %d), none twice" % (self.n_rows, self.n_rows))
+            arr = (C.c_int32 * len(idx))(*idx)
+            r = self.lib.solo_resample_reset_rows(self.h, arr, len(idx), self._stream())
+        if r:
+            raise RuntimeError("solo_resample_reset -> %d" % r)

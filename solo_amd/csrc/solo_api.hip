@@ -31,6 +31,7 @@
 #include "solo_mix.h"           // the mixing bridge (solo_mix): likewise
 #include "solo_recv_report.h"   // the read side of the receiver ring (solo_recv_report, solo_recv_track): likewise
 #include "solo_migrate.h"       // stream states out of a handle and into another (solo_batch_export_streams / _import_streams): likewise
+#include "solo_resample.h"      // PCM rate conversion between handles and towards 8 / 48 kHz endpoints (solo_resample): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -875,6 +876,80 @@ int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_
     a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
     SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + 5, st));
     return 0;
+}
+
+// ---- PCM rate conversion (solo_resample.h): an object of its own, it sits between two handles of different rates ----------------------
+static_assert(sizeof(solo_resample_count_t) == sizeof(SxRsCount), "include/solo_mi355x.h and solo_resample.h agree");
+struct solo_resampler {
+    int32_t n_rows, fs_in, fs_out;
+    SxRsCfg cfg;
+    int32_t* d_state;                // [n_rows][SX_RS_STATE_WORDS]
+    uint32_t* d_verdict;             // the verdict word of a solo_resample_rows call
+};
+solo_resampler_t* solo_resample_create(int32_t n_rows, int32_t fs_in, int32_t fs_out) {
+    SxRsCfg cfg;
+    if (n_rows <= 0 || !sx_rs_config(fs_in, fs_out, &cfg)) return NULL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
+        return NULL;
+    }
+    solo_resampler* r = new (std::nothrow) solo_resampler();
+    if (!r) return NULL;
+    memset(r, 0, sizeof(*r));
+    r->n_rows = n_rows; r->fs_in = fs_in; r->fs_out = fs_out; r->cfg = cfg;
+    const size_t bytes = (size_t)n_rows * SX_RS_STATE_WORDS * sizeof(int32_t);
+    if (hipMalloc((void**)&r->d_state, bytes) != hipSuccess || hipMalloc((void**)&r->d_verdict, sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(r->d_state, 0, bytes) != hipSuccess || hipMemset(r->d_verdict, 0, sizeof(uint32_t)) != hipSuccess) {
+        solo_resample_destroy(r);
+        return NULL;
+    }
+    return r;
+}
+void solo_resample_destroy(solo_resampler_t* r) {
+    if (!r) return;
+    dev_free(r->d_state);
+    dev_free(r->d_verdict);
+    delete r;
+}
+int32_t solo_resample_out_samples(const solo_resampler_t* r, int32_t in_samples) { return r ? sx_rs_out_samples(r->cfg, in_samples) : -1; }
+int32_t solo_resample_reset(solo_resampler_t* r, void* hip_stream) {
+    if (!r) return -1;
+    SOLO_CHECK(hipMemsetAsync(r->d_state, 0, (size_t)r->n_rows * SX_RS_STATE_WORDS * sizeof(int32_t), (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_resample_reset_rows(solo_resampler_t* r, const int32_t* h_rows, int32_t n, void* hip_stream) {
+    if (!r || !sx_rs_list_ok(h_rows, n, r->n_rows)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<SxStreamCtl> recs((size_t)n);
+    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
+    int32_t* state = r->d_state;
+    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
+        hipLaunchKernelGGL(solo_resample_reset_kernel, dim3((unsigned)k), dim3(64), 0, st, state, l);
+    }));
+    return 0;
+}
+static int32_t resample_call(solo_resampler* r, const int32_t* d_rows, int32_t n, const int16_t* d_in, int32_t n_packets, int32_t in_samples,
+                             int16_t* d_out, solo_resample_count_t* d_count, hipStream_t st) {
+    if (!sx_rs_call_ok(r->cfg, r->n_rows, n, n_packets, in_samples, d_in, d_out)) return -1;
+    SxRsArgs a;
+    a.c = r->cfg; a.in = d_in; a.out = d_out; a.state = r->d_state; a.map = d_rows; a.n = n;
+    a.batches = n_packets * (in_samples / r->cfg.n_in);
+    if (d_rows) {
+        hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, r->n_rows, r->d_verdict, (i32*)NULL);
+        SOLO_CHECK(hipGetLastError());
+    }
+    SOLO_CHECK(solo_resample_launch(a, (SxRsCount*)d_count, r->d_verdict, st));
+    return 0;
+}
+int32_t solo_resample(solo_resampler_t* r, const int16_t* d_in, int32_t n_packets, int32_t in_samples, int16_t* d_out, void* hip_stream) {
+    if (!r) return -1;
+    return resample_call(r, NULL, r->n_rows, d_in, n_packets, in_samples, d_out, NULL, (hipStream_t)hip_stream);
+}
+int32_t solo_resample_rows(solo_resampler_t* r, const int32_t* d_rows, int32_t n, const int16_t* d_in, int32_t n_packets, int32_t in_samples,
+                           int16_t* d_out, solo_resample_count_t* d_count, void* hip_stream) {
+    if (!r || !d_rows || !d_count) return -1;
+    return resample_call(r, d_rows, n, d_in, n_packets, in_samples, d_out, d_count, (hipStream_t)hip_stream);
 }
 
 // ---- stream migration (solo_migrate.h): encoder state, decoder state and receive queue of listed streams <-> a device blob ---------
