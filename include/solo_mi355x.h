@@ -95,10 +95,10 @@ int32_t AGR_Sate_Decoder_Uninit(void *SATEDec_State);
  * Return value: 0 or a negative hipError_t.  solo_batch_encode returns -1 for n_packets >= ~700 000 (16 kHz) / ~350 000 (32 kHz) per
  * call -- split longer (offline) inputs over several calls; state carries over.
  * Device memory a handle holds besides the stream states: encode -- the hand-over records of one call, 4.3 KB per packet of the call
- * (n_streams x n_packets), and 32 KB of quantiser ring per four streams; decode -- up to two buffers of extraction records, 2216 B per
+ * (n_streams x n_packets), and 32 KB of quantiser ring per four streams; decode -- one buffer of extraction records, 2216 B per
  * packet of a CHUNK (16 kHz API rate; 2 x sizeof(SxExtracted) + two entries of the list of slots that carry bytes: solo_api.hip asserts the figure): a call is cut into chunks of
- * min(64, SOLO_DEC_SCRATCH_CAP / (n_streams x 2216)) packets but never less than ONE, so one buffer holds max(n_streams x 2216 B, at most
- * SOLO_DEC_SCRATCH_CAP bytes) (environment, read when the handle decodes for the first time; default -- also for 0 or an unparsable
+ * min(64, SOLO_DEC_SCRATCH_CAP / (n_streams x 2216)) packets but never less than ONE, and the chunks of a call use the buffer one after the other, so it holds at most
+ * max(n_streams x 2216 B, SOLO_DEC_SCRATCH_CAP bytes) (environment, read when the handle decodes for the first time; default -- also for 0 or an unparsable
  * value -- 1 GiB: 4096 streams x 64 packets are 581 MB, 8192 streams get chunks of 59 packets).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct solo_batch solo_batch_t;
@@ -123,8 +123,8 @@ int32_t solo_batch_reset(solo_batch_t *b, void *hip_stream);
  * Returns -1 and changes nothing (the checks run on the host before anything is enqueued) when n <= 0 or n > N, an index is out of
  * range or listed twice, `which` names a direction the handle does not have, a control is given for a direction the call does not
  * reset, or a control fails the checks of solo_batch_create (in the 32 kHz mode every stream's rate must leave SILK >= 14000 bps).
- * Ordering as solo_batch_reset: the init kernels wait for this handle's encode / decode work still in flight on its internal streams
- * (async joins included); work enqueued on hip_stream after the call sees the new states.  The host arrays are free when the call
+ * Ordering as solo_batch_reset: the init kernels wait for this handle's encode work still in flight on its internal streams
+ * (async joins included) and for its latest decode call, whichever stream that was issued on; work enqueued on hip_stream after the call sees the new states.  The host arrays are free when the call
  * returns (the records travel as kernel arguments).  Reset streams play on with the receiver ring as it is: see solo_recv_reset_streams.
  * A handle created with one control and given per-stream controls here is the way to run mixed rates / DTX / useMDIndex in one batch. */
 int32_t solo_batch_reset_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, int32_t which,
@@ -401,8 +401,8 @@ int32_t solo_resample_rows(solo_resampler_t *r, const int32_t *d_rows, int32_t n
  *   untouched and d_count = {n, 0, bytes taken}.  A blob may hold more sections than the call takes.  With section 4 the queue of a listed
  *   stream is replaced entirely; the handle-wide solo_recv_stats words do not change; the per-stream counters are written only if the
  *   handle has allocated them (solo_recv_track(b, 1) at any time before).
- * Ordering as solo_batch_reset_streams: the kernels wait for this handle's encode / decode work still in flight on its internal streams
- * (async joins included); work enqueued on hip_stream after the call sees the result.  No host synchronisation, no allocation.  The words
+ * Ordering as solo_batch_reset_streams: the kernels wait for this handle's encode work still in flight on its internal streams
+ * (async joins included) and for its latest decode call, whichever stream that was issued on; work enqueued on hip_stream after the call sees the result.  No host synchronisation, no allocation.  The words
  * of the persistent encoder schedule (flags, tickets) belong to the handle and do not travel: an imported stream encodes under the
  * default schedule like any other.  The legacy AGR_Sate_* handles are not covered. */
 typedef struct { int32_t streams, refused; int64_t bytes; } solo_migrate_count_t;   /* 16 bytes */

@@ -171,7 +171,19 @@ extern "C" const solo_enc_ops* solo_wb_enc_ops();                               
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
 #define SOLO_MAX_CHUNKS 64
-#define SOLO_N_VERDICTS 10
+// verdict words of subset calls (solo_stream_list_check_kernel), one per kind of call so that calls of different kinds in flight on
+// different streams do not share one
+enum {
+    SOLO_VERDICT_ENC = 0,            // [0, 1] encode calls (by enc_seq: two can be in flight with asynchronous joins)
+    SOLO_VERDICT_DEC = 2,            // decode
+    SOLO_VERDICT_RING,               // receiver play-out
+    SOLO_VERDICT_SEND,               // solo_send_pack_streams
+    SOLO_VERDICT_MIX,                // solo_mix (its room ids)
+    SOLO_VERDICT_REPORT,             // solo_recv_report
+    SOLO_VERDICT_EXPORT,             // solo_batch_export_streams
+    SOLO_VERDICT_IMPORT,             // [8, 9] solo_batch_import_streams (its list, its records)
+    SOLO_N_VERDICTS = SOLO_VERDICT_IMPORT + 2
+};
 struct solo_batch {
     int32_t n_streams;
     int32_t slot;
@@ -183,15 +195,14 @@ struct solo_batch {
     const solo_enc_ops* eops;        // launch table of the build that matches the encoder's rate (solo_enc_kernels.h)
 #endif
     void* d_nsq_ring;                // emission-ring scratch of the quantiser launches (one launch group of streams; frame-local data)
-    // decoder pipeline: symbol extraction (stream sP) one chunk of packets ahead of the decoder proper (stream sS)
-    hipStream_t sP, sS;
-    hipEvent_t evDFork, evDJoin, evDJoin2, evP[2], evS[2];
-    void* d_parsed[2];               // extraction records of the chunk being extracted / being decoded
-    size_t parsed_bytes;             // size of each
-    int parsed_two;                  // both buffers have that size (a call of one chunk needs only the first)
+    // decoder: every kernel of a decode call runs on the caller's stream; two-kernel path: per chunk of packets the symbol extraction,
+    // then the decoder proper
+    hipEvent_t evDecDone;            // end of the most recent decode call, on whichever stream it was issued
+    int dec_done_recorded;           // (a decode call has happened: evDecDone can be waited for)
+    void* d_parsed;                  // extraction records of one chunk, grown on demand
+    size_t parsed_bytes;
     int dec_pipe_ready, dec_split, dec_chunk, dec_first;
     size_t dec_scratch_cap;          // env SOLO_DEC_SCRATCH_CAP, read when the handle's decode pipeline is set up
-    unsigned int dec_calls;          // two-kernel decode calls so far (evDJoin / evDJoin2 are recorded once > 0)
     void* d_rc_scratch;              // range-coder byte buffers of one coding launch (the launches of a call run in order on sC)
     size_t rc_scratch_bytes;
     void* d_enc_work;                // hand-over records of one launch: SxNsqIn[N][P][2] | SxNsqOut[N][P][2] | SxCodeIn[N][P]
@@ -235,10 +246,7 @@ struct solo_batch {
     uint32_t* d_recv_trk;
     int recv_track;
     int32_t* d_recv_sel;
-    // verdict words of subset calls (solo_stream_list_check_kernel): [0, 1] encode calls (by enc_seq: two can be in flight with
-    // asynchronous joins), [2] decode, [3] receiver play-out, [4] solo_send_pack_streams, [5] solo_mix (its room ids), [6] solo_recv_report,
-    // [7] solo_batch_export_streams, [8, 9] solo_batch_import_streams (its list, its records)
-    uint32_t* d_verdict;
+    uint32_t* d_verdict;             // [SOLO_N_VERDICTS], indexed by SOLO_VERDICT_*
     void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack call (solo_send.h), grown on demand
     size_t send_scratch_bytes;
     void* d_mix_scratch;             // room plan, energies and flags of a solo_mix call (solo_mix.h), grown on demand
@@ -285,6 +293,20 @@ template <typename T>
 static void dev_free(T*& p) {
     if (p) (void)hipFree(p);
     p = NULL;
+}
+// Grows a device scratch of the handle to `need` bytes (it never shrinks).  `s` is the stream whose kernels may still use the old
+// buffer: growing synchronises it, steady-state calls do not.
+static hipError_t grow_scratch(void*& p, size_t& bytes, size_t need, hipStream_t s) {
+    if (need <= bytes) return hipSuccess;
+    if (p) {
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        dev_free(p);
+        bytes = 0;
+    }
+    const hipError_t e = hipMalloc(&p, need);
+    if (e == hipSuccess) bytes = need;
+    return e;
 }
 
 #ifdef SOLO_WITH_ENCODER
@@ -369,7 +391,8 @@ int32_t solo_batch_wait_encode(solo_batch_t* b, void* hip_stream, int32_t which)
 }
 int32_t solo_batch_last_encode_chunks(const solo_batch_t* b) { return b ? b->last_chunks : 0; }
 
-// Makes `s` wait for the handle's encode / decode work still in flight on its internal streams (before init kernels overwrite states).
+// Makes `s` wait for the handle's encode work still in flight on its internal streams and for its most recent decode call (before
+// init kernels overwrite states).
 static int32_t solo_wait_in_flight(solo_batch_t* b, hipStream_t s) {
     if (b->pipe_ready && b->enc_seq > 0) {
         // kernels of the most recent encode calls may still run on the internal streams (always so with async joins, and when
@@ -381,11 +404,8 @@ static int32_t solo_wait_in_flight(solo_batch_t* b, hipStream_t s) {
             SOLO_CHECK(hipStreamWaitEvent(s, b->evJoinC[js], 0));
         }
     }
-    if (b->have_dec && b->dec_pipe_ready && b->dec_split && b->dec_calls > 0) {
-        // like the encoder above: a decode call issued on another stream may still run on the internal streams
-        SOLO_CHECK(hipStreamWaitEvent(s, b->evDJoin, 0));
-        SOLO_CHECK(hipStreamWaitEvent(s, b->evDJoin2, 0));
-    }
+    // (the most recent decode call may have been issued on another stream than `s`)
+    if (b->dec_done_recorded) SOLO_CHECK(hipStreamWaitEvent(s, b->evDecDone, 0));
     return 0;
 }
 
@@ -536,13 +556,8 @@ void solo_batch_destroy(solo_batch_t* b) {
     if (!b) return;
     solo_recv_free(b);
     dev_free(b->d_recv_trk);
-    if (b->dec_pipe_ready && b->dec_split) {
-        (void)hipStreamSynchronize(b->sP); (void)hipStreamSynchronize(b->sS);
-        (void)hipStreamDestroy(b->sP); (void)hipStreamDestroy(b->sS);
-        (void)hipEventDestroy(b->evDFork); (void)hipEventDestroy(b->evDJoin); (void)hipEventDestroy(b->evDJoin2);
-        for (int i = 0; i < 2; i++) { (void)hipEventDestroy(b->evP[i]); (void)hipEventDestroy(b->evS[i]); }
-    }
-    for (int i = 0; i < 2; i++) dev_free(b->d_parsed[i]);
+    if (b->dec_pipe_ready) (void)hipEventDestroy(b->evDecDone);
+    dev_free(b->d_parsed);
     dev_free(b->d_dec_state);
     dev_free(b->d_verdict);
     dev_free(b->d_send_scratch);
@@ -564,109 +579,85 @@ void solo_batch_destroy(solo_batch_t* b) {
     delete b;
 }
 
-// Chunks of the two-kernel decoder.  The extraction of chunk c + 1 was meant to hide behind the synthesis of chunk c, but the two
-// kernels never share a compute unit (the synthesis kernel's 16 workgroups take all of its LDS and registers), so every chunk
-// boundary only costs: a synthesis launch reloads and stores 4096 stream states, and its last workgroups run in a thinly populated
-// tail.  Measured (4096 streams x 50 packets): chunks of 24 packets after a first one of 4: 9.0 ms; 6 + 44: 7.7 ms; ONE chunk:
-// 7.4 ms (8192 streams, 30 % description loss: 17.5 / 16.2 / 16.0 ms).  So a call is one chunk up to 64 packets (the extraction
-// records of a chunk are 2216 B per packet: 581 MB for 4096 streams x 64 packets), longer calls are cut into chunks of 64.
+// Chunks of the two-kernel decoder.  A call runs on the caller's stream, chunk after chunk: the extraction of a chunk's symbols, then
+// the decoder proper over the same packets, both on ONE buffer of records.  Nothing overlaps, and nothing could: the two kernels never
+// share a compute unit (the synthesis kernel's 16 workgroups take all of its LDS and registers), so an extraction running ahead on a
+// stream of its own would hide nothing.  Every chunk boundary only costs: a synthesis launch reloads and stores 4096 stream states,
+// and its last workgroups run in a thinly populated tail.  Measured (4096 streams x 50 packets): chunks of 24 packets after a first
+// one of 4: 9.0 ms; 6 + 44: 7.7 ms; ONE chunk: 7.4 ms (8192 streams, 30 % description loss: 17.5 / 16.2 / 16.0 ms).  So a call is
+// one chunk up to 64 packets (the extraction records of a chunk are 2216 B per packet: 581 MB for 4096 streams x 64 packets), longer
+// calls are cut into chunks of 64; chunks exist to bound that buffer, not to gain time.
 #define SOLO_DEC_FIRST_CHUNK 64
 #define SOLO_DEC_CHUNK_DEFAULT 64
 static_assert(2 * sizeof(SxExtracted) + 8 == 2216, "include/solo_mi355x.h documents 2216 bytes of extraction records (2 x 1104 B + two list entries) per packet (16 kHz API rate)");
+// one-time set-up of a handle's decode pipeline: the knobs and the event that marks the end of a decode call
+static int32_t solo_dec_pipe_setup(solo_batch* b) {
+    b->dec_split = env_int("SOLO_DEC_SPLIT", 1);
+    if (ctrl_frames_per_packet(b->dec_ctrl.framesize_ms) == 1) b->dec_split = 0;      // (the extraction records describe two-frame packets)
+    b->dec_chunk = env_int("SOLO_DEC_CHUNK", SOLO_DEC_CHUNK_DEFAULT);
+    if (b->dec_chunk <= 0) b->dec_chunk = 1 << 30;
+    b->dec_first = env_int("SOLO_DEC_FIRST_CHUNK", SOLO_DEC_FIRST_CHUNK);
+    if (b->dec_first <= 0) b->dec_first = SOLO_DEC_FIRST_CHUNK;
+    // (read per handle like the other SOLO_DEC_* knobs; a value that does not parse to a positive number means the default)
+    const char* e = getenv("SOLO_DEC_SCRATCH_CAP");
+    b->dec_scratch_cap = e ? (size_t)strtoull(e, NULL, 10) : 0;
+    if (b->dec_scratch_cap == 0) b->dec_scratch_cap = (size_t)1 << 30;
+    SOLO_CHECK(hipEventCreateWithFlags(&b->evDecDone, hipEventDisableTiming));
+    b->dec_pipe_ready = 1;
+    return 0;
+}
+// Two kernels, chunk by chunk on `st`: the symbols of every description of a chunk of packets are read off the range coder at once, one
+// lane each (X_c); the decoder proper, one wavefront per stream, packets in order, follows on the same record buffer (D_c).  Stream order
+// is all the ordering there is: X_c after D_{c-1} (the buffer is free again), D_c after X_c.
+static hipError_t solo_decode_chunks(solo_batch_t* b, const int32_t* map, int ns, const uint32_t* verdict, const uint8_t* d_bits, const int16_t* d_nbytes,
+                                     const uint8_t* d_recv, int32_t n_packets, int16_t* d_pcm, int32_t* d_status, hipStream_t st) {
+    // packets per chunk: the knob, capped so that the buffer of extraction records stays below SOLO_DEC_SCRATCH_CAP bytes (default 1 GiB;
+    // the records are 2216 B per packet at the 16 kHz API rate: 4096 streams x 64 packets = 581 MB, 65536 streams -> 7 packets per chunk).
+    // include/solo_mi355x.h states the footprint.
+    const size_t rec_bytes = b->dops->extracted_bytes;
+    int cp = n_packets < b->dec_chunk ? n_packets : b->dec_chunk;
+    {   // (floor: one packet per chunk -- a handle with more than cap / 2216 streams holds n_streams x 2216 B, see the header)
+        const size_t fit = b->dec_scratch_cap / ((size_t)ns * rec_bytes);
+        if ((size_t)cp > fit) cp = fit < 1 ? 1 : (int)fit;
+    }
+    // (a first chunk of SOLO_DEC_FIRST_CHUNK packets where the call is longer than two of them; never larger than the buffer: c0 <= cp)
+    const int c0 = (n_packets > 2 * b->dec_first && cp > b->dec_first) ? b->dec_first : cp;
+    const int nchunks = 1 + (n_packets - c0 + cp - 1) / cp;
+    const size_t need = (size_t)ns * (size_t)cp * rec_bytes + 256;      // (+ the count of the listed description slots)
+    if (need > b->parsed_bytes && b->dec_done_recorded) {
+        // (belt and braces: `st` already waits for the previous call, on whichever stream that was issued, and growing synchronises `st`)
+        const hipError_t e = hipEventSynchronize(b->evDecDone);
+        if (e != hipSuccess) return e;
+    }
+    hipError_t lerr = grow_scratch(b->d_parsed, b->parsed_bytes, need, st);
+    for (int c = 0; c < nchunks && lerr == hipSuccess; c++) {
+        const int p0 = c == 0 ? 0 : c0 + (c - 1) * cp, pc = c == 0 ? c0 : ((p0 + cp <= n_packets) ? cp : n_packets - p0);
+        lerr = b->dops->extract(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot, b->d_parsed, map, verdict, st);
+        if (lerr != hipSuccess) break;
+        lerr = b->dops->synth(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot, b->d_parsed, d_pcm, d_status, map, verdict, st);
+    }
+    return lerr;
+}
 // map = NULL: every stream (solo_batch_decode); else the n listed streams of solo_batch_decode_streams, their records / PCM / status compact
 static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_recv,
                                 int32_t n_packets, int16_t* d_pcm, int32_t* d_status, hipStream_t st) {
     const int ns = map ? n : b->n_streams;
-    uint32_t* verdict = map ? b->d_verdict + 2 : NULL;
+    uint32_t* verdict = map ? b->d_verdict + SOLO_VERDICT_DEC : NULL;
     const bool tm = b->timing && b->ev_ready;
     if (!b->dec_pipe_ready) {
-        b->dec_split = env_int("SOLO_DEC_SPLIT", 1);
-        if (ctrl_frames_per_packet(b->dec_ctrl.framesize_ms) == 1) b->dec_split = 0;      // (the read-ahead records describe two-frame packets)
-        b->dec_chunk = env_int("SOLO_DEC_CHUNK", SOLO_DEC_CHUNK_DEFAULT);
-        if (b->dec_chunk <= 0) b->dec_chunk = 1 << 30;
-        b->dec_first = env_int("SOLO_DEC_FIRST_CHUNK", SOLO_DEC_FIRST_CHUNK);
-        if (b->dec_first <= 0) b->dec_first = SOLO_DEC_FIRST_CHUNK;
-        // (read per handle like the other SOLO_DEC_* knobs; a value that does not parse to a positive number means the default)
-        const char* e = getenv("SOLO_DEC_SCRATCH_CAP");
-        b->dec_scratch_cap = e ? (size_t)strtoull(e, NULL, 10) : 0;
-        if (b->dec_scratch_cap == 0) b->dec_scratch_cap = (size_t)1 << 30;
-        if (b->dec_split) {
-            SOLO_CHECK(hipStreamCreateWithFlags(&b->sP, hipStreamNonBlocking));
-            SOLO_CHECK(hipStreamCreateWithFlags(&b->sS, hipStreamNonBlocking));
-            SOLO_CHECK(hipEventCreateWithFlags(&b->evDFork, hipEventDisableTiming));
-            SOLO_CHECK(hipEventCreateWithFlags(&b->evDJoin, hipEventDisableTiming));
-            SOLO_CHECK(hipEventCreateWithFlags(&b->evDJoin2, hipEventDisableTiming));
-            for (int i = 0; i < 2; i++) {
-                SOLO_CHECK(hipEventCreateWithFlags(&b->evP[i], hipEventDisableTiming));
-                SOLO_CHECK(hipEventCreateWithFlags(&b->evS[i], hipEventDisableTiming));
-            }
-        }
-        b->dec_pipe_ready = 1;
+        const int32_t r = solo_dec_pipe_setup(b);
+        if (r) return r;
     }
+    // the previous decode call may have been issued on ANOTHER stream than this one: it used the same states, record buffer and verdict word
+    if (b->dec_done_recorded) SOLO_CHECK(hipStreamWaitEvent(st, b->evDecDone, 0));
     if (tm) (void)hipEventRecord(b->evDec[0], st);
-    if (!b->dec_split) {
-        // single kernel: one wavefront per stream parses (two lanes) and synthesises
-        if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));
-        const hipError_t e = b->dops->decode(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, b->slot, d_pcm, d_status, map, verdict, st);
-        if (tm) { (void)hipEventRecord(b->evDec[1], st); b->ev_dec = 1; }
-        SOLO_CHECK(e);
-        return 0;
-    }
-    // Two kernels: the symbols of every description of a chunk of packets are read off the range coder at once, one lane each; the
-    // decoder proper (one wavefront per stream, packets in order) follows a chunk behind on a second stream; the records go through
-    // two alternating buffers.  X_c follows X_{c-1} and D_{c-2} (buffer free), D_c follows X_c and D_{c-1}.
-    // (a short first chunk -- its extraction has nothing to hide behind -- then long ones: every decoder launch reloads the stream states)
-    // packets per chunk: the knob, capped so that ONE buffer of extraction records stays below SOLO_DEC_SCRATCH_CAP bytes (default 1 GiB;
-    // the records are 2216 B per packet at the 16 kHz API rate: 4096 streams x 64 packets = 581 MB, 65536 streams -> 7 packets per chunk).
-    // A handle holds at most two such buffers (calls longer than one chunk); include/solo_mi355x.h states the footprint.
-    const size_t rec_bytes = b->dops->extracted_bytes;
-    int cp = n_packets < b->dec_chunk ? n_packets : b->dec_chunk;
-    {   // (floor: one packet per chunk -- a handle with more than cap / 2216 streams holds n_streams x 2216 B per buffer, see the header)
-        const size_t fit = b->dec_scratch_cap / ((size_t)ns * rec_bytes);
-        if ((size_t)cp > fit) cp = fit < 1 ? 1 : (int)fit;
-    }
-    const int c0 = (n_packets > 2 * b->dec_first && cp > b->dec_first) ? b->dec_first : cp;      // (never larger than the buffers: c0 <= cp)
-    const int nchunks = 1 + (n_packets - c0 + cp - 1) / cp;
-    const size_t need = (size_t)ns * (size_t)cp * rec_bytes + 256;      // (+ the count of the listed description slots)
-    if (need > b->parsed_bytes || (nchunks > 1 && !b->parsed_two)) {
-        SOLO_CHECK(hipStreamSynchronize(st));
-        (void)hipStreamSynchronize(b->sP);
-        (void)hipStreamSynchronize(b->sS);
-        for (int i = 0; i < 2; i++) dev_free(b->d_parsed[i]);
-        b->parsed_bytes = 0;
-        for (int i = 0; i < 2; i++) SOLO_CHECK(hipMalloc(&b->d_parsed[i], i == 0 || nchunks > 1 ? need : 256));     // (one chunk: one buffer)
-        b->parsed_bytes = need;
-        b->parsed_two = nchunks > 1;
-    }
-    if (b->dec_calls > 0) {
-        // the previous decode call may have been issued on ANOTHER stream than this one: its kernels on sP / sS (and their use of
-        // d_parsed[]) must be done before this call's fork lets the internal streams run on
-        SOLO_CHECK(hipStreamWaitEvent(st, b->evDJoin, 0));
-        SOLO_CHECK(hipStreamWaitEvent(st, b->evDJoin2, 0));
-    }
-    if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));      // (the previous call's kernels, which read the verdict, are done)
-    SOLO_CHECK(hipEventRecord(b->evDFork, st));
-    SOLO_CHECK(hipStreamWaitEvent(b->sP, b->evDFork, 0));
-    SOLO_CHECK(hipStreamWaitEvent(b->sS, b->evDFork, 0));
-    b->dec_calls++;
-    hipError_t lerr = hipSuccess;
-    for (int c = 0; c < nchunks && lerr == hipSuccess; c++) {
-        const int p0 = c == 0 ? 0 : c0 + (c - 1) * cp, pc = c == 0 ? c0 : ((p0 + cp <= n_packets) ? cp : n_packets - p0), k = c & 1;
-        // (every failure inside the loop goes through the join block below: nothing of this call stays forked)
-        if (c >= 2 && (lerr = hipStreamWaitEvent(b->sP, b->evS[k], 0)) != hipSuccess) break;
-        lerr = b->dops->extract(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot, b->d_parsed[k], map, verdict, b->sP);
-        if (lerr != hipSuccess) break;
-        if ((lerr = hipEventRecord(b->evP[k], b->sP)) != hipSuccess) break;
-        if ((lerr = hipStreamWaitEvent(b->sS, b->evP[k], 0)) != hipSuccess) break;
-        lerr = b->dops->synth(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, p0, pc, b->slot, b->d_parsed[k], d_pcm, d_status, map, verdict, b->sS);
-        if (lerr != hipSuccess) break;
-        if ((lerr = hipEventRecord(b->evS[k], b->sS)) != hipSuccess) break;
-    }
-    // join both internal streams back into the caller's (also after a refused launch: nothing stays forked)
-    (void)hipEventRecord(b->evDJoin, b->sP);
-    (void)hipStreamWaitEvent(st, b->evDJoin, 0);
-    (void)hipEventRecord(b->evDJoin2, b->sS);
-    (void)hipStreamWaitEvent(st, b->evDJoin2, 0);
+    hipError_t lerr = map ? launch_list_check(b, map, n, verdict, d_status, st) : hipSuccess;
+    if (lerr == hipSuccess && b->dec_split)
+        lerr = solo_decode_chunks(b, map, ns, verdict, d_bits, d_nbytes, d_recv, n_packets, d_pcm, d_status, st);
+    else if (lerr == hipSuccess)         // single kernel: one wavefront per stream parses (two lanes) and synthesises
+        lerr = b->dops->decode(b->d_dec_state, d_bits, d_nbytes, d_recv, ns, n_packets, b->slot, d_pcm, d_status, map, verdict, st);
+    // (also after a refused launch: what was enqueued still runs)
+    if (hipEventRecord(b->evDecDone, st) == hipSuccess) b->dec_done_recorded = 1;
     if (tm) { (void)hipEventRecord(b->evDec[1], st); b->ev_dec = 1; }
     SOLO_CHECK(lerr);
     return 0;
@@ -751,7 +742,7 @@ int32_t solo_recv_decode_streams(solo_batch_t* b, const int32_t* d_streams, int3
                                  void* hip_stream) {
     if (!b || !b->d_recv_ring || !d_streams || n <= 0 || n > b->n_streams || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
-    uint32_t* verdict = b->d_verdict + 3;
+    uint32_t* verdict = b->d_verdict + SOLO_VERDICT_RING;
     SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, d_status, st));
     if (b->recv_track) SOLO_CHECK(solo_recv_account_launch(b->d_recv_lens, b->d_recv_play, b->d_recv_trk, n, n_packets, b->recv_depth, d_streams, verdict, st));
     SOLO_CHECK(b->dops->ring(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, n, n_packets, b->recv_depth, b->recv_slot, d_pcm, d_status,
@@ -786,7 +777,7 @@ int32_t solo_recv_report(solo_batch_t* b, const int32_t* d_streams, int32_t n, c
     if ((!d_reports && !d_play_list && !d_play_rows) || ((d_play_list || d_play_rows) && !d_count) || (flags & ~SOLO_RECV_REPORT_CLEAR_MARGIN)) return -1;
     if ((uintptr_t)d_reports & 15) return -1;               // (the records are stored 16 bytes at a time)
     hipStream_t st = (hipStream_t)hip_stream;
-    uint32_t* verdict = b->d_verdict + 6;
+    uint32_t* verdict = b->d_verdict + SOLO_VERDICT_REPORT;
     if (d_streams) SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
     SxRecvReportArgs a;
     a.lens = b->d_recv_lens; a.play = b->d_recv_play; a.trk = b->d_recv_trk; a.map = d_streams; a.min_ready_v = d_min_ready;
@@ -804,20 +795,11 @@ static int32_t solo_send_impl(solo_batch_t* b, const int32_t* map, int32_t n, co
                               uint8_t* d_payload, int64_t payload_capacity, solo_send_count_t* d_count, hipStream_t st) {
     if (!d_bits || !d_nbytes || !d_records || !d_payload || !d_count || n_packets <= 0 || max_records < 0 || payload_capacity < 0) return -1;
     if ((int64_t)n * (int64_t)n_packets * 2 >= ((int64_t)1 << 31)) return -1;
-    const size_t need = solo_send_scratch_bytes(n * n_packets);
-    if (need > b->send_scratch_bytes) {                    // grow the scan's scratch (synchronises; steady-state calls do not)
-        if (b->d_send_scratch) {
-            SOLO_CHECK(hipStreamSynchronize(st));
-            dev_free(b->d_send_scratch);
-            b->send_scratch_bytes = 0;
-        }
-        SOLO_CHECK(hipMalloc(&b->d_send_scratch, need));
-        b->send_scratch_bytes = need;
-    }
+    SOLO_CHECK(grow_scratch(b->d_send_scratch, b->send_scratch_bytes, solo_send_scratch_bytes(n * n_packets), st));
     // the packet geometry is the handle's: that of its encoder, or of its decoder when it has none
     const int hbb = b->have_enc ? ctrl_hb_bytes(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode, b->enc_ctrl.framesize_ms)
                                 : ctrl_hb_bytes(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode, b->dec_ctrl.framesize_ms);
-    uint32_t* verdict = b->d_verdict + 4;
+    uint32_t* verdict = b->d_verdict + SOLO_VERDICT_SEND;
     if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, NULL, st));
     SxSendArgs a;
     a.bits = d_bits; a.nbytes = d_nbytes; a.send = d_send; a.seq_base = d_seq_base; a.map = map;
@@ -860,21 +842,12 @@ int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_
     const uintptr_t bytes = (uintptr_t)n * (uintptr_t)n_packets * (uintptr_t)L * sizeof(int16_t);
     if ((in0 & 15) || (out0 & 15) || (in0 < out0 + bytes && out0 < in0 + bytes)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
-    const size_t need = solo_mix_scratch_bytes(n, n_packets);
-    if (need > b->mix_scratch_bytes) {                     // grow the scratch (synchronises; steady-state calls do not)
-        if (b->d_mix_scratch) {
-            SOLO_CHECK(hipStreamSynchronize(st));
-            dev_free(b->d_mix_scratch);
-            b->mix_scratch_bytes = 0;
-        }
-        SOLO_CHECK(hipMalloc(&b->d_mix_scratch, need));
-        b->mix_scratch_bytes = need;
-    }
+    SOLO_CHECK(grow_scratch(b->d_mix_scratch, b->mix_scratch_bytes, solo_mix_scratch_bytes(n, n_packets), st));
     SxMixArgs a;
     a.pcm_in = d_pcm_in; a.gain = d_gain_q12; a.pcm_out = d_pcm_out; a.energy = d_energy; a.mixed = d_mixed;
     a.counts = NULL; a.starts = NULL; a.members = NULL;
     a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
-    SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + 5, st));
+    SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
     return 0;
 }
 
@@ -999,7 +972,7 @@ int32_t solo_batch_export_streams(solo_batch_t* b, const int32_t* d_streams, int
         const int32_t r = solo_wait_in_flight(b, st);
         if (r) return r;
     }
-    uint32_t* verdict = b->d_verdict + 7;
+    uint32_t* verdict = b->d_verdict + SOLO_VERDICT_EXPORT;
     SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
     SOLO_CHECK(solo_migrate_export_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
     return 0;
@@ -1012,7 +985,7 @@ int32_t solo_batch_import_streams(solo_batch_t* b, const int32_t* d_streams, int
         const int32_t r = solo_wait_in_flight(b, st);
         if (r) return r;
     }
-    uint32_t* verdict = b->d_verdict + 8;
+    uint32_t* verdict = b->d_verdict + SOLO_VERDICT_IMPORT;
     SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
     SOLO_CHECK(solo_migrate_import_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
     return 0;
@@ -1206,16 +1179,8 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     if (nchunks > SOLO_MAX_CHUNKS) { cp = (n_packets + SOLO_MAX_CHUNKS - 1) / SOLO_MAX_CHUNKS; nchunks = (n_packets + cp - 1) / cp; }
     {   // scratch of one coding launch: the byte buffers of its descriptions
         const int gs = (b->group_streams > 0 && b->group_streams < b->n_streams) ? b->group_streams : b->n_streams;
-        const size_t need = ops->rc_scratch_bytes(gs, cp);
-        if (need > b->rc_scratch_bytes) {
-            if (b->d_rc_scratch) {
-                SOLO_CHECK(hipStreamSynchronize(b->sC));             // (a coding launch of the previous call may still read the old one)
-                dev_free(b->d_rc_scratch);
-                b->rc_scratch_bytes = 0;
-            }
-            SOLO_CHECK(hipMalloc(&b->d_rc_scratch, need));
-            b->rc_scratch_bytes = need;
-        }
+        // (sC: a coding launch of the previous call may still read the old one)
+        SOLO_CHECK(grow_scratch(b->d_rc_scratch, b->rc_scratch_bytes, ops->rc_scratch_bytes(gs, cp), b->sC));
     }
     const bool tm_req = b->timing && b->tev_ready;
     uint32_t* verdict = NULL;
@@ -1223,7 +1188,7 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         // the layout of the hand-over records depends on the list: no chunk-wise reuse across a subset call, either side
         b->evC_valid = 0;
         // the verdict word of this call; the call two before used the same one: its kernels must be through
-        verdict = b->d_verdict + (b->enc_seq & 1u);
+        verdict = b->d_verdict + SOLO_VERDICT_ENC + (b->enc_seq & 1u);
         if (b->enc_seq >= 2) {
             SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinA[b->enc_seq & 1u], 0));
             SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinC[b->enc_seq & 1u], 0));
