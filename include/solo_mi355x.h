@@ -334,6 +334,75 @@ int32_t solo_mix(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t n_
                  const int32_t *d_room, int32_t n_rooms, const int16_t *d_gain_q12, int32_t max_speakers,
                  int16_t *d_pcm_out, int64_t *d_energy, uint8_t *d_mixed,
                  solo_mix_count_t *d_count, void *hip_stream);
+/* Mixing bridge with SHARED listener mixes: with max_speakers = k every member of a room that is not among the picked speakers hears the
+ * same samples, sat16(S), so this form writes that row once per room and a personal row only per speaker -- the encoder behind it then runs
+ * once per speaker and once per room instead of once per listener.  c_j, e_j, sel (per room and packet) and S are EXACTLY those of solo_mix
+ * (same arithmetic, same order: larger energy first, then smaller row index); max_speakers must be in [1, 64], so the 8191-row limit of the
+ * mix-everyone form does not apply.  d_pcm_in, d_room, n_rooms, d_gain_q12, d_energy, d_mixed: as for solo_mix.
+ *   speaker of the call   a row in a room that is in sel in at least one of the call's packets, or whose d_keep[i] != 0 (d_keep: uint8 [n] or
+ *                         NULL -- the caller's hangover policy: a row keeps its own encoder for a while after it stopped talking)
+ *   shared room           a room with at least one member that is not a speaker of the call
+ *   d_pcm_spk   int16 [n][P][L], only the first `speakers` rows are written: row k belongs to the k-th speaker i in increasing row order,
+ *               packet p of it is sat16(S_p - (i in sel_p ? c_i : 0))
+ *   d_spk_rows  int32 [n] or NULL: d_spk_rows[k] = i
+ *   d_spk_list  int32 [n]: d_spk_list[k] = d_slots ? d_slots[i] : i.  d_slots (int32 [n] or NULL) maps rows to transmit slots, strictly
+ *               increasing and non-negative (the list the rows were decoded by); the list is then strictly increasing: a valid d_streams of
+ *               solo_batch_encode_streams on the participants' handle
+ *   d_pcm_room  int16 [n_rooms][P][L], only the first `shared` rows are written: row j belongs to the j-th shared room in increasing room
+ *               order, packet p of it is sat16(S_p)
+ *   d_room_list int32 [n_rooms]: d_room_list[j] = that room's id; strictly increasing: a valid d_streams on a second handle with one slot per room
+ *   d_source    int32 [n]: k for a speaker, n + j for any other member of the j-th shared room, -1 for a row in no room.  With the encoded
+ *               speakers in rows 0.. and the encoded rooms in rows n.. of ONE table this is the d_source of solo_send_fanout.
+ *   d_count     rows, rooms as for solo_mix; speakers, shared; clipped: saturated samples among the rows that were written
+ * Nothing beyond the counts is written (rows `speakers`.. of d_pcm_spk, d_spk_list, d_spk_rows, rows `shared`.. of d_pcm_room, d_room_list),
+ * and of d_energy / d_mixed nothing for rows in no room.
+ * Returns -1 with nothing enqueued for everything solo_mix refuses; max_speakers outside [1, 64]; a NULL d_pcm_spk, d_spk_list, d_pcm_room,
+ * d_room_list, d_source or d_count; PCM outputs that are not 16-byte aligned or overlap the input or each other.  A room id outside
+ * [-1, n_rooms) or a d_slots that is not strictly increasing from a non-negative start is found on the device, ahead of the other kernels:
+ * nothing is written except d_count->rows = -1.
+ * Any handle will do.  Ten short kernels on hip_stream only, no host synchronisation, capturable -- except that the handle's scratch (the
+ * one of solo_mix; 13 bytes per row and packet + 28 per row) grows, with a stream synchronisation, when a call is larger than every one
+ * before it.  The energies are computed by one wavefront per (row, packet), so one room of thousands costs what thousands of small rooms
+ * cost.  The call does not wait for the handle's internal streams, and calls on one handle must be ordered. */
+typedef struct {
+    int32_t rows, rooms;        /* as solo_mix_count_t; rows = -1: call refused on the device */
+    int32_t speakers, shared;   /* rows of d_pcm_spk / d_pcm_room that were written */
+    int64_t clipped;            /* samples of those rows that saturated */
+} solo_mix_shared_count_t;     /* 24 bytes */
+int32_t solo_mix_shared(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t n_packets,
+                        const int32_t *d_room, int32_t n_rooms, const int16_t *d_gain_q12, int32_t max_speakers,
+                        const uint8_t *d_keep, const int32_t *d_slots,
+                        int16_t *d_pcm_spk, int32_t *d_spk_list, int32_t *d_spk_rows,
+                        int16_t *d_pcm_room, int32_t *d_room_list, int32_t *d_source,
+                        int64_t *d_energy, uint8_t *d_mixed,
+                        solo_mix_shared_count_t *d_count, void *hip_stream);
+/* Sender back end for shared sources: ONE table of encoded packets (d_bits [n_src][P][slot], d_nbytes [n_src][P][2], the layout the encode
+ * calls write), MANY destinations.  Destination i of n_dst sends the packets of source row d_source[i] (-1: it sends nothing and is not
+ * counted) as stream d_dst_stream ? d_dst_stream[i] : i, with the sequence numbers first_seq + (d_seq_base ? d_seq_base[i] : 0) + p and under
+ * the mask d_send[i][p] (uint8 [n_dst][P], bit 0 = MD1, bit 1 = MD2 || HB, NULL = both).  The send step behind solo_mix_shared, and a
+ * forwarding server's copy of one sender to many receivers without transcoding.
+ * Which datagrams a source packet yields, and when it counts as `empty` or `refused`, are the rules of solo_send_pack applied to the
+ * source's length record with the destination's mask and sequence number; empty / refused are counted once per (destination, packet).
+ *   pool      every source datagram is stored ONCE: the valid datagrams (both descriptions, whatever the masks say) of every source row that
+ *             at least one destination names, back to back, per packet (outer), then source row, then description 0 before 1.  Rows nobody
+ *             names are never read -- in the bridge their length words are uninitialised.
+ *   records   per packet (outer), then destination i, then description 0 before 1: {stream, seq, desc, offset of the shared datagram, len}.
+ *             Records of destinations with one source carry the same offset; solo_recv_insert files every one of them.
+ * A pool datagram is written iff it ends inside min(payload_capacity, 2^31 - 1) -- a prefix of the pool; record k is written iff
+ * k < max_records and its datagram was.  (A byte cap that cuts inside a packet's pool can therefore leave holes among that packet's
+ * records; the record cap alone cuts a prefix.)  d_count: records / bytes written, records_needed / bytes_needed (the pool's) without the
+ * caps; caps of 0 only count.
+ * Returns -1 with nothing enqueued for a NULL handle, d_bits, d_nbytes, d_source, d_records, d_payload or d_count; n_src, n_dst or
+ * n_packets <= 0; a negative cap; n_dst x n_packets x 2 >= 2^31 or n_src x n_packets x 2 >= 2^31.  A d_source entry outside [-1, n_src) is
+ * found on the device, ahead of the other kernels: nothing is written except d_count->records = -1.
+ * Any handle will do (slot_bytes and the packet geometry are used, and the scratch of solo_send_pack: 8 bytes per source packet, 4 per source
+ * row and 24 per 256 packets, grown as there).  Six short kernels on hip_stream only, no host synchronisation; the call does not wait for the handle's
+ * internal streams, and calls on one handle must be ordered. */
+int32_t solo_send_fanout(solo_batch_t *b, const uint8_t *d_bits, const int16_t *d_nbytes, int32_t n_src,
+                         const int32_t *d_source, const int32_t *d_dst_stream, int32_t n_dst,
+                         const uint8_t *d_send, int32_t n_packets, const int32_t *d_seq_base, int32_t first_seq,
+                         solo_arrival_t *d_records, int32_t max_records, uint8_t *d_payload, int64_t payload_capacity,
+                         solo_send_count_t *d_count, void *hip_stream);
 /* PCM rate conversion on the device: the reference SDK's own fixed-point resampler (SKP_Silk_resampler_init / SKP_Silk_resampler), bit for
  * bit and with its stream state, so that callers on handles of different rates meet in one mix and 8 / 48 kHz endpoints need no host
  * round trip.  A resampler is an object of its own -- it sits BETWEEN two handles -- with n_rows independent rows of filter memory.

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "solo_batch_state_bytes", "solo_batch_export_streams", "solo_batch_import_streams",
     "solo_resample_create", "solo_resample_destroy", "solo_resample_out_samples", "solo_resample_reset", "solo_resample_reset_rows",
     "solo_resample", "solo_resample_rows",
+    "solo_mix_shared", "solo_send_fanout",
 ]
 
 
@@ -55,6 +56,11 @@ class solo_send_count_t(C.Structure):
 class solo_mix_count_t(C.Structure):
     """what a solo_mix call did (include/solo_mi355x.h); 16 bytes"""
     _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("clipped", C.c_int64)]
+
+
+class solo_mix_shared_count_t(C.Structure):
+    """what a solo_mix_shared call did (include/solo_mi355x.h); 24 bytes"""
+    _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("speakers", C.c_int32), ("shared", C.c_int32), ("clipped", C.c_int64)]
 
 
 class solo_resample_count_t(C.Structure):
@@ -172,6 +178,10 @@ def load_library():
     lib.solo_mix.restype = C.c_int32
     lib.solo_mix.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p]
+    lib.solo_mix_shared.restype = C.c_int32
+    lib.solo_mix_shared.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12
+    lib.solo_send_fanout.restype = C.c_int32
+    lib.solo_send_fanout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + _send[2:]
     lib.solo_batch_state_bytes.restype = C.c_int64
     lib.solo_batch_state_bytes.argtypes = [C.c_void_p, C.c_int32]
     for f in (lib.solo_batch_export_streams, lib.solo_batch_import_streams):
@@ -723,6 +733,120 @@ class SoloBatch:
         rows == -1: a room id was refused on the device"""
         c = solo_mix_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
         return {k: int(getattr(c, k)) for k in self.MIX_COUNT}
+
+    # ---- shared listener mixes (solo_mix_shared, solo_send_fanout): a personal mix per speaker, one mix per room for everybody else ----
+    MIX_SHARED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped")
+
+    def mix_shared(self, pcm, room, gain=None, max_speakers=3, keep=None, slots=None, n_rooms=None, energy=None, mixed=None, pcm_spk=None,
+                   pcm_room=None):
+        """solo_mix_shared: pcm int16 [n,P,samples], room int32 [n], gain int16 [n] or None as for mix(); max_speakers in [1, 64];
+        keep uint8 [n] or None (non-zero: the row stays a speaker of the call whether it is picked or not); slots int32 [n] or None (row ->
+        transmit slot, strictly increasing; None = the row index); n_rooms: room ids run up to n_rooms - 1 (default n) ->
+        (pcm_spk int16 [n,P,samples], spk_list int32 [n], spk_rows int32 [n], pcm_room int16 [n_rooms,P,samples], room_list int32 [n_rooms],
+        source int32 [n], count int32 [6] on the device: read it with mix_shared_count()).  Only the first `speakers` rows of pcm_spk /
+        spk_list / spk_rows and the first `shared` rows of pcm_room / room_list are written: pcm_spk[:speakers] is what encode(streams=
+        spk_list[:speakers]) takes on the participants' handle, pcm_room[:shared] what encode(streams=room_list[:shared]) takes on a
+        handle with one slot per room; with both results in one table (speakers in rows 0.., rooms in rows n..) `source` is the source
+        of send_fanout().  A room id outside [-1, n_rooms) or slots that do not grow strictly from a non-negative start refuse the call
+        on the device: rows == -1 in the count, nothing else written.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
+        if not dev(pcm, t.int16, 3):
+            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
+        n, P, L = pcm.shape
+        if L != self.packet_samples or n <= 0 or P <= 0:
+            raise ValueError("pcm: packets of %d samples, at least one row and one packet" % self.packet_samples)
+        if n * P >= 2 ** 31:
+            raise ValueError("n * P must stay below 2^31")
+        n_rooms = n if n_rooms is None else int(n_rooms)
+        if not 0 < n_rooms <= n:
+            raise ValueError("n_rooms: between 1 and the number of rows")
+        max_speakers = int(max_speakers)
+        if not 1 <= max_speakers <= 64:
+            raise ValueError("max_speakers: between 1 and 64")
+        for name, x, dt in (("room", room, t.int32), ("gain", gain, t.int16), ("keep", keep, t.uint8), ("slots", slots, t.int32)):
+            if (x is not None or name == "room") and not (dev(x, dt, 1) and x.shape[0] == n):
+                raise ValueError("%s: a contiguous %s CUDA tensor [%d]" % (name, str(dt).split(".")[-1], n))
+        if energy is not None and not (dev(energy, t.int64, 2) and tuple(energy.shape) == (n, P)):
+            raise ValueError("energy: a contiguous int64 CUDA tensor [%d, %d]" % (n, P))
+        if mixed is not None and not (dev(mixed, t.uint8, 2) and tuple(mixed.shape) == (n, P)):
+            raise ValueError("mixed: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
+        if pcm_spk is not None and not (dev(pcm_spk, t.int16, 3) and tuple(pcm_spk.shape) == (n, P, L)):
+            raise ValueError("pcm_spk: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, L))
+        if pcm_room is not None and not (dev(pcm_room, t.int16, 3) and tuple(pcm_room.shape) == (n_rooms, P, L)):
+            raise ValueError("pcm_room: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n_rooms, P, L))
+        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=pcm.device)
+        if pcm_spk is None:
+            pcm_spk = z((n, P, L), t.int16)
+        if pcm_room is None:
+            pcm_room = z((n_rooms, P, L), t.int16)
+        spk_list, spk_rows, room_list, source = z((n,), t.int32), z((n,), t.int32), z((n_rooms,), t.int32), z((n,), t.int32)
+        count = z((6,), t.int32)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        r = self.lib.solo_mix_shared(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n_rooms, ptr(gain), max_speakers, ptr(keep), ptr(slots),
+                                     pcm_spk.data_ptr(), spk_list.data_ptr(), spk_rows.data_ptr(), pcm_room.data_ptr(), room_list.data_ptr(),
+                                     source.data_ptr(), ptr(energy), ptr(mixed), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_mix_shared -> %d" % r)
+        return pcm_spk, spk_list, spk_rows, pcm_room, room_list, source, count
+
+    def mix_shared_count(self, count):
+        """the count tensor of mix_shared() as a dict (synchronises): rows in a room, rooms with a member, speakers (rows of pcm_spk
+        written), shared (rows of pcm_room written), saturated samples among them; rows == -1: the call was refused on the device"""
+        c = solo_mix_shared_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.MIX_SHARED_COUNT}
+
+    def send_fanout(self, bits, nbytes, source, dst_stream=None, send=None, first_seq=0, seq_base=None, records=None, payload=None):
+        """solo_send_fanout: one table of encoded packets (bits uint8 [n_src,P,slot], nbytes int16 [n_src,P,2]), many destinations: source
+        int32 [n_dst] (the table row destination i sends, -1 = nothing), dst_stream int32 [n_dst] or None (= i), send uint8 [n_dst,P] or
+        None (= both descriptions), seq_base int32 [n_dst] or None -> (records int32 [max,5], payload uint8 [cap], count int32 [8] on the
+        device: read it with send_count()).  Every source datagram is in the pool once; the records of destinations with one source carry
+        the same offset, and recv_insert() of the receiving handle files them all.  Order: packet-major, then destination, then
+        description.  records / payload: the caller's buffers (their sizes are the caps); the defaults, 2*n_dst*P records and
+        n_src*P*slot bytes, never overflow.  A source outside [-1, n_src) refuses the call on the device: records == -1 in the count.
+        Enqueued on the current stream, no synchronisation; with asynchronous joins call wait_encode() first."""
+        t = self.torch
+        dev = lambda x, dt, shape: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
+        if not (getattr(bits, "is_cuda", False) and bits.dtype == t.uint8 and bits.is_contiguous() and len(bits.shape) == 3):
+            raise ValueError("bits: a contiguous uint8 CUDA tensor [n_src, P, slot]")
+        n_src, P, S = bits.shape
+        if S != self.slot or P <= 0 or n_src <= 0:
+            raise ValueError("bits: slots of %d bytes, at least one row and one packet" % self.slot)
+        if not dev(nbytes, t.int16, (n_src, P, 2)):
+            raise ValueError("nbytes: a contiguous int16 CUDA tensor [%d, %d, 2]" % (n_src, P))
+        if not (getattr(source, "is_cuda", False) and source.dtype == t.int32 and source.is_contiguous() and len(source.shape) == 1 and source.shape[0] > 0):
+            raise ValueError("source: a contiguous int32 CUDA tensor [n_dst]")
+        n_dst = source.shape[0]
+        if dst_stream is not None and not dev(dst_stream, t.int32, (n_dst,)):
+            raise ValueError("dst_stream: a contiguous int32 CUDA tensor [%d]" % n_dst)
+        if send is not None and not dev(send, t.uint8, (n_dst, P)):
+            raise ValueError("send: a contiguous uint8 CUDA tensor [%d, %d]" % (n_dst, P))
+        if seq_base is not None and not dev(seq_base, t.int32, (n_dst,)):
+            raise ValueError("seq_base: a contiguous int32 CUDA tensor [%d]" % n_dst)
+        first_seq = int(first_seq)
+        if not -2 ** 31 <= first_seq < 2 ** 31:
+            raise ValueError("first_seq must fit int32")
+        if 2 * n_dst * P >= 2 ** 31 or 2 * n_src * P >= 2 ** 31:
+            raise ValueError("n_dst * P * 2 and n_src * P * 2 must stay below 2^31")
+        if records is not None and not (getattr(records, "is_cuda", False) and records.dtype == t.int32 and records.is_contiguous()
+                                        and len(records.shape) == 2 and records.shape[1] == 5):
+            raise ValueError("records: a contiguous int32 CUDA tensor [max, 5]")
+        if payload is not None and not (getattr(payload, "is_cuda", False) and payload.dtype == t.uint8 and payload.is_contiguous()
+                                        and len(payload.shape) == 1):
+            raise ValueError("payload: a contiguous 1-D uint8 CUDA tensor")
+        if records is None:
+            records = t.zeros((2 * n_dst * P, 5), dtype=t.int32, device=bits.device)
+        if payload is None:
+            payload = t.zeros((n_src * P * S,), dtype=t.uint8, device=bits.device)
+        count = t.zeros((8,), dtype=t.int32, device=bits.device)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
+        r = self.lib.solo_send_fanout(self.h, bits.data_ptr(), nbytes.data_ptr(), n_src, source.data_ptr(), ptr(dst_stream), n_dst, ptr(send), P,
+                                      ptr(seq_base), first_seq, records.data_ptr() or count.data_ptr(), records.shape[0],
+                                      payload.data_ptr() or count.data_ptr(), payload.shape[0], count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_send_fanout -> %d" % r)
+        return records, payload, count
 
     # ---- stream migration (solo_batch_export_streams / solo_batch_import_streams): a running call moves between handles ----
     MIGRATE_COUNT = ("streams", "refused", "bytes")

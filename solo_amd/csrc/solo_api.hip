@@ -29,6 +29,8 @@
 #include "solo_l0_probe.h"
 #include "solo_send.h"          // the sender back end (solo_send_pack): rate-independent, compiled once, not a member of the launch tables
 #include "solo_mix.h"           // the mixing bridge (solo_mix): likewise
+#include "solo_mix_shared.h"    // ... with shared listener mixes (solo_mix_shared)
+#include "solo_fanout.h"        // one source table, many destinations (solo_send_fanout)
 #include "solo_recv_report.h"   // the read side of the receiver ring (solo_recv_report, solo_recv_track): likewise
 #include "solo_migrate.h"       // stream states out of a handle and into another (solo_batch_export_streams / _import_streams): likewise
 #include "solo_resample.h"      // PCM rate conversion between handles and towards 8 / 48 kHz endpoints (solo_resample): likewise
@@ -177,8 +179,8 @@ enum {
     SOLO_VERDICT_ENC = 0,            // [0, 1] encode calls (by enc_seq: two can be in flight with asynchronous joins)
     SOLO_VERDICT_DEC = 2,            // decode
     SOLO_VERDICT_RING,               // receiver play-out
-    SOLO_VERDICT_SEND,               // solo_send_pack_streams
-    SOLO_VERDICT_MIX,                // solo_mix (its room ids)
+    SOLO_VERDICT_SEND,               // solo_send_pack_streams, solo_send_fanout (its source rows)
+    SOLO_VERDICT_MIX,                // solo_mix, solo_mix_shared (their room ids, its slots)
     SOLO_VERDICT_REPORT,             // solo_recv_report
     SOLO_VERDICT_EXPORT,             // solo_batch_export_streams
     SOLO_VERDICT_IMPORT,             // [8, 9] solo_batch_import_streams (its list, its records)
@@ -247,9 +249,9 @@ struct solo_batch {
     int recv_track;
     int32_t* d_recv_sel;
     uint32_t* d_verdict;             // [SOLO_N_VERDICTS], indexed by SOLO_VERDICT_*
-    void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack call (solo_send.h), grown on demand
+    void* d_send_scratch;            // tile totals and tile bases of a solo_send_pack / solo_send_fanout call (solo_send.h, solo_fanout.h), grown on demand
     size_t send_scratch_bytes;
-    void* d_mix_scratch;             // room plan, energies and flags of a solo_mix call (solo_mix.h), grown on demand
+    void* d_mix_scratch;             // room plan, energies and flags of a solo_mix / solo_mix_shared call (solo_mix.h, solo_mix_shared.h), grown on demand
     size_t mix_scratch_bytes;
 };
 
@@ -823,6 +825,24 @@ int32_t solo_send_pack_streams(solo_batch_t* b, const int32_t* d_streams, int32_
                           payload_capacity, d_count, (hipStream_t)hip_stream);
 }
 
+// one source table, many destinations (solo_fanout.h); the handle lends its geometry and its scratch, as above
+int32_t solo_send_fanout(solo_batch_t* b, const uint8_t* d_bits, const int16_t* d_nbytes, int32_t n_src, const int32_t* d_source, const int32_t* d_dst_stream,
+                         int32_t n_dst, const uint8_t* d_send, int32_t n_packets, const int32_t* d_seq_base, int32_t first_seq, solo_arrival_t* d_records,
+                         int32_t max_records, uint8_t* d_payload, int64_t payload_capacity, solo_send_count_t* d_count, void* hip_stream) {
+    if (!b || !sx_fan_args_ok(d_bits, d_nbytes, n_src, d_source, n_dst, n_packets, d_records, max_records, d_payload, payload_capacity, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(b->d_send_scratch, b->send_scratch_bytes, solo_fan_scratch_bytes(n_src, n_dst, n_packets), st));
+    SxFanArgs a;
+    a.bits = d_bits; a.nbytes = d_nbytes; a.source = d_source; a.dst_stream = d_dst_stream; a.send = d_send; a.seq_base = d_seq_base;
+    a.named = NULL; a.pool_off = NULL;
+    a.n_src = n_src; a.n_dst = n_dst; a.n_packets = n_packets; a.slot = b->slot; a.first_seq = first_seq;
+    a.hbb = b->have_enc ? ctrl_hb_bytes(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode, b->enc_ctrl.framesize_ms)
+                        : ctrl_hb_bytes(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode, b->dec_ctrl.framesize_ms);
+    SOLO_CHECK(solo_fan_launch(a, b->d_send_scratch, (SxSendRecord*)d_records, max_records, d_payload, (long long)payload_capacity, (SxSendCount*)d_count,
+                               b->d_verdict + SOLO_VERDICT_SEND, st));
+    return 0;
+}
+
 // ---- mixing bridge (solo_mix.h): decoded rows -> mix-minus rows, room by room ------------------------------------------------------
 static_assert(sizeof(solo_mix_count_t) == sizeof(SxMixCount), "include/solo_mi355x.h and solo_mix.h agree");
 int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
@@ -848,6 +868,30 @@ int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_
     a.counts = NULL; a.starts = NULL; a.members = NULL;
     a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
     SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
+    return 0;
+}
+
+// ... with shared listener mixes (solo_mix_shared.h): a personal row per speaker, one row per room for everybody else
+static_assert(sizeof(solo_mix_shared_count_t) == sizeof(SxMixShCount), "include/solo_mi355x.h and solo_mix_shared.h agree");
+int32_t solo_mix_shared(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
+                        const int16_t* d_gain_q12, int32_t max_speakers, const uint8_t* d_keep, const int32_t* d_slots, int16_t* d_pcm_spk,
+                        int32_t* d_spk_list, int32_t* d_spk_rows, int16_t* d_pcm_room, int32_t* d_room_list, int32_t* d_source, int64_t* d_energy,
+                        uint8_t* d_mixed, solo_mix_shared_count_t* d_count, void* hip_stream) {
+    if (!b) return -1;
+    int L = 0;                       // the packet geometry is the handle's, as for solo_mix
+    if (b->have_dec) L = dec_packet_samples(b);
+#ifdef SOLO_WITH_ENCODER
+    else if (b->have_enc) L = enc_packet_samples(b);
+#endif
+    if (!sx_mixsh_args_ok(d_pcm_in, n, n_packets, L, d_room, n_rooms, max_speakers, d_pcm_spk, d_spk_list, d_pcm_room, d_room_list, d_source, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(b->d_mix_scratch, b->mix_scratch_bytes, solo_mixsh_scratch_bytes(n, n_packets), st));
+    SxMixShArgs a = {};
+    a.pcm_in = d_pcm_in; a.gain = d_gain_q12; a.room = d_room; a.keep = d_keep; a.slots = d_slots;
+    a.pcm_spk = d_pcm_spk; a.spk_list = d_spk_list; a.spk_rows = d_spk_rows; a.pcm_room = d_pcm_room; a.room_list = d_room_list; a.source = d_source;
+    a.energy = d_energy; a.mixed = d_mixed;
+    a.n = n; a.n_rooms = n_rooms; a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
+    SOLO_CHECK(solo_mixsh_launch(a, b->d_mix_scratch, (SxMixShCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
     return 0;
 }
 
