@@ -45,114 +45,80 @@ struct alignas(16) SxV4i { i32 v[4]; };        // 16-byte LDS moves
 // recursions left to the scalar unit are the dearest instructions of the analysis kernel (tools/debug/mb_issue.hip,
 // DESIGN.md section 4).  SX_VEC(x) pins a value to a vector register and hides its uniformity from the compiler, so the
 // arithmetic that depends on it is emitted for the vector unit.
+//
 // Two first-order all-pass chains side by side -- the structure of SKP_Silk_ana_filt_bank_1 (ana_filt_bank_1.c:45) and of
 // SKP_Silk_resampler_down2 (resampler_down2.c:41): lane 0 runs the chain of the EVEN input samples, X = Y + (Y * cA >> 16),
-// lane 1 that of the ODD ones, X = Y * cB >> 16; per pair of samples the two chain outputs are exchanged inside the lane pair
-// (DPP) and lane 0 stores the low band sat16(rshift_round(o1 + o0, 11)), lane 1 the high band sat16(rshift_round(o1 - o0, 11))
-// (a caller that has no use for it passes a dump area).  S: the two chain states (null = zero state, not written back).  `in` may alias outL (in-place decimation):
-// every block of four pairs is read before any of its outputs is stored, and outputs trail the inputs.
-// npairs must be a multiple of 4 and >= 4 (blocks of four pairs with the next block's inputs prefetched): the callers pass
-// SX_FRAME / 2, / 4, / 8 pairs (VAD filter banks) and 320 / 160 pairs (pitch analysis decimators at the 16 kHz internal rate)
+// lane 1 that of the ODD ones, X = Y * cB >> 16.  Only the state feeds back, so only the state recursion is left in the serial loop:
+//   * sx_allpass2_spread (all lanes) puts the samples where the chains want them: in[2k] << 10 to ev[k], in[2k + 1] << 10 to od[k];
+//   * sx_allpass2_chain (lanes 0 and 1) replaces each lane's inputs IN PLACE by its chain's 32-bit outputs o = s + X, sixteen bytes
+//     (four pairs) a load and a store -- five instructions a step: Y = in32 - s, the high-word product m, the lane's choice of in32 or s,
+//     o = m + that, s = o + Y (in32 + X = s + X + in32 - s, all of it 32-bit wrapping);
+//   * the caller's finish pass (all lanes) forms the bands, low = sat16(rshift_round(od[k] + ev[k], 11)), high = ... (od[k] - ev[k]) ...:
+//     the same wrapping sums the reference forms inside its loop.
+// Input, coefficient, state and place are the lane's own (cA / cB, S[lane], od = ev + od_at words), the length is common.  S: the two
+// chain states (null = zero state, not written back).  ev and od are 16-byte aligned.  `in` of sx_allpass2_spread must not overlap ev /
+// od: the VAD banks that decimate "in place" in the reference (`in` = the low band output) hand their low band from one finish pass to
+// the next bank's ev / od instead.
+// NPAIRS must be a multiple of 4 and >= 4: the callers pass SX_FRAME / 2, / 4, / 8 pairs (VAD filter banks) and 320 / 160 pairs
+// (pitch analysis decimators at the 16 kHz internal rate)
 static_assert((SX_FRAME / 8) % 4 == 0 && SX_FRAME / 8 >= 4, "all-pass pairs are processed in blocks of four");
-SX_HD void sx_allpass2_lanes(const i16* in, int npairs, i32* S, i32 cA, i32 cB, i16* outL, i16* outH) {
-    if (SX_LANE < 2) {
-        const int l = SX_LANE;
-        i32 s = S ? S[l] : 0;
-        i32 cpre = sx_pre16(l ? cB : cA);
-        SX_VEC(cpre);
-        const i32 mask = l ? 0 : -1;
-        const i16* ip = in + l;                       // the lane's samples: in[2k + l]
-        i16* op = l ? outH : outL;
-        i32 x[4], xn[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) xn[u] = ip[2 * u];
-        for (int k = 0; k < npairs; k += 4) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) x[u] = xn[u];
-            if (k + 4 < npairs) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) xn[u] = ip[2 * (k + 4 + u)];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const i32 in32 = sx_shl(x[u], 10);
-                const i32 Y = sx_sub(in32, s);
-                const i32 X = sx_add(sx_smulw_pre(Y, cpre), Y & mask);
-                const i32 o = sx_add(s, X);
-                s = sx_add(in32, X);
-                // lane 0 stores o1 + o0, lane 1 o1 - o0: each lane hands the other what that one has to ADD (quad_perm [1,0,3,2]).
-                // |in32| <= 2^25 and the sections are all-pass: |o| < 2^28, so the rounding cannot overflow (sx_rshift_round_small)
-                const i32 p = SX_DPP_(l ? o : sx_neg(o), 0xB1);
-                const i32 v = sx_add(o, p);
-                op[k + u] = (i16)sx_sat16(sx_rshift_round_small(v, 11));
-            }
-        }
-        if (S) S[l] = s;
-    }
-    wv_sync();
+// pair k of the lane-strided loops below, turn j (64 is even: a lane stays with its chain, its place moves on by 32 words a turn)
+#define SX_ALLPASS2_PAR(k, j, NPAIRS) _Pragma("unroll") for (int j = 0; j < ((NPAIRS) + 63) / 64; j++) if (const int k = SX_LANE + 64 * j; k < (NPAIRS))
+template <int N>
+SX_HD void sx_allpass2_spread(const i16* in, i32* ev, int od_at) {
+    i32* const q = ev + (SX_LANE & 1) * od_at + (SX_LANE >> 1);
+    SX_ALLPASS2_PAR(i, j, N) q[32 * j] = sx_shl((i32)in[i], 10);
 }
-#endif
-
-#ifdef SX_LANE_STREAM
-// The same pair of chains with the band sums left as they are: lane 0 writes o1 + o0, lane 1 o1 - o0, 32 bits each, to rawL / rawH
-// (rawH null: nowhere); the caller rounds and saturates them afterwards, all samples side by side (sx_allpass2_finish) -- three
-// instructions less in every step of the recursion.  `in` must not overlap the raw buffers.
-SX_HD void sx_allpass2_lanes_raw(const i16* in, int npairs, i32* S, i32 cA, i32 cB, i32* rawL, i32* rawH, i32* dump4) {
+template <int NPAIRS>
+SX_HD void sx_allpass2_chain(i32* ev, int od_at, i32* S, i32 cA, i32 cB) {
+    static_assert(NPAIRS % 4 == 0 && NPAIRS >= 4, "blocks of four pairs");
     if (SX_LANE < 2) {
         const int l = SX_LANE;
         i32 s = S ? S[l] : 0;
         i32 cpre = sx_pre16(l ? cB : cA);
         SX_VEC(cpre);
-        const i32 mask = l ? 0 : -1;
-        const i16* ip = in + l;                       // the lane's samples: in[2k + l]
-        SxV4i* op = (SxV4i*)(l ? (rawH ? rawH : dump4) : rawL);
-        const int ostep = (l && !rawH) ? 0 : 1;
-        i32 x[4], xn[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) xn[u] = ip[2 * u];
-        for (int k = 0; k < npairs; k += 4) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) x[u] = xn[u];
-            if (k + 4 < npairs) {
-#pragma unroll
-                for (int u = 0; u < 4; u++) xn[u] = ip[2 * (k + 4 + u)];
-            }
+        SxV4i* p = (SxV4i*)(ev + l * od_at);
+        auto block = [&](const SxV4i& x) {
             SxV4i r;
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const i32 in32 = sx_shl(x[u], 10);
-                const i32 Y = sx_sub(in32, s);
-                const i32 X = sx_add(sx_smulw_pre(Y, cpre), Y & mask);
-                const i32 o = sx_add(s, X);
-                s = sx_add(in32, X);
-                const i32 p = SX_DPP_(l ? o : sx_neg(o), 0xB1);
-                r.v[u] = sx_add(o, p);
+                // o = s + X with X = m + Y (lane 0) or m (lane 1), m the high-word product: in32 + m or s + m.  |o| < 2^28: |in32| <= 2^25, all-pass sections
+                const i32 in32 = x.v[u], Y = sx_sub(in32, s);
+                const i32 o = sx_add(sx_smulw_pre(Y, cpre), l ? s : in32);
+                r.v[u] = o;
+                s = sx_add(o, Y);                     // in32 + X
             }
-            *op = r;
-            op += ostep;
+            return r;
+        };
+        // two blocks a turn
+        constexpr int nb = NPAIRS / 4;
+        for (int b = 0; b + 2 <= nb; b += 2) {
+            const SxV4i xa = p[b], xb = p[b + 1];
+            p[b] = block(xa);
+            p[b + 1] = block(xb);
         }
+        if (nb & 1) p[nb - 1] = block(p[nb - 1]);
         if (S) S[l] = s;
     }
     wv_sync();
 }
-// out[i] = sat16(RSHIFT_ROUND(raw[i], 11)) (|raw| < 2^29: sx_rshift_round_small)
-SX_HD void sx_allpass2_finish(i16* out, const i32* raw, int n) {
-    SX_PAR(i, n) out[i] = (i16)sx_sat16(sx_rshift_round_small(raw[i], 11));
+// one band sample from the two chain outputs (v = their wrapping sum or difference, |v| < 2^29: sx_rshift_round_small)
+SX_HD i32 sx_allpass2_band(i32 v) { return sx_sat16(sx_rshift_round_small(v, 11)); }
+// finish pass of a decimator: the low band alone
+template <int NPAIRS>
+SX_HD void sx_allpass2_finish_low(i16* out, const i32* ev, int od_at) {
+    SX_ALLPASS2_PAR(k, j, NPAIRS) out[k] = (i16)sx_allpass2_band(sx_add(ev[od_at + k], ev[k]));
 }
 #endif
 
-// SKP_Silk_ana_filt_bank_1, SKP_Silk_ana_filt_bank_1.c:45 (serial first-order all-pass pair)
-// raw: N words of LDS scratch (gfx950 build: the band sums before rounding)
-SX_HD void sx_ana_filt_bank_1(const i16* in, i32* S, i16* outL, i16* outH, int N, i32* raw) {
-    const i32 A20 = (i16)(5394 << 1), A21 = (i16)(20623 << 1);   // the int16 wrap of A_fb1_21 is intentional
-#if defined(SX_LANE_STREAM) && !defined(SX_NO_RAW_VAD)
-    sx_allpass2_lanes_raw(in, N >> 1, S, A21, A20, raw, raw + (N >> 1), (i32*)0);
-    sx_allpass2_finish(outL, raw, N >> 1);
-    sx_allpass2_finish(outH, raw + (N >> 1), N >> 1);
-    wv_sync();
-#elif defined(SX_LANE_STREAM)
-    sx_allpass2_lanes(in, N >> 1, S, A21, A20, outL, outH);
-#elif 0
+// the all-pass coefficients of SKP_Silk_ana_filt_bank_1 (the int16 wrap of A_fb1_21 is intentional)
+constexpr i32 SX_A_FB1_20 = (i16)(5394 << 1), SX_A_FB1_21 = (i16)(20623 << 1);
+
+// SKP_Silk_ana_filt_bank_1, SKP_Silk_ana_filt_bank_1.c:45 (serial first-order all-pass pair); the gfx950 build runs the VAD's banks
+// through sx_allpass2_chain instead (sx_vad)
+SX_HD void sx_ana_filt_bank_1(const i16* in, i32* S, i16* outL, i16* outH, int N) {
+    const i32 A20 = SX_A_FB1_20, A21 = SX_A_FB1_21;
+#if 0
     // N <= 64 * SX_FCH samples in (a frame), half as many out per band (in may alias outL: everything is read before anything is stored)
     i32 r[SX_FCH], oL[(SX_FCH + 1) / 2], oH[(SX_FCH + 1) / 2];
 #pragma unroll
@@ -207,15 +173,52 @@ SX_HD void sx_ana_filt_bank_1(const i16* in, i32* S, i16* outL, i16* outH, int N
 #endif
 }
 
+#ifdef SX_LANE_STREAM
+// finish pass of a VAD filter bank: the high band to outH; the low band to outL (LAST: the third bank) or, shifted and spread, to the
+// next bank's chains at nev (the reference's in-place decimation, `in` = outL, without the in-place)
+template <int NPAIRS, bool LAST>
+SX_HD void sx_vad_bank_finish(const i32* ev, i16* outH, i16* outL, i32* nev) {
+    i32* const q = nev + (SX_LANE & 1) * (NPAIRS / 2) + (SX_LANE >> 1);
+    SX_ALLPASS2_PAR(k, j, NPAIRS) {
+        const i32 o0 = ev[k], o1 = ev[NPAIRS + k];
+        const i32 lo = sx_allpass2_band(sx_add(o1, o0));
+        outH[k] = (i16)sx_allpass2_band(sx_sub(o1, o0));
+        if (LAST) outL[k] = (i16)lo;
+        else q[32 * j] = sx_shl(lo, 10);
+    }
+    wv_sync();
+}
+#endif
+
+// words of LDS scratch sx_vad wants (gfx950 build: the chain inputs / outputs of the three filter banks, SX_FRAME, / 2 and / 4 words)
+#define SX_VAD_RAW_WORDS (SX_FRAME + SX_FRAME / 2 + SX_FRAME / 4)
 // SKP_Silk_VAD_GetSA_Q8 (+ GetNoiseLevels), SKP_Silk_VAD.c:75-318.  X is a 4 x 80 int16 scratch (LDS).
-// raw: SX_FRAME words of LDS scratch (see sx_ana_filt_bank_1)
+// raw: SX_VAD_RAW_WORDS words of LDS scratch, 16-byte aligned, overlapping neither pIn nor X
 SX_FN1 void sx_vad(SxEncState* st, SxEncCtrl* c, const i16* pIn, i16* X, i32* pSNR_dB_Q7, i32* raw) {
     SX_IN_LDS(st); SX_IN_LDS(c); SX_IN_LDS(X); SX_IN_LDS(raw);
     SxVAD* v = &st->vad;
     i16* X0 = X, *X1 = X + 80, *X2 = X + 160, *X3 = X + 240;
-    sx_ana_filt_bank_1(pIn, v->AnaState, X0, X3, SX_FRAME, raw);
-    sx_ana_filt_bank_1(X0, v->AnaState1, X0, X2, SX_FRAME >> 1, raw);
-    sx_ana_filt_bank_1(X0, v->AnaState2, X0, X1, SX_FRAME >> 2, raw);
+#ifdef SX_LANE_STREAM
+    {
+        // the three banks one after the other (each reads the rounded low band of the one before), every bank's low band going straight
+        // from its finish pass into the next bank's chain inputs; only the last one's is stored to X0
+        constexpr int h1 = SX_FRAME / 2, h2 = SX_FRAME / 4, h3 = SX_FRAME / 8;
+        i32* a1 = raw, *a2 = raw + 2 * h1, *a3 = a2 + 2 * h2;       // each bank: its even chain, then its odd chain
+        static_assert(2 * (h1 + h2 + h3) == SX_VAD_RAW_WORDS, "chain inputs of the three banks");
+        sx_allpass2_spread<SX_FRAME>(pIn, a1, h1);
+        wv_sync();
+        sx_allpass2_chain<h1>(a1, h1, v->AnaState, SX_A_FB1_21, SX_A_FB1_20);
+        sx_vad_bank_finish<h1, false>(a1, X3, (i16*)0, a2);
+        sx_allpass2_chain<h2>(a2, h2, v->AnaState1, SX_A_FB1_21, SX_A_FB1_20);
+        sx_vad_bank_finish<h2, false>(a2, X2, (i16*)0, a3);
+        sx_allpass2_chain<h3>(a3, h3, v->AnaState2, SX_A_FB1_21, SX_A_FB1_20);
+        sx_vad_bank_finish<h3, true>(a3, X1, X0, (i32*)0);
+    }
+#else
+    sx_ana_filt_bank_1(pIn, v->AnaState, X0, X3, SX_FRAME);
+    sx_ana_filt_bank_1(X0, v->AnaState1, X0, X2, SX_FRAME >> 1);
+    sx_ana_filt_bank_1(X0, v->AnaState2, X0, X1, SX_FRAME >> 2);
+#endif
     // HP filter on lowest band (differentiator): h[i] = X0[i] >> 1, X0[i] = h[i] - h[i - 1] (h[-1] = the state), state = h[last]
     const int dfl = SX_FRAME >> 3;
     static_assert((SX_FRAME >> 3) % 2 == 0 && (SX_FRAME >> 3) + 2 * 16 <= 80, "the tail of X0 (its band is SX_FRAME / 8 long by now) is the scratch of the band statistics");
@@ -535,12 +538,19 @@ SX_HD void sx_k2a(i32* A_Q24, const i16* rc_Q15, int order) {
 
 // SKP_Silk_resampler_down2, SKP_Silk_resampler_down2.c:41 (zero initial state, serial)
 #define SX_DOWN2_MAXIN (40 * SX_FS_KHZ)      // the longest input: the pitch analysis buffer, 40 ms at the internal rate
-// dump: inLen / 2 samples of LDS that may be overwritten (GPU build: the unused high band of the all-pass pair lands there)
-SX_HD void sx_down2_zero_state(i16* out, const i16* in, int inLen, i16* dump) {
+// ev: INLEN / 2 words of 16-byte aligned LDS that may be overwritten, and as many od_at words further on (GPU build: the two all-pass
+// chains' inputs and outputs)
+template <int INLEN>
+SX_HD void sx_down2_zero_state(i16* out, const i16* in, i32* ev, int od_at) {
 #ifdef SX_LANE_STREAM
-    sx_allpass2_lanes(in, inLen >> 1, (i32*)0, T_down2_c1[0], T_down2_c0[0], out, dump);
+    sx_allpass2_spread<INLEN>(in, ev, od_at);
+    wv_sync();
+    sx_allpass2_chain<INLEN / 2>(ev, od_at, (i32*)0, T_down2_c1[0], T_down2_c0[0]);
+    sx_allpass2_finish_low<INLEN / 2>(out, ev, od_at);
+    wv_sync();
     return;
 #endif
+    const int inLen = INLEN;
     i32 S0 = 0, S1 = 0;
     const i32 c0 = SX_UNI(T_down2_c0[0]), c1 = SX_UNI(T_down2_c1[0]);
 #if 0
@@ -603,7 +613,7 @@ SX_HD i32 sx_pitch_find_scaling(const i16* sig, int len, int sum_sqr_len) {
 }
 
 struct SxPitchWork {                 // LDS scratch of the pitch analysis
-    alignas(16) i32 tmp32[160];      // (first, 16-byte aligned: also the raw band sums of the 8 -> 4 kHz decimator, stored 16 bytes at a time)
+    alignas(16) i32 tmp32[160];      // (first, 16-byte aligned: also the even chain of the 8 -> 4 kHz decimator, moved 16 bytes at a time)
     alignas(16) i32 d_srch[24];
     i16 sig8[320];
     i16 sig4[160];
@@ -621,23 +631,20 @@ SX_FN1 int sx_pitch_analysis_core(const i16* signal, i32* pitch_out, i32* lagInd
                                  i32 prevLag, i32 search_thres1_Q16, i32 search_thres2_Q15, SxPitchWork* w) {
     SX_IN_LDS(signal); SX_IN_LDS(pitch_out); SX_IN_LDS(lagIndex); SX_IN_LDS(contourIndex); SX_IN_LDS(LTPCorr_Q15); SX_IN_LDS(w);
     const int min_lag_4 = 8, max_lag_4 = 72, min_lag_8 = 16, max_lag_8 = 144, sf8 = 40;
-    SX_PAR(i, 4 * 221) (&w->C[0][0])[i] = 0;
+    // (the decimators' chains work in tmp32 and in the area that starts with C, which is cleared once they are done)
+    constexpr int dn_C = (int)((offsetof(SxPitchWork, C) - offsetof(SxPitchWork, tmp32)) / sizeof(i32));
+    static_assert(offsetof(SxPitchWork, tmp32) % 16 == 0 && offsetof(SxPitchWork, C) % 16 == 0 && sizeof(w->tmp32) >= 160 * sizeof(i32) &&
+                  sizeof(w->C) >= 160 * sizeof(i32), "all-pass chains of the 8 -> 4 kHz decimator");
 #if SX_FS_KHZ == 8
     SX_PAR(i, 320) w->sig8[i] = signal[i];
     wv_sync();
 #else
-    sx_down2_zero_state(w->sig8, signal, 640, (i16*)w->tmp32);      // 16 -> 8 kHz (pitch_analysis_core.c:127-129)
-    wv_sync();
+    // 16 -> 8 kHz (pitch_analysis_core.c:127-129): 2 x 320 words in C, d_comp and sig16, all of them written later
+    static_assert(offsetof(SxPitchWork, sig16) + sizeof(w->sig16) - offsetof(SxPitchWork, C) >= 640 * sizeof(i32), "all-pass chains of the 16 -> 8 kHz decimator");
+    sx_down2_zero_state<640>(w->sig8, signal, w->tmp32 + dn_C, 320);
 #endif
-#if defined(SX_LANE_STREAM) && !defined(SX_NO_RAW_DECIM)
-    // (the 160 low-band sums land in tmp32 as they are, the unused high band on d_srch, which is free until the first stage; rounded below)
-    static_assert(sizeof(w->tmp32) >= 160 * sizeof(i32) && sizeof(w->d_srch) >= 16, "raw band sums of the 8 -> 4 kHz decimator");
-    sx_allpass2_lanes_raw(w->sig8, 160, (i32*)0, T_down2_c1[0], T_down2_c0[0], w->tmp32, (i32*)0, w->d_srch);
-    sx_allpass2_finish(w->sig4, w->tmp32, 160);
-    wv_sync();
-#else
-    sx_down2_zero_state(w->sig4, w->sig8, 320, (i16*)w->tmp32);
-#endif
+    sx_down2_zero_state<320>(w->sig4, w->sig8, w->tmp32, dn_C);
+    SX_PAR(i, 4 * 221) (&w->C[0][0])[i] = 0;
 #if SX_NLANES == 1
     for (int i = 159; i > 0; i--) w->sig4[i] = (i16)sx_sat16((i32)w->sig4[i] + (i32)w->sig4[i - 1]);
 #else
