@@ -403,6 +403,36 @@ int32_t solo_send_fanout(solo_batch_t *b, const uint8_t *d_bits, const int16_t *
                          const uint8_t *d_send, int32_t n_packets, const int32_t *d_seq_base, int32_t first_seq,
                          solo_arrival_t *d_records, int32_t max_records, uint8_t *d_payload, int64_t payload_capacity,
                          solo_send_count_t *d_count, void *hip_stream);
+/* Play-out time scaling by whole packets: the step between play-out and mix that MOVES a stream's play-out delay -- in_packets = a decoded
+ * packets of a row become out_packets = b packets of audio without a click (waveform-similarity overlap-add).  d_pcm_in: int16 [n][a][L],
+ * d_pcm_out: int16 [n][b][L], L = the handle's packet samples: the compact rows every other call reads and writes.  Integer arithmetic with
+ * a total order for every choice: the output is a pure function of the input.  Per row, statelessly: input x[0 .. Li), Li = a L; output
+ * y[0 .. Lo), Lo = b L; H = samplerate / 200 (5 ms: 80 or 160 samples), D = 3H / 2, M = Lo / H output blocks, j = 0 .. H - 1.
+ *   n_m    = floor((2 m (Li - H) + (M - 1)) / (2 (M - 1)))     the nominal source position of block m: n_0 = 0, n_{M-1} = Li - H
+ *   block 0:          y[j] = x[j], s_0 = 0
+ *   blocks m >= 1:    the template t[j] = x[s_{m-1} + H + j]: what the previous block's segment would have played next
+ *   1 <= m <= M - 2:  the candidates are every d in [max(-D, -n_m), min(D, Li - 2H - n_m)] (never fewer than 57),
+ *                       cost(d) = sum_j |t[j] - x[n_m + d + j]|
+ *                               + sum_j |x[n_m + d + H + j] - x[Li - H + j]|    for m = M - 2 only: how the candidate's own continuation
+ *                                                                               meets the pinned last block
+ *                     d_m = the candidate with the least (cost, |d|, d) in lexicographic order; s_m = n_m + d_m
+ *   m = M - 1:        s_m = Li - H (pinned), d_m = 0, cost = sum_j |t[j] - x[s_m + j]|
+ *   blocks m >= 1:    y[m H + j] = floor((t[j] (H - 1 - j) + x[s_m + j] (j + 1) + H / 2) / H)      (floor towards minus infinity)
+ * So the first H output samples are the input's first H and the last output sample is the input's last: a row joins the packets played
+ * before and after it exactly as the unscaled signal would.  a == b is the identity (every d_m = 0, every cost 0).  No output sample
+ * leaves the range of its two sources: nothing saturates.  A cost is at most 2 H 65535 < 2^25.
+ * d_shift, d_cost (int32 [n][M] or NULL): d_m and the least cost of block m (the cost above, second term included at m = M - 2); 0 for
+ * block 0.  They are the caller's quality gate: a row whose splices were expensive can be played unscaled instead.  d_count (may be
+ * NULL): rows written, blocks searched (n (M - 2)), the sum of all costs.
+ * Returns -1 with nothing enqueued for a NULL handle, d_pcm_in or d_pcm_out; n <= 0; in_packets or out_packets outside 1 .. 4;
+ * n x max(a, b) x L >= 2^31; PCM pointers that are not 16-byte aligned; input and output ranges that overlap.
+ * Any handle will do (only L and the sample rate are read).  No scratch, no allocation, no host synchronisation: one kernel on hip_stream
+ * (one wavefront per row; a second, one-lane kernel ahead of it when d_count is given), so the call can be captured in a graph.  Like
+ * solo_mix it does NOT wait for the handle's internal streams.  The policy -- when to scale which stream -- is the caller's
+ * ("Moving a stream's play-out delay"). */
+typedef struct { int32_t rows, blocks; int64_t cost; } solo_timescale_count_t;   /* 16 bytes: rows written, blocks searched, sum of all splice costs */
+int32_t solo_timescale(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t in_packets, int32_t out_packets,
+                       int16_t *d_pcm_out, int32_t *d_shift, int32_t *d_cost, solo_timescale_count_t *d_count, void *hip_stream);
 /* PCM rate conversion on the device: the reference SDK's own fixed-point resampler (SKP_Silk_resampler_init / SKP_Silk_resampler), bit for
  * bit and with its stream state, so that callers on handles of different rates meet in one mix and 8 / 48 kHz endpoints need no host
  * round trip.  A resampler is an object of its own -- it sits BETWEEN two handles -- with n_rows independent rows of filter memory.

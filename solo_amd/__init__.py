@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "solo_resample_create", "solo_resample_destroy", "solo_resample_out_samples", "solo_resample_reset", "solo_resample_reset_rows",
     "solo_resample", "solo_resample_rows",
     "solo_mix_shared", "solo_send_fanout",
+    "solo_timescale",
 ]
 
 
@@ -61,6 +62,11 @@ class solo_mix_count_t(C.Structure):
 class solo_mix_shared_count_t(C.Structure):
     """what a solo_mix_shared call did (include/solo_mi355x.h); 24 bytes"""
     _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("speakers", C.c_int32), ("shared", C.c_int32), ("clipped", C.c_int64)]
+
+
+class solo_timescale_count_t(C.Structure):
+    """what a solo_timescale call did (include/solo_mi355x.h); 16 bytes"""
+    _fields_ = [("rows", C.c_int32), ("blocks", C.c_int32), ("cost", C.c_int64)]
 
 
 class solo_resample_count_t(C.Structure):
@@ -180,6 +186,8 @@ def load_library():
                              C.c_void_p, C.c_void_p]
     lib.solo_mix_shared.restype = C.c_int32
     lib.solo_mix_shared.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12
+    lib.solo_timescale.restype = C.c_int32
+    lib.solo_timescale.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_send_fanout.restype = C.c_int32
     lib.solo_send_fanout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + _send[2:]
     lib.solo_batch_state_bytes.restype = C.c_int64
@@ -284,6 +292,7 @@ class SoloBatch:
         if samplerate not in (16000, 32000):
             raise ValueError("samplerate must be 16000 or 32000")
         self.packet_samples = PACKET_SAMPLES * samplerate // 16000 * framesize_ms // 40
+        self.samplerate = samplerate
         self._dec = default_dec_ctrl(use_md_index, joint, samplerate, framesize_ms) if decoder else None
         self.h = self.lib.solo_batch_create(self.n_streams, C.byref(self._enc) if encoder else None,
                                             C.byref(self._dec) if decoder else None, self.slot)
@@ -733,6 +742,49 @@ class SoloBatch:
         rows == -1: a room id was refused on the device"""
         c = solo_mix_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
         return {k: int(getattr(c, k)) for k in self.MIX_COUNT}
+
+    # ---- play-out time scaling (solo_timescale): a decoded packets of a row -> b packets of audio ----
+    TIMESCALE_COUNT = ("rows", "blocks", "cost")
+
+    def timescale(self, pcm, out_packets, out=None, shift=None, cost=None):
+        """Shorten or stretch play-out by whole packets on the device: pcm int16 [n,a,samples] (what recv_decode() wrote, compact rows
+        included), a and out_packets = b in 1 .. 4 -> (out int16 [n,b,samples] = what mix() / encode() take, count int32 [4] on the device:
+        read it with timescale_count()).  Waveform-similarity overlap-add in integer arithmetic, per row and stateless; the first 5 ms and
+        the last sample of a row are the input's, a == b is the identity (include/solo_mi355x.h has the arithmetic).  shift / cost int32
+        [n, M], M = b * samples / (samplerate / 200) blocks of 5 ms: optional outputs, the lag every block was cut at and what its splice
+        cost (the sum of absolute differences) -- the caller's quality gate.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
+        if not dev(pcm, t.int16, 3):
+            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, a, samples]")
+        n, a, L = pcm.shape
+        if L != self.packet_samples or n <= 0:
+            raise ValueError("pcm: packets of %d samples, at least one row" % self.packet_samples)
+        b = int(out_packets)
+        if not (1 <= a <= 4 and 1 <= b <= 4):
+            raise ValueError("between 1 and 4 packets in and out")
+        if n * max(a, b) * L >= 2 ** 31:
+            raise ValueError("n * max(a, b) * samples must stay below 2^31")
+        M = b * L // (self.samplerate // 200)
+        if out is not None and not (dev(out, t.int16, 3) and tuple(out.shape) == (n, b, L)):
+            raise ValueError("out: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, b, L))
+        if shift is not None and not (dev(shift, t.int32, 2) and tuple(shift.shape) == (n, M)):
+            raise ValueError("shift: a contiguous int32 CUDA tensor [%d, %d]" % (n, M))
+        if cost is not None and not (dev(cost, t.int32, 2) and tuple(cost.shape) == (n, M)):
+            raise ValueError("cost: a contiguous int32 CUDA tensor [%d, %d]" % (n, M))
+        if out is None:
+            out = t.empty((n, b, L), dtype=t.int16, device=pcm.device)
+        count = t.zeros((4,), dtype=t.int32, device=pcm.device)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        r = self.lib.solo_timescale(self.h, pcm.data_ptr(), n, a, b, out.data_ptr(), ptr(shift), ptr(cost), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_timescale -> %d" % r)
+        return out, count
+
+    def timescale_count(self, count):
+        """the count tensor of timescale() as a dict (synchronises): rows written, blocks searched, the sum of all splice costs"""
+        c = solo_timescale_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.TIMESCALE_COUNT}
 
     # ---- shared listener mixes (solo_mix_shared, solo_send_fanout): a personal mix per speaker, one mix per room for everybody else ----
     MIX_SHARED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped")

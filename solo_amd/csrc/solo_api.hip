@@ -34,6 +34,7 @@
 #include "solo_recv_report.h"   // the read side of the receiver ring (solo_recv_report, solo_recv_track): likewise
 #include "solo_migrate.h"       // stream states out of a handle and into another (solo_batch_export_streams / _import_streams): likewise
 #include "solo_resample.h"      // PCM rate conversion between handles and towards 8 / 48 kHz endpoints (solo_resample): likewise
+#include "solo_timescale.h"     // play-out time scaling by whole packets (solo_timescale): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -892,6 +893,24 @@ int32_t solo_mix_shared(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int
     a.energy = d_energy; a.mixed = d_mixed;
     a.n = n; a.n_rooms = n_rooms; a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
     SOLO_CHECK(solo_mixsh_launch(a, b->d_mix_scratch, (SxMixShCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
+    return 0;
+}
+
+// ---- play-out time scaling (solo_timescale.h): in_packets decoded packets of a row -> out_packets packets of audio ---------------------
+static_assert(sizeof(solo_timescale_count_t) == sizeof(SxTsCount), "include/solo_mi355x.h and solo_timescale.h agree");
+int32_t solo_timescale(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t in_packets, int32_t out_packets, int16_t* d_pcm_out,
+                       int32_t* d_shift, int32_t* d_cost, solo_timescale_count_t* d_count, void* hip_stream) {
+    if (!b) return -1;
+    int L = 0, fs = 0;               // the packet geometry and the sample rate are the handle's, as for solo_mix
+    if (b->have_dec) { L = dec_packet_samples(b); fs = b->dec_ctrl.samplerate; }
+#ifdef SOLO_WITH_ENCODER
+    else if (b->have_enc) { L = enc_packet_samples(b); fs = b->enc_ctrl.samplerate; }
+#endif
+    if (!sx_ts_args_ok(d_pcm_in, n, in_packets, out_packets, fs, L, d_pcm_out)) return -1;
+    SxTsArgs a;
+    a.pcm_in = d_pcm_in; a.pcm_out = d_pcm_out; a.shift = d_shift; a.cost = d_cost;
+    a.Li = in_packets * L; a.Lo = out_packets * L; a.H = fs / 200;
+    SOLO_CHECK(solo_timescale_launch(a, n, (SxTsCount*)d_count, (hipStream_t)hip_stream));
     return 0;
 }
 
