@@ -468,6 +468,68 @@ int32_t solo_resample(solo_resampler_t *r, const int16_t *d_in, int32_t n_packet
                       int16_t *d_out, void *hip_stream);
 int32_t solo_resample_rows(solo_resampler_t *r, const int32_t *d_rows, int32_t n, const int16_t *d_in, int32_t n_packets,
                            int32_t in_samples, int16_t *d_out, solo_resample_count_t *d_count, void *hip_stream);
+/* Voice activity, audio level and speaker selection for decoded rows: who is speaking, with memory.  solo_mix and solo_mix_shared pick
+ * by the energy of one packet, statelessly; these calls give a bridge the facts for a better decision without a host round trip.  A
+ * solo_vad_t is an object of its own, like a resampler, with n_rows independent rows of state.
+ *   frame_samples  320 (SILK's wide-band configuration: 20 ms at 16 kHz) or 160 (20 ms at 8 kHz); anything else: NULL.  A 32 kHz row
+ *              either goes through solo_resample 32 -> 16 first, or runs 320-sample frames of 10 ms: every time constant of the noise
+ *              tracker then runs twice as fast.
+ *   state      SOLO_VAD_STATE_BYTES = 128 bytes per row in device memory.  Bytes [0, 112) are the reference's SKP_Silk_VAD_state in its
+ *              own layout -- AnaState[2], AnaState1[2], AnaState2[2], XnrgSubfr[4], NrgRatioSmth_Q8[4], HPstate (int16 + 2 zero bytes),
+ *              NL[4], inv_NL[4], NoiseLevelBias[4], counter --, bytes [112, 128) the selection state {int32 talking, hang, picked, 0}.
+ *              Create and the two reset calls (every row, or a HOST list of 1 .. n_rows indices inside [0, n_rows), none twice, else -1)
+ *              leave what SKP_Silk_VAD_Init leaves, selection state zero.  solo_vad_get_state / solo_vad_set_state copy the records
+ *              of listed rows to / from d_blob, uint8 [n][128] (4-byte aligned): d_rows is a DEVICE list, or NULL for rows 0 .. n - 1;
+ *              plain copies -- an index outside [0, n_rows) moves nothing.  They are what a migrating call takes along (VAD state is
+ *              not part of a migration blob).
+ * solo_vad: d_pcm is int16 [n][n_packets][packet_samples], the compact rows every other call reads and writes; packet_samples is a
+ *   positive multiple of frame_samples and at most 1920, F = packet_samples / frame_samples.  Frame by frame, in order, the call does
+ *   exactly what SKP_Silk_VAD_GetSA_Q8(state, ..., frame, frame_samples) does, bit for bit: d_sa_q8 (uint8 [n][P][F]) receives *pSA_Q8,
+ *   d_detail (int32 [n][P][F][6] or NULL) {SNR_dB_Q7, Tilt_Q15, Quality_Q15[0 .. 3]}.  The state carries from frame to frame and from
+ *   call to call: P packets in one call equal P calls of one packet.
+ *   d_level (uint8 [n][P] or NULL) is the RFC 6464 audio level of each packet in -dBov, 0 = loudest -- what goes into the RTP audio-level
+ *   header extension: E = sum x^2, exact in 64 bits; level = the smallest k in [0, 127] with E * 2^20 >= packet_samples * T_k,
+ *   T_k = round(2^50 * 10^(-k / 10)); 127 if there is none.  (All products fit 64 unsigned bits at packet_samples <= 1920.)
+ *   With d_rows (a DEVICE list, strictly increasing inside [0, n_rows), checked on the device ahead of the work) row i of the buffers
+ *   belongs to state row d_rows[i]; unlisted rows keep their state bit for bit; d_count is then required.  A refused list changes no
+ *   state and writes nothing except d_count->rows = -1.  Otherwise d_count (if given) = {n, 0, 0, 0}.
+ *   Returns -1 with nothing enqueued: NULL v, d_pcm or d_sa_q8; d_rows without d_count; n outside (0, n_rows]; n_packets <= 0;
+ *   packet_samples not a positive multiple of frame_samples or above 1920; n x P x packet_samples or n x P x F x 6 >= 2^31; d_pcm not
+ *   16-byte aligned.  No allocation, no host synchronisation, one kernel (two with a list) on hip_stream: it can sit in a captured tick.
+ * solo_vad_select: the stateful selection, room by room (room ids as in solo_mix: -1 = in no room -- nothing is written for such a row
+ *   and its state does not move; an id outside [-1, n_rooms) is found on the device and refuses the call: d_count->rows = -1, nothing
+ *   else written, no state changed; the same for a bad d_rows).  d_sa_q8 uint8 [n][P][frames] and d_level uint8 [n][P] (values above
+ *   127 count as 127) are what solo_vad wrote.  The packets run in order; for every row i in a room, with state (t, h, s):
+ *     a   = max over f of sa[i][p][f];   thr = t ? off_q8 : on_q8
+ *     a >= thr:  t = 1, h = hang_packets, cand = 1;   otherwise:  t = 0, cand = (h > 0), h = max(h - 1, 0)
+ *     key = cand ? (127 - level[i][p]) + (s ? stick : 0) : -1
+ *   Per room, sel = the first max_speakers CANDIDATES in the total order: larger key, then s = 1 before s = 0, then smaller row position
+ *   i; a row that is no candidate is never selected.  Then s = (i in sel), d_sel[i][p] = s, d_dominant[room][p] (or NULL) = the first
+ *   row of the order, -1 when the room has no candidate.  After the last packet d_gain_out[i] (or NULL) = s ? max(gain_in[i], 0) : 0
+ *   (d_gain_in NULL = 4096) and d_keep[i] (or NULL) = cand.  d_count = {rows in rooms, rooms with a member, selected (row, packet) pairs,
+ *   changes of s from one packet to the next, the s a row brings into the call included}.  Only integers: the output is a pure function
+ *   of inputs and state, and P packets in one call equal P calls of one packet.
+ *   Returns -1 with nothing enqueued: NULL v, d_sa_q8, d_level, d_room, params, d_sel or d_count; n outside (0, n_rows]; n_packets or
+ *   frames <= 0; n_rooms outside (0, n_rows]; n x P x frames or n_rooms x P >= 2^31; max_speakers outside 1 .. 64; not
+ *   0 <= off_q8 <= on_q8 <= 255; hang_packets outside 0 .. 1000; stick outside 0 .. 127.  No allocation (the room plan's scratch is the
+ *   object's, sized at create), no host synchronisation, five short kernels (six with a list) on hip_stream.
+ * Calls on one object must be ordered (same stream, or events).  INTEGRATION.md section 2 has the tick. */
+#define SOLO_VAD_STATE_BYTES 128
+typedef struct solo_vad_obj solo_vad_t;
+typedef struct { int32_t rows, rooms, selected, changes; } solo_vad_count_t;    /* 16 bytes; rows = -1: refused on the device */
+typedef struct { int32_t max_speakers, on_q8, off_q8, hang_packets, stick; } solo_vad_select_params_t;
+solo_vad_t *solo_vad_create(int32_t n_rows, int32_t frame_samples);
+void solo_vad_destroy(solo_vad_t *v);
+int32_t solo_vad_reset(solo_vad_t *v, void *hip_stream);
+int32_t solo_vad_reset_rows(solo_vad_t *v, const int32_t *h_rows, int32_t n, void *hip_stream);
+int32_t solo_vad_get_state(solo_vad_t *v, const int32_t *d_rows, int32_t n, uint8_t *d_blob, void *hip_stream);
+int32_t solo_vad_set_state(solo_vad_t *v, const int32_t *d_rows, int32_t n, const uint8_t *d_blob, void *hip_stream);
+int32_t solo_vad(solo_vad_t *v, const int32_t *d_rows, int32_t n, const int16_t *d_pcm, int32_t n_packets, int32_t packet_samples,
+                 uint8_t *d_sa_q8, int32_t *d_detail, uint8_t *d_level, solo_vad_count_t *d_count, void *hip_stream);
+int32_t solo_vad_select(solo_vad_t *v, const int32_t *d_rows, int32_t n, const uint8_t *d_sa_q8, const uint8_t *d_level,
+                        int32_t n_packets, int32_t frames, const int32_t *d_room, int32_t n_rooms,
+                        const solo_vad_select_params_t *params, const int16_t *d_gain_in, uint8_t *d_sel, int16_t *d_gain_out,
+                        uint8_t *d_keep, int32_t *d_dominant, solo_vad_count_t *d_count, void *hip_stream);
 /* Stream migration: the state of a running call leaves a handle as a DEVICE blob and enters any slot of any handle of the same
  * geometry -- on this GPU, or on another one after the caller has moved the bytes (the blob is plain device memory: a torch.distributed
  * send, a hipMemcpyPeer).  The call goes on where it stood: no first-frame logic, no cold-start concealment, VAD / DTX / CNG / PLC and

@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "solo_resample", "solo_resample_rows",
     "solo_mix_shared", "solo_send_fanout",
     "solo_timescale",
+    "solo_vad_create", "solo_vad_destroy", "solo_vad_reset", "solo_vad_reset_rows", "solo_vad_get_state", "solo_vad_set_state",
+    "solo_vad", "solo_vad_select",
 ]
 
 
@@ -72,6 +74,16 @@ class solo_timescale_count_t(C.Structure):
 class solo_resample_count_t(C.Structure):
     """what a solo_resample_rows call did (include/solo_mi355x.h); 8 bytes"""
     _fields_ = [("rows", C.c_int32), ("listed", C.c_int32)]
+
+
+class solo_vad_count_t(C.Structure):
+    """what a solo_vad / solo_vad_select call did (include/solo_mi355x.h); 16 bytes; rows = -1: refused on the device"""
+    _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("selected", C.c_int32), ("changes", C.c_int32)]
+
+
+class solo_vad_select_params_t(C.Structure):
+    """the policy of a solo_vad_select call (include/solo_mi355x.h); 20 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("max_speakers", "on_q8", "off_q8", "hang_packets", "stick")]
 
 
 class solo_migrate_count_t(C.Structure):
@@ -207,6 +219,23 @@ def load_library():
     lib.solo_resample_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.solo_resample.restype = C.c_int32
     lib.solo_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_vad_create.restype = C.c_void_p
+    lib.solo_vad_create.argtypes = [C.c_int32, C.c_int32]
+    lib.solo_vad_destroy.restype = None
+    lib.solo_vad_destroy.argtypes = [C.c_void_p]
+    lib.solo_vad_reset.restype = C.c_int32
+    lib.solo_vad_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.solo_vad_reset_rows.restype = C.c_int32
+    lib.solo_vad_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_vad_get_state.restype = C.c_int32
+    lib.solo_vad_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_vad_set_state.restype = C.c_int32
+    lib.solo_vad_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_vad.restype = C.c_int32
+    lib.solo_vad.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_vad_select.restype = C.c_int32
+    lib.solo_vad_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.POINTER(solo_vad_select_params_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1100,3 +1129,162 @@ class Resampler:
             r = self.lib.solo_resample_reset_rows(self.h, arr, len(idx), self._stream())
         if r:
             raise RuntimeError("solo_resample_reset -> %d" % r)
+
+
+VAD_STATE_BYTES = 128
+
+
+class Vad:
+    """n_rows independent voice activity detectors on the current HIP device (solo_vad, include/solo_mi355x.h): the reference's
+    fixed-point VAD bit for bit on frames of 160 or 320 samples, the RFC 6464 audio level of every packet, and a stateful speaker
+    selection per room (solo_vad_select).  State carries from call to call."""
+
+    COUNT = ("rows", "rooms", "selected", "changes")
+
+    def __init__(self, n_rows, frame_samples):
+        import torch
+        self.n_rows, self.frame = int(n_rows), int(frame_samples)
+        if self.n_rows <= 0:
+            raise ValueError("n_rows must be positive")
+        if self.frame not in (160, 320):
+            raise ValueError("frame_samples must be 160 or 320")
+        self.h = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
+        self.torch = torch
+        self.lib = load_library()
+        self.h = self.lib.solo_vad_create(self.n_rows, self.frame)
+        if not self.h:
+            raise RuntimeError("solo_vad_create failed (no GPU, or out of memory)")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.solo_vad_destroy(self.h)
+            self.h = None
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def _dev(self, x, dt, nd):
+        return getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
+
+    def _rows(self, rows, n=None):
+        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
+        t = self.torch
+        if rows is None:
+            return None
+        if not getattr(rows, "is_cuda", False):
+            idx = [int(v) for v in rows]
+            if not idx or any(b <= a for a, b in zip(idx, idx[1:])) or idx[0] < 0 or idx[-1] >= self.n_rows:
+                raise ValueError("rows: strictly increasing indices inside [0, %d)" % self.n_rows)
+            rows = t.tensor(idx, dtype=t.int32, device=self.device)
+        if not (self._dev(rows, t.int32, 1) and 0 < rows.shape[0] <= self.n_rows and (n is None or rows.shape[0] == n)):
+            raise ValueError("rows: a contiguous int32 CUDA tensor of at most %d indices, one per row of the call" % self.n_rows)
+        return rows
+
+    def run(self, pcm, rows=None, detail=False, level=True):
+        """pcm int16 [n,P,samples] (what decode() / mix() wrote; samples a multiple of frame_samples, at most 1920) -> dict(sa uint8 [n,P,F],
+        detail int32 [n,P,F,6] = {SNR_dB_Q7, Tilt_Q15, Quality_Q15[4]} with detail=True, level uint8 [n,P] in -dBov with level=True, count
+        int32 [4] on the device with rows=, read with count()).  rows=None: rows 0 .. n-1 of the object.  rows = a strictly increasing
+        sequence or int32 CUDA tensor: row i of pcm belongs to rows[i], the others keep their state; a bad list is refused on the device:
+        rows == -1 in the count, nothing else written.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        if not self._dev(pcm, t.int16, 3):
+            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
+        n, P, L = pcm.shape
+        if not (0 < n <= self.n_rows and P > 0):
+            raise ValueError("pcm: 1 .. %d rows and at least one packet" % self.n_rows)
+        if L <= 0 or L % self.frame or L > 1920:
+            raise ValueError("samples: a positive multiple of %d, at most 1920" % self.frame)
+        rows = self._rows(rows, n)
+        F = L // self.frame
+        out = {"sa": t.empty((n, P, F), dtype=t.uint8, device=pcm.device)}
+        if detail:
+            out["detail"] = t.empty((n, P, F, 6), dtype=t.int32, device=pcm.device)
+        if level:
+            out["level"] = t.empty((n, P), dtype=t.uint8, device=pcm.device)
+        if rows is not None:
+            out["count"] = t.zeros((4,), dtype=t.int32, device=pcm.device)
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        r = self.lib.solo_vad(self.h, None if rows is None else rows.data_ptr(), n, pcm.data_ptr(), P, L, ptr("sa"), ptr("detail"), ptr("level"),
+                              ptr("count"), self._stream())
+        if r:
+            raise RuntimeError("solo_vad -> %d" % r)
+        return out
+
+    def select(self, sa, level, room, n_rooms=None, max_speakers=3, on=128, off=64, hang=5, stick=6, gain=None, rows=None):
+        """sa uint8 [n,P,F] and level uint8 [n,P] as run() wrote them, room int32 [n] (-1 = in no room; n_rooms=None: the largest id + 1,
+        which synchronises) -> dict(sel uint8 [n,P], gain_out int16 [n] (what mix(gain=) takes: the row's gain if it is selected after the
+        last packet, else 0), keep uint8 [n] (candidates: what mix_shared(keep=) takes), dominant int32 [n_rooms,P], count int32 [4],
+        read with count()).  Entries of rows in no room are not written (they are zero here).  on / off: the thresholds on the largest SA_Q8
+        of a packet for a silent / a talking row, hang: packets a row stays a candidate after it fell silent, stick: what an incumbent's
+        key is raised by.  A room id outside [-1, n_rooms) or a bad list is refused on the device: rows == -1 in the count."""
+        t = self.torch
+        if not (self._dev(sa, t.uint8, 3) and self._dev(level, t.uint8, 2) and tuple(level.shape) == tuple(sa.shape[:2])):
+            raise ValueError("sa: a contiguous uint8 CUDA tensor [n, P, F]; level: one [n, P]")
+        n, P, F = sa.shape
+        if not (0 < n <= self.n_rows and P > 0 and F > 0):
+            raise ValueError("sa: 1 .. %d rows, at least one packet and one frame" % self.n_rows)
+        if not (self._dev(room, t.int32, 1) and room.shape[0] == n):
+            raise ValueError("room: a contiguous int32 CUDA tensor [%d]" % n)
+        if gain is not None and not (self._dev(gain, t.int16, 1) and gain.shape[0] == n):
+            raise ValueError("gain: a contiguous int16 CUDA tensor [%d]" % n)
+        rows = self._rows(rows, n)
+        if n_rooms is None:
+            n_rooms = max(int(room.max()) + 1, 1)
+        n_rooms = int(n_rooms)
+        if not 0 < n_rooms <= self.n_rows:
+            raise ValueError("n_rooms: 1 .. %d" % self.n_rows)
+        prm = solo_vad_select_params_t(int(max_speakers), int(on), int(off), int(hang), int(stick))
+        if not (1 <= prm.max_speakers <= 64 and 0 <= prm.off_q8 <= prm.on_q8 <= 255 and 0 <= prm.hang_packets <= 1000 and 0 <= prm.stick <= 127):
+            raise ValueError("max_speakers 1 .. 64, 0 <= off <= on <= 255, hang 0 .. 1000, stick 0 .. 127")
+        out = {"sel": t.zeros((n, P), dtype=t.uint8, device=sa.device), "gain_out": t.zeros((n,), dtype=t.int16, device=sa.device),
+               "keep": t.zeros((n,), dtype=t.uint8, device=sa.device), "dominant": t.full((n_rooms, P), -1, dtype=t.int32, device=sa.device),
+               "count": t.zeros((4,), dtype=t.int32, device=sa.device)}
+        r = self.lib.solo_vad_select(self.h, None if rows is None else rows.data_ptr(), n, sa.data_ptr(), level.data_ptr(), P, F, room.data_ptr(), n_rooms,
+                                     C.byref(prm), None if gain is None else gain.data_ptr(), out["sel"].data_ptr(), out["gain_out"].data_ptr(),
+                                     out["keep"].data_ptr(), out["dominant"].data_ptr(), out["count"].data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_vad_select -> %d" % r)
+        return out
+
+    def count(self, count):
+        """a count tensor of run(rows=) / select() as a dict (synchronises); rows == -1: the call was refused on the device"""
+        c = solo_vad_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.COUNT}
+
+    def reset(self, rows=None):
+        """every row, or the listed rows (a host sequence: inside [0, n_rows), none twice), back to the initial state"""
+        if rows is None:
+            r = self.lib.solo_vad_reset(self.h, self._stream())
+        else:
+            idx = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+            if not 0 < len(idx) <= self.n_rows or any(v < 0 or v >= self.n_rows for v in idx) or len(set(idx)) != len(idx):
+                raise ValueError("rows: 1 .. %d indices inside [0, %d), none twice" % (self.n_rows, self.n_rows))
+            arr = (C.c_int32 * len(idx))(*idx)
+            r = self.lib.solo_vad_reset_rows(self.h, arr, len(idx), self._stream())
+        if r:
+            raise RuntimeError("solo_vad_reset -> %d" % r)
+
+    def get_state(self, rows=None):
+        """the 128-byte records of the listed rows (None: all rows) -> uint8 [n,128] on the device"""
+        t = self.torch
+        rows = self._rows(rows)
+        n = self.n_rows if rows is None else int(rows.shape[0])
+        blob = t.empty((n, VAD_STATE_BYTES), dtype=t.uint8, device=self.device)
+        r = self.lib.solo_vad_get_state(self.h, None if rows is None else rows.data_ptr(), n, blob.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_vad_get_state -> %d" % r)
+        return blob
+
+    def set_state(self, blob, rows=None):
+        """blob uint8 [n,128] on the device -> the records of the listed rows (None: rows 0 .. n-1)"""
+        t = self.torch
+        rows = self._rows(rows)
+        if not (self._dev(blob, t.uint8, 2) and blob.shape[1] == VAD_STATE_BYTES and 0 < blob.shape[0] <= self.n_rows and
+                (rows is None or rows.shape[0] == blob.shape[0])):
+            raise ValueError("blob: a contiguous uint8 CUDA tensor [n, %d], one record per listed row" % VAD_STATE_BYTES)
+        r = self.lib.solo_vad_set_state(self.h, None if rows is None else rows.data_ptr(), int(blob.shape[0]), blob.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_vad_set_state -> %d" % r)

@@ -35,6 +35,7 @@
 #include "solo_migrate.h"       // stream states out of a handle and into another (solo_batch_export_streams / _import_streams): likewise
 #include "solo_resample.h"      // PCM rate conversion between handles and towards 8 / 48 kHz endpoints (solo_resample): likewise
 #include "solo_timescale.h"     // play-out time scaling by whole packets (solo_timescale): likewise
+#include "solo_vad.h"           // voice activity, audio level and speaker selection of decoded rows (solo_vad, solo_vad_select): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -986,6 +987,102 @@ int32_t solo_resample_rows(solo_resampler_t* r, const int32_t* d_rows, int32_t n
                            int16_t* d_out, solo_resample_count_t* d_count, void* hip_stream) {
     if (!r || !d_rows || !d_count) return -1;
     return resample_call(r, d_rows, n, d_in, n_packets, in_samples, d_out, d_count, (hipStream_t)hip_stream);
+}
+
+// ---- voice activity, audio level, speaker selection (solo_vad.h): an object of its own, with a state record per row -------------------
+static_assert(sizeof(solo_vad_count_t) == sizeof(SxVadCount) && sizeof(solo_vad_select_params_t) == sizeof(SxVadSelectParams) &&
+              SOLO_VAD_STATE_BYTES == SX_VAD_STATE_WORDS * 4, "include/solo_mi355x.h and solo_vad.h agree");
+struct solo_vad_obj {
+    int32_t n_rows, frame;
+    int32_t* d_state;                // [n_rows][SX_VAD_STATE_WORDS]
+    uint32_t* d_verdict;             // [2]: the verdict words of solo_vad and of solo_vad_select
+    void* d_scratch;                 // the room plan and the keys of solo_vad_select (solo_vad_scratch_bytes)
+};
+solo_vad_t* solo_vad_create(int32_t n_rows, int32_t frame_samples) {
+    if (n_rows <= 0 || !sx_vad_frame_ok(frame_samples) || (int64_t)n_rows * SX_VAD_STATE_WORDS >= ((int64_t)1 << 31)) return NULL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
+        return NULL;
+    }
+    solo_vad_obj* v = new (std::nothrow) solo_vad_obj();
+    if (!v) return NULL;
+    memset(v, 0, sizeof(*v));
+    v->n_rows = n_rows; v->frame = frame_samples;
+    if (hipMalloc((void**)&v->d_state, (size_t)n_rows * SX_VAD_STATE_WORDS * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&v->d_verdict, 2 * sizeof(uint32_t)) != hipSuccess || hipMalloc(&v->d_scratch, solo_vad_scratch_bytes(n_rows)) != hipSuccess ||
+        hipMemset(v->d_verdict, 0, 2 * sizeof(uint32_t)) != hipSuccess || solo_vad_reset(v, NULL) != 0 || hipStreamSynchronize(NULL) != hipSuccess) {
+        solo_vad_destroy(v);
+        return NULL;
+    }
+    return v;
+}
+void solo_vad_destroy(solo_vad_t* v) {
+    if (!v) return;
+    dev_free(v->d_state);
+    dev_free(v->d_verdict);
+    dev_free(v->d_scratch);
+    delete v;
+}
+int32_t solo_vad_reset(solo_vad_t* v, void* hip_stream) {
+    if (!v) return -1;
+    const size_t words = (size_t)v->n_rows * SX_VAD_STATE_WORDS;
+    hipLaunchKernelGGL(solo_vad_reset_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, v->d_state, v->n_rows);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+int32_t solo_vad_reset_rows(solo_vad_t* v, const int32_t* h_rows, int32_t n, void* hip_stream) {
+    if (!v || !sx_vad_list_ok(h_rows, n, v->n_rows)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<SxStreamCtl> recs((size_t)n);
+    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
+    int32_t* state = v->d_state;
+    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
+        hipLaunchKernelGGL(solo_vad_reset_rows_kernel, dim3((unsigned)k), dim3(64), 0, st, state, l);
+    }));
+    return 0;
+}
+static int32_t vad_copy_state(solo_vad_obj* v, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
+    if (!v || !d_blob || n <= 0 || n > v->n_rows || ((uintptr_t)d_blob & 3)) return -1;
+    const size_t words = (size_t)n * SX_VAD_STATE_WORDS;
+    hipLaunchKernelGGL(solo_vad_copy_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, v->d_state, v->n_rows, d_rows, n, (i32*)d_blob, put);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+int32_t solo_vad_get_state(solo_vad_t* v, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
+    return vad_copy_state(v, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+}
+int32_t solo_vad_set_state(solo_vad_t* v, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
+    return vad_copy_state(v, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+}
+int32_t solo_vad(solo_vad_t* v, const int32_t* d_rows, int32_t n, const int16_t* d_pcm, int32_t n_packets, int32_t packet_samples, uint8_t* d_sa_q8,
+                 int32_t* d_detail, uint8_t* d_level, solo_vad_count_t* d_count, void* hip_stream) {
+    if (!v || !sx_vad_call_ok(v->frame, v->n_rows, d_rows, n, d_pcm, n_packets, packet_samples, d_sa_q8, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SxVadArgs a;
+    a.pcm = d_pcm; a.state = v->d_state; a.map = d_rows; a.sa = d_sa_q8; a.detail = d_detail; a.level = d_level;
+    a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples;
+    if (d_rows) {
+        hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, v->n_rows, v->d_verdict, (i32*)NULL);
+        SOLO_CHECK(hipGetLastError());
+    }
+    SOLO_CHECK(solo_vad_launch(v->frame, a, (SxVadCount*)d_count, v->d_verdict, st));
+    return 0;
+}
+int32_t solo_vad_select(solo_vad_t* v, const int32_t* d_rows, int32_t n, const uint8_t* d_sa_q8, const uint8_t* d_level, int32_t n_packets, int32_t frames,
+                        const int32_t* d_room, int32_t n_rooms, const solo_vad_select_params_t* params, const int16_t* d_gain_in, uint8_t* d_sel,
+                        int16_t* d_gain_out, uint8_t* d_keep, int32_t* d_dominant, solo_vad_count_t* d_count, void* hip_stream) {
+    if (!v || !sx_vsel_call_ok(v->n_rows, n, d_sa_q8, d_level, n_packets, frames, d_room, n_rooms, (const SxVadSelectParams*)params, d_sel, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SxVselArgs a = {};
+    a.sa = d_sa_q8; a.level = d_level; a.gain_in = d_gain_in; a.map = d_rows;
+    a.sel = d_sel; a.gain_out = d_gain_out; a.keep = d_keep; a.dominant = d_dominant; a.state = v->d_state;
+    a.n_packets = n_packets; a.frames = frames; a.prm = *(const SxVadSelectParams*)params;
+    const int32_t n_rows = v->n_rows;
+    SOLO_CHECK(solo_vad_select_launch(a, d_room, n, n_rooms, n_rows, v->d_scratch, (SxVadCount*)d_count, v->d_verdict + 1, [&](u32* verdict) {
+        if (d_rows) hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, n_rows, verdict, (i32*)NULL);
+    }, st));
+    return 0;
 }
 
 // ---- stream migration (solo_migrate.h): encoder state, decoder state and receive queue of listed streams <-> a device blob ---------
