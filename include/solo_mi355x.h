@@ -376,6 +376,47 @@ int32_t solo_mix_shared(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int
                         int16_t *d_pcm_room, int32_t *d_room_list, int32_t *d_source,
                         int64_t *d_energy, uint8_t *d_mixed,
                         solo_mix_shared_count_t *d_count, void *hip_stream);
+/* Shared listener mixes from a GIVEN selection: solo_mix_shared for a bridge that has already decided who speaks (solo_vad_select, or any
+ * policy of its own).  Everything is as in solo_mix_shared except where the selection comes from: there is no max_speakers, no energy is
+ * needed, and a room may have no speaker at all.  d_pcm_in, n, n_packets, d_room, n_rooms, d_keep, d_slots and the layouts and ordering
+ * rules of d_pcm_spk, d_spk_list, d_spk_rows, d_pcm_room, d_room_list and d_source: as there, so they feed solo_batch_encode_streams and
+ * solo_send_fanout unchanged.  d_gain_q12 is the callers' own gains (not the masked d_gain_out of solo_vad_select).
+ *   d_sel       uint8 [n][P], required: exactly what solo_vad_select writes to its d_sel.  sel_p(r) = { i in room r : d_sel[i][p] != 0 }; it
+ *               may be empty and it may hold every member; a non-zero entry of a row in no room is ignored
+ *   c_j         solo_mix's;  S_p = sum over sel_p of c_j (at most 64 terms of |c| < 2^18: the 32-bit sum is exact and independent of the order)
+ *   speaker of the call   a row that is in sel_p for at least one p, or whose d_keep[i] != 0.  A selected row with gain 0 is a speaker: the
+ *               selection is taken as given
+ *   shared room a room with at least one member that is not a speaker of the call
+ *   d_pcm_spk   packet p of speaker i is sat16(S_p - (i in sel_p ? c_i : 0))
+ *   d_pcm_room  packet p of a shared room is sat16(S_p)
+ *   d_room_nsel uint8 [n_rooms][P] or NULL, only the first `shared` rows are written: [j][p] = |sel_p| of the j-th shared room.  0 means that
+ *               packet of d_pcm_room[j] is all zeros: the caller may clear that destination's bits in the d_send mask of solo_send_fanout,
+ *               or let DTX handle it
+ *   d_energy    int64 [n][P] or NULL: solo_mix's e_j.  NULL: the energy pass, one full read of the input, is not launched at all
+ *   d_count     rows, rooms, speakers, shared, clipped as for solo_mix_shared; selected: (row, packet) pairs selected among rows in a room;
+ *               silent: (shared room, packet) pairs with an empty selection
+ * There is no d_mixed: it would be d_sel.
+ * Returns -1 with nothing enqueued for everything solo_mix_shared refuses (max_speakers does not exist here); a NULL d_sel; PCM outputs that
+ * are not 16-byte aligned or overlap the input or each other.  Found on the device, ahead of anything written to a caller's buffer (d_energy
+ * included): a room id outside [-1, n_rooms); a d_slots that does not grow strictly from a non-negative start; more than 64 selected
+ * members in any one (room, packet).  Nothing is then written except d_count->rows = -1.
+ * Any handle will do.  Nine short kernels (ten with d_energy) on hip_stream only, no host synchronisation, capturable -- except that the
+ * handle's scratch (the one of solo_mix; here 8 bytes per row and packet + 28 per row) grows, with a stream synchronisation, when a call is
+ * larger than every one before it.  The call does not wait for the handle's internal streams, and calls on one handle must be ordered.
+ * INTEGRATION.md section 2 has the tick. */
+typedef struct {
+    int32_t rows, rooms;        /* as solo_mix_count_t; rows = -1: call refused on the device */
+    int32_t speakers, shared;   /* rows of d_pcm_spk / d_pcm_room that were written */
+    int64_t clipped;            /* samples of those rows that saturated */
+    int32_t selected, silent;   /* (row, packet) pairs selected among rows in a room / (shared room, packet) pairs with an empty selection */
+} solo_mix_selected_count_t;   /* 32 bytes */
+int32_t solo_mix_selected(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, int32_t n_packets,
+                          const int32_t *d_room, int32_t n_rooms, const int16_t *d_gain_q12, const uint8_t *d_sel,
+                          const uint8_t *d_keep, const int32_t *d_slots,
+                          int16_t *d_pcm_spk, int32_t *d_spk_list, int32_t *d_spk_rows,
+                          int16_t *d_pcm_room, int32_t *d_room_list, int32_t *d_source,
+                          uint8_t *d_room_nsel, int64_t *d_energy,
+                          solo_mix_selected_count_t *d_count, void *hip_stream);
 /* Sender back end for shared sources: ONE table of encoded packets (d_bits [n_src][P][slot], d_nbytes [n_src][P][2], the layout the encode
  * calls write), MANY destinations.  Destination i of n_dst sends the packets of source row d_source[i] (-1: it sends nothing and is not
  * counted) as stream d_dst_stream ? d_dst_stream[i] : i, with the sequence numbers first_seq + (d_seq_base ? d_seq_base[i] : 0) + p and under

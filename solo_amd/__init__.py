@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "solo_batch_state_bytes", "solo_batch_export_streams", "solo_batch_import_streams",
     "solo_resample_create", "solo_resample_destroy", "solo_resample_out_samples", "solo_resample_reset", "solo_resample_reset_rows",
     "solo_resample", "solo_resample_rows",
-    "solo_mix_shared", "solo_send_fanout",
+    "solo_mix_shared", "solo_send_fanout", "solo_mix_selected",
     "solo_timescale",
     "solo_vad_create", "solo_vad_destroy", "solo_vad_reset", "solo_vad_reset_rows", "solo_vad_get_state", "solo_vad_set_state",
     "solo_vad", "solo_vad_select",
@@ -64,6 +64,12 @@ class solo_mix_count_t(C.Structure):
 class solo_mix_shared_count_t(C.Structure):
     """what a solo_mix_shared call did (include/solo_mi355x.h); 24 bytes"""
     _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("speakers", C.c_int32), ("shared", C.c_int32), ("clipped", C.c_int64)]
+
+
+class solo_mix_selected_count_t(C.Structure):
+    """what a solo_mix_selected call did (include/solo_mi355x.h); 32 bytes"""
+    _fields_ = [("rows", C.c_int32), ("rooms", C.c_int32), ("speakers", C.c_int32), ("shared", C.c_int32), ("clipped", C.c_int64),
+                ("selected", C.c_int32), ("silent", C.c_int32)]
 
 
 class solo_timescale_count_t(C.Structure):
@@ -198,6 +204,8 @@ def load_library():
                              C.c_void_p, C.c_void_p]
     lib.solo_mix_shared.restype = C.c_int32
     lib.solo_mix_shared.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 12
+    lib.solo_mix_selected.restype = C.c_int32
+    lib.solo_mix_selected.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 14
     lib.solo_timescale.restype = C.c_int32
     lib.solo_timescale.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_send_fanout.restype = C.c_int32
@@ -876,6 +884,69 @@ class SoloBatch:
         written), shared (rows of pcm_room written), saturated samples among them; rows == -1: the call was refused on the device"""
         c = solo_mix_shared_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
         return {k: int(getattr(c, k)) for k in self.MIX_SHARED_COUNT}
+
+    # ---- shared listener mixes from a given selection (solo_mix_selected): the end of a tick that ran Vad.select ----
+    MIX_SELECTED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped", "selected", "silent")
+
+    def mix_selected(self, pcm, room, sel, gain=None, keep=None, slots=None, n_rooms=None, energy=None, room_nsel=None, pcm_spk=None,
+                     pcm_room=None):
+        """solo_mix_selected: mix_shared() for a selection the caller brings.  pcm int16 [n,P,samples], room int32 [n], sel uint8 [n,P] (the
+        tensor Vad.select returns: non-zero = row i speaks in packet p; a room may have no speaker, or only speakers; at most 64 per room
+        and packet), gain int16 [n] or None (the callers' own gains), keep / slots / n_rooms as for mix_shared() ->
+        (pcm_spk, spk_list, spk_rows, pcm_room, room_list, source, count int32 [8] on the device: read it with mix_selected_count(),
+        room_nsel uint8 [n_rooms,P]).  The first seven are what mix_shared() returns, with its layouts; room_nsel[j, p] (first `shared`
+        rows) is the number of speakers of the j-th shared room in packet p: 0 = that packet of pcm_room[j] is digital silence, which
+        the caller may leave unsent (the send mask of send_fanout()).  energy int64 [n,P]: optional output, solo_mix's energies; without
+        it the input is never read for them.  A room id outside [-1, n_rooms), slots that do not grow strictly from a non-negative start
+        or more than 64 selected rows in a room and packet refuse the call on the device: rows == -1 in the count, nothing else written.
+        Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
+        if not dev(pcm, t.int16, 3):
+            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
+        n, P, L = pcm.shape
+        if L != self.packet_samples or n <= 0 or P <= 0:
+            raise ValueError("pcm: packets of %d samples, at least one row and one packet" % self.packet_samples)
+        if n * P >= 2 ** 31:
+            raise ValueError("n * P must stay below 2^31")
+        n_rooms = n if n_rooms is None else int(n_rooms)
+        if not 0 < n_rooms <= n:
+            raise ValueError("n_rooms: between 1 and the number of rows")
+        if not (dev(sel, t.uint8, 2) and tuple(sel.shape) == (n, P)):
+            raise ValueError("sel: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
+        for name, x, dt in (("room", room, t.int32), ("gain", gain, t.int16), ("keep", keep, t.uint8), ("slots", slots, t.int32)):
+            if (x is not None or name == "room") and not (dev(x, dt, 1) and x.shape[0] == n):
+                raise ValueError("%s: a contiguous %s CUDA tensor [%d]" % (name, str(dt).split(".")[-1], n))
+        if energy is not None and not (dev(energy, t.int64, 2) and tuple(energy.shape) == (n, P)):
+            raise ValueError("energy: a contiguous int64 CUDA tensor [%d, %d]" % (n, P))
+        if room_nsel is not None and not (dev(room_nsel, t.uint8, 2) and tuple(room_nsel.shape) == (n_rooms, P)):
+            raise ValueError("room_nsel: a contiguous uint8 CUDA tensor [%d, %d]" % (n_rooms, P))
+        if pcm_spk is not None and not (dev(pcm_spk, t.int16, 3) and tuple(pcm_spk.shape) == (n, P, L)):
+            raise ValueError("pcm_spk: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, L))
+        if pcm_room is not None and not (dev(pcm_room, t.int16, 3) and tuple(pcm_room.shape) == (n_rooms, P, L)):
+            raise ValueError("pcm_room: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n_rooms, P, L))
+        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=pcm.device)
+        if pcm_spk is None:
+            pcm_spk = z((n, P, L), t.int16)
+        if pcm_room is None:
+            pcm_room = z((n_rooms, P, L), t.int16)
+        if room_nsel is None:
+            room_nsel = z((n_rooms, P), t.uint8)
+        spk_list, spk_rows, room_list, source = z((n,), t.int32), z((n,), t.int32), z((n_rooms,), t.int32), z((n,), t.int32)
+        count = z((8,), t.int32)
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        r = self.lib.solo_mix_selected(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n_rooms, ptr(gain), sel.data_ptr(), ptr(keep), ptr(slots),
+                                       pcm_spk.data_ptr(), spk_list.data_ptr(), spk_rows.data_ptr(), pcm_room.data_ptr(), room_list.data_ptr(),
+                                       source.data_ptr(), room_nsel.data_ptr(), ptr(energy), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_mix_selected -> %d" % r)
+        return pcm_spk, spk_list, spk_rows, pcm_room, room_list, source, count, room_nsel
+
+    def mix_selected_count(self, count):
+        """the count tensor of mix_selected() as a dict (synchronises): the five counts of mix_shared_count(), selected ((row, packet) pairs
+        selected among rows in a room) and silent ((shared room, packet) pairs nobody speaks in); rows == -1: refused on the device"""
+        c = solo_mix_selected_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
+        return {k: int(getattr(c, k)) for k in self.MIX_SELECTED_COUNT}
 
     def send_fanout(self, bits, nbytes, source, dst_stream=None, send=None, first_seq=0, seq_base=None, records=None, payload=None):
         """solo_send_fanout: one table of encoded packets (bits uint8 [n_src,P,slot], nbytes int16 [n_src,P,2]), many destinations: source

@@ -30,6 +30,7 @@
 #include "solo_send.h"          // the sender back end (solo_send_pack): rate-independent, compiled once, not a member of the launch tables
 #include "solo_mix.h"           // the mixing bridge (solo_mix): likewise
 #include "solo_mix_shared.h"    // ... with shared listener mixes (solo_mix_shared)
+#include "solo_mix_selected.h"  // ... from a selection the caller brings (solo_mix_selected)
 #include "solo_fanout.h"        // one source table, many destinations (solo_send_fanout)
 #include "solo_recv_report.h"   // the read side of the receiver ring (solo_recv_report, solo_recv_track): likewise
 #include "solo_migrate.h"       // stream states out of a handle and into another (solo_batch_export_streams / _import_streams): likewise
@@ -182,7 +183,7 @@ enum {
     SOLO_VERDICT_DEC = 2,            // decode
     SOLO_VERDICT_RING,               // receiver play-out
     SOLO_VERDICT_SEND,               // solo_send_pack_streams, solo_send_fanout (its source rows)
-    SOLO_VERDICT_MIX,                // solo_mix, solo_mix_shared (their room ids, its slots)
+    SOLO_VERDICT_MIX,                // solo_mix, solo_mix_shared, solo_mix_selected (their room ids, slots, picks per room and packet)
     SOLO_VERDICT_REPORT,             // solo_recv_report
     SOLO_VERDICT_EXPORT,             // solo_batch_export_streams
     SOLO_VERDICT_IMPORT,             // [8, 9] solo_batch_import_streams (its list, its records)
@@ -894,6 +895,31 @@ int32_t solo_mix_shared(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int
     a.energy = d_energy; a.mixed = d_mixed;
     a.n = n; a.n_rooms = n_rooms; a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
     SOLO_CHECK(solo_mixsh_launch(a, b->d_mix_scratch, (SxMixShCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
+    return 0;
+}
+
+// ... from a selection the caller brings (solo_mix_selected.h): no energies, no select pass
+static_assert(sizeof(solo_mix_selected_count_t) == sizeof(SxMixSelCount), "include/solo_mi355x.h and solo_mix_selected.h agree");
+int32_t solo_mix_selected(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
+                          const int16_t* d_gain_q12, const uint8_t* d_sel, const uint8_t* d_keep, const int32_t* d_slots, int16_t* d_pcm_spk,
+                          int32_t* d_spk_list, int32_t* d_spk_rows, int16_t* d_pcm_room, int32_t* d_room_list, int32_t* d_source,
+                          uint8_t* d_room_nsel, int64_t* d_energy, solo_mix_selected_count_t* d_count, void* hip_stream) {
+    if (!b) return -1;
+    int L = 0;                       // the packet geometry is the handle's, as for solo_mix
+    if (b->have_dec) L = dec_packet_samples(b);
+#ifdef SOLO_WITH_ENCODER
+    else if (b->have_enc) L = enc_packet_samples(b);
+#endif
+    if (!sx_mixsel_args_ok(d_pcm_in, n, n_packets, L, d_room, n_rooms, d_sel, d_pcm_spk, d_spk_list, d_pcm_room, d_room_list, d_source, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(b->d_mix_scratch, b->mix_scratch_bytes, solo_mixsel_scratch_bytes(n, n_packets), st));
+    SxMixSelArgs a = {};
+    a.sh.pcm_in = d_pcm_in; a.sh.gain = d_gain_q12; a.sh.room = d_room; a.sh.keep = d_keep; a.sh.slots = d_slots;
+    a.sh.pcm_spk = d_pcm_spk; a.sh.spk_list = d_spk_list; a.sh.spk_rows = d_spk_rows; a.sh.pcm_room = d_pcm_room; a.sh.room_list = d_room_list;
+    a.sh.source = d_source; a.sh.energy = d_energy; a.sh.mixed = const_cast<uint8_t*>(d_sel);       // (read only on this path)
+    a.sh.n = n; a.sh.n_rooms = n_rooms; a.sh.n_packets = n_packets; a.sh.L = L; a.sh.max_speakers = SX_MIX_MAX_SPEAKERS;
+    a.room_nsel = d_room_nsel;
+    SOLO_CHECK(solo_mixsel_launch(a, b->d_mix_scratch, (SxMixSelCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
     return 0;
 }
 

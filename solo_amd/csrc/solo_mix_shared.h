@@ -127,14 +127,11 @@ SX_HD void sx_mixsh_select_unit(const SxMixShArgs& a, int room, int p) {
     }
 }
 
-// pass 10, one (room, packet) -> the saturated output samples of the unit (the wave's total, in every lane)
-SX_HD i64 sx_mixsh_write_unit(const SxMixShArgs& a, int room, int p) {
-    const int m = SX_UNI(a.counts[room]);
-    if (m <= 0) return 0;
-    const int start = SX_UNI(a.starts[room]), P = a.n_packets, CH = a.L >> 3;
+// pass 10, one (room of m > 0 members, packet) whose K picks are sel[0 .. K) and are flagged in a.mixed (solo_mix_selected.h brings a K
+// and a list of its own) -> the saturated output samples of the unit (the wave's total, in every lane)
+SX_HD i64 sx_mixsh_write_picks(const SxMixShArgs& a, int room, int p, int m, int start, int K, const i32* sel) {
+    const int P = a.n_packets, CH = a.L >> 3;
     const i32* mem = a.members + start;
-    const int K = sx_mixsh_picks(a, m);
-    const i32* sel = sx_mixsh_sel(a, start, K, p);
     const size_t row_chunks = (size_t)P * (size_t)CH;       // chunks between rows
     const SxMixX8* in_p = (const SxMixX8*)a.pcm_in + (size_t)p * (size_t)CH;
     SxMixX8* spk_p = (SxMixX8*)a.pcm_spk + (size_t)p * (size_t)CH;
@@ -184,6 +181,12 @@ SX_HD i64 sx_mixsh_write_unit(const SxMixShArgs& a, int room, int p) {
         }
     }
     return wv_sum64(clipped);
+}
+SX_HD i64 sx_mixsh_write_unit(const SxMixShArgs& a, int room, int p) {
+    const int m = SX_UNI(a.counts[room]);
+    if (m <= 0) return 0;
+    const int start = SX_UNI(a.starts[room]), K = sx_mixsh_picks(a, m);
+    return sx_mixsh_write_picks(a, room, p, m, start, K, sx_mixsh_sel(a, start, K, p));
 }
 
 // bytes of device scratch a call needs (n_rooms <= n): energy [n][P] | seven words per row (counts, starts, cursors, members, speaker
@@ -243,12 +246,13 @@ __global__ void __launch_bounds__(256) solo_mixsh_tally_kernel(const SxMixShArgs
     const i32 r = a.room[i];
     if (r >= 0 && !a.spk[i]) atomicAdd(&a.nonspk[r], 1);
 }
-// one workgroup: lane t owns the rows [t * per, (t + 1) * per) and the rooms [t * per_r, (t + 1) * per_r)
-__global__ void __launch_bounds__(256) solo_mixsh_compact_kernel(const SxMixShArgs a, SxMixShCount* count, const u32* verdict) {
+// one workgroup of 256: lane t owns the rows [t * per, (t + 1) * per) and the rooms [t * per_r, (t + 1) * per_r).  -> false, in every lane,
+// when the call was refused (solo_mix_selected.h adds counts of its own behind it)
+__device__ __forceinline__ bool sx_mixsh_compact_group(const SxMixShArgs& a, SxMixShCount* count, const u32* verdict) {
     __shared__ i32 w_spk[4], w_shared[4], w_rows[4], w_rooms[4];
     if (sx_map_refused(a.room, verdict)) {
         if (threadIdx.x == 0) count->rows = -1;
-        return;
+        return false;
     }
     const int tid = (int)threadIdx.x, wave = tid >> 6;
     const int per = (a.n + 255) / 256, per_r = (a.n_rooms + 255) / 256;
@@ -283,6 +287,10 @@ __global__ void __launch_bounds__(256) solo_mixsh_compact_kernel(const SxMixShAr
         c.clipped = 0;                                      // (the write pass adds what each workgroup saturated)
         *count = c;
     }
+    return true;
+}
+__global__ void __launch_bounds__(256) solo_mixsh_compact_kernel(const SxMixShArgs a, SxMixShCount* count, const u32* verdict) {
+    (void)sx_mixsh_compact_group(a, count, verdict);
 }
 __global__ void __launch_bounds__(256) solo_mixsh_source_kernel(const SxMixShArgs a, const u32* verdict) {
     if (sx_map_refused(a.room, verdict)) return;
@@ -318,26 +326,30 @@ static inline hipError_t solo_mixsh_launch(SxMixShArgs a, void* scratch, SxMixSh
 }
 #else
 // Host form of the launches (tests): the same passes in the same order, serially, the member lists filled from the LAST row down (any
-// order will do).  -> false: refused "on the device", nothing but count->rows = -1 is written
-static inline bool sx_mixsh_host(SxMixShArgs a, SxMixShCount* count) {
-    const int n = a.n, R = a.n_rooms, P = a.n_packets;
-    for (int i = 0; i < n; i++) {
-        bool bad = a.room[i] < -1 || a.room[i] >= R;
+// order will do), in three stages that solo_mix_selected.h runs as well.
+// the check pass -> false: refused "on the device"
+static inline bool sx_mixsh_host_check(const SxMixShArgs& a) {
+    for (int i = 0; i < a.n; i++) {
+        bool bad = a.room[i] < -1 || a.room[i] >= a.n_rooms;
         if (a.slots) bad |= a.slots[i] < 0 || (i > 0 && a.slots[i - 1] >= a.slots[i]);
-        if (bad) { count->rows = -1; return false; }
+        if (bad) return false;
     }
-    const size_t bytes = solo_mixsh_scratch_bytes(n, P);
-    i64* scratch = new i64[bytes / sizeof(i64) + 1]();
-    solo_mixsh_plan(a, scratch);
-    SxMixShCount c; c.rows = 0; c.rooms = 0; c.speakers = 0; c.shared = 0; c.clipped = 0;
+    return true;
+}
+// the room plan (the scratch starts zeroed): member counts and lists, spk[i] = d_keep[i], the counts rows and rooms
+static inline void sx_mixsh_host_rooms(const SxMixShArgs& a, SxMixShCount& c) {
+    const int n = a.n, R = a.n_rooms;
+    c.rows = 0; c.rooms = 0; c.speakers = 0; c.shared = 0; c.clipped = 0;
     for (int i = 0; i < n; i++) {
         if (a.room[i] >= 0) a.counts[a.room[i]]++;
         a.spk[i] = (a.room[i] >= 0 && a.keep && a.keep[i]) ? 1 : 0;
     }
     for (int r = 0; r < R; r++) { a.starts[r] = a.cursor[r] = c.rows; c.rows += a.counts[r]; c.rooms += a.counts[r] > 0; }
     for (int i = n - 1; i >= 0; i--) if (a.room[i] >= 0) a.members[a.cursor[a.room[i]]++] = i;
-    for (int i = 0; i < n; i++) for (int p = 0; p < P; p++) sx_mixsh_energy_unit(a, i, p);
-    for (int r = 0; r < R; r++) for (int p = 0; p < P; p++) sx_mixsh_select_unit(a, r, p);
+}
+// tally, compact, source: the two lists, source[], every room's index, the counts speakers and shared
+static inline void sx_mixsh_host_lists(const SxMixShArgs& a, SxMixShCount& c) {
+    const int n = a.n, R = a.n_rooms;
     for (int i = 0; i < n; i++) if (a.room[i] >= 0 && !a.spk[i]) a.nonspk[a.room[i]]++;
     for (int i = 0; i < n; i++)
         if (a.spk[i]) {
@@ -354,6 +366,19 @@ static inline bool sx_mixsh_host(SxMixShArgs a, SxMixShCount* count) {
         if (a.room[i] < 0) a.source[i] = -1;
         else if (!a.spk[i]) a.source[i] = n + a.room_idx[a.room[i]];
     }
+}
+// -> false: refused "on the device", nothing but count->rows = -1 is written
+static inline bool sx_mixsh_host(SxMixShArgs a, SxMixShCount* count) {
+    const int n = a.n, R = a.n_rooms, P = a.n_packets;
+    if (!sx_mixsh_host_check(a)) { count->rows = -1; return false; }
+    const size_t bytes = solo_mixsh_scratch_bytes(n, P);
+    i64* scratch = new i64[bytes / sizeof(i64) + 1]();
+    solo_mixsh_plan(a, scratch);
+    SxMixShCount c;
+    sx_mixsh_host_rooms(a, c);
+    for (int i = 0; i < n; i++) for (int p = 0; p < P; p++) sx_mixsh_energy_unit(a, i, p);
+    for (int r = 0; r < R; r++) for (int p = 0; p < P; p++) sx_mixsh_select_unit(a, r, p);
+    sx_mixsh_host_lists(a, c);
     for (int r = 0; r < R; r++) for (int p = 0; p < P; p++) c.clipped += sx_mixsh_write_unit(a, r, p);
     *count = c;
     delete[] scratch;
