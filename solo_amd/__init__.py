@@ -9,6 +9,7 @@ The C ABI bound here is declared in include/solo_mi355x.h (the six AGR_Sate_* en
 reference's interface/AGR_JC1_SDK_API.h plus the batched device-pointer API).
 """
 import ctypes as C
+import operator
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -308,6 +309,55 @@ def default_dec_ctrl(use_md_index=0, joint=0, samplerate=16000, framesize_ms=40)
                          joint_mode=1 if joint else 0, useMDIndex=use_md_index)
 
 
+# ---- the argument checks every method below shares: a bad argument raises ValueError before anything reaches the library ----
+def _tensor(name, x, dtype, shape, optional=False):
+    """x must be a contiguous CUDA tensor of `dtype` whose shape is `shape` (None = that dimension is free), or None where `optional`
+    -> its shape as a tuple (None for an absent optional).  Reads is_cuda, dtype, is_contiguous() and shape, nothing else, and
+    does no work on the device."""
+    if x is None and optional:
+        return None
+    if getattr(x, "is_cuda", False) and x.dtype == dtype and x.is_contiguous():
+        got = tuple(x.shape)
+        if len(got) == len(shape):
+            for w, g in zip(shape, got):             # (a plain loop: this runs a dozen times in a one-packet call)
+                if w is not None and w != g:
+                    break
+            else:
+                return got
+    raise ValueError("%s: a contiguous %s CUDA tensor [%s]%s" % (name, str(dtype).split(".")[-1], ", ".join("n" if w is None else str(w) for w in shape),
+                                                                 " or None" if optional else ""))
+
+
+def _ptr(x):
+    return None if x is None else x.data_ptr()
+
+
+def _counts(struct, count):
+    """a count tensor as the dict of the fields of `struct` (synchronises)"""
+    c = struct.from_buffer_copy(count.cpu().numpy().tobytes())
+    return {k: int(getattr(c, k)) for k, _ in struct._fields_}
+
+
+def _host_list(rows):
+    return [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
+
+
+def _increasing(name, rows, n):
+    """a host sequence of indices inside [0, n), strictly increasing -> list"""
+    idx = _host_list(rows)
+    if not idx or any(b <= a for a, b in zip(idx, idx[1:])) or idx[0] < 0 or idx[-1] >= n:
+        raise ValueError("%s: strictly increasing indices inside [0, %d)" % (name, n))
+    return idx
+
+
+def _distinct(name, rows, n):
+    """a host sequence of indices inside [0, n), none twice -> list"""
+    idx = _host_list(rows)
+    if not 0 < len(idx) <= n or any(v < 0 or v >= n for v in idx) or len(set(idx)) != len(idx):
+        raise ValueError("%s: 1 .. %d indices inside [0, %d), none twice" % (name, n, n))
+    return idx
+
+
 class SoloBatch:
     """N independent SOLO streams on the current HIP device (one wavefront per stream)."""
 
@@ -347,30 +397,32 @@ class SoloBatch:
 
     _WHICH = {"enc": 1, "encoder": 1, "dec": 2, "decoder": 2, "both": 3, 1: 1, 2: 2, 3: 3}
 
-    def _stream_list(self, streams):
-        idx = [int(s) for s in (streams.tolist() if hasattr(streams, "tolist") else streams)]
-        if not 0 < len(idx) <= self.n_streams:
-            raise ValueError("between 1 and %d streams must be listed" % self.n_streams)
-        if any(s < 0 or s >= self.n_streams for s in idx):
-            raise ValueError("stream index out of range")
-        if len(set(idx)) != len(idx):
-            raise ValueError("a stream is listed twice")
-        return idx
-
     def _subset(self, streams):
         """streams= of encode / decode / recv_decode: a sequence or an int32 CUDA tensor of stream indices, strictly increasing ->
-        (int32 tensor on the device, n).  Checked here like _stream_list (the library checks the device list once more and refuses
+        (int32 tensor on the device, n).  Checked here (the library checks the device list once more and refuses
         a bad one with status -1, but by then the call is enqueued)."""
         t = self.torch
         on_dev = getattr(streams, "is_cuda", False)
-        if on_dev and (streams.dtype != t.int32 or streams.dim() != 1):
+        if on_dev and (streams.dtype != t.int32 or len(streams.shape) != 1):     # (need not be contiguous: it is made so below)
             raise ValueError("streams: a sequence or a 1-D int32 CUDA tensor")
-        idx = self._stream_list(streams)
-        if any(a >= b for a, b in zip(idx, idx[1:])):
-            raise ValueError("streams must be listed in increasing order")
+        idx = _increasing("streams", streams, self.n_streams)
         if on_dev:
             return streams.contiguous(), len(idx)
         return t.tensor(idx, dtype=t.int32, device=self.device), len(idx)
+
+    def _list_as_is(self, streams):
+        """streams= of recv_report / export_streams / import_streams: a 1-D int32 CUDA tensor is taken as it is and checked on the
+        device (a bad one is refused there), a sequence goes through _subset -> (int32 tensor on the device, n)"""
+        if getattr(streams, "is_cuda", False):
+            n, = _tensor("streams", streams, self.torch.int32, (None,))
+            if not 0 < n <= self.n_streams:
+                raise ValueError("streams: 1 .. %d indices" % self.n_streams)
+            return streams, n
+        return self._subset(streams)
+
+    def _rows_of(self, streams):
+        """streams= of a call -> (None, N) for every stream of the handle, else _subset(streams)"""
+        return (None, self.n_streams) if streams is None else self._subset(streams)
 
     @staticmethod
     def _per_stream(v, n, name):
@@ -384,7 +436,7 @@ class SoloBatch:
     def _ctl_arrays(self, streams, rate, dtx, use_md_index, which):
         """the arguments of solo_batch_reset_streams / solo_batch_update_streams: (stream indices, which, encoder controls or None,
         decoder controls or None); None controls mean the handle's create-time control"""
-        idx = self._stream_list(streams)
+        idx = _distinct("streams", streams, self.n_streams)
         n = len(idx)
         if which not in self._WHICH:
             raise ValueError("which must be 'enc', 'dec' or 'both'")
@@ -444,14 +496,13 @@ class SoloBatch:
         streams: encode only these streams (solo_batch_encode_streams); every shape then has n = len(streams) rows in place of N,
         row i belonging to streams[i]; the other streams keep their state."""
         t = self.torch
-        assert pcm.is_cuda and pcm.dtype == t.int16 and pcm.is_contiguous()
-        N, P, L = pcm.shape
-        smap = None
-        if streams is not None:
-            smap, n = self._subset(streams)
-            if N != n:
-                raise ValueError("pcm has %d rows for %d listed streams" % (N, n))
-        assert (smap is not None or N == self.n_streams) and L == self.packet_samples
+        N, P, _ = _tensor("pcm", pcm, t.int16, (None, None, self.packet_samples))
+        smap, n = self._rows_of(streams)
+        if N != n or P < 1:
+            raise ValueError("pcm: %d rows and at least one packet" % n)
+        _tensor("bits", bits, t.uint8, (N, P, self.slot), optional=True)
+        _tensor("nbytes", nbytes, t.int16, (N, P, 2), optional=True)
+        _tensor("status", status, t.int32, (N,), optional=True)
         if bits is None:
             bits = t.zeros((N, P, self.slot), dtype=t.uint8, device=pcm.device)
         if nbytes is None:
@@ -499,27 +550,23 @@ class SoloBatch:
         """bits uint8 [N,P,slot], nbytes int16 [N,P,2], recv uint8 [N,P] (bit0 MD1, bit1 MD2) -> pcm int16 [N,P,640] (1280 in the 32 kHz mode).
         streams: decode only these streams (solo_batch_decode_streams): n = len(streams) rows in place of N."""
         t = self.torch
-        assert bits.is_cuda and bits.dtype == t.uint8 and bits.is_contiguous()
-        assert nbytes.dtype == t.int16 and nbytes.is_contiguous()
-        N, P, S = bits.shape
-        smap = None
-        if streams is not None:
-            smap, n = self._subset(streams)
-            if N != n:
-                raise ValueError("bits has %d rows for %d listed streams" % (N, n))
-        assert (smap is not None or N == self.n_streams) and S == self.slot
-        if recv is not None:
-            assert recv.dtype == t.uint8 and recv.is_contiguous() and tuple(recv.shape) == (N, P)
+        N, P, _ = _tensor("bits", bits, t.uint8, (None, None, self.slot))
+        smap, n = self._rows_of(streams)
+        if N != n or P < 1:
+            raise ValueError("bits: %d rows and at least one packet" % n)
+        _tensor("nbytes", nbytes, t.int16, (N, P, 2))
+        _tensor("recv", recv, t.uint8, (N, P), optional=True)
+        _tensor("pcm", pcm, t.int16, (N, P, self.packet_samples), optional=True)
+        _tensor("status", status, t.int32, (N,), optional=True)
         if pcm is None:
             pcm = t.zeros((N, P, self.packet_samples), dtype=t.int16, device=bits.device)
         if status is None:
             status = t.zeros((N,), dtype=t.int32, device=bits.device)
         if smap is not None:
-            r = self.lib.solo_batch_decode_streams(self.h, smap.data_ptr(), N, bits.data_ptr(), nbytes.data_ptr(),
-                                                   recv.data_ptr() if recv is not None else None, P, pcm.data_ptr(), status.data_ptr(), self._stream())
+            r = self.lib.solo_batch_decode_streams(self.h, smap.data_ptr(), N, bits.data_ptr(), nbytes.data_ptr(), _ptr(recv), P, pcm.data_ptr(),
+                                                   status.data_ptr(), self._stream())
         else:
-            r = self.lib.solo_batch_decode(self.h, bits.data_ptr(), nbytes.data_ptr(), recv.data_ptr() if recv is not None else None,
-                                           P, pcm.data_ptr(), status.data_ptr(), self._stream())
+            r = self.lib.solo_batch_decode(self.h, bits.data_ptr(), nbytes.data_ptr(), _ptr(recv), P, pcm.data_ptr(), status.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_batch_decode%s -> %d" % ("_streams" if smap is not None else "", r))
         return pcm, status
@@ -528,10 +575,14 @@ class SoloBatch:
         """Receiver front end: the two descriptions of every packet in two arrival slots.  desc_a / desc_b uint8 [N,P,S],
         len_a / len_b int16 [N,P] (0 = nothing arrived) -> pcm int16 [N,P,640] (see solo_batch_decode_split)."""
         t = self.torch
-        for d, n in ((desc_a, len_a), (desc_b, len_b)):
-            assert d.is_cuda and d.dtype == t.uint8 and d.is_contiguous() and n.dtype == t.int16 and n.is_contiguous()
-        N, P, S = desc_a.shape
-        assert N == self.n_streams and tuple(desc_b.shape) == (N, P, S) and tuple(len_a.shape) == (N, P) == tuple(len_b.shape)
+        N, P, S = _tensor("desc_a", desc_a, t.uint8, (self.n_streams, None, None))
+        if P < 1:
+            raise ValueError("desc_a: at least one packet")
+        _tensor("desc_b", desc_b, t.uint8, (N, P, S))
+        _tensor("len_a", len_a, t.int16, (N, P))
+        _tensor("len_b", len_b, t.int16, (N, P))
+        _tensor("pcm", pcm, t.int16, (N, P, self.packet_samples), optional=True)
+        _tensor("status", status, t.int32, (N,), optional=True)
         if pcm is None:
             pcm = t.zeros((N, P, self.packet_samples), dtype=t.int16, device=desc_a.device)
         if status is None:
@@ -553,9 +604,9 @@ class SoloBatch:
     def recv_insert(self, arrivals, payload):
         """arrivals: int32 [n,5] (stream, seq, desc, offset, len) on the device; payload: uint8 [bytes] on the device."""
         t = self.torch
-        assert arrivals.is_cuda and arrivals.dtype == t.int32 and arrivals.is_contiguous() and arrivals.dim() == 2 and arrivals.shape[1] == 5
-        assert payload.is_cuda and payload.dtype == t.uint8 and payload.is_contiguous()
-        r = self.lib.solo_recv_insert(self.h, arrivals.data_ptr(), arrivals.shape[0], payload.data_ptr(), payload.numel(), self._stream())
+        n, _ = _tensor("arrivals", arrivals, t.int32, (None, 5))
+        nbytes, = _tensor("payload", payload, t.uint8, (None,))
+        r = self.lib.solo_recv_insert(self.h, arrivals.data_ptr(), n, payload.data_ptr(), nbytes, self._stream())
         if r:
             raise RuntimeError("solo_recv_insert -> %d" % r)
 
@@ -564,9 +615,15 @@ class SoloBatch:
         streams: play out only these streams (solo_recv_decode_streams): pcm [n,n_packets,samples], status [n]; the others keep
         their queue and play-out position."""
         t = self.torch
-        smap, N = None, self.n_streams
-        if streams is not None:
-            smap, N = self._subset(streams)
+        try:
+            n_packets = operator.index(n_packets)
+        except TypeError:
+            n_packets = 0
+        if n_packets < 1:
+            raise ValueError("n_packets: a positive int")
+        smap, N = self._rows_of(streams)
+        _tensor("pcm", pcm, t.int16, (N, n_packets, self.packet_samples), optional=True)
+        _tensor("status", status, t.int32, (N,), optional=True)
         if pcm is None:
             pcm = t.zeros((N, n_packets, self.packet_samples), dtype=t.int16, device=self.device)
         if status is None:
@@ -582,7 +639,7 @@ class SoloBatch:
     def recv_reset_streams(self, streams, first_seq):
         """Empty the staging queue of the listed streams and set their play-out positions (solo_recv_reset_streams); first_seq: a
         scalar or one sequence number (>= 0) per listed stream.  Statistics and the other streams are untouched."""
-        idx = self._stream_list(streams)
+        idx = _distinct("streams", streams, self.n_streams)
         seqs = [int(v) for v in self._per_stream(first_seq, len(idx), "first_seq")]
         if any(v < 0 for v in seqs):
             raise ValueError("first_seq must be >= 0")
@@ -617,30 +674,19 @@ class SoloBatch:
         what recv_decode(streams=...) takes.  clear_margin: margin_min of the listed streams starts afresh after this report.
         Enqueued on the current stream, no synchronisation."""
         t = self.torch
-        dev = lambda x, nd: getattr(x, "is_cuda", False) and x.dtype == t.int32 and x.is_contiguous() and len(x.shape) == nd
-        smap, n = None, self.n_streams
-        if streams is not None:
-            if getattr(streams, "is_cuda", False):
-                if not dev(streams, 1) or not 0 < streams.shape[0] <= self.n_streams:
-                    raise ValueError("streams: a sequence or a contiguous 1-D int32 CUDA tensor of 1 .. %d indices" % self.n_streams)
-                smap, n = streams, int(streams.shape[0])
-            else:
-                smap, n = self._subset(streams)
+        smap, n = (None, self.n_streams) if streams is None else self._list_as_is(streams)
         mr_v, mr = None, 0
         if isinstance(min_ready, int) and not isinstance(min_ready, bool):
             mr = min_ready
-        elif dev(min_ready, 1) and min_ready.shape[0] == n:
-            mr_v = min_ready
         else:
-            raise ValueError("min_ready: an int or a contiguous int32 CUDA tensor [%d]" % n)
+            _tensor("min_ready (unless an int)", min_ready, t.int32, (n,))
+            mr_v = min_ready
         max_span = int(max_span)
         if not (-2 ** 31 <= mr < 2 ** 31 and -2 ** 31 <= max_span < 2 ** 31):
             raise ValueError("min_ready / max_span must fit int32")
-        if reports is not None and not (dev(reports, 2) and tuple(reports.shape) == (n, 16)):
-            raise ValueError("reports: a contiguous int32 CUDA tensor [%d, 16]" % n)
-        for x, name in ((play_list, "play_list"), (play_rows, "play_rows")):
-            if x is not None and not (dev(x, 1) and x.shape[0] == n):
-                raise ValueError("%s: a contiguous int32 CUDA tensor [%d]" % (name, n))
+        _tensor("reports", reports, t.int32, (n, 16), optional=True)
+        _tensor("play_list", play_list, t.int32, (n,), optional=True)
+        _tensor("play_rows", play_rows, t.int32, (n,), optional=True)
         if reports is None:
             reports = t.zeros((n, 16), dtype=t.int32, device=self.device)
         if play_list is None:
@@ -648,9 +694,8 @@ class SoloBatch:
         if play_rows is None:
             play_rows = t.zeros((n,), dtype=t.int32, device=self.device)
         count = t.zeros((2,), dtype=t.int32, device=self.device)
-        r = self.lib.solo_recv_report(self.h, smap.data_ptr() if smap is not None else None, n, mr_v.data_ptr() if mr_v is not None else None, mr,
-                                      max_span, RECV_REPORT_CLEAR_MARGIN if clear_margin else 0, reports.data_ptr(), play_list.data_ptr(),
-                                      play_rows.data_ptr(), count.data_ptr(), self._stream())
+        r = self.lib.solo_recv_report(self.h, _ptr(smap), n, _ptr(mr_v), mr, max_span, RECV_REPORT_CLEAR_MARGIN if clear_margin else 0,
+                                      reports.data_ptr(), play_list.data_ptr(), play_rows.data_ptr(), count.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_recv_report -> %d" % r)
         return reports, play_list, play_rows, count
@@ -658,8 +703,7 @@ class SoloBatch:
     def recv_report_count(self, count):
         """the count tensor of recv_report() as a dict (synchronises): selected rows, listed rows; selected == -1: the stream list was
         refused on the device"""
-        c = solo_recv_report_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {"selected": int(c.selected), "listed": int(c.listed)}
+        return _counts(solo_recv_report_count_t, count)
 
     # ---- sender back end (solo_send_pack): slots + length records -> datagram records + a dense payload pool ----
     SEND_COUNT = ("records", "records_needed", "bytes", "bytes_needed", "empty", "refused")
@@ -674,45 +718,17 @@ class SoloBatch:
         recv_insert() of the receiving handle takes.  Enqueued on the current stream, no synchronisation; with asynchronous joins call
         wait_encode() first."""
         t = self.torch
-        if not (getattr(bits, "is_cuda", False) and bits.dtype == t.uint8 and bits.is_contiguous() and len(bits.shape) == 3):
-            raise ValueError("bits: a contiguous uint8 CUDA tensor [n, P, slot]")
-        n, P, S = bits.shape
-        if S != self.slot or P <= 0:
-            raise ValueError("bits: slots of %d bytes and at least one packet" % self.slot)
-        if not (getattr(nbytes, "is_cuda", False) and nbytes.dtype == t.int16 and nbytes.is_contiguous() and tuple(nbytes.shape) == (n, P, 2)):
-            raise ValueError("nbytes: a contiguous int16 CUDA tensor [%d, %d, 2]" % (n, P))
-        smap = None
-        if streams is not None:
-            smap, k = self._subset(streams)
-            if n != k:
-                raise ValueError("bits has %d rows for %d listed streams" % (n, k))
-        elif n != self.n_streams:
-            raise ValueError("bits has %d rows, the handle %d streams" % (n, self.n_streams))
-        if send is not None and not (getattr(send, "is_cuda", False) and send.dtype == t.uint8 and send.is_contiguous() and tuple(send.shape) == (n, P)):
-            raise ValueError("send: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
-        if seq_base is not None and not (getattr(seq_base, "is_cuda", False) and seq_base.dtype == t.int32 and seq_base.is_contiguous()
-                                         and tuple(seq_base.shape) == (n,)):
-            raise ValueError("seq_base: a contiguous int32 CUDA tensor [%d]" % n)
-        first_seq = int(first_seq)
-        if not -2 ** 31 <= first_seq < 2 ** 31:
-            raise ValueError("first_seq must fit int32")
+        n, P, S = _tensor("bits", bits, t.uint8, (None, None, self.slot))
+        _tensor("nbytes", nbytes, t.int16, (n, P, 2))
+        smap, k = self._rows_of(streams)
+        if n != k or P < 1:
+            raise ValueError("bits: %d rows and at least one packet" % k)
+        _tensor("send", send, t.uint8, (n, P), optional=True)
+        _tensor("seq_base", seq_base, t.int32, (n,), optional=True)
         if 2 * n * P >= 2 ** 31:
             raise ValueError("n * P * 2 must stay below 2^31")
-        if records is not None and not (getattr(records, "is_cuda", False) and records.dtype == t.int32 and records.is_contiguous()
-                                        and len(records.shape) == 2 and records.shape[1] == 5):
-            raise ValueError("records: a contiguous int32 CUDA tensor [max, 5]")
-        if payload is not None and not (getattr(payload, "is_cuda", False) and payload.dtype == t.uint8 and payload.is_contiguous()
-                                        and len(payload.shape) == 1):
-            raise ValueError("payload: a contiguous 1-D uint8 CUDA tensor")
-        if records is None:
-            records = t.zeros((2 * n * P, 5), dtype=t.int32, device=bits.device)
-        if payload is None:
-            payload = t.zeros((n * P * S,), dtype=t.uint8, device=bits.device)
-        count = t.zeros((8,), dtype=t.int32, device=bits.device)
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
-        tail = (bits.data_ptr(), nbytes.data_ptr(), ptr(send), P, ptr(seq_base), first_seq, records.data_ptr() or count.data_ptr(), records.shape[0],
-                payload.data_ptr() or count.data_ptr(), payload.shape[0], count.data_ptr(), self._stream())
+        records, payload, count, out = self._send_out(first_seq, records, payload, 2 * n * P, n * P * S, bits)
+        tail = (bits.data_ptr(), nbytes.data_ptr(), _ptr(send), P, _ptr(seq_base)) + out + (self._stream(),)
         if smap is not None:
             r = self.lib.solo_send_pack_streams(self.h, smap.data_ptr(), n, *tail)
         else:
@@ -721,11 +737,29 @@ class SoloBatch:
             raise RuntimeError("solo_send_pack%s -> %d" % ("_streams" if smap is not None else "", r))
         return records, payload, count
 
+    def _send_out(self, first_seq, records, payload, max_records, capacity, bits):
+        """what send_pack() and send_fanout() share: first_seq fits int32; records int32 [max, 5] and payload uint8 [cap] are the
+        caller's or, by default, max_records and capacity large, on the device of bits -> (records, payload, count int32 [8], the
+        arguments of the library from first_seq to d_count)"""
+        t = self.torch
+        first_seq = int(first_seq)
+        if not -2 ** 31 <= first_seq < 2 ** 31:
+            raise ValueError("first_seq must fit int32")
+        _tensor("records", records, t.int32, (None, 5), optional=True)
+        _tensor("payload", payload, t.uint8, (None,), optional=True)
+        if records is None:
+            records = t.zeros((max_records, 5), dtype=t.int32, device=bits.device)
+        if payload is None:
+            payload = t.zeros((capacity,), dtype=t.uint8, device=bits.device)
+        count = t.zeros((8,), dtype=t.int32, device=bits.device)
+        # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
+        return records, payload, count, (first_seq, records.data_ptr() or count.data_ptr(), records.shape[0],
+                                         payload.data_ptr() or count.data_ptr(), payload.shape[0], count.data_ptr())
+
     def send_count(self, count):
         """the count tensor of send_pack() as a dict (synchronises): records / bytes written, records_needed / bytes_needed without the
         caps, empty (DTX) and refused packets; records == -1: the stream list was refused on the device"""
-        c = solo_send_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.SEND_COUNT}
+        return _counts(solo_send_count_t, count)
 
     # ---- mixing bridge (solo_mix): decoded rows -> what every participant of a room hears ----
     MIX_COUNT = ("rows", "rooms", "clipped")
@@ -741,34 +775,25 @@ class SoloBatch:
         the count, nothing else written.  Without a selection (max_speakers <= 0) at most 8191 rows.  Enqueued on the current stream,
         no synchronisation."""
         t = self.torch
-        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
-        if not dev(pcm, t.int16, 3):
-            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
-        n, P, L = pcm.shape
-        if L != self.packet_samples or n <= 0 or P <= 0:
-            raise ValueError("pcm: packets of %d samples, at least one row and one packet" % self.packet_samples)
+        n, P, L = _tensor("pcm", pcm, t.int16, (None, None, self.packet_samples))
+        if n <= 0 or P <= 0:
+            raise ValueError("pcm: at least one row and one packet")
         if n * P >= 2 ** 31:
             raise ValueError("n * P must stay below 2^31")
-        if not (dev(room, t.int32, 1) and room.shape[0] == n):
-            raise ValueError("room: a contiguous int32 CUDA tensor [%d]" % n)
-        if gain is not None and not (dev(gain, t.int16, 1) and gain.shape[0] == n):
-            raise ValueError("gain: a contiguous int16 CUDA tensor [%d]" % n)
+        _tensor("room", room, t.int32, (n,))
+        _tensor("gain", gain, t.int16, (n,), optional=True)
         max_speakers = int(max_speakers)
         if max_speakers > 64:
             raise ValueError("max_speakers: at most 64")
         if max_speakers <= 0 and n > 8191:
             raise ValueError("more than 8191 rows need 0 < max_speakers <= 64")
-        if out is not None and not (dev(out, t.int16, 3) and tuple(out.shape) == (n, P, L)):
-            raise ValueError("out: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, L))
-        if energy is not None and not (dev(energy, t.int64, 2) and tuple(energy.shape) == (n, P)):
-            raise ValueError("energy: a contiguous int64 CUDA tensor [%d, %d]" % (n, P))
-        if mixed is not None and not (dev(mixed, t.uint8, 2) and tuple(mixed.shape) == (n, P)):
-            raise ValueError("mixed: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
+        _tensor("out", out, t.int16, (n, P, L), optional=True)
+        _tensor("energy", energy, t.int64, (n, P), optional=True)
+        _tensor("mixed", mixed, t.uint8, (n, P), optional=True)
         if out is None:
             out = t.zeros((n, P, L), dtype=t.int16, device=pcm.device)
         count = t.zeros((4,), dtype=t.int32, device=pcm.device)
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        r = self.lib.solo_mix(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n, ptr(gain), max_speakers, out.data_ptr(), ptr(energy), ptr(mixed),
+        r = self.lib.solo_mix(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n, _ptr(gain), max_speakers, out.data_ptr(), _ptr(energy), _ptr(mixed),
                               count.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_mix -> %d" % r)
@@ -777,8 +802,7 @@ class SoloBatch:
     def mix_count(self, count):
         """the count tensor of mix() as a dict (synchronises): rows that got an output, rooms with a member, saturated output samples;
         rows == -1: a room id was refused on the device"""
-        c = solo_mix_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.MIX_COUNT}
+        return _counts(solo_mix_count_t, count)
 
     # ---- play-out time scaling (solo_timescale): a decoded packets of a row -> b packets of audio ----
     TIMESCALE_COUNT = ("rows", "blocks", "cost")
@@ -791,40 +815,63 @@ class SoloBatch:
         [n, M], M = b * samples / (samplerate / 200) blocks of 5 ms: optional outputs, the lag every block was cut at and what its splice
         cost (the sum of absolute differences) -- the caller's quality gate.  Enqueued on the current stream, no synchronisation."""
         t = self.torch
-        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
-        if not dev(pcm, t.int16, 3):
-            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, a, samples]")
-        n, a, L = pcm.shape
-        if L != self.packet_samples or n <= 0:
-            raise ValueError("pcm: packets of %d samples, at least one row" % self.packet_samples)
+        n, a, L = _tensor("pcm", pcm, t.int16, (None, None, self.packet_samples))
+        if n <= 0:
+            raise ValueError("pcm: at least one row")
         b = int(out_packets)
         if not (1 <= a <= 4 and 1 <= b <= 4):
             raise ValueError("between 1 and 4 packets in and out")
         if n * max(a, b) * L >= 2 ** 31:
             raise ValueError("n * max(a, b) * samples must stay below 2^31")
         M = b * L // (self.samplerate // 200)
-        if out is not None and not (dev(out, t.int16, 3) and tuple(out.shape) == (n, b, L)):
-            raise ValueError("out: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, b, L))
-        if shift is not None and not (dev(shift, t.int32, 2) and tuple(shift.shape) == (n, M)):
-            raise ValueError("shift: a contiguous int32 CUDA tensor [%d, %d]" % (n, M))
-        if cost is not None and not (dev(cost, t.int32, 2) and tuple(cost.shape) == (n, M)):
-            raise ValueError("cost: a contiguous int32 CUDA tensor [%d, %d]" % (n, M))
+        _tensor("out", out, t.int16, (n, b, L), optional=True)
+        _tensor("shift", shift, t.int32, (n, M), optional=True)
+        _tensor("cost", cost, t.int32, (n, M), optional=True)
         if out is None:
             out = t.empty((n, b, L), dtype=t.int16, device=pcm.device)
         count = t.zeros((4,), dtype=t.int32, device=pcm.device)
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        r = self.lib.solo_timescale(self.h, pcm.data_ptr(), n, a, b, out.data_ptr(), ptr(shift), ptr(cost), count.data_ptr(), self._stream())
+        r = self.lib.solo_timescale(self.h, pcm.data_ptr(), n, a, b, out.data_ptr(), _ptr(shift), _ptr(cost), count.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_timescale -> %d" % r)
         return out, count
 
     def timescale_count(self, count):
         """the count tensor of timescale() as a dict (synchronises): rows written, blocks searched, the sum of all splice costs"""
-        c = solo_timescale_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.TIMESCALE_COUNT}
+        return _counts(solo_timescale_count_t, count)
 
     # ---- shared listener mixes (solo_mix_shared, solo_send_fanout): a personal mix per speaker, one mix per room for everybody else ----
     MIX_SHARED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped")
+
+    def _shared_mix_args(self, pcm, room, gain, keep, slots, n_rooms, energy, pcm_spk, pcm_room):
+        """the checks of the arguments mix_shared() and mix_selected() both take -> (n, P, samples, n_rooms)"""
+        t = self.torch
+        n, P, L = _tensor("pcm", pcm, t.int16, (None, None, self.packet_samples))
+        if n <= 0 or P <= 0:
+            raise ValueError("pcm: at least one row and one packet")
+        if n * P >= 2 ** 31:
+            raise ValueError("n * P must stay below 2^31")
+        n_rooms = n if n_rooms is None else int(n_rooms)
+        if not 0 < n_rooms <= n:
+            raise ValueError("n_rooms: between 1 and the number of rows")
+        _tensor("room", room, t.int32, (n,))
+        _tensor("gain", gain, t.int16, (n,), optional=True)
+        _tensor("keep", keep, t.uint8, (n,), optional=True)
+        _tensor("slots", slots, t.int32, (n,), optional=True)
+        _tensor("energy", energy, t.int64, (n, P), optional=True)
+        _tensor("pcm_spk", pcm_spk, t.int16, (n, P, L), optional=True)
+        _tensor("pcm_room", pcm_room, t.int16, (n_rooms, P, L), optional=True)
+        return n, P, L, n_rooms
+
+    def _shared_mix_outputs(self, device, n, P, L, n_rooms, pcm_spk, pcm_room):
+        """the outputs mix_shared() and mix_selected() both return, the two PCM tables being the caller's or zeros ->
+        (pcm_spk, spk_list, spk_rows, pcm_room, room_list, source)"""
+        t = self.torch
+        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=device)
+        if pcm_spk is None:
+            pcm_spk = z((n, P, L), t.int16)
+        if pcm_room is None:
+            pcm_room = z((n_rooms, P, L), t.int16)
+        return pcm_spk, z((n,), t.int32), z((n,), t.int32), pcm_room, z((n_rooms,), t.int32), z((n,), t.int32)
 
     def mix_shared(self, pcm, room, gain=None, max_speakers=3, keep=None, slots=None, n_rooms=None, energy=None, mixed=None, pcm_spk=None,
                    pcm_room=None):
@@ -839,42 +886,16 @@ class SoloBatch:
         of send_fanout().  A room id outside [-1, n_rooms) or slots that do not grow strictly from a non-negative start refuse the call
         on the device: rows == -1 in the count, nothing else written.  Enqueued on the current stream, no synchronisation."""
         t = self.torch
-        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
-        if not dev(pcm, t.int16, 3):
-            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
-        n, P, L = pcm.shape
-        if L != self.packet_samples or n <= 0 or P <= 0:
-            raise ValueError("pcm: packets of %d samples, at least one row and one packet" % self.packet_samples)
-        if n * P >= 2 ** 31:
-            raise ValueError("n * P must stay below 2^31")
-        n_rooms = n if n_rooms is None else int(n_rooms)
-        if not 0 < n_rooms <= n:
-            raise ValueError("n_rooms: between 1 and the number of rows")
         max_speakers = int(max_speakers)
         if not 1 <= max_speakers <= 64:
             raise ValueError("max_speakers: between 1 and 64")
-        for name, x, dt in (("room", room, t.int32), ("gain", gain, t.int16), ("keep", keep, t.uint8), ("slots", slots, t.int32)):
-            if (x is not None or name == "room") and not (dev(x, dt, 1) and x.shape[0] == n):
-                raise ValueError("%s: a contiguous %s CUDA tensor [%d]" % (name, str(dt).split(".")[-1], n))
-        if energy is not None and not (dev(energy, t.int64, 2) and tuple(energy.shape) == (n, P)):
-            raise ValueError("energy: a contiguous int64 CUDA tensor [%d, %d]" % (n, P))
-        if mixed is not None and not (dev(mixed, t.uint8, 2) and tuple(mixed.shape) == (n, P)):
-            raise ValueError("mixed: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
-        if pcm_spk is not None and not (dev(pcm_spk, t.int16, 3) and tuple(pcm_spk.shape) == (n, P, L)):
-            raise ValueError("pcm_spk: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, L))
-        if pcm_room is not None and not (dev(pcm_room, t.int16, 3) and tuple(pcm_room.shape) == (n_rooms, P, L)):
-            raise ValueError("pcm_room: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n_rooms, P, L))
-        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=pcm.device)
-        if pcm_spk is None:
-            pcm_spk = z((n, P, L), t.int16)
-        if pcm_room is None:
-            pcm_room = z((n_rooms, P, L), t.int16)
-        spk_list, spk_rows, room_list, source = z((n,), t.int32), z((n,), t.int32), z((n_rooms,), t.int32), z((n,), t.int32)
-        count = z((6,), t.int32)
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        r = self.lib.solo_mix_shared(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n_rooms, ptr(gain), max_speakers, ptr(keep), ptr(slots),
+        n, P, L, n_rooms = self._shared_mix_args(pcm, room, gain, keep, slots, n_rooms, energy, pcm_spk, pcm_room)
+        _tensor("mixed", mixed, t.uint8, (n, P), optional=True)
+        pcm_spk, spk_list, spk_rows, pcm_room, room_list, source = self._shared_mix_outputs(pcm.device, n, P, L, n_rooms, pcm_spk, pcm_room)
+        count = t.zeros((6,), dtype=t.int32, device=pcm.device)
+        r = self.lib.solo_mix_shared(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n_rooms, _ptr(gain), max_speakers, _ptr(keep), _ptr(slots),
                                      pcm_spk.data_ptr(), spk_list.data_ptr(), spk_rows.data_ptr(), pcm_room.data_ptr(), room_list.data_ptr(),
-                                     source.data_ptr(), ptr(energy), ptr(mixed), count.data_ptr(), self._stream())
+                                     source.data_ptr(), _ptr(energy), _ptr(mixed), count.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_mix_shared -> %d" % r)
         return pcm_spk, spk_list, spk_rows, pcm_room, room_list, source, count
@@ -882,8 +903,7 @@ class SoloBatch:
     def mix_shared_count(self, count):
         """the count tensor of mix_shared() as a dict (synchronises): rows in a room, rooms with a member, speakers (rows of pcm_spk
         written), shared (rows of pcm_room written), saturated samples among them; rows == -1: the call was refused on the device"""
-        c = solo_mix_shared_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.MIX_SHARED_COUNT}
+        return _counts(solo_mix_shared_count_t, count)
 
     # ---- shared listener mixes from a given selection (solo_mix_selected): the end of a tick that ran Vad.select ----
     MIX_SELECTED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped", "selected", "silent")
@@ -901,43 +921,16 @@ class SoloBatch:
         or more than 64 selected rows in a room and packet refuse the call on the device: rows == -1 in the count, nothing else written.
         Enqueued on the current stream, no synchronisation."""
         t = self.torch
-        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
-        if not dev(pcm, t.int16, 3):
-            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
-        n, P, L = pcm.shape
-        if L != self.packet_samples or n <= 0 or P <= 0:
-            raise ValueError("pcm: packets of %d samples, at least one row and one packet" % self.packet_samples)
-        if n * P >= 2 ** 31:
-            raise ValueError("n * P must stay below 2^31")
-        n_rooms = n if n_rooms is None else int(n_rooms)
-        if not 0 < n_rooms <= n:
-            raise ValueError("n_rooms: between 1 and the number of rows")
-        if not (dev(sel, t.uint8, 2) and tuple(sel.shape) == (n, P)):
-            raise ValueError("sel: a contiguous uint8 CUDA tensor [%d, %d]" % (n, P))
-        for name, x, dt in (("room", room, t.int32), ("gain", gain, t.int16), ("keep", keep, t.uint8), ("slots", slots, t.int32)):
-            if (x is not None or name == "room") and not (dev(x, dt, 1) and x.shape[0] == n):
-                raise ValueError("%s: a contiguous %s CUDA tensor [%d]" % (name, str(dt).split(".")[-1], n))
-        if energy is not None and not (dev(energy, t.int64, 2) and tuple(energy.shape) == (n, P)):
-            raise ValueError("energy: a contiguous int64 CUDA tensor [%d, %d]" % (n, P))
-        if room_nsel is not None and not (dev(room_nsel, t.uint8, 2) and tuple(room_nsel.shape) == (n_rooms, P)):
-            raise ValueError("room_nsel: a contiguous uint8 CUDA tensor [%d, %d]" % (n_rooms, P))
-        if pcm_spk is not None and not (dev(pcm_spk, t.int16, 3) and tuple(pcm_spk.shape) == (n, P, L)):
-            raise ValueError("pcm_spk: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, L))
-        if pcm_room is not None and not (dev(pcm_room, t.int16, 3) and tuple(pcm_room.shape) == (n_rooms, P, L)):
-            raise ValueError("pcm_room: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n_rooms, P, L))
-        z = lambda shape, dt: t.zeros(shape, dtype=dt, device=pcm.device)
-        if pcm_spk is None:
-            pcm_spk = z((n, P, L), t.int16)
-        if pcm_room is None:
-            pcm_room = z((n_rooms, P, L), t.int16)
+        n, P, L, n_rooms = self._shared_mix_args(pcm, room, gain, keep, slots, n_rooms, energy, pcm_spk, pcm_room)
+        _tensor("sel", sel, t.uint8, (n, P))
+        _tensor("room_nsel", room_nsel, t.uint8, (n_rooms, P), optional=True)
+        pcm_spk, spk_list, spk_rows, pcm_room, room_list, source = self._shared_mix_outputs(pcm.device, n, P, L, n_rooms, pcm_spk, pcm_room)
         if room_nsel is None:
-            room_nsel = z((n_rooms, P), t.uint8)
-        spk_list, spk_rows, room_list, source = z((n,), t.int32), z((n,), t.int32), z((n_rooms,), t.int32), z((n,), t.int32)
-        count = z((8,), t.int32)
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        r = self.lib.solo_mix_selected(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n_rooms, ptr(gain), sel.data_ptr(), ptr(keep), ptr(slots),
+            room_nsel = t.zeros((n_rooms, P), dtype=t.uint8, device=pcm.device)
+        count = t.zeros((8,), dtype=t.int32, device=pcm.device)
+        r = self.lib.solo_mix_selected(self.h, pcm.data_ptr(), n, P, room.data_ptr(), n_rooms, _ptr(gain), sel.data_ptr(), _ptr(keep), _ptr(slots),
                                        pcm_spk.data_ptr(), spk_list.data_ptr(), spk_rows.data_ptr(), pcm_room.data_ptr(), room_list.data_ptr(),
-                                       source.data_ptr(), room_nsel.data_ptr(), ptr(energy), count.data_ptr(), self._stream())
+                                       source.data_ptr(), room_nsel.data_ptr(), _ptr(energy), count.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_mix_selected -> %d" % r)
         return pcm_spk, spk_list, spk_rows, pcm_room, room_list, source, count, room_nsel
@@ -945,8 +938,7 @@ class SoloBatch:
     def mix_selected_count(self, count):
         """the count tensor of mix_selected() as a dict (synchronises): the five counts of mix_shared_count(), selected ((row, packet) pairs
         selected among rows in a room) and silent ((shared room, packet) pairs nobody speaks in); rows == -1: refused on the device"""
-        c = solo_mix_selected_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.MIX_SELECTED_COUNT}
+        return _counts(solo_mix_selected_count_t, count)
 
     def send_fanout(self, bits, nbytes, source, dst_stream=None, send=None, first_seq=0, seq_base=None, records=None, payload=None):
         """solo_send_fanout: one table of encoded packets (bits uint8 [n_src,P,slot], nbytes int16 [n_src,P,2]), many destinations: source
@@ -958,44 +950,21 @@ class SoloBatch:
         n_src*P*slot bytes, never overflow.  A source outside [-1, n_src) refuses the call on the device: records == -1 in the count.
         Enqueued on the current stream, no synchronisation; with asynchronous joins call wait_encode() first."""
         t = self.torch
-        dev = lambda x, dt, shape: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and tuple(x.shape) == shape
-        if not (getattr(bits, "is_cuda", False) and bits.dtype == t.uint8 and bits.is_contiguous() and len(bits.shape) == 3):
-            raise ValueError("bits: a contiguous uint8 CUDA tensor [n_src, P, slot]")
-        n_src, P, S = bits.shape
-        if S != self.slot or P <= 0 or n_src <= 0:
-            raise ValueError("bits: slots of %d bytes, at least one row and one packet" % self.slot)
-        if not dev(nbytes, t.int16, (n_src, P, 2)):
-            raise ValueError("nbytes: a contiguous int16 CUDA tensor [%d, %d, 2]" % (n_src, P))
-        if not (getattr(source, "is_cuda", False) and source.dtype == t.int32 and source.is_contiguous() and len(source.shape) == 1 and source.shape[0] > 0):
-            raise ValueError("source: a contiguous int32 CUDA tensor [n_dst]")
-        n_dst = source.shape[0]
-        if dst_stream is not None and not dev(dst_stream, t.int32, (n_dst,)):
-            raise ValueError("dst_stream: a contiguous int32 CUDA tensor [%d]" % n_dst)
-        if send is not None and not dev(send, t.uint8, (n_dst, P)):
-            raise ValueError("send: a contiguous uint8 CUDA tensor [%d, %d]" % (n_dst, P))
-        if seq_base is not None and not dev(seq_base, t.int32, (n_dst,)):
-            raise ValueError("seq_base: a contiguous int32 CUDA tensor [%d]" % n_dst)
-        first_seq = int(first_seq)
-        if not -2 ** 31 <= first_seq < 2 ** 31:
-            raise ValueError("first_seq must fit int32")
+        n_src, P, S = _tensor("bits", bits, t.uint8, (None, None, self.slot))
+        if P <= 0 or n_src <= 0:
+            raise ValueError("bits: at least one row and one packet")
+        _tensor("nbytes", nbytes, t.int16, (n_src, P, 2))
+        n_dst, = _tensor("source", source, t.int32, (None,))
+        if n_dst <= 0:
+            raise ValueError("source: at least one destination")
+        _tensor("dst_stream", dst_stream, t.int32, (n_dst,), optional=True)
+        _tensor("send", send, t.uint8, (n_dst, P), optional=True)
+        _tensor("seq_base", seq_base, t.int32, (n_dst,), optional=True)
         if 2 * n_dst * P >= 2 ** 31 or 2 * n_src * P >= 2 ** 31:
             raise ValueError("n_dst * P * 2 and n_src * P * 2 must stay below 2^31")
-        if records is not None and not (getattr(records, "is_cuda", False) and records.dtype == t.int32 and records.is_contiguous()
-                                        and len(records.shape) == 2 and records.shape[1] == 5):
-            raise ValueError("records: a contiguous int32 CUDA tensor [max, 5]")
-        if payload is not None and not (getattr(payload, "is_cuda", False) and payload.dtype == t.uint8 and payload.is_contiguous()
-                                        and len(payload.shape) == 1):
-            raise ValueError("payload: a contiguous 1-D uint8 CUDA tensor")
-        if records is None:
-            records = t.zeros((2 * n_dst * P, 5), dtype=t.int32, device=bits.device)
-        if payload is None:
-            payload = t.zeros((n_src * P * S,), dtype=t.uint8, device=bits.device)
-        count = t.zeros((8,), dtype=t.int32, device=bits.device)
-        ptr = lambda x: x.data_ptr() if x is not None else None
-        # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
-        r = self.lib.solo_send_fanout(self.h, bits.data_ptr(), nbytes.data_ptr(), n_src, source.data_ptr(), ptr(dst_stream), n_dst, ptr(send), P,
-                                      ptr(seq_base), first_seq, records.data_ptr() or count.data_ptr(), records.shape[0],
-                                      payload.data_ptr() or count.data_ptr(), payload.shape[0], count.data_ptr(), self._stream())
+        records, payload, count, out = self._send_out(first_seq, records, payload, 2 * n_dst * P, n_src * P * S, bits)
+        r = self.lib.solo_send_fanout(self.h, bits.data_ptr(), nbytes.data_ptr(), n_src, source.data_ptr(), _ptr(dst_stream), n_dst, _ptr(send), P,
+                                      _ptr(seq_base), *out, self._stream())
         if r:
             raise RuntimeError("solo_send_fanout -> %d" % r)
         return records, payload, count
@@ -1029,14 +998,6 @@ class SoloBatch:
             raise ValueError("the handle lacks a direction or the receiver ring that `which` names")
         return r
 
-    def _migrate_list(self, streams):
-        t = self.torch
-        if getattr(streams, "is_cuda", False):               # (taken as it is and checked on the device: a bad one is refused there)
-            if streams.dtype != t.int32 or streams.dim() != 1 or not streams.is_contiguous() or not 0 < streams.shape[0] <= self.n_streams:
-                raise ValueError("streams: a sequence or a contiguous 1-D int32 CUDA tensor of 1 .. %d indices" % self.n_streams)
-            return streams, int(streams.shape[0])
-        return self._subset(streams)
-
     def export_streams(self, streams, which="both", blob=None):
         """The state of the listed streams as a device blob (solo_batch_export_streams) -> (blob uint8 [n, stride], count int32 [4] on the
         device: read it with migrate_count()).  which: "enc", "dec", "both", "recv" (the receive queue) or a combination ("dec+recv").
@@ -1045,12 +1006,12 @@ class SoloBatch:
         plain torch.distributed send of the tensor.  Enqueued on the current stream, no synchronisation."""
         t = self.torch
         w = self._migrate_which(which)
-        smap, n = self._migrate_list(streams)
+        smap, n = self._list_as_is(streams)
         need = self.state_bytes(w)
         if blob is None:
             blob = t.zeros((n, need), dtype=t.uint8, device=self.device)
-        elif not (getattr(blob, "is_cuda", False) and blob.dtype == t.uint8 and blob.is_contiguous() and blob.dim() == 2 and blob.shape[0] == n):
-            raise ValueError("blob: a contiguous uint8 CUDA tensor [%d, stride]" % n)
+        else:
+            _tensor("blob", blob, t.uint8, (n, None))
         count = t.zeros((4,), dtype=t.int32, device=self.device)
         r = self.lib.solo_batch_export_streams(self.h, smap.data_ptr(), n, w, blob.data_ptr(), blob.shape[1], count.data_ptr(), self._stream())
         if r:
@@ -1064,9 +1025,8 @@ class SoloBatch:
         their own rate, DTX and useMDIndex.  The blob may hold more sections than `which` takes."""
         t = self.torch
         w = self._migrate_which(which)
-        smap, n = self._migrate_list(streams)
-        if not (getattr(blob, "is_cuda", False) and blob.dtype == t.uint8 and blob.is_contiguous() and blob.dim() == 2 and blob.shape[0] == n):
-            raise ValueError("blob: a contiguous uint8 CUDA tensor [%d, stride]" % n)
+        smap, n = self._list_as_is(streams)
+        _tensor("blob", blob, t.uint8, (n, None))
         count = t.zeros((4,), dtype=t.int32, device=self.device)
         r = self.lib.solo_batch_import_streams(self.h, smap.data_ptr(), n, w, blob.data_ptr(), blob.shape[1], count.data_ptr(), self._stream())
         if r:
@@ -1078,8 +1038,7 @@ class SoloBatch:
         first bad record + 1), bytes written / taken; streams == -1: the call was refused on the device.  A refused EXPORT writes that word
         and nothing else: `refused` and `bytes` are then not defined by the library (0 here only because export_streams() hands it a
         zeroed count)"""
-        c = solo_migrate_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.MIGRATE_COUNT}
+        return _counts(solo_migrate_count_t, count)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1139,22 +1098,16 @@ class Resampler:
     def check(self, pcm, rows=None, out=None):
         """the argument checks of run() -> (n, P, in_samples, out_samples); rows: None or an int32 CUDA tensor"""
         t = self.torch
-        dev = lambda x, dt, nd: getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
-        if not dev(pcm, t.int16, 3):
-            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
-        n, P, L = pcm.shape
+        n, P, L = _tensor("pcm", pcm, t.int16, (None, None, None))
         if n <= 0 or P <= 0:
             raise ValueError("pcm: at least one row and one packet")
         outs = self.out_samples(L)
-        if rows is None:
-            if n != self.n_rows:
-                raise ValueError("pcm: %d rows (or pass rows=)" % self.n_rows)
-        elif not (dev(rows, t.int32, 1) and rows.shape[0] == n and n <= self.n_rows):
-            raise ValueError("rows: a contiguous int32 CUDA tensor [%d] of at most %d indices" % (n, self.n_rows))
+        _tensor("rows", rows, t.int32, (n,), optional=True)
+        if n > self.n_rows or (rows is None and n != self.n_rows):
+            raise ValueError("pcm: %d rows, or at most as many with rows=" % self.n_rows)
         if n * P * max(L, outs) >= 2 ** 31:
             raise ValueError("n * P * samples must stay below 2^31")
-        if out is not None and not (dev(out, t.int16, 3) and tuple(out.shape) == (n, P, outs)):
-            raise ValueError("out: a contiguous int16 CUDA tensor [%d, %d, %d]" % (n, P, outs))
+        _tensor("out", out, t.int16, (n, P, outs), optional=True)
         return n, P, L, outs
 
     def run(self, pcm, rows=None, out=None):
@@ -1165,10 +1118,7 @@ class Resampler:
         count, nothing else written.  Enqueued on the current stream, no synchronisation."""
         t = self.torch
         if rows is not None and not getattr(rows, "is_cuda", False):
-            idx = [int(v) for v in rows]
-            if not idx or any(b <= a for a, b in zip(idx, idx[1:])) or idx[0] < 0 or idx[-1] >= self.n_rows:
-                raise ValueError("rows: strictly increasing indices inside [0, %d)" % self.n_rows)
-            rows = t.tensor(idx, dtype=t.int32, device=self.device)
+            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
         n, P, L, outs = self.check(pcm, rows, out)
         if out is None:
             out = t.empty((n, P, outs), dtype=t.int16, device=pcm.device)
@@ -1185,17 +1135,14 @@ class Resampler:
 
     def count(self, count):
         """the count tensor of run(rows=) as a dict (synchronises): rows converted, rows listed; rows == -1: the list was refused"""
-        c = solo_resample_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.COUNT}
+        return _counts(solo_resample_count_t, count)
 
     def reset(self, rows=None):
         """zero the filter memory of every row, or of the listed rows (a host sequence: inside [0, n_rows), none twice)"""
         if rows is None:
             r = self.lib.solo_resample_reset(self.h, self._stream())
         else:
-            idx = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
-            if not 0 < len(idx) <= self.n_rows or any(v < 0 or v >= self.n_rows for v in idx) or len(set(idx)) != len(idx):
-                raise ValueError("rows: 1 .. %d indices inside [0, %d), none twice" % (self.n_rows, self.n_rows))
+            idx = _distinct("rows", rows, self.n_rows)
             arr = (C.c_int32 * len(idx))(*idx)
             r = self.lib.solo_resample_reset_rows(self.h, arr, len(idx), self._stream())
         if r:
@@ -1237,21 +1184,16 @@ class Vad:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
 
-    def _dev(self, x, dt, nd):
-        return getattr(x, "is_cuda", False) and x.dtype == dt and x.is_contiguous() and len(x.shape) == nd
-
     def _rows(self, rows, n=None):
         """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
         t = self.torch
         if rows is None:
             return None
         if not getattr(rows, "is_cuda", False):
-            idx = [int(v) for v in rows]
-            if not idx or any(b <= a for a, b in zip(idx, idx[1:])) or idx[0] < 0 or idx[-1] >= self.n_rows:
-                raise ValueError("rows: strictly increasing indices inside [0, %d)" % self.n_rows)
-            rows = t.tensor(idx, dtype=t.int32, device=self.device)
-        if not (self._dev(rows, t.int32, 1) and 0 < rows.shape[0] <= self.n_rows and (n is None or rows.shape[0] == n)):
-            raise ValueError("rows: a contiguous int32 CUDA tensor of at most %d indices, one per row of the call" % self.n_rows)
+            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
+        k, = _tensor("rows", rows, t.int32, (n,))
+        if not 0 < k <= self.n_rows:
+            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
         return rows
 
     def run(self, pcm, rows=None, detail=False, level=True):
@@ -1261,9 +1203,7 @@ class Vad:
         sequence or int32 CUDA tensor: row i of pcm belongs to rows[i], the others keep their state; a bad list is refused on the device:
         rows == -1 in the count, nothing else written.  Enqueued on the current stream, no synchronisation."""
         t = self.torch
-        if not self._dev(pcm, t.int16, 3):
-            raise ValueError("pcm: a contiguous int16 CUDA tensor [n, P, samples]")
-        n, P, L = pcm.shape
+        n, P, L = _tensor("pcm", pcm, t.int16, (None, None, None))
         if not (0 < n <= self.n_rows and P > 0):
             raise ValueError("pcm: 1 .. %d rows and at least one packet" % self.n_rows)
         if L <= 0 or L % self.frame or L > 1920:
@@ -1277,9 +1217,8 @@ class Vad:
             out["level"] = t.empty((n, P), dtype=t.uint8, device=pcm.device)
         if rows is not None:
             out["count"] = t.zeros((4,), dtype=t.int32, device=pcm.device)
-        ptr = lambda k: out[k].data_ptr() if k in out else None
-        r = self.lib.solo_vad(self.h, None if rows is None else rows.data_ptr(), n, pcm.data_ptr(), P, L, ptr("sa"), ptr("detail"), ptr("level"),
-                              ptr("count"), self._stream())
+        r = self.lib.solo_vad(self.h, _ptr(rows), n, pcm.data_ptr(), P, L, out["sa"].data_ptr(), _ptr(out.get("detail")), _ptr(out.get("level")),
+                              _ptr(out.get("count")), self._stream())
         if r:
             raise RuntimeError("solo_vad -> %d" % r)
         return out
@@ -1292,15 +1231,12 @@ class Vad:
         of a packet for a silent / a talking row, hang: packets a row stays a candidate after it fell silent, stick: what an incumbent's
         key is raised by.  A room id outside [-1, n_rooms) or a bad list is refused on the device: rows == -1 in the count."""
         t = self.torch
-        if not (self._dev(sa, t.uint8, 3) and self._dev(level, t.uint8, 2) and tuple(level.shape) == tuple(sa.shape[:2])):
-            raise ValueError("sa: a contiguous uint8 CUDA tensor [n, P, F]; level: one [n, P]")
-        n, P, F = sa.shape
+        n, P, F = _tensor("sa", sa, t.uint8, (None, None, None))
         if not (0 < n <= self.n_rows and P > 0 and F > 0):
             raise ValueError("sa: 1 .. %d rows, at least one packet and one frame" % self.n_rows)
-        if not (self._dev(room, t.int32, 1) and room.shape[0] == n):
-            raise ValueError("room: a contiguous int32 CUDA tensor [%d]" % n)
-        if gain is not None and not (self._dev(gain, t.int16, 1) and gain.shape[0] == n):
-            raise ValueError("gain: a contiguous int16 CUDA tensor [%d]" % n)
+        _tensor("level", level, t.uint8, (n, P))
+        _tensor("room", room, t.int32, (n,))
+        _tensor("gain", gain, t.int16, (n,), optional=True)
         rows = self._rows(rows, n)
         if n_rooms is None:
             n_rooms = max(int(room.max()) + 1, 1)
@@ -1313,8 +1249,8 @@ class Vad:
         out = {"sel": t.zeros((n, P), dtype=t.uint8, device=sa.device), "gain_out": t.zeros((n,), dtype=t.int16, device=sa.device),
                "keep": t.zeros((n,), dtype=t.uint8, device=sa.device), "dominant": t.full((n_rooms, P), -1, dtype=t.int32, device=sa.device),
                "count": t.zeros((4,), dtype=t.int32, device=sa.device)}
-        r = self.lib.solo_vad_select(self.h, None if rows is None else rows.data_ptr(), n, sa.data_ptr(), level.data_ptr(), P, F, room.data_ptr(), n_rooms,
-                                     C.byref(prm), None if gain is None else gain.data_ptr(), out["sel"].data_ptr(), out["gain_out"].data_ptr(),
+        r = self.lib.solo_vad_select(self.h, _ptr(rows), n, sa.data_ptr(), level.data_ptr(), P, F, room.data_ptr(), n_rooms,
+                                     C.byref(prm), _ptr(gain), out["sel"].data_ptr(), out["gain_out"].data_ptr(),
                                      out["keep"].data_ptr(), out["dominant"].data_ptr(), out["count"].data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_vad_select -> %d" % r)
@@ -1322,17 +1258,14 @@ class Vad:
 
     def count(self, count):
         """a count tensor of run(rows=) / select() as a dict (synchronises); rows == -1: the call was refused on the device"""
-        c = solo_vad_count_t.from_buffer_copy(count.cpu().numpy().tobytes())
-        return {k: int(getattr(c, k)) for k in self.COUNT}
+        return _counts(solo_vad_count_t, count)
 
     def reset(self, rows=None):
         """every row, or the listed rows (a host sequence: inside [0, n_rows), none twice), back to the initial state"""
         if rows is None:
             r = self.lib.solo_vad_reset(self.h, self._stream())
         else:
-            idx = [int(v) for v in (rows.tolist() if hasattr(rows, "tolist") else rows)]
-            if not 0 < len(idx) <= self.n_rows or any(v < 0 or v >= self.n_rows for v in idx) or len(set(idx)) != len(idx):
-                raise ValueError("rows: 1 .. %d indices inside [0, %d), none twice" % (self.n_rows, self.n_rows))
+            idx = _distinct("rows", rows, self.n_rows)
             arr = (C.c_int32 * len(idx))(*idx)
             r = self.lib.solo_vad_reset_rows(self.h, arr, len(idx), self._stream())
         if r:
@@ -1344,7 +1277,7 @@ class Vad:
         rows = self._rows(rows)
         n = self.n_rows if rows is None else int(rows.shape[0])
         blob = t.empty((n, VAD_STATE_BYTES), dtype=t.uint8, device=self.device)
-        r = self.lib.solo_vad_get_state(self.h, None if rows is None else rows.data_ptr(), n, blob.data_ptr(), self._stream())
+        r = self.lib.solo_vad_get_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_vad_get_state -> %d" % r)
         return blob
@@ -1352,10 +1285,10 @@ class Vad:
     def set_state(self, blob, rows=None):
         """blob uint8 [n,128] on the device -> the records of the listed rows (None: rows 0 .. n-1)"""
         t = self.torch
-        rows = self._rows(rows)
-        if not (self._dev(blob, t.uint8, 2) and blob.shape[1] == VAD_STATE_BYTES and 0 < blob.shape[0] <= self.n_rows and
-                (rows is None or rows.shape[0] == blob.shape[0])):
-            raise ValueError("blob: a contiguous uint8 CUDA tensor [n, %d], one record per listed row" % VAD_STATE_BYTES)
-        r = self.lib.solo_vad_set_state(self.h, None if rows is None else rows.data_ptr(), int(blob.shape[0]), blob.data_ptr(), self._stream())
+        n, _ = _tensor("blob", blob, t.uint8, (None, VAD_STATE_BYTES))
+        if not 0 < n <= self.n_rows:
+            raise ValueError("blob: 1 .. %d records" % self.n_rows)
+        rows = self._rows(rows, n)
+        r = self.lib.solo_vad_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_vad_set_state -> %d" % r)

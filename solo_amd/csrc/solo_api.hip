@@ -792,6 +792,24 @@ int32_t solo_recv_report(solo_batch_t* b, const int32_t* d_streams, int32_t n, c
     return 0;
 }
 
+// ---- the handle's geometry, for the bridge stages below (they run no codec kernel: the handle lends them its geometry and its scratch) ----
+// samples of a packet and, where asked for, the sample rate: the decoder's, or the encoder's when the handle has no decoder; 0 when it
+// has neither
+static int handle_packet_samples(const solo_batch* b, int* fs = NULL) {
+    int L = 0, rate = 0;
+    if (b->have_dec) { L = dec_packet_samples(b); rate = b->dec_ctrl.samplerate; }
+#ifdef SOLO_WITH_ENCODER
+    else if (b->have_enc) { L = enc_packet_samples(b); rate = b->enc_ctrl.samplerate; }
+#endif
+    if (fs) *fs = rate;
+    return L;
+}
+// high-band bytes of a packet: the encoder's, or the decoder's when the handle has no encoder
+static int handle_hb_bytes(const solo_batch* b) {
+    return b->have_enc ? ctrl_hb_bytes(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode, b->enc_ctrl.framesize_ms)
+                       : ctrl_hb_bytes(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode, b->dec_ctrl.framesize_ms);
+}
+
 // ---- sender back end (solo_send.h): slots + length records -> datagram records + a dense payload pool ----------------------------
 static_assert(sizeof(solo_send_count_t) == sizeof(SxSendCount) && sizeof(solo_arrival_t) == sizeof(SxSendRecord), "include/solo_mi355x.h and solo_send.h agree");
 // map = NULL: the rows are the handle's streams 0 .. n - 1; else row i is stream map[i] (checked on the device, ahead of the passes)
@@ -801,14 +819,11 @@ static int32_t solo_send_impl(solo_batch_t* b, const int32_t* map, int32_t n, co
     if (!d_bits || !d_nbytes || !d_records || !d_payload || !d_count || n_packets <= 0 || max_records < 0 || payload_capacity < 0) return -1;
     if ((int64_t)n * (int64_t)n_packets * 2 >= ((int64_t)1 << 31)) return -1;
     SOLO_CHECK(grow_scratch(b->d_send_scratch, b->send_scratch_bytes, solo_send_scratch_bytes(n * n_packets), st));
-    // the packet geometry is the handle's: that of its encoder, or of its decoder when it has none
-    const int hbb = b->have_enc ? ctrl_hb_bytes(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode, b->enc_ctrl.framesize_ms)
-                                : ctrl_hb_bytes(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode, b->dec_ctrl.framesize_ms);
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_SEND;
     if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, NULL, st));
     SxSendArgs a;
     a.bits = d_bits; a.nbytes = d_nbytes; a.send = d_send; a.seq_base = d_seq_base; a.map = map;
-    a.n = n; a.n_packets = n_packets; a.slot = b->slot; a.hbb = hbb; a.first_seq = first_seq;
+    a.n = n; a.n_packets = n_packets; a.slot = b->slot; a.hbb = handle_hb_bytes(b); a.first_seq = first_seq;
     SOLO_CHECK(solo_send_launch(a, b->d_send_scratch, (SxSendRecord*)d_records, max_records, d_payload, (long long)payload_capacity, (SxSendCount*)d_count,
                                 verdict, st));
     return 0;
@@ -839,8 +854,7 @@ int32_t solo_send_fanout(solo_batch_t* b, const uint8_t* d_bits, const int16_t* 
     a.bits = d_bits; a.nbytes = d_nbytes; a.source = d_source; a.dst_stream = d_dst_stream; a.send = d_send; a.seq_base = d_seq_base;
     a.named = NULL; a.pool_off = NULL;
     a.n_src = n_src; a.n_dst = n_dst; a.n_packets = n_packets; a.slot = b->slot; a.first_seq = first_seq;
-    a.hbb = b->have_enc ? ctrl_hb_bytes(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode, b->enc_ctrl.framesize_ms)
-                        : ctrl_hb_bytes(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode, b->dec_ctrl.framesize_ms);
+    a.hbb = handle_hb_bytes(b);
     SOLO_CHECK(solo_fan_launch(a, b->d_send_scratch, (SxSendRecord*)d_records, max_records, d_payload, (long long)payload_capacity, (SxSendCount*)d_count,
                                b->d_verdict + SOLO_VERDICT_SEND, st));
     return 0;
@@ -854,12 +868,7 @@ int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_
     if (!b || !d_pcm_in || !d_room || !d_pcm_out || n <= 0 || n_packets <= 0 || n_rooms <= 0 || n_rooms > n) return -1;
     if ((int64_t)n * (int64_t)n_packets >= ((int64_t)1 << 31)) return -1;
     if (max_speakers > SX_MIX_MAX_SPEAKERS || (max_speakers <= 0 && n > SX_MIX_MAX_ALL_ROWS)) return -1;
-    // the packet geometry is the handle's: that of its decoder, or of its encoder when it has none
-    int L = 0;
-    if (b->have_dec) L = dec_packet_samples(b);
-#ifdef SOLO_WITH_ENCODER
-    else if (b->have_enc) L = enc_packet_samples(b);
-#endif
+    const int L = handle_packet_samples(b);
     if (L <= 0 || L > SX_MIX_MAX_L || (L & 7)) return -1;
     const uintptr_t in0 = (uintptr_t)d_pcm_in, out0 = (uintptr_t)d_pcm_out;
     const uintptr_t bytes = (uintptr_t)n * (uintptr_t)n_packets * (uintptr_t)L * sizeof(int16_t);
@@ -881,11 +890,7 @@ int32_t solo_mix_shared(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int
                         int32_t* d_spk_list, int32_t* d_spk_rows, int16_t* d_pcm_room, int32_t* d_room_list, int32_t* d_source, int64_t* d_energy,
                         uint8_t* d_mixed, solo_mix_shared_count_t* d_count, void* hip_stream) {
     if (!b) return -1;
-    int L = 0;                       // the packet geometry is the handle's, as for solo_mix
-    if (b->have_dec) L = dec_packet_samples(b);
-#ifdef SOLO_WITH_ENCODER
-    else if (b->have_enc) L = enc_packet_samples(b);
-#endif
+    const int L = handle_packet_samples(b);
     if (!sx_mixsh_args_ok(d_pcm_in, n, n_packets, L, d_room, n_rooms, max_speakers, d_pcm_spk, d_spk_list, d_pcm_room, d_room_list, d_source, d_count)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     SOLO_CHECK(grow_scratch(b->d_mix_scratch, b->mix_scratch_bytes, solo_mixsh_scratch_bytes(n, n_packets), st));
@@ -905,11 +910,7 @@ int32_t solo_mix_selected(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, i
                           int32_t* d_spk_list, int32_t* d_spk_rows, int16_t* d_pcm_room, int32_t* d_room_list, int32_t* d_source,
                           uint8_t* d_room_nsel, int64_t* d_energy, solo_mix_selected_count_t* d_count, void* hip_stream) {
     if (!b) return -1;
-    int L = 0;                       // the packet geometry is the handle's, as for solo_mix
-    if (b->have_dec) L = dec_packet_samples(b);
-#ifdef SOLO_WITH_ENCODER
-    else if (b->have_enc) L = enc_packet_samples(b);
-#endif
+    const int L = handle_packet_samples(b);
     if (!sx_mixsel_args_ok(d_pcm_in, n, n_packets, L, d_room, n_rooms, d_sel, d_pcm_spk, d_spk_list, d_pcm_room, d_room_list, d_source, d_count)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     SOLO_CHECK(grow_scratch(b->d_mix_scratch, b->mix_scratch_bytes, solo_mixsel_scratch_bytes(n, n_packets), st));
@@ -928,11 +929,8 @@ static_assert(sizeof(solo_timescale_count_t) == sizeof(SxTsCount), "include/solo
 int32_t solo_timescale(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t in_packets, int32_t out_packets, int16_t* d_pcm_out,
                        int32_t* d_shift, int32_t* d_cost, solo_timescale_count_t* d_count, void* hip_stream) {
     if (!b) return -1;
-    int L = 0, fs = 0;               // the packet geometry and the sample rate are the handle's, as for solo_mix
-    if (b->have_dec) { L = dec_packet_samples(b); fs = b->dec_ctrl.samplerate; }
-#ifdef SOLO_WITH_ENCODER
-    else if (b->have_enc) { L = enc_packet_samples(b); fs = b->enc_ctrl.samplerate; }
-#endif
+    int fs;
+    const int L = handle_packet_samples(b, &fs);
     if (!sx_ts_args_ok(d_pcm_in, n, in_packets, out_packets, fs, L, d_pcm_out)) return -1;
     SxTsArgs a;
     a.pcm_in = d_pcm_in; a.pcm_out = d_pcm_out; a.shift = d_shift; a.cost = d_cost;

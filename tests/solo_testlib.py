@@ -3,6 +3,7 @@ import ctypes as C
 import hashlib
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -10,6 +11,38 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 SLOT = 512
+
+
+# ---- scaffolding of the ABI tests (tests/test_*_abi.py, tests/test_binding_checks.py) ----------------
+class NoLib:
+    """stands in for the library: any call reaching it fails the test"""
+
+    def __getattr__(self, name):
+        raise AssertionError("%s reached the library" % name)
+
+
+class FakeDev:
+    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
+
+    def __init__(self, shape, dtype, cuda=True, contiguous=True):
+        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
+
+    def is_contiguous(self):
+        return self._c
+
+
+def header_text():
+    """include/solo_mi355x.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+
+
+def built_library():
+    """the built library as a plain CDLL (no prototypes), built first if it is not there"""
+    import solo_amd
+    if not os.path.exists(solo_amd.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return C.CDLL(solo_amd.LIB_PATH)
 
 
 def md5(a):

@@ -16,14 +16,11 @@ NEW = {"solo_batch_encode_streams": 9, "solo_batch_decode_streams": 10, "solo_re
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
+    return T.built_library()
 
 
 def test_declared_exported_bound(lib):
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    hdr = T.header_text()
     loaded = solo_amd.load_library()
     for n, nargs in NEW.items():
         m = re.search(r"\bint32_t\s+%s\s*\(([^)]*)\)" % n, hdr)
@@ -46,27 +43,10 @@ def test_null_handle_and_bad_counts_are_refused(lib):
     assert lib.solo_recv_decode_streams(None, idx, 1, 1, idx, None, None) == -1
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype):
-        self.shape, self.dtype, self.is_cuda = shape, dtype, True
-
-    def is_contiguous(self):
-        return True
-
-
 def _batch(n_streams=8):
     torch = pytest.importorskip("torch")
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = torch, _NoLib(), None
+    b.torch, b.lib, b.h = torch, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.device = n_streams, 512, 640, torch.device("cpu")
     return b, torch
 
@@ -76,9 +56,9 @@ def test_python_checks_raise_before_the_library(streams):
     b, torch = _batch()
     n = max(len(streams), 1)
     with pytest.raises(ValueError):
-        b.encode(_FakeDev((n, 1, 640), torch.int16), streams=streams)
+        b.encode(T.FakeDev((n, 1, 640), torch.int16), streams=streams)
     with pytest.raises(ValueError):
-        b.decode(_FakeDev((n, 1, 512), torch.uint8), _FakeDev((n, 1, 2), torch.int16), streams=streams)
+        b.decode(T.FakeDev((n, 1, 512), torch.uint8), T.FakeDev((n, 1, 2), torch.int16), streams=streams)
     with pytest.raises(ValueError):
         b.recv_decode(1, streams=streams)
 
@@ -86,9 +66,9 @@ def test_python_checks_raise_before_the_library(streams):
 def test_rows_must_match_the_list():
     b, torch = _batch()
     with pytest.raises(ValueError):
-        b.encode(_FakeDev((3, 1, 640), torch.int16), streams=[0, 1])
+        b.encode(T.FakeDev((3, 1, 640), torch.int16), streams=[0, 1])
     with pytest.raises(ValueError):
-        b.decode(_FakeDev((8, 1, 512), torch.uint8), _FakeDev((8, 1, 2), torch.int16), streams=[0, 5])
+        b.decode(T.FakeDev((8, 1, 512), torch.uint8), T.FakeDev((8, 1, 2), torch.int16), streams=[0, 5])
 
 
 def test_positional_signatures_unchanged():

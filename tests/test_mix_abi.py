@@ -17,18 +17,11 @@ KERNELS = ("solo_mix_clear_kernel", "solo_mix_check_kernel", "solo_mix_scan_kern
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    return T.built_library()
 
 
 def test_declared_exported_bound(lib):
-    m = re.search(r"\bint32_t\s+solo_mix\s*\(([^)]*)\)", _header())
+    m = re.search(r"\bint32_t\s+solo_mix\s*\(([^)]*)\)", T.header_text())
     assert m
     args = [a.strip() for a in m.group(1).split(",")]
     assert len(args) == 13
@@ -41,7 +34,7 @@ def test_declared_exported_bound(lib):
 
 
 def test_count_struct_is_16_bytes_on_both_sides():
-    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_mix_count_t;", _header())
+    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_mix_count_t;", T.header_text())
     assert m
     fields = re.findall(r"(int32_t|int64_t)\s+([^;]+);", m.group(1))
     names = [x.strip() for _, group in fields for x in group.split(",")]
@@ -68,48 +61,31 @@ def test_mix_kernels_use_no_scratch(lib):
         assert hits[0]["scratch"] == 0, (frag, hits[0])
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype, cuda=True, contiguous=True):
-        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_python_checks_raise_before_the_library():
     t = pytest.importorskip("torch")
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = t, _NoLib(), None
+    b.torch, b.lib, b.h = t, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.device = 8, 512, 640, t.device("cpu")
-    pcm, room = _FakeDev((8, 3, 640), t.int16), _FakeDev((8,), t.int32)
+    pcm, room = T.FakeDev((8, 3, 640), t.int16), T.FakeDev((8,), t.int32)
     bad = [
-        dict(pcm=_FakeDev((8, 3, 1280), t.int16), room=room),                       # another packet length
-        dict(pcm=_FakeDev((8, 3, 640), t.int32), room=room),
-        dict(pcm=_FakeDev((8, 3, 640), t.int16, cuda=False), room=room),
-        dict(pcm=_FakeDev((8, 3, 640), t.int16, contiguous=False), room=room),
-        dict(pcm=_FakeDev((8, 0, 640), t.int16), room=room),
-        dict(pcm=_FakeDev((8, 640), t.int16), room=room),
-        dict(pcm=pcm, room=_FakeDev((7,), t.int32)),
-        dict(pcm=pcm, room=_FakeDev((8,), t.int64)),
-        dict(pcm=pcm, room=room, gain=_FakeDev((8,), t.int32)),
-        dict(pcm=pcm, room=room, gain=_FakeDev((9,), t.int16)),
+        dict(pcm=T.FakeDev((8, 3, 1280), t.int16), room=room),                       # another packet length
+        dict(pcm=T.FakeDev((8, 3, 640), t.int32), room=room),
+        dict(pcm=T.FakeDev((8, 3, 640), t.int16, cuda=False), room=room),
+        dict(pcm=T.FakeDev((8, 3, 640), t.int16, contiguous=False), room=room),
+        dict(pcm=T.FakeDev((8, 0, 640), t.int16), room=room),
+        dict(pcm=T.FakeDev((8, 640), t.int16), room=room),
+        dict(pcm=pcm, room=T.FakeDev((7,), t.int32)),
+        dict(pcm=pcm, room=T.FakeDev((8,), t.int64)),
+        dict(pcm=pcm, room=room, gain=T.FakeDev((8,), t.int32)),
+        dict(pcm=pcm, room=room, gain=T.FakeDev((9,), t.int16)),
         dict(pcm=pcm, room=room, max_speakers=65),
-        dict(pcm=_FakeDev((8192, 1, 640), t.int16), room=_FakeDev((8192,), t.int32), max_speakers=0),
-        dict(pcm=pcm, room=room, out=_FakeDev((8, 3, 320), t.int16)),
-        dict(pcm=pcm, room=room, out=_FakeDev((8, 3, 640), t.int32)),
-        dict(pcm=pcm, room=room, energy=_FakeDev((8, 3), t.int32)),
-        dict(pcm=pcm, room=room, energy=_FakeDev((8, 4), t.int64)),
-        dict(pcm=pcm, room=room, mixed=_FakeDev((8, 3), t.int8)),
-        dict(pcm=pcm, room=room, mixed=_FakeDev((3, 8), t.uint8)),
+        dict(pcm=T.FakeDev((8192, 1, 640), t.int16), room=T.FakeDev((8192,), t.int32), max_speakers=0),
+        dict(pcm=pcm, room=room, out=T.FakeDev((8, 3, 320), t.int16)),
+        dict(pcm=pcm, room=room, out=T.FakeDev((8, 3, 640), t.int32)),
+        dict(pcm=pcm, room=room, energy=T.FakeDev((8, 3), t.int32)),
+        dict(pcm=pcm, room=room, energy=T.FakeDev((8, 4), t.int64)),
+        dict(pcm=pcm, room=room, mixed=T.FakeDev((8, 3), t.int8)),
+        dict(pcm=pcm, room=room, mixed=T.FakeDev((3, 8), t.uint8)),
     ]
     for kw in bad:
         with pytest.raises(ValueError):

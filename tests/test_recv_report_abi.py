@@ -3,7 +3,6 @@ solo_amd with their argument types; both structures have the same size and field
 SoloBatch.RECV_REPORT; a NULL handle is refused whatever else is passed; the Python checks of recv_report() raise before anything
 reaches the library.  No compute call (no GPU here; the refusals that need a handle are in tests/test_gpu_recv_report.py)."""
 import ctypes as C
-import os
 import re
 
 import pytest
@@ -17,18 +16,11 @@ NEW = {"solo_recv_track": 3, "solo_recv_report": 12}
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    return T.built_library()
 
 
 def test_declared_exported_bound(lib):
-    hdr = _header()
+    hdr = T.header_text()
     loaded = solo_amd.load_library()
     for n, nargs in NEW.items():
         m = re.search(r"\bint32_t\s+%s\s*\(([^)]*)\)" % n, hdr)
@@ -46,7 +38,7 @@ def test_declared_exported_bound(lib):
 
 
 def _struct_fields(name):
-    m = re.search(r"typedef struct \{([^}]*)\}\s*%s;" % name, _header())
+    m = re.search(r"typedef struct \{([^}]*)\}\s*%s;" % name, T.header_text())
     assert m, name
     fields = re.findall(r"(int32_t|uint32_t)\s+([^;]+);", m.group(1))
     return [(ty, x.strip()) for ty, group in fields for x in group.split(",")]
@@ -73,27 +65,10 @@ def test_null_handle_is_refused(lib):
     assert loaded.solo_recv_report(None, p, 1, p, 1, 1, 1, p, None, None, None, None) == -1
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype, cuda=True, contiguous=True):
-        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
-
-    def is_contiguous(self):
-        return self._c
-
-
 def _batch(n_streams=8):
     torch = pytest.importorskip("torch")
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = torch, _NoLib(), None
+    b.torch, b.lib, b.h = torch, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.device = n_streams, 512, 640, torch.device("cpu")
     return b, torch
 
@@ -102,14 +77,14 @@ def test_python_checks_raise_before_the_library():
     b, t = _batch()
     bad = [
         dict(streams=[3, 1]), dict(streams=[2, 2]), dict(streams=[0, 8]), dict(streams=[]), dict(streams=list(range(9))),
-        dict(streams=_FakeDev((3,), t.int64)), dict(streams=_FakeDev((3, 1), t.int32)), dict(streams=_FakeDev((9,), t.int32)),
-        dict(streams=_FakeDev((0,), t.int32)), dict(streams=_FakeDev((3,), t.int32, contiguous=False)),
-        dict(min_ready=1.5), dict(min_ready=True), dict(min_ready=_FakeDev((7,), t.int32)), dict(min_ready=_FakeDev((8,), t.int16)),
-        dict(min_ready=_FakeDev((8,), t.int32, cuda=False)), dict(min_ready=2 ** 31), dict(max_span=2 ** 31),
-        dict(streams=_FakeDev((3,), t.int32), min_ready=_FakeDev((8,), t.int32)),
-        dict(reports=_FakeDev((8, 15), t.int32)), dict(reports=_FakeDev((8, 16), t.uint8)), dict(reports=_FakeDev((7, 16), t.int32)),
-        dict(play_list=_FakeDev((7,), t.int32)), dict(play_list=_FakeDev((8,), t.int64)), dict(play_rows=_FakeDev((8, 1), t.int32)),
-        dict(play_rows=_FakeDev((8,), t.int32, cuda=False)),
+        dict(streams=T.FakeDev((3,), t.int64)), dict(streams=T.FakeDev((3, 1), t.int32)), dict(streams=T.FakeDev((9,), t.int32)),
+        dict(streams=T.FakeDev((0,), t.int32)), dict(streams=T.FakeDev((3,), t.int32, contiguous=False)),
+        dict(min_ready=1.5), dict(min_ready=True), dict(min_ready=T.FakeDev((7,), t.int32)), dict(min_ready=T.FakeDev((8,), t.int16)),
+        dict(min_ready=T.FakeDev((8,), t.int32, cuda=False)), dict(min_ready=2 ** 31), dict(max_span=2 ** 31),
+        dict(streams=T.FakeDev((3,), t.int32), min_ready=T.FakeDev((8,), t.int32)),
+        dict(reports=T.FakeDev((8, 15), t.int32)), dict(reports=T.FakeDev((8, 16), t.uint8)), dict(reports=T.FakeDev((7, 16), t.int32)),
+        dict(play_list=T.FakeDev((7,), t.int32)), dict(play_list=T.FakeDev((8,), t.int64)), dict(play_rows=T.FakeDev((8, 1), t.int32)),
+        dict(play_rows=T.FakeDev((8,), t.int32, cuda=False)),
     ]
     for kw in bad:
         with pytest.raises(ValueError):

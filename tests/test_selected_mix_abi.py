@@ -18,18 +18,11 @@ KERNELS = ("solo_mixsel_gather_kernel", "solo_mixsel_compact_kernel", "solo_mixs
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    return T.built_library()
 
 
 def test_mix_selected_declared_exported_bound(lib):
-    m = re.search(r"\bint32_t\s+solo_mix_selected\s*\(([^)]*)\)", _header())
+    m = re.search(r"\bint32_t\s+solo_mix_selected\s*\(([^)]*)\)", T.header_text())
     assert m
     args = [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
     assert args == ["solo_batch_t *b", "const int16_t *d_pcm_in", "int32_t n", "int32_t n_packets", "const int32_t *d_room", "int32_t n_rooms",
@@ -44,7 +37,7 @@ def test_mix_selected_declared_exported_bound(lib):
 
 
 def test_count_struct_is_32_bytes_on_both_sides():
-    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_mix_selected_count_t;", _header())
+    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_mix_selected_count_t;", T.header_text())
     assert m
     fields = re.findall(r"(int32_t|int64_t)\s+([^;]+);", m.group(1))
     names = [x.strip() for _, group in fields for x in group.split(",")]
@@ -76,56 +69,39 @@ def test_kernels_exist_once_and_use_no_scratch(lib):
     assert len([name for name in seen if "solo_mixsel_" in name]) == len(KERNELS)
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype, cuda=True, contiguous=True):
-        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_python_checks_of_mix_selected_raise_before_the_library():
     t = pytest.importorskip("torch")
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = t, _NoLib(), None
+    b.torch, b.lib, b.h = t, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.device = 8, 512, 640, t.device("cpu")
-    pcm, room, sel = _FakeDev((8, 3, 640), t.int16), _FakeDev((8,), t.int32), _FakeDev((8, 3), t.uint8)
+    pcm, room, sel = T.FakeDev((8, 3, 640), t.int16), T.FakeDev((8,), t.int32), T.FakeDev((8, 3), t.uint8)
     bad = [
-        dict(pcm=_FakeDev((8, 3, 1280), t.int16), room=room, sel=sel),
-        dict(pcm=_FakeDev((8, 3, 640), t.int16, cuda=False), room=room, sel=sel),
-        dict(pcm=_FakeDev((8, 3, 640), t.int16, contiguous=False), room=room, sel=sel),
-        dict(pcm=_FakeDev((8, 0, 640), t.int16), room=room, sel=_FakeDev((8, 0), t.uint8)),
-        dict(pcm=pcm, room=_FakeDev((7,), t.int32), sel=sel),
-        dict(pcm=pcm, room=_FakeDev((8,), t.int64), sel=sel),
+        dict(pcm=T.FakeDev((8, 3, 1280), t.int16), room=room, sel=sel),
+        dict(pcm=T.FakeDev((8, 3, 640), t.int16, cuda=False), room=room, sel=sel),
+        dict(pcm=T.FakeDev((8, 3, 640), t.int16, contiguous=False), room=room, sel=sel),
+        dict(pcm=T.FakeDev((8, 0, 640), t.int16), room=room, sel=T.FakeDev((8, 0), t.uint8)),
+        dict(pcm=pcm, room=T.FakeDev((7,), t.int32), sel=sel),
+        dict(pcm=pcm, room=T.FakeDev((8,), t.int64), sel=sel),
         dict(pcm=pcm, room=room, sel=None),
-        dict(pcm=pcm, room=room, sel=_FakeDev((8, 3), t.int8)),
-        dict(pcm=pcm, room=room, sel=_FakeDev((8, 3), t.bool)),
-        dict(pcm=pcm, room=room, sel=_FakeDev((8,), t.uint8)),
-        dict(pcm=pcm, room=room, sel=_FakeDev((8, 2), t.uint8)),
-        dict(pcm=pcm, room=room, sel=_FakeDev((8, 3), t.uint8, cuda=False)),
-        dict(pcm=pcm, room=room, sel=_FakeDev((8, 3), t.uint8, contiguous=False)),
-        dict(pcm=pcm, room=room, sel=sel, gain=_FakeDev((9,), t.int16)),
-        dict(pcm=pcm, room=room, sel=sel, keep=_FakeDev((8,), t.int8)),
-        dict(pcm=pcm, room=room, sel=sel, keep=_FakeDev((8, 3), t.uint8)),
-        dict(pcm=pcm, room=room, sel=sel, slots=_FakeDev((8,), t.int64)),
-        dict(pcm=pcm, room=room, sel=sel, slots=_FakeDev((7,), t.int32)),
+        dict(pcm=pcm, room=room, sel=T.FakeDev((8, 3), t.int8)),
+        dict(pcm=pcm, room=room, sel=T.FakeDev((8, 3), t.bool)),
+        dict(pcm=pcm, room=room, sel=T.FakeDev((8,), t.uint8)),
+        dict(pcm=pcm, room=room, sel=T.FakeDev((8, 2), t.uint8)),
+        dict(pcm=pcm, room=room, sel=T.FakeDev((8, 3), t.uint8, cuda=False)),
+        dict(pcm=pcm, room=room, sel=T.FakeDev((8, 3), t.uint8, contiguous=False)),
+        dict(pcm=pcm, room=room, sel=sel, gain=T.FakeDev((9,), t.int16)),
+        dict(pcm=pcm, room=room, sel=sel, keep=T.FakeDev((8,), t.int8)),
+        dict(pcm=pcm, room=room, sel=sel, keep=T.FakeDev((8, 3), t.uint8)),
+        dict(pcm=pcm, room=room, sel=sel, slots=T.FakeDev((8,), t.int64)),
+        dict(pcm=pcm, room=room, sel=sel, slots=T.FakeDev((7,), t.int32)),
         dict(pcm=pcm, room=room, sel=sel, n_rooms=0),
         dict(pcm=pcm, room=room, sel=sel, n_rooms=9),
-        dict(pcm=pcm, room=room, sel=sel, energy=_FakeDev((8, 4), t.int64)),
-        dict(pcm=pcm, room=room, sel=sel, energy=_FakeDev((8, 3), t.int32)),
-        dict(pcm=pcm, room=room, sel=sel, n_rooms=4, room_nsel=_FakeDev((8, 3), t.uint8)),
-        dict(pcm=pcm, room=room, sel=sel, room_nsel=_FakeDev((8, 3), t.int8)),
-        dict(pcm=pcm, room=room, sel=sel, pcm_spk=_FakeDev((7, 3, 640), t.int16)),
-        dict(pcm=pcm, room=room, sel=sel, n_rooms=4, pcm_room=_FakeDev((8, 3, 640), t.int16)),
+        dict(pcm=pcm, room=room, sel=sel, energy=T.FakeDev((8, 4), t.int64)),
+        dict(pcm=pcm, room=room, sel=sel, energy=T.FakeDev((8, 3), t.int32)),
+        dict(pcm=pcm, room=room, sel=sel, n_rooms=4, room_nsel=T.FakeDev((8, 3), t.uint8)),
+        dict(pcm=pcm, room=room, sel=sel, room_nsel=T.FakeDev((8, 3), t.int8)),
+        dict(pcm=pcm, room=room, sel=sel, pcm_spk=T.FakeDev((7, 3, 640), t.int16)),
+        dict(pcm=pcm, room=room, sel=sel, n_rooms=4, pcm_room=T.FakeDev((8, 3, 640), t.int16)),
     ]
     for kw in bad:
         with pytest.raises(ValueError):

@@ -2,7 +2,6 @@
 with their argument types; the count structure is 32 bytes on both sides; a NULL handle and bad counts are refused; the Python checks of
 send_pack() raise before anything reaches the library.  No compute call (no GPU here)."""
 import ctypes as C
-import os
 import re
 
 import pytest
@@ -15,18 +14,11 @@ NEW = {"solo_send_pack": 13, "solo_send_pack_streams": 15}
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    return T.built_library()
 
 
 def test_declared_exported_bound(lib):
-    hdr = _header()
+    hdr = T.header_text()
     loaded = solo_amd.load_library()
     for n, nargs in NEW.items():
         m = re.search(r"\bint32_t\s+%s\s*\(([^)]*)\)" % n, hdr)
@@ -42,7 +34,7 @@ def test_declared_exported_bound(lib):
 
 
 def test_count_struct_is_32_bytes_on_both_sides():
-    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_send_count_t;", _header())
+    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_send_count_t;", T.header_text())
     assert m
     fields = re.findall(r"(int32_t|int64_t)\s+([^;]+);", m.group(1))
     names = [x.strip() for _, group in fields for x in group.split(",")]
@@ -60,52 +52,35 @@ def test_null_handle_and_bad_counts_are_refused(lib):
     assert loaded.solo_send_pack_streams(None, p, 1, p, p, None, 1, None, 0, p, 1, p, 1, p, None) == -1
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype, cuda=True, contiguous=True):
-        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
-
-    def is_contiguous(self):
-        return self._c
-
-
 def _batch(n_streams=8):
     torch = pytest.importorskip("torch")
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = torch, _NoLib(), None
+    b.torch, b.lib, b.h = torch, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.device = n_streams, 512, 640, torch.device("cpu")
     return b, torch
 
 
 def test_python_checks_raise_before_the_library():
     b, t = _batch()
-    bits, nb = _FakeDev((8, 3, 512), t.uint8), _FakeDev((8, 3, 2), t.int16)
+    bits, nb = T.FakeDev((8, 3, 512), t.uint8), T.FakeDev((8, 3, 2), t.int16)
     bad = [
-        dict(bits=_FakeDev((8, 3, 256), t.uint8), nbytes=nb),                           # another slot size
-        dict(bits=_FakeDev((7, 3, 512), t.uint8), nbytes=_FakeDev((7, 3, 2), t.int16)),  # rows != N without a list
-        dict(bits=_FakeDev((8, 3, 512), t.int8), nbytes=nb),
-        dict(bits=_FakeDev((8, 3, 512), t.uint8, cuda=False), nbytes=nb),
-        dict(bits=_FakeDev((8, 3, 512), t.uint8, contiguous=False), nbytes=nb),
-        dict(bits=_FakeDev((8, 0, 512), t.uint8), nbytes=_FakeDev((8, 0, 2), t.int16)),
-        dict(bits=bits, nbytes=_FakeDev((8, 3), t.int16)),
-        dict(bits=bits, nbytes=_FakeDev((8, 3, 2), t.int32)),
-        dict(bits=bits, nbytes=nb, send=_FakeDev((8, 4), t.uint8)),
-        dict(bits=bits, nbytes=nb, send=_FakeDev((8, 3), t.int32)),
-        dict(bits=bits, nbytes=nb, seq_base=_FakeDev((7,), t.int32)),
-        dict(bits=bits, nbytes=nb, seq_base=_FakeDev((8,), t.int64)),
+        dict(bits=T.FakeDev((8, 3, 256), t.uint8), nbytes=nb),                           # another slot size
+        dict(bits=T.FakeDev((7, 3, 512), t.uint8), nbytes=T.FakeDev((7, 3, 2), t.int16)),  # rows != N without a list
+        dict(bits=T.FakeDev((8, 3, 512), t.int8), nbytes=nb),
+        dict(bits=T.FakeDev((8, 3, 512), t.uint8, cuda=False), nbytes=nb),
+        dict(bits=T.FakeDev((8, 3, 512), t.uint8, contiguous=False), nbytes=nb),
+        dict(bits=T.FakeDev((8, 0, 512), t.uint8), nbytes=T.FakeDev((8, 0, 2), t.int16)),
+        dict(bits=bits, nbytes=T.FakeDev((8, 3), t.int16)),
+        dict(bits=bits, nbytes=T.FakeDev((8, 3, 2), t.int32)),
+        dict(bits=bits, nbytes=nb, send=T.FakeDev((8, 4), t.uint8)),
+        dict(bits=bits, nbytes=nb, send=T.FakeDev((8, 3), t.int32)),
+        dict(bits=bits, nbytes=nb, seq_base=T.FakeDev((7,), t.int32)),
+        dict(bits=bits, nbytes=nb, seq_base=T.FakeDev((8,), t.int64)),
         dict(bits=bits, nbytes=nb, first_seq=2 ** 31),
-        dict(bits=bits, nbytes=nb, records=_FakeDev((10, 4), t.int32)),
-        dict(bits=bits, nbytes=nb, records=_FakeDev((10, 5), t.int64)),
-        dict(bits=bits, nbytes=nb, payload=_FakeDev((10, 5), t.uint8)),
-        dict(bits=bits, nbytes=nb, payload=_FakeDev((10,), t.int8)),
+        dict(bits=bits, nbytes=nb, records=T.FakeDev((10, 4), t.int32)),
+        dict(bits=bits, nbytes=nb, records=T.FakeDev((10, 5), t.int64)),
+        dict(bits=bits, nbytes=nb, payload=T.FakeDev((10, 5), t.uint8)),
+        dict(bits=bits, nbytes=nb, payload=T.FakeDev((10,), t.int8)),
         dict(bits=bits, nbytes=nb, streams=[0, 1, 2]),                                  # rows != listed streams
     ]
     for kw in bad:
@@ -118,7 +93,7 @@ def test_stream_lists_are_checked_before_the_library(streams):
     b, t = _batch()
     n = max(len(streams), 1)
     with pytest.raises(ValueError):
-        b.send_pack(_FakeDev((n, 1, 512), t.uint8), _FakeDev((n, 1, 2), t.int16), streams=streams)
+        b.send_pack(T.FakeDev((n, 1, 512), t.uint8), T.FakeDev((n, 1, 2), t.int16), streams=streams)
 
 
 def test_signature():

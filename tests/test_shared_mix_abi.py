@@ -19,18 +19,11 @@ KERNELS = ("solo_mixsh_clear_kernel", "solo_mixsh_check_kernel", "solo_mixsh_ene
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    return T.built_library()
 
 
 def _declared(name):
-    m = re.search(r"\bint32_t\s+%s\s*\(([^)]*)\)" % name, _header())
+    m = re.search(r"\bint32_t\s+%s\s*\(([^)]*)\)" % name, T.header_text())
     assert m, name
     return [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
 
@@ -60,7 +53,7 @@ def test_send_fanout_declared_exported_bound(lib):
 
 
 def test_count_struct_is_24_bytes_on_both_sides():
-    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_mix_shared_count_t;", _header())
+    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_mix_shared_count_t;", T.header_text())
     assert m
     fields = re.findall(r"(int32_t|int64_t)\s+([^;]+);", m.group(1))
     names = [x.strip() for _, group in fields for x in group.split(",")]
@@ -91,26 +84,9 @@ def test_kernels_use_no_scratch(lib):
             assert hits[0]["lds"] == 0, (frag, hits[0])           # nothing but registers bounds the waves per SIMD
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype, cuda=True, contiguous=True):
-        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
-
-    def is_contiguous(self):
-        return self._c
-
-
 def _binding(t):
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = t, _NoLib(), None
+    b.torch, b.lib, b.h = t, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.device = 8, 512, 640, t.device("cpu")
     return b
 
@@ -118,27 +94,27 @@ def _binding(t):
 def test_python_checks_of_mix_shared_raise_before_the_library():
     t = pytest.importorskip("torch")
     b = _binding(t)
-    pcm, room = _FakeDev((8, 3, 640), t.int16), _FakeDev((8,), t.int32)
+    pcm, room = T.FakeDev((8, 3, 640), t.int16), T.FakeDev((8,), t.int32)
     bad = [
-        dict(pcm=_FakeDev((8, 3, 1280), t.int16), room=room),
-        dict(pcm=_FakeDev((8, 3, 640), t.int16, cuda=False), room=room),
-        dict(pcm=_FakeDev((8, 3, 640), t.int16, contiguous=False), room=room),
-        dict(pcm=_FakeDev((8, 0, 640), t.int16), room=room),
-        dict(pcm=pcm, room=_FakeDev((7,), t.int32)),
-        dict(pcm=pcm, room=_FakeDev((8,), t.int64)),
-        dict(pcm=pcm, room=room, gain=_FakeDev((9,), t.int16)),
+        dict(pcm=T.FakeDev((8, 3, 1280), t.int16), room=room),
+        dict(pcm=T.FakeDev((8, 3, 640), t.int16, cuda=False), room=room),
+        dict(pcm=T.FakeDev((8, 3, 640), t.int16, contiguous=False), room=room),
+        dict(pcm=T.FakeDev((8, 0, 640), t.int16), room=room),
+        dict(pcm=pcm, room=T.FakeDev((7,), t.int32)),
+        dict(pcm=pcm, room=T.FakeDev((8,), t.int64)),
+        dict(pcm=pcm, room=room, gain=T.FakeDev((9,), t.int16)),
         dict(pcm=pcm, room=room, max_speakers=0),
         dict(pcm=pcm, room=room, max_speakers=65),
-        dict(pcm=pcm, room=room, keep=_FakeDev((8,), t.int8)),
-        dict(pcm=pcm, room=room, keep=_FakeDev((8, 3), t.uint8)),
-        dict(pcm=pcm, room=room, slots=_FakeDev((8,), t.int64)),
-        dict(pcm=pcm, room=room, slots=_FakeDev((7,), t.int32)),
+        dict(pcm=pcm, room=room, keep=T.FakeDev((8,), t.int8)),
+        dict(pcm=pcm, room=room, keep=T.FakeDev((8, 3), t.uint8)),
+        dict(pcm=pcm, room=room, slots=T.FakeDev((8,), t.int64)),
+        dict(pcm=pcm, room=room, slots=T.FakeDev((7,), t.int32)),
         dict(pcm=pcm, room=room, n_rooms=0),
         dict(pcm=pcm, room=room, n_rooms=9),
-        dict(pcm=pcm, room=room, energy=_FakeDev((8, 4), t.int64)),
-        dict(pcm=pcm, room=room, mixed=_FakeDev((8, 3), t.int8)),
-        dict(pcm=pcm, room=room, pcm_spk=_FakeDev((7, 3, 640), t.int16)),
-        dict(pcm=pcm, room=room, n_rooms=4, pcm_room=_FakeDev((8, 3, 640), t.int16)),
+        dict(pcm=pcm, room=room, energy=T.FakeDev((8, 4), t.int64)),
+        dict(pcm=pcm, room=room, mixed=T.FakeDev((8, 3), t.int8)),
+        dict(pcm=pcm, room=room, pcm_spk=T.FakeDev((7, 3, 640), t.int16)),
+        dict(pcm=pcm, room=room, n_rooms=4, pcm_room=T.FakeDev((8, 3, 640), t.int16)),
     ]
     for kw in bad:
         with pytest.raises(ValueError):
@@ -148,21 +124,21 @@ def test_python_checks_of_mix_shared_raise_before_the_library():
 def test_python_checks_of_send_fanout_raise_before_the_library():
     t = pytest.importorskip("torch")
     b = _binding(t)
-    bits, nb, src = _FakeDev((6, 3, 512), t.uint8), _FakeDev((6, 3, 2), t.int16), _FakeDev((9,), t.int32)
+    bits, nb, src = T.FakeDev((6, 3, 512), t.uint8), T.FakeDev((6, 3, 2), t.int16), T.FakeDev((9,), t.int32)
     bad = [
-        dict(bits=_FakeDev((6, 3, 256), t.uint8), nbytes=nb, source=src),
-        dict(bits=_FakeDev((6, 3, 512), t.int8), nbytes=nb, source=src),
-        dict(bits=_FakeDev((6, 0, 512), t.uint8), nbytes=_FakeDev((6, 0, 2), t.int16), source=src),
-        dict(bits=bits, nbytes=_FakeDev((9, 3, 2), t.int16), source=src),
-        dict(bits=bits, nbytes=nb, source=_FakeDev((9,), t.int64)),
-        dict(bits=bits, nbytes=nb, source=_FakeDev((0,), t.int32)),
-        dict(bits=bits, nbytes=nb, source=_FakeDev((9, 1), t.int32)),
-        dict(bits=bits, nbytes=nb, source=src, dst_stream=_FakeDev((6,), t.int32)),
-        dict(bits=bits, nbytes=nb, source=src, send=_FakeDev((6, 3), t.uint8)),
-        dict(bits=bits, nbytes=nb, source=src, seq_base=_FakeDev((9,), t.int16)),
+        dict(bits=T.FakeDev((6, 3, 256), t.uint8), nbytes=nb, source=src),
+        dict(bits=T.FakeDev((6, 3, 512), t.int8), nbytes=nb, source=src),
+        dict(bits=T.FakeDev((6, 0, 512), t.uint8), nbytes=T.FakeDev((6, 0, 2), t.int16), source=src),
+        dict(bits=bits, nbytes=T.FakeDev((9, 3, 2), t.int16), source=src),
+        dict(bits=bits, nbytes=nb, source=T.FakeDev((9,), t.int64)),
+        dict(bits=bits, nbytes=nb, source=T.FakeDev((0,), t.int32)),
+        dict(bits=bits, nbytes=nb, source=T.FakeDev((9, 1), t.int32)),
+        dict(bits=bits, nbytes=nb, source=src, dst_stream=T.FakeDev((6,), t.int32)),
+        dict(bits=bits, nbytes=nb, source=src, send=T.FakeDev((6, 3), t.uint8)),
+        dict(bits=bits, nbytes=nb, source=src, seq_base=T.FakeDev((9,), t.int16)),
         dict(bits=bits, nbytes=nb, source=src, first_seq=2 ** 31),
-        dict(bits=bits, nbytes=nb, source=src, records=_FakeDev((10, 4), t.int32)),
-        dict(bits=bits, nbytes=nb, source=src, payload=_FakeDev((10, 2), t.uint8)),
+        dict(bits=bits, nbytes=nb, source=src, records=T.FakeDev((10, 4), t.int32)),
+        dict(bits=bits, nbytes=nb, source=src, payload=T.FakeDev((10, 2), t.uint8)),
     ]
     for kw in bad:
         with pytest.raises(ValueError):

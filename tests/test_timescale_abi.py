@@ -17,18 +17,11 @@ KERNELS = ("solo_timescale_count_kernel", "solo_timescale_kernel")
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(solo_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return C.CDLL(solo_amd.LIB_PATH)
-
-
-def _header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(T.ROOT, "include", "solo_mi355x.h")).read(), flags=re.S)
+    return T.built_library()
 
 
 def test_declared_exported_bound(lib):
-    m = re.search(r"\bint32_t\s+solo_timescale\s*\(([^)]*)\)", _header())
+    m = re.search(r"\bint32_t\s+solo_timescale\s*\(([^)]*)\)", T.header_text())
     assert m
     args = [" ".join(a.split()) for a in m.group(1).split(",")]
     assert args == ["solo_batch_t *b", "const int16_t *d_pcm_in", "int32_t n", "int32_t in_packets", "int32_t out_packets", "int16_t *d_pcm_out",
@@ -41,7 +34,7 @@ def test_declared_exported_bound(lib):
 
 
 def test_count_struct_is_16_bytes_on_both_sides():
-    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_timescale_count_t;", _header())
+    m = re.search(r"typedef struct \{([^}]*)\}\s*solo_timescale_count_t;", T.header_text())
     assert m
     fields = re.findall(r"(int32_t|int64_t)\s+([^;]+);", m.group(1))
     names = [x.strip() for _, group in fields for x in group.split(",")]
@@ -70,48 +63,31 @@ def test_timescale_kernels_use_no_scratch(lib):
         assert hits[0]["scratch"] == 0, (frag, hits[0])
 
 
-class _NoLib:
-    """stands in for the library: any call reaching it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("%s reached the library" % name)
-
-
-class _FakeDev:
-    """the attributes of a CUDA tensor that the binding reads before it calls the library"""
-
-    def __init__(self, shape, dtype, cuda=True, contiguous=True):
-        self.shape, self.dtype, self.is_cuda, self._c = shape, dtype, cuda, contiguous
-
-    def is_contiguous(self):
-        return self._c
-
-
 def test_python_checks_raise_before_the_library():
     t = pytest.importorskip("torch")
     b = object.__new__(solo_amd.SoloBatch)
-    b.torch, b.lib, b.h = t, _NoLib(), None
+    b.torch, b.lib, b.h = t, T.NoLib(), None
     b.n_streams, b.slot, b.packet_samples, b.samplerate, b.device = 8, 512, 640, 16000, t.device("cpu")
-    pcm = _FakeDev((8, 2, 640), t.int16)
+    pcm = T.FakeDev((8, 2, 640), t.int16)
     bad = [
-        dict(pcm=_FakeDev((8, 2, 1280), t.int16), out_packets=1),                   # another packet length
-        dict(pcm=_FakeDev((8, 2, 640), t.int32), out_packets=1),
-        dict(pcm=_FakeDev((8, 2, 640), t.int16, cuda=False), out_packets=1),
-        dict(pcm=_FakeDev((8, 2, 640), t.int16, contiguous=False), out_packets=1),
-        dict(pcm=_FakeDev((8, 640), t.int16), out_packets=1),
-        dict(pcm=_FakeDev((0, 2, 640), t.int16), out_packets=1),
-        dict(pcm=_FakeDev((8, 0, 640), t.int16), out_packets=1),
-        dict(pcm=_FakeDev((8, 5, 640), t.int16), out_packets=1),
+        dict(pcm=T.FakeDev((8, 2, 1280), t.int16), out_packets=1),                   # another packet length
+        dict(pcm=T.FakeDev((8, 2, 640), t.int32), out_packets=1),
+        dict(pcm=T.FakeDev((8, 2, 640), t.int16, cuda=False), out_packets=1),
+        dict(pcm=T.FakeDev((8, 2, 640), t.int16, contiguous=False), out_packets=1),
+        dict(pcm=T.FakeDev((8, 640), t.int16), out_packets=1),
+        dict(pcm=T.FakeDev((0, 2, 640), t.int16), out_packets=1),
+        dict(pcm=T.FakeDev((8, 0, 640), t.int16), out_packets=1),
+        dict(pcm=T.FakeDev((8, 5, 640), t.int16), out_packets=1),
         dict(pcm=pcm, out_packets=0),
         dict(pcm=pcm, out_packets=5),
-        dict(pcm=_FakeDev((2 ** 20, 2, 640), t.int16), out_packets=4),              # n x max(a, b) x L = 2^31
-        dict(pcm=pcm, out_packets=1, out=_FakeDev((8, 2, 640), t.int16)),
-        dict(pcm=pcm, out_packets=1, out=_FakeDev((8, 1, 640), t.int32)),
-        dict(pcm=pcm, out_packets=1, out=_FakeDev((8, 1, 640), t.int16, contiguous=False)),
-        dict(pcm=pcm, out_packets=1, shift=_FakeDev((8, 7), t.int32)),              # M = 640 / 80 = 8 blocks
-        dict(pcm=pcm, out_packets=1, shift=_FakeDev((8, 8), t.int64)),
-        dict(pcm=pcm, out_packets=3, cost=_FakeDev((8, 8), t.int32)),               # M = 24
-        dict(pcm=pcm, out_packets=1, cost=_FakeDev((8, 8), t.int32, cuda=False)),
+        dict(pcm=T.FakeDev((2 ** 20, 2, 640), t.int16), out_packets=4),              # n x max(a, b) x L = 2^31
+        dict(pcm=pcm, out_packets=1, out=T.FakeDev((8, 2, 640), t.int16)),
+        dict(pcm=pcm, out_packets=1, out=T.FakeDev((8, 1, 640), t.int32)),
+        dict(pcm=pcm, out_packets=1, out=T.FakeDev((8, 1, 640), t.int16, contiguous=False)),
+        dict(pcm=pcm, out_packets=1, shift=T.FakeDev((8, 7), t.int32)),              # M = 640 / 80 = 8 blocks
+        dict(pcm=pcm, out_packets=1, shift=T.FakeDev((8, 8), t.int64)),
+        dict(pcm=pcm, out_packets=3, cost=T.FakeDev((8, 8), t.int32)),               # M = 24
+        dict(pcm=pcm, out_packets=1, cost=T.FakeDev((8, 8), t.int32, cuda=False)),
     ]
     for kw in bad:
         with pytest.raises(ValueError):
