@@ -650,8 +650,10 @@ int32_t solo_debug_sum_sqr_shift(const int16_t *d_x, int32_t rows, int32_t len, 
  * codec kernels get it.  d_v, d_aux: n_vec vectors of 64 words each (aux: the index operand of the arg functions, the high word of
  * wv_sum64, the source lane of wv_bcast; its word 0 the LCG seed, the rotation and the trip count); one wavefront per vector,
  * waves_per_block = 1 or 4 wavefronts per workgroup.  mode 0: every primitive on the raw input; mode 1: the primitives chained on each
- * other's results, straight and in a loop of (aux[0] & 7) + 1 rounds.  d_out: int32 [n_vec][rows][64], every lane's own copy of
- * every result; returns rows (27 / 18; also for n_vec == 0, which launches nothing) or a negative error.  The rows are listed in
+ * other's results, straight and in a loop of (aux[0] & 7) + 1 rounds; mode 2 (waves_per_block = 4 only): the workgroup vocabulary
+ * (wg_sum, wg_scan_incl, wg_total), the four vectors of a workgroup being its 256 lanes and vectors beyond n_vec zeros.  d_out: int32
+ * [n_vec][rows][64], every lane's own copy of
+ * every result; returns rows (27 / 18 / 3; also for n_vec == 0, which launches nothing) or a negative error.  The rows are listed in
  * tests/wave_model.py, which defines what each must hold (tests/test_gpu_wave_ops.py). */
 int32_t solo_debug_waveops(int32_t mode, int32_t n_vec, int32_t waves_per_block, const int32_t *d_v, const int32_t *d_aux,
                            int32_t *d_out);

@@ -59,8 +59,11 @@ __global__ void __launch_bounds__(64) solo_sum_sqr_probe_kernel(const i16* x, in
 // wavefronts (1, or 4: the geometry of the front kernel), each with a vector of its own.  One output row of 64 words per result,
 // EVERY lane stores its own copy: out[vector][row][lane].  No input reaches an address except the source lanes of wv_bcast and of
 // the lane-register round trip, masked to 0 .. 63 (0 .. 127 samples) here.  The row numbers are restated by tests/wave_model.py.
+// Mode 2 is the workgroup vocabulary (wg_sum, wg_scan_incl, wg_total), for wpb = 4 only: the four vectors of a workgroup are its 256
+// lanes.  A wavefront whose vector lies beyond n_vec contributes zeros, stays for the barriers and stores nothing.
 #define SOLO_WAVEOPS_ROWS0 27
 #define SOLO_WAVEOPS_ROWS1 18
+#define SOLO_WAVEOPS_ROWS2 3
 // the chain of mode 1: every primitive consumes the result of the one before it, nothing else in between
 #define SOLO_WAVEOPS_CHAIN(v)                                                                     \
     a = wv_sum(v);                                                                                \
@@ -73,6 +76,17 @@ __global__ void __launch_bounds__(64) solo_sum_sqr_probe_kernel(const i16* x, in
 __global__ void __launch_bounds__(256) solo_waveops_probe_kernel(int mode, int n_vec, int wpb, const i32* vin, const i32* auxin, i32* out) {
 #if defined(__HIP_DEVICE_COMPILE__)                         // (the host pass has the 1-lane vocabulary: no lane registers, no column sum)
     const int vec = (int)blockIdx.x * wpb + (int)(threadIdx.x >> 6);
+    if (mode == 2) {                                        // (mode is the launch's: every wavefront of the workgroup comes here)
+        __shared__ i32 red[4], part[1][4];
+        const bool live = vec < n_vec;
+        const i32 x = live ? vin[(size_t)vec * 64 + SX_LANE] : 0;
+        const i32 sum = wg_sum(x, red), incl = wg_scan_incl(x, part), total = wg_total(part[0]);
+        if (live) {
+            i32* o2 = out + (size_t)vec * SOLO_WAVEOPS_ROWS2 * 64 + SX_LANE;
+            o2[0] = sum; o2[64] = incl; o2[128] = total;
+        }
+        return;
+    }
     if (vec >= n_vec) return;                               // (whole wavefronts leave: every lane of a working wave stays active)
     const int lane = SX_LANE;
     const i32 v = vin[(size_t)vec * 64 + lane], aux = auxin[(size_t)vec * 64 + lane];
@@ -229,7 +243,7 @@ struct solo_batch {
     unsigned int started_target[SOLO_MAX_CHUNKS];
     int group_streams;               // streams per launch group (env SOLO_ENC_GROUP; default: launch per chunk 8192, persistent = what is resident at once)
     int gate;                        // env SOLO_ENC_GATE: the front / next analysis launch starts once the quantiser's workgroups are resident
-    // persistent schedule (calls of two or more packets; env SOLO_ENC_PERSIST=0 turns it off): per-stream hand-over flags, tickets
+    // persistent schedule (calls of two or more packets; off unless env SOLO_ENC_PERSIST=1 turns it on): per-stream hand-over flags, tickets
     int persist;
     int persist_group;               // streams per launch group: all of a group's front workgroups are resident beside its quantiser's
     unsigned int* d_flags;           // ana[n_streams] | nsq[n_streams / 4 + 1] | prog[n_streams] | err[4]
@@ -1628,11 +1642,11 @@ int32_t solo_debug_sum_sqr_shift(const int16_t* d_x, int32_t rows, int32_t len, 
 }
 
 // The lane-crossing vocabulary of solo_wave.h (solo_waveops_probe_kernel above): n_vec vectors of 64 words in d_v and in d_aux, one
-// wavefront each, waves_per_block (1 or 4) of them per workgroup; d_out = int32 [n_vec][rows][64].  Returns `rows` of the mode (also
+// wavefront each, waves_per_block (1 or 4; mode 2, the workgroup vocabulary: 4) of them per workgroup; d_out = int32 [n_vec][rows][64].  Returns `rows` of the mode (also
 // for n_vec == 0, which launches nothing: how a caller sizes d_out).
 int32_t solo_debug_waveops(int32_t mode, int32_t n_vec, int32_t waves_per_block, const int32_t* d_v, const int32_t* d_aux, int32_t* d_out) {
-    if ((mode != 0 && mode != 1) || n_vec < 0 || (waves_per_block != 1 && waves_per_block != 4)) return -1;
-    const int32_t rows = mode == 0 ? SOLO_WAVEOPS_ROWS0 : SOLO_WAVEOPS_ROWS1;
+    if (mode < 0 || mode > 2 || n_vec < 0 || (waves_per_block != 1 && waves_per_block != 4) || (mode == 2 && waves_per_block != 4)) return -1;
+    const int32_t rows = mode == 0 ? SOLO_WAVEOPS_ROWS0 : (mode == 1 ? SOLO_WAVEOPS_ROWS1 : SOLO_WAVEOPS_ROWS2);
     if (n_vec == 0) return rows;
     if (!d_v || !d_aux || !d_out) return -1;
     hipLaunchKernelGGL(solo_waveops_probe_kernel, dim3((n_vec + waves_per_block - 1) / waves_per_block), dim3(64 * waves_per_block), 0, (hipStream_t)0,

@@ -16,7 +16,8 @@
 //                 touches anything); named[d_source[i]] = 1
 //     3. totals   one workgroup per tile of SX_SEND_TILE packets, the source tiles first, then the destination tiles: pool bytes of a source
 //                 tile, {records, empty, refused} of a destination tile
-//     4. scan     ONE wavefront walks both runs of tile totals 64 at a time (wv_scan_incl) -> every tile's base, the call's counts
+//     4. scan     ONE wavefront walks both runs of tile totals 64 at a time (solo_send_pack's kernel, solo_send_scan_kernel) -> every
+//                 tile's base, the call's counts
 //     5. pool     the source tiles again: a scan inside the tile gives every packet its pool offset (kept for pass 6), the bytes are copied
 //                 by a 16-lane row per packet (sx_send_copy)
 //     6. records  the destination tiles again: a scan inside the tile gives every packet its record index; the offsets are its source's
@@ -49,10 +50,7 @@ static inline bool sx_fan_args_ok(const void* bits, const void* nbytes, long lon
 SX_HD SxSendPlan sx_fan_src_plan(const SxFanArgs& a, int q, size_t* pk) {
     const int p = q / a.n_src, s = q - p * a.n_src;
     *pk = (size_t)s * (size_t)a.n_packets + (size_t)p;
-    if (!a.named[s]) {
-        SxSendPlan r; r.why = SX_SEND_EMPTY; r.len0 = 0; r.len1 = 0; r.src1 = 0; r.seq = 0;
-        return r;
-    }
+    if (!a.named[s]) return sx_send_no_plan(SX_SEND_EMPTY);
     return sx_send_plan(a.nbytes[*pk * 2 + 0], a.nbytes[*pk * 2 + 1], a.slot, a.hbb, 3, 0);
 }
 // destination packet q of the record order (q = p * n_dst + i) -> its stream, its source packet, its plan
@@ -61,10 +59,7 @@ SX_HD SxSendPlan sx_fan_dst_plan(const SxFanArgs& a, int q, int* stream, size_t*
     const i32 s = a.source[i];
     *stream = a.dst_stream ? a.dst_stream[i] : i;
     *pk = 0;
-    if (s < 0) {
-        SxSendPlan r; r.why = SX_FAN_NOTHING; r.len0 = 0; r.len1 = 0; r.src1 = 0; r.seq = 0;
-        return r;
-    }
+    if (s < 0) return sx_send_no_plan(SX_FAN_NOTHING);
     *pk = (size_t)s * (size_t)a.n_packets + (size_t)p;
     const long long seq = (long long)a.first_seq + (a.seq_base ? (long long)a.seq_base[i] : 0) + (long long)p;
     const int mask = a.send ? (int)a.send[(size_t)i * (size_t)a.n_packets + (size_t)p] & 3 : 3;
@@ -72,8 +67,7 @@ SX_HD SxSendPlan sx_fan_dst_plan(const SxFanArgs& a, int q, int* stream, size_t*
 }
 // the run of a source packet whose first datagram lies at `off`: what ends inside cap (both datagrams are neighbours in the slot and in the pool)
 SX_HD SxSendRun sx_fan_run(const SxSendPlan& pl, size_t pk, int slot, i64 off, i64 cap) {
-    SxSendRun run;
-    run.src = 0; run.dst = 0; run.len = 0;
+    SxSendRun run = sx_send_no_run();
     const bool w0 = pl.len0 > 0 && off + pl.len0 <= cap;
     const bool w1 = pl.len1 > 0 && off + pl.len0 + pl.len1 <= cap;
     if (w0 | w1) {
@@ -84,19 +78,10 @@ SX_HD SxSendRun sx_fan_run(const SxSendPlan& pl, size_t pk, int slot, i64 off, i
     return run;
 }
 // the records of a destination packet, the first of which has index k; off: the pool offset of its source packet -> records written
+// (sx_send_record's rule; MD2 follows the source's MD1, sent or not)
 SX_HD int sx_fan_emit(const SxSendPlan& pl, int stream, i32 k, i64 off, SxSendRecord* records, int max_records, i64 cap) {
-    const i64 off1 = off + pl.src1;                         // (MD2 follows the source's MD1, sent or not)
-    const i32 k1 = k + (pl.len0 > 0);
-    const bool w0 = pl.len0 > 0 && k < max_records && off + pl.len0 <= cap;
-    const bool w1 = pl.len1 > 0 && k1 < max_records && off1 + pl.len1 <= cap;
-    if (w0) {
-        SxSendRecord r; r.stream = stream; r.seq = pl.seq; r.desc = 0; r.offset = (i32)off; r.len = pl.len0;
-        records[k] = r;
-    }
-    if (w1) {
-        SxSendRecord r; r.stream = stream; r.seq = pl.seq; r.desc = 1; r.offset = (i32)off1; r.len = pl.len1;
-        records[k1] = r;
-    }
+    const bool w0 = sx_send_record(records, k, max_records, cap, stream, pl.seq, 0, off, pl.len0);
+    const bool w1 = sx_send_record(records, k + (pl.len0 > 0), max_records, cap, stream, pl.seq, 1, off + pl.src1, pl.len1);
     return (int)w0 + (int)w1;
 }
 
@@ -148,91 +133,50 @@ __global__ void __launch_bounds__(SX_SEND_TILE) solo_fan_totals_kernel(const SxF
         const SxSendPlan pl = sx_fan_dst_plan(a, q, &stream, &pk);
         cnt = sx_send_counts(pl);
     }
-    cnt = sx_send_block_sum(cnt, red);
-    bytes = sx_send_block_sum(bytes, red);
+    cnt = wg_sum(cnt, red);
+    bytes = wg_sum(bytes, red);
     if (threadIdx.x == 0) { totals[blockIdx.x * 2 + 0] = cnt; totals[blockIdx.x * 2 + 1] = bytes; }
 }
-// pass 4: one wavefront; a tile holds at most 2^23 bytes, so 64 of them scan in 32 bits and the running base is carried in 64
-__global__ void __launch_bounds__(64) solo_fan_scan_kernel(const i32* __restrict__ totals, SxSendBase* __restrict__ bases, int src_tiles, int dst_tiles,
-                                                           SxSendCount* count, const i32* source, const u32* verdict) {
-    if (sx_map_refused(source, verdict)) {
-        if (threadIdx.x == 0) count->records = -1;
-        return;
-    }
-    i64 byte_base = 0;
-    i32 rec_base = 0, empty = 0, refused = 0;
-    const int n_tiles = src_tiles + dst_tiles;
-    for (int t0 = 0; t0 < n_tiles; t0 += 64) {
-        const int t = t0 + (int)threadIdx.x;
-        const i32 cnt = t < n_tiles ? totals[t * 2 + 0] : 0, bytes = t < n_tiles ? totals[t * 2 + 1] : 0;
-        const i32 rec = cnt & 1023;
-        const i32 irec = wv_scan_incl(rec), ibytes = wv_scan_incl(bytes);
-        if (t < n_tiles) {
-            SxSendBase b; b.bytes = byte_base + (i64)(ibytes - bytes); b.records = rec_base + irec - rec; b.pad = 0;
-            bases[t] = b;
-        }
-        rec_base += __builtin_amdgcn_readlane(irec, 63);
-        byte_base += (i64)__builtin_amdgcn_readlane(ibytes, 63);
-        empty += wv_sum((cnt >> 10) & 1023);
-        refused += wv_sum((cnt >> 20) & 1023);
-    }
-    if (threadIdx.x == 0) {         // (records / bytes WRITTEN: passes 5 and 6 add what each tile wrote)
-        SxSendCount c; c.records = 0; c.records_needed = rec_base; c.bytes = 0; c.bytes_needed = byte_base; c.empty = empty; c.refused = refused;
-        *count = c;
-    }
-}
+// pass 4 is solo_send_scan_kernel (solo_send.h) over both runs of tile totals
 // pass 5: the pool
 __global__ void __launch_bounds__(SX_SEND_TILE) solo_fan_pool_kernel(const SxFanArgs a, const SxSendBase* __restrict__ bases, u8* __restrict__ payload,
                                                                      long long cap, SxSendCount* count, const u32* verdict) {
-    __shared__ i32 red[4], wave_bytes[4];
+    __shared__ i32 red[4], part[1][4];
     __shared__ SxSendRun runs[SX_SEND_TILE];
     if (sx_map_refused(a.source, verdict)) return;
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int q = (int)blockIdx.x * SX_SEND_TILE + tid;
-    SxSendPlan pl;
-    pl.why = SX_SEND_EMPTY; pl.len0 = 0; pl.len1 = 0; pl.src1 = 0; pl.seq = 0;
+    SxSendPlan pl = sx_send_no_plan(SX_SEND_EMPTY);
     size_t pk = 0;
     if (q < a.n_src * a.n_packets) pl = sx_fan_src_plan(a, q, &pk);
     const i32 bytes = pl.len0 + pl.len1;
-    i32 ibytes = wv_scan_incl(bytes);
-    if ((tid & 63) == 63) wave_bytes[wave] = ibytes;
-    __syncthreads();
-    for (int w = 0; w < wave; w++) ibytes += wave_bytes[w];
-    SxSendRun run;
-    run.src = 0; run.dst = 0; run.len = 0;
+    const i32 ibytes = wg_scan_incl(bytes, part);
+    SxSendRun run = sx_send_no_run();
     if (bytes) {
         const i64 off = bases[blockIdx.x].bytes + (i64)(ibytes - bytes);
         a.pool_off[pk] = off;
         run = sx_fan_run(pl, pk, a.slot, off, cap);
     }
     runs[tid] = run;
-    const i32 tile_bytes = sx_send_block_sum(run.len, red);                // (its barriers publish runs[])
+    const i32 tile_bytes = wg_sum(run.len, red);                // (its barriers publish runs[])
     if (tid == 0 && tile_bytes) atomicAdd((unsigned long long*)&count->bytes, (unsigned long long)tile_bytes);
-    const int lane = tid & (SX_SEND_ROW - 1);
-    for (int t = tid / SX_SEND_ROW; t < SX_SEND_TILE; t += SX_SEND_TILE / SX_SEND_ROW) {
-        const SxSendRun r = runs[t];
-        if (r.len > 0) sx_send_copy(payload + r.dst, a.bits + r.src, r.len, lane, SX_SEND_ROW);
-    }
+    sx_send_copy_runs(runs, payload, a.bits);
 }
 // pass 6: the records (bases: those of the destination tiles)
 __global__ void __launch_bounds__(SX_SEND_TILE) solo_fan_records_kernel(const SxFanArgs a, const SxSendBase* __restrict__ bases, SxSendRecord* __restrict__ records,
                                                                         int max_records, long long cap, SxSendCount* count, const u32* verdict) {
-    __shared__ i32 red[4], wave_rec[4];
+    __shared__ i32 red[4], part[1][4];
     if (sx_map_refused(a.source, verdict)) return;
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int q = (int)blockIdx.x * SX_SEND_TILE + tid;
-    SxSendPlan pl;
-    pl.why = SX_FAN_NOTHING; pl.len0 = 0; pl.len1 = 0; pl.src1 = 0; pl.seq = 0;
+    SxSendPlan pl = sx_send_no_plan(SX_FAN_NOTHING);
     int stream = 0; size_t pk = 0;
     if (q < a.n_dst * a.n_packets) pl = sx_fan_dst_plan(a, q, &stream, &pk);
     const i32 rec = (pl.len0 > 0) + (pl.len1 > 0);
-    i32 irec = wv_scan_incl(rec);
-    if ((tid & 63) == 63) wave_rec[wave] = irec;
-    __syncthreads();
-    for (int w = 0; w < wave; w++) irec += wave_rec[w];
+    const i32 irec = wg_scan_incl(rec, part);
     int n_written = 0;
     if (rec) n_written = sx_fan_emit(pl, stream, bases[blockIdx.x].records + irec - rec, a.pool_off[pk], records, max_records, cap);
-    const i32 tile_written = sx_send_block_sum(n_written, red);
+    const i32 tile_written = wg_sum(n_written, red);
     if (tid == 0 && tile_written) atomicAdd(&count->records, tile_written);
 }
 
@@ -245,7 +189,7 @@ static inline hipError_t solo_fan_launch(SxFanArgs a, void* scratch, SxSendRecor
     hipLaunchKernelGGL(solo_fan_clear_kernel, dim3((a.n_src + 255) / 256), dim3(256), 0, s, l.named, a.n_src, verdict);
     hipLaunchKernelGGL(solo_fan_mark_kernel, dim3((a.n_dst + 255) / 256), dim3(256), 0, s, a.source, a.n_dst, a.n_src, l.named, verdict);
     hipLaunchKernelGGL(solo_fan_totals_kernel, dim3(l.src_tiles + l.dst_tiles), dim3(SX_SEND_TILE), 0, s, a, l.src_tiles, l.totals, verdict);
-    hipLaunchKernelGGL(solo_fan_scan_kernel, dim3(1), dim3(64), 0, s, l.totals, l.bases, l.src_tiles, l.dst_tiles, count, a.source, verdict);
+    hipLaunchKernelGGL(solo_send_scan_kernel, dim3(1), dim3(64), 0, s, l.totals, l.bases, l.src_tiles + l.dst_tiles, count, a.source, verdict);
     hipLaunchKernelGGL(solo_fan_pool_kernel, dim3(l.src_tiles), dim3(SX_SEND_TILE), 0, s, a, l.bases, payload, cap, count, verdict);
     hipLaunchKernelGGL(solo_fan_records_kernel, dim3(l.dst_tiles), dim3(SX_SEND_TILE), 0, s, a, l.bases + l.src_tiles, records, max_records, cap, count, verdict);
     return hipGetLastError();

@@ -39,7 +39,8 @@
 // independent numpy model).
 #pragma once
 #include "solo_recv.h"
-#include "solo_send.h"          // sx_send_block_sum
+#include "solo_wave.h"          // wg_sum
+#include "solo_stream_ctl.h"
 
 #define SX_MIG_MAGIC 0x4D474953u
 #define SX_MIG_VERSION 1
@@ -359,7 +360,7 @@ __global__ void __launch_bounds__(256) solo_migrate_export_kernel(const SxMigHan
         out[q] = v;
         sx_mig_acc(&a, (u32)((off >> 2) + 4 * q), v);
     }
-    const u32 s1 = (u32)sx_send_block_sum((i32)a.s1, red), s2 = (u32)sx_send_block_sum((i32)a.s2, red);
+    const u32 s1 = (u32)wg_sum((i32)a.s1, red), s2 = (u32)wg_sum((i32)a.s2, red);
     if (threadIdx.x == 0) {
         u32* hd = (u32*)row;
         atomicAdd(&hd[SX_MIG_H_S1], s1);

@@ -13,7 +13,7 @@
 //     1. clear    the room counters and the call's verdict word
 //     2. check    one lane per row: a room id outside [-1, n_rooms) sets the verdict (every later kernel then leaves before it touches
 //                 anything, solo_stream_ctl.h); the others are counted per room
-//     3. scan     ONE workgroup: a run of rooms per lane, wv_scan_incl over the lanes' sums -> every room's first slot in the member
+//     3. scan     ONE workgroup: a run of rooms per lane, wg_scan_incl over the lanes' sums -> every room's first slot in the member
 //                 list (CSR), and the call's counts
 //     4. scatter  one lane per row: the row index into its room's list.  The order inside a list is whatever the atomics give; the sums
 //                 are integer and the selection order is total, so the result does not depend on it
@@ -141,6 +141,39 @@ SX_HD void sx_mix_cache_put(SxMixX8* slot, int CH, const SxMixX8 (&x)[SX_MIX_ITE
     }
 }
 
+// The selection, of solo_vad_select (solo_vad.h) as well: K rounds of a wave-wide arg-best over the keys (key(row), row) of a room's m
+// members; round k picks the first key that comes after pick k - 1 and hands it to pick(k, row, key).  A key below -1 is no candidate.
+// A round that finds none ends the selection, so that no caller indexes a row by the sentinel (with K < m and no key negative there
+// always is one: solo_mix, solo_mix_shared) -> the picks made
+template <typename Key, typename Pick>
+SX_HD int sx_mix_select(const i32* mem, int m, int K, Key key, Pick pick) {
+    i64 pe = 0;
+    i32 pi = 0;
+    for (int k = 0; k < K; k++) {
+        i64 be = -1;                                        // (any candidate beats this)
+        i32 bi = 0x7FFFFFFF;
+        for (int j = SX_LANE; j < m; j += SX_NLANES) {
+            const i32 row = mem[j];
+            const i64 e = key(row);
+            if ((k == 0 || sx_mix_before(pe, pi, e, row)) && sx_mix_before(e, row, be, bi)) { be = e; bi = row; }
+        }
+        wv_mix_best(&be, &bi);
+        if (bi == 0x7FFFFFFF) return k;
+        pick(k, bi, be);
+        pe = be; pi = bi;
+    }
+    return K;
+}
+// what everybody who was not picked hears: o = sat16(S), this lane's chunks, computed once -> this lane's saturated samples of it
+SX_HD i32 sx_mix_sat_tile(const i32 (&S)[SX_MIX_ITERS][8], int CH, SxMixX8 (&o)[SX_MIX_ITERS]) {
+    i32 clip_s = 0;
+#pragma unroll
+    for (int k = 0; k < SX_MIX_ITERS; k++)
+#pragma unroll
+        for (int s = 0; s < 8; s++) o[k].s[s] = (k * SX_NLANES + SX_LANE < CH) ? sx_mix_sat(S[k][s], &clip_s) : (i16)0;
+    return clip_s;
+}
+
 // One (room, packet): what one wavefront does.  cache: SX_MIX_CACHE_CHUNKS chunks, sel: SX_MIX_MAX_SPEAKERS words (LDS on the device).
 // -> the saturated output samples of the unit (the wave's total, in every lane)
 SX_HD i64 sx_mix_unit(const SxMixArgs& a, int room, int p, SxMixX8* cache, i32* sel) {
@@ -206,22 +239,8 @@ SX_HD i64 sx_mix_unit(const SxMixArgs& a, int room, int p, SxMixX8* cache, i32* 
         return wv_sum64(clipped);
     }
 
-    // the selection: round k picks the first key that comes after pick k - 1 (K < m: there always is one)
-    i64 pe = 0;
-    i32 pi = 0;
-    for (int k = 0; k < K; k++) {
-        i64 be = -1;                                        // (no energy is negative: any member beats this)
-        i32 bi = 0x7FFFFFFF;
-        for (int j = SX_LANE; j < m; j += SX_NLANES) {
-            const i32 row = mem[j];
-            const i64 e = a.energy[(size_t)row * P + p];
-            if ((k == 0 || sx_mix_before(pe, pi, e, row)) && sx_mix_before(e, row, be, bi)) { be = e; bi = row; }
-        }
-        wv_mix_best(&be, &bi);
-        if (bi == 0x7FFFFFFF) { K = k; break; }             // (cannot happen with K < m; never index a row by the sentinel)
-        if (SX_LANE == 0) { sel[k] = bi; a.mixed[(size_t)bi * P + p] = 1; }
-        pe = be; pi = bi;
-    }
+    K = sx_mix_select(mem, m, K, [&](i32 row) { return a.energy[(size_t)row * P + p]; },
+                      [&](int k, i32 row, i64) { if (SX_LANE == 0) { sel[k] = row; a.mixed[(size_t)row * P + p] = 1; } });
     wv_sync();
     // S over the chosen rows (their second read), which stay in the cache for their own output
     for (int k = 0; k < K; k++) {
@@ -241,11 +260,7 @@ SX_HD i64 sx_mix_unit(const SxMixArgs& a, int room, int p, SxMixX8* cache, i32* 
     }
     // everybody else hears sat16(S): computed once, stored per row, nothing read but the flags
     SxMixX8 o[SX_MIX_ITERS];
-    i32 clip_s = 0;
-#pragma unroll
-    for (int k = 0; k < SX_MIX_ITERS; k++)
-#pragma unroll
-        for (int s = 0; s < 8; s++) o[k].s[s] = (k * SX_NLANES + SX_LANE < CH) ? sx_mix_sat(S[k][s], &clip_s) : (i16)0;
+    const i32 clip_s = sx_mix_sat_tile(S, CH, o);
     for (int j0 = 0; j0 < m; j0 += SX_NLANES) {
         const int jl = j0 + SX_LANE;
         const i32 row_l = jl < m ? mem[jl] : 0;
@@ -260,18 +275,29 @@ SX_HD i64 sx_mix_unit(const SxMixArgs& a, int room, int p, SxMixX8* cache, i32* 
     return wv_sum64(clipped);
 }
 
-// bytes of device scratch a call needs (n_rooms <= n): energy [n][P] | counts, starts, cursors, members [n] each | mixed [n][P]
+// The room plan, of solo_mix, solo_mix_shared, solo_mix_selected and solo_vad_select alike: members[starts[r] .. + counts[r]) are the rows
+// of room r; cursor[] is what the scatter counts up.  Four arrays of n words (n_rooms <= n) carved out of scratch at `at`; what a stage
+// keeps behind them starts at sx_room_plan_end.
+struct SxRoomPlan { i32* counts; i32* starts; i32* cursor; i32* members; };
+static inline size_t sx_room_plan_bytes(int n) { return 4 * (size_t)n * sizeof(i32); }
+static inline SxRoomPlan sx_room_plan(void* at, int n) {
+    SxRoomPlan rp;
+    rp.counts = (i32*)at; rp.starts = rp.counts + n; rp.cursor = rp.starts + n; rp.members = rp.cursor + n;
+    return rp;
+}
+static inline i32* sx_room_plan_end(const SxRoomPlan& rp, int n) { return rp.members + n; }
+
+// bytes of device scratch a call needs (n_rooms <= n): energy [n][P] | the room plan | mixed [n][P]
 static inline size_t solo_mix_scratch_bytes(int n, int n_packets) {
     const size_t np = (size_t)n * (size_t)n_packets;
-    return np * sizeof(i64) + 4 * (size_t)n * sizeof(i32) + np;
+    return np * sizeof(i64) + sx_room_plan_bytes(n) + np;
 }
-struct SxMixPlan { i64* energy; i32* counts; i32* starts; i32* cursor; i32* members; u8* mixed; };
+struct SxMixPlan { i64* energy; SxRoomPlan rooms; u8* mixed; };
 static inline SxMixPlan solo_mix_plan(void* scratch, int n, int n_packets) {
     SxMixPlan pl;
     pl.energy = (i64*)scratch;
-    pl.counts = (i32*)(pl.energy + (size_t)n * (size_t)n_packets);
-    pl.starts = pl.counts + n; pl.cursor = pl.starts + n; pl.members = pl.cursor + n;
-    pl.mixed = (u8*)(pl.members + n);
+    pl.rooms = sx_room_plan(pl.energy + (size_t)n * (size_t)n_packets, n);
+    pl.mixed = (u8*)sx_room_plan_end(pl.rooms, n);
     return pl;
 }
 
@@ -291,26 +317,23 @@ __global__ void __launch_bounds__(256) solo_mix_check_kernel(const i32* __restri
 // one workgroup: lane t owns the rooms [t * per, (t + 1) * per)
 __global__ void __launch_bounds__(256) solo_mix_scan_kernel(const i32* __restrict__ counts, int n_rooms, i32* __restrict__ starts, i32* __restrict__ cursor,
                                                             SxMixCount* count, const i32* room, const u32* verdict) {
-    __shared__ i32 wave_rows[4], wave_rooms[4];
+    __shared__ i32 part[2][4];                              // rows, rooms
     if (sx_map_refused(room, verdict)) {
         if (threadIdx.x == 0 && count) count->rows = -1;
         return;
     }
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int per = (n_rooms + 255) / 256;
     const int r0 = sx_min(tid * per, n_rooms), r1 = sx_min(r0 + per, n_rooms);
     i32 rows = 0, rooms = 0;
     for (int r = r0; r < r1; r++) { const i32 c = counts[r]; rows += c; rooms += c > 0; }
-    const i32 irows = wv_scan_incl(rows), irooms = wv_scan_incl(rooms);
-    if ((tid & 63) == 63) { wave_rows[wave] = irows; wave_rooms[wave] = irooms; }
-    __syncthreads();
-    i32 base = irows - rows;
-    for (int w = 0; w < wave; w++) base += wave_rows[w];
+    i32 incl[2] = {rows, rooms};
+    wg_scan_incl(incl, part);
+    i32 base = incl[0] - rows;
     for (int r = r0; r < r1; r++) { starts[r] = base; cursor[r] = base; base += counts[r]; }
     if (tid == 0 && count) {
         SxMixCount c;
-        c.rows = wave_rows[0] + wave_rows[1] + wave_rows[2] + wave_rows[3];
-        c.rooms = wave_rooms[0] + wave_rooms[1] + wave_rooms[2] + wave_rooms[3];
+        c.rows = wg_total(part[0]); c.rooms = wg_total(part[1]);
         c.clipped = 0;                                      // (the mix adds what each workgroup saturated)
         *count = c;
     }
@@ -332,22 +355,43 @@ __global__ void __launch_bounds__(64) solo_mix_kernel(const SxMixArgs a, SxMixCo
     if (threadIdx.x == 0 && count && clipped) atomicAdd((unsigned long long*)&count->clipped, (unsigned long long)clipped);
 }
 
+// The room plan's launches.  Its second half, scan and scatter over counts that a check has filled: solo_mix_shared and solo_mix_selected
+// come here behind a clear and a check of their own (count NULL: their compaction counts)
+static inline void sx_room_plan_finish(const SxRoomPlan& rp, const i32* room, int n, int n_rooms, SxMixCount* count, const u32* verdict, hipStream_t s) {
+    hipLaunchKernelGGL(solo_mix_scan_kernel, dim3(1), dim3(256), 0, s, rp.counts, n_rooms, rp.starts, rp.cursor, count, room, verdict);
+    hipLaunchKernelGGL(solo_mix_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, room, n, rp.cursor, rp.members, verdict);
+}
+// ... and all four: clear, check, scan, scatter.  between(verdict) enqueues what else may set the verdict word, behind the clear that
+// zeroes it and ahead of everything that reads it (solo_vad_select: its list check)
+template <typename Between>
+static inline void sx_room_plan_launch(const SxRoomPlan& rp, const i32* room, int n, int n_rooms, SxMixCount* count, u32* verdict, Between between, hipStream_t s) {
+    hipLaunchKernelGGL(solo_mix_clear_kernel, dim3((n_rooms + 255) / 256), dim3(256), 0, s, rp.counts, n_rooms, verdict);
+    between(verdict);
+    hipLaunchKernelGGL(solo_mix_check_kernel, dim3((n + 255) / 256), dim3(256), 0, s, room, n, n_rooms, rp.counts, verdict);
+    sx_room_plan_finish(rp, room, n, n_rooms, count, verdict, s);
+}
+
 // (scratch: solo_mix_scratch_bytes(n, n_packets) bytes, 16-byte aligned; a.energy / a.mixed NULL = the scratch's)
 static inline hipError_t solo_mix_launch(SxMixArgs a, const i32* room, int n, int n_rooms, void* scratch, SxMixCount* count, u32* verdict, hipStream_t s) {
     const SxMixPlan pl = solo_mix_plan(scratch, n, a.n_packets);
     if (!a.energy) a.energy = pl.energy;
     if (!a.mixed) a.mixed = pl.mixed;
-    a.counts = pl.counts; a.starts = pl.starts; a.members = pl.members;
-    hipLaunchKernelGGL(solo_mix_clear_kernel, dim3((n_rooms + 255) / 256), dim3(256), 0, s, pl.counts, n_rooms, verdict);
-    hipLaunchKernelGGL(solo_mix_check_kernel, dim3((n + 255) / 256), dim3(256), 0, s, room, n, n_rooms, pl.counts, verdict);
-    hipLaunchKernelGGL(solo_mix_scan_kernel, dim3(1), dim3(256), 0, s, pl.counts, n_rooms, pl.starts, pl.cursor, count, room, verdict);
-    hipLaunchKernelGGL(solo_mix_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, room, n, pl.cursor, pl.members, verdict);
+    a.counts = pl.rooms.counts; a.starts = pl.rooms.starts; a.members = pl.rooms.members;
+    sx_room_plan_launch(pl.rooms, room, n, n_rooms, count, verdict, [](u32*) {}, s);
     hipLaunchKernelGGL(solo_mix_kernel, dim3((unsigned)(n_rooms * a.n_packets)), dim3(64), 0, s, a, count, room, verdict);
     return hipGetLastError();
 }
 #else
-// Host form of the launches (tests): the same plan, the member lists filled from the LAST row down (any order will do), then every
-// (room, packet) through sx_mix_unit.  -> false: a room id is outside [-1, n_rooms), nothing but count->rows = -1 is written
+// Host form of the room plan's launches (tests), over counts that start at zero and room ids that are all inside [-1, n_rooms): the member
+// lists filled from the LAST row down (the device's order is whatever its atomics give; any order will do) -> rows in rooms, rooms with members
+static inline void sx_room_plan_host(const SxRoomPlan& rp, const i32* room, int n, int n_rooms, i32* rows, i32* rooms) {
+    *rows = 0; *rooms = 0;
+    for (int i = 0; i < n; i++) if (room[i] >= 0) rp.counts[room[i]]++;
+    for (int r = 0; r < n_rooms; r++) { rp.starts[r] = rp.cursor[r] = *rows; *rows += rp.counts[r]; *rooms += rp.counts[r] > 0; }
+    for (int i = n - 1; i >= 0; i--) if (room[i] >= 0) rp.members[rp.cursor[room[i]]++] = i;
+}
+// Host form of the launches (tests): the same plan, then every (room, packet) through sx_mix_unit.
+// -> false: a room id is outside [-1, n_rooms), nothing but count->rows = -1 is written
 static inline bool sx_mix_host(SxMixArgs a, const i32* room, int n, int n_rooms, SxMixCount* count) {
     for (int i = 0; i < n; i++)
         if (room[i] < -1 || room[i] >= n_rooms) {
@@ -355,25 +399,22 @@ static inline bool sx_mix_host(SxMixArgs a, const i32* room, int n, int n_rooms,
             return false;
         }
     const size_t np = (size_t)n * (size_t)a.n_packets;
-    i32* counts = new i32[(size_t)n_rooms]();
-    i32* starts = new i32[(size_t)n_rooms];
-    i32* cursor = new i32[(size_t)n_rooms];
-    i32* members = new i32[(size_t)n];
+    const int cap = sx_max(n, n_rooms);
+    i32* words = new i32[4 * (size_t)cap]();
+    const SxRoomPlan rp = sx_room_plan(words, cap);
     i64* energy = a.energy ? NULL : new i64[np];
     u8* mixed = a.mixed ? NULL : new u8[np];
     SxMixX8* cache = new SxMixX8[SX_MIX_CACHE_CHUNKS];
     i32 sel[SX_MIX_MAX_SPEAKERS];
     SxMixCount c; c.rows = 0; c.rooms = 0; c.clipped = 0;
-    for (int i = 0; i < n; i++) if (room[i] >= 0) counts[room[i]]++;
-    for (int r = 0; r < n_rooms; r++) { starts[r] = cursor[r] = c.rows; c.rows += counts[r]; c.rooms += counts[r] > 0; }
-    for (int i = n - 1; i >= 0; i--) if (room[i] >= 0) members[cursor[room[i]]++] = i;
+    sx_room_plan_host(rp, room, n, n_rooms, &c.rows, &c.rooms);
     if (!a.energy) a.energy = energy;
     if (!a.mixed) a.mixed = mixed;
-    a.counts = counts; a.starts = starts; a.members = members;
+    a.counts = rp.counts; a.starts = rp.starts; a.members = rp.members;
     for (int r = 0; r < n_rooms; r++)
         for (int p = 0; p < a.n_packets; p++) c.clipped += sx_mix_unit(a, r, p, cache, sel);
     if (count) *count = c;
-    delete[] counts; delete[] starts; delete[] cursor; delete[] members; delete[] energy; delete[] mixed; delete[] cache;
+    delete[] words; delete[] energy; delete[] mixed; delete[] cache;
     return true;
 }
 #endif

@@ -107,19 +107,15 @@ SX_HD i64 sx_mixsel_write_unit(const SxMixSelArgs& a, int room, int p) {
     return sx_mixsh_write_picks(a.sh, room, p, m, start, K, sx_mixsel_picks(a.sh, start, m, p));
 }
 
-// bytes of device scratch a call needs (n_rooms <= n): seven words per row (counts, starts, cursors, members, speaker flags, non-speaker
-// counts, room indices) | the picks [n][P] | their number per (room, packet) [n_rooms][P]
+// bytes of device scratch a call needs (n_rooms <= n): solo_mix_shared's words per row | the picks [n][P] | their number per (room,
+// packet) [n_rooms][P]
 static inline size_t solo_mixsel_scratch_bytes(int n, int n_packets) {
     const size_t np = (size_t)n * (size_t)n_packets;
-    return 7 * (size_t)n * sizeof(i32) + 2 * np * sizeof(i32);
+    return sx_mixsh_rows_bytes(n) + 2 * np * sizeof(i32);
 }
 static inline void solo_mixsel_plan(SxMixSelArgs& a, void* scratch) {
-    const size_t n = (size_t)a.sh.n, np = n * (size_t)a.sh.n_packets;
-    SxMixShArgs& s = a.sh;
-    s.counts = (i32*)scratch;
-    s.starts = s.counts + n; s.cursor = s.starts + n; s.members = s.cursor + n; s.spk = s.members + n; s.nonspk = s.spk + n; s.room_idx = s.nonspk + n;
-    s.sel = s.room_idx + n;
-    a.nsel = s.sel + np;
+    a.sh.sel = sx_mixsh_rows(a.sh, scratch);
+    a.nsel = a.sh.sel + (size_t)a.sh.n * (size_t)a.sh.n_packets;
 }
 
 #if defined(__HIPCC__)
@@ -130,19 +126,15 @@ __global__ void __launch_bounds__(64) solo_mixsel_gather_kernel(const SxMixSelAr
     if (threadIdx.x == 0 && picks > SX_MIX_MAX_SPEAKERS) atomicOr(verdict, 1u);
 }
 __global__ void __launch_bounds__(256) solo_mixsel_compact_kernel(const SxMixSelArgs a, SxMixSelCount* count, const u32* verdict) {
-    __shared__ i32 w_selected[4], w_silent[4];
+    __shared__ i32 part[2][4];                              // selected, silent
     if (!sx_mixsh_compact_group(a.sh, (SxMixShCount*)count, verdict)) return;
     const int tid = (int)threadIdx.x, per_r = (a.sh.n_rooms + 255) / 256;
     const int r0 = sx_min(tid * per_r, a.sh.n_rooms), r1 = sx_min(r0 + per_r, a.sh.n_rooms);
     i32 selected = 0, silent = 0;
     for (int r = r0; r < r1; r++) sx_mixsel_room_counts(a, r, &selected, &silent);
-    selected = wv_sum(selected); silent = wv_sum(silent);
-    if ((tid & 63) == 0) { w_selected[tid >> 6] = selected; w_silent[tid >> 6] = silent; }
-    __syncthreads();
-    if (tid == 0) {
-        count->selected = w_selected[0] + w_selected[1] + w_selected[2] + w_selected[3];
-        count->silent = w_silent[0] + w_silent[1] + w_silent[2] + w_silent[3];
-    }
+    i32 incl[2] = {selected, silent};                       // (only the totals are wanted: the scan's one barrier, where two wg_sum take four)
+    wg_scan_incl(incl, part);
+    if (tid == 0) { count->selected = wg_total(part[0]); count->silent = wg_total(part[1]); }
 }
 __global__ void __launch_bounds__(64) solo_mixsel_write_kernel(const SxMixSelArgs a, SxMixSelCount* count, const u32* verdict) {
     if (sx_map_refused(a.sh.room, verdict)) return;
@@ -158,8 +150,7 @@ static inline hipError_t solo_mixsel_launch(SxMixSelArgs a, void* scratch, SxMix
     const dim3 rows((h.n + 255) / 256), units((unsigned)(h.n_rooms * h.n_packets));
     hipLaunchKernelGGL(solo_mixsh_clear_kernel, dim3((h.n_rooms + 255) / 256), dim3(256), 0, s, h.counts, h.nonspk, h.n_rooms, verdict);
     hipLaunchKernelGGL(solo_mixsh_check_kernel, rows, dim3(256), 0, s, h, verdict);
-    hipLaunchKernelGGL(solo_mix_scan_kernel, dim3(1), dim3(256), 0, s, h.counts, h.n_rooms, h.starts, h.cursor, (SxMixCount*)NULL, h.room, verdict);
-    hipLaunchKernelGGL(solo_mix_scatter_kernel, rows, dim3(256), 0, s, h.room, h.n, h.cursor, h.members, verdict);
+    sx_room_plan_finish(sx_mixsh_rooms(h), h.room, h.n, h.n_rooms, (SxMixCount*)NULL, verdict, s);
     hipLaunchKernelGGL(solo_mixsel_gather_kernel, units, dim3(64), 0, s, a, verdict);
     if (h.energy) {
         const unsigned energy_blocks = (unsigned)(((long long)h.n * h.n_packets + 3) / 4);

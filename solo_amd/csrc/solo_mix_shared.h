@@ -14,13 +14,13 @@
 //     1. clear    the room counters and the call's verdict word
 //     2. check    one lane per row: a room id outside [-1, n_rooms) or a d_slots that does not grow strictly from a non-negative start sets
 //                 the verdict (every later kernel then leaves before it touches anything); members are counted per room, spk[i] = d_keep[i]
-//     3. scan, 4. scatter    the room plan of solo_mix (its kernels): members[starts[r] .. + counts[r]) are the rows of room r
+//     3. scan, 4. scatter    the room plan of solo_mix (its kernels, sx_room_plan_finish): members[starts[r] .. + counts[r]) are the rows of room r
 //     5. energy   ONE wavefront per (row, packet): e_j.  The work is spread over the rows, so one room of thousands costs what thousands of
 //                 small rooms cost; no LDS, so nothing but registers bounds the waves per SIMD
 //     6. select   one wavefront per (room, packet): max_speakers rounds of a wave-wide arg-best over the energies (solo_mix's); the picks go
 //                 to a list in scratch, d_mixed and spk[] are set
 //     7. tally    one lane per row: the members of every room that are not speakers
-//     8. compact  ONE workgroup: wv_scan_incl over runs of rows (speakers) and of rooms (shared rooms) -> the two lists, source[] of the
+//     8. compact  ONE workgroup: wg_scan_incl over runs of rows (speakers) and of rooms (shared rooms) -> the two lists, source[] of the
 //                 speakers, every room's index, the call's counts
 //     9. source   one lane per row: source[] of everybody else
 //    10. write    one wavefront per (room, packet): S over the picks (at most 64 rows), S - c_i for each of them, sat16(S) once for the
@@ -110,21 +110,8 @@ SX_HD void sx_mixsh_select_unit(const SxMixShArgs& a, int room, int p) {
     }
     if (!choose) return;
     wv_sync();
-    i64 pe = 0;
-    i32 pi = 0;
-    for (int k = 0; k < K; k++) {                           // round k picks the first key that comes after pick k - 1 (K < m: there always is one)
-        i64 be = -1;                                        // (no energy is negative: any member beats this)
-        i32 bi = 0x7FFFFFFF;
-        for (int j = SX_LANE; j < m; j += SX_NLANES) {
-            const i32 row = mem[j];
-            const i64 e = a.energy[(size_t)row * P + p];
-            if ((k == 0 || sx_mix_before(pe, pi, e, row)) && sx_mix_before(e, row, be, bi)) { be = e; bi = row; }
-        }
-        wv_mix_best(&be, &bi);
-        if (bi == 0x7FFFFFFF) bi = mem[0];                  // (cannot happen with K < m; never index a row by the sentinel)
-        if (SX_LANE == 0) { sel[k] = bi; a.mixed[(size_t)bi * P + p] = 1; a.spk[bi] = 1; }
-        pe = be; pi = bi;
-    }
+    (void)sx_mix_select(mem, m, K, [&](i32 row) { return a.energy[(size_t)row * P + p]; },      // (K < m: K picks)
+                  [&](int k, i32 row, i64) { if (SX_LANE == 0) { sel[k] = row; a.mixed[(size_t)row * P + p] = 1; a.spk[row] = 1; } });
 }
 
 // pass 10, one (room of m > 0 members, packet) whose K picks are sel[0 .. K) and are flagged in a.mixed (solo_mix_selected.h brings a K
@@ -157,11 +144,7 @@ SX_HD i64 sx_mixsh_write_picks(const SxMixShArgs& a, int room, int p, int m, int
     if (K == m) return wv_sum64(clipped);                   // (everybody was picked: no room row, no other speaker)
     // sat16(S): computed once, stored for the room and for every speaker of the call that was not picked here
     SxMixX8 o[SX_MIX_ITERS];
-    i32 clip_s = 0;
-#pragma unroll
-    for (int k = 0; k < SX_MIX_ITERS; k++)
-#pragma unroll
-        for (int s = 0; s < 8; s++) o[k].s[s] = (k * SX_NLANES + SX_LANE < CH) ? sx_mix_sat(S[k][s], &clip_s) : (i16)0;
+    const i32 clip_s = sx_mix_sat_tile(S, CH, o);
     const int ri = SX_UNI(a.room_idx[room]);
     if (ri >= 0) {
         sx_mix_cache_put((SxMixX8*)a.pcm_room + ((size_t)ri * (size_t)P + (size_t)p) * (size_t)CH, CH, o);
@@ -189,19 +172,30 @@ SX_HD i64 sx_mixsh_write_unit(const SxMixShArgs& a, int room, int p) {
     return sx_mixsh_write_picks(a, room, p, m, start, K, sx_mixsh_sel(a, start, K, p));
 }
 
-// bytes of device scratch a call needs (n_rooms <= n): energy [n][P] | seven words per row (counts, starts, cursors, members, speaker
-// flags, non-speaker counts, room indices) | the picks [n][P] | mixed [n][P]
+// The words per row of a call (n_rooms <= n), of solo_mix_selected as well: the room plan (solo_mix.h) | speaker flags, non-speaker counts,
+// room indices, carved out of scratch at `at` -> what lies behind them
+static inline size_t sx_mixsh_rows_bytes(int n) { return sx_room_plan_bytes(n) + 3 * (size_t)n * sizeof(i32); }
+static inline i32* sx_mixsh_rows(SxMixShArgs& a, void* at) {
+    const SxRoomPlan rp = sx_room_plan(at, a.n);
+    a.counts = rp.counts; a.starts = rp.starts; a.cursor = rp.cursor; a.members = rp.members;
+    a.spk = sx_room_plan_end(rp, a.n); a.nonspk = a.spk + a.n; a.room_idx = a.nonspk + a.n;
+    return a.room_idx + a.n;
+}
+static inline SxRoomPlan sx_mixsh_rooms(const SxMixShArgs& a) {
+    SxRoomPlan rp;
+    rp.counts = a.counts; rp.starts = a.starts; rp.cursor = a.cursor; rp.members = a.members;
+    return rp;
+}
+// bytes of device scratch a call needs: energy [n][P] | the words per row | the picks [n][P] | mixed [n][P]
 static inline size_t solo_mixsh_scratch_bytes(int n, int n_packets) {
     const size_t np = (size_t)n * (size_t)n_packets;
-    return np * sizeof(i64) + 7 * (size_t)n * sizeof(i32) + np * sizeof(i32) + np;
+    return np * sizeof(i64) + sx_mixsh_rows_bytes(n) + np * sizeof(i32) + np;
 }
 // (a.energy / a.mixed NULL = the scratch's)
 static inline void solo_mixsh_plan(SxMixShArgs& a, void* scratch) {
-    const size_t n = (size_t)a.n, np = n * (size_t)a.n_packets;
+    const size_t np = (size_t)a.n * (size_t)a.n_packets;
     i64* energy = (i64*)scratch;
-    a.counts = (i32*)(energy + np);
-    a.starts = a.counts + n; a.cursor = a.starts + n; a.members = a.cursor + n; a.spk = a.members + n; a.nonspk = a.spk + n; a.room_idx = a.nonspk + n;
-    a.sel = a.room_idx + n;
+    a.sel = sx_mixsh_rows(a, energy + np);
     u8* mixed = (u8*)(a.sel + np);
     if (!a.energy) a.energy = energy;
     if (!a.mixed) a.mixed = mixed;
@@ -249,23 +243,21 @@ __global__ void __launch_bounds__(256) solo_mixsh_tally_kernel(const SxMixShArgs
 // one workgroup of 256: lane t owns the rows [t * per, (t + 1) * per) and the rooms [t * per_r, (t + 1) * per_r).  -> false, in every lane,
 // when the call was refused (solo_mix_selected.h adds counts of its own behind it)
 __device__ __forceinline__ bool sx_mixsh_compact_group(const SxMixShArgs& a, SxMixShCount* count, const u32* verdict) {
-    __shared__ i32 w_spk[4], w_shared[4], w_rows[4], w_rooms[4];
+    __shared__ i32 part[4][4];                              // speakers, shared rooms, rows, rooms
     if (sx_map_refused(a.room, verdict)) {
         if (threadIdx.x == 0) count->rows = -1;
         return false;
     }
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int per = (a.n + 255) / 256, per_r = (a.n_rooms + 255) / 256;
     const int i0 = sx_min(tid * per, a.n), i1 = sx_min(i0 + per, a.n);
     const int r0 = sx_min(tid * per_r, a.n_rooms), r1 = sx_min(r0 + per_r, a.n_rooms);
     i32 spk = 0, shared = 0, rows = 0, rooms = 0;
     for (int i = i0; i < i1; i++) spk += a.spk[i] != 0;
     for (int r = r0; r < r1; r++) { const i32 c = a.counts[r]; rows += c; rooms += c > 0; shared += a.nonspk[r] > 0; }
-    const i32 ispk = wv_scan_incl(spk), ishared = wv_scan_incl(shared), irows = wv_scan_incl(rows), irooms = wv_scan_incl(rooms);
-    if ((tid & 63) == 63) { w_spk[wave] = ispk; w_shared[wave] = ishared; w_rows[wave] = irows; w_rooms[wave] = irooms; }
-    __syncthreads();
-    i32 k = ispk - spk, j = ishared - shared;
-    for (int w = 0; w < wave; w++) { k += w_spk[w]; j += w_shared[w]; }
+    i32 incl[4] = {spk, shared, rows, rooms};
+    wg_scan_incl(incl, part);
+    i32 k = incl[0] - spk, j = incl[1] - shared;
     for (int i = i0; i < i1; i++)
         if (a.spk[i]) {
             a.source[i] = k;
@@ -280,10 +272,7 @@ __device__ __forceinline__ bool sx_mixsh_compact_group(const SxMixShArgs& a, SxM
     }
     if (tid == 0) {
         SxMixShCount c;
-        c.rows = w_rows[0] + w_rows[1] + w_rows[2] + w_rows[3];
-        c.rooms = w_rooms[0] + w_rooms[1] + w_rooms[2] + w_rooms[3];
-        c.speakers = w_spk[0] + w_spk[1] + w_spk[2] + w_spk[3];
-        c.shared = w_shared[0] + w_shared[1] + w_shared[2] + w_shared[3];
+        c.rows = wg_total(part[2]); c.rooms = wg_total(part[3]); c.speakers = wg_total(part[0]); c.shared = wg_total(part[1]);
         c.clipped = 0;                                      // (the write pass adds what each workgroup saturated)
         *count = c;
     }
@@ -314,8 +303,7 @@ static inline hipError_t solo_mixsh_launch(SxMixShArgs a, void* scratch, SxMixSh
     const unsigned energy_blocks = (unsigned)(((long long)a.n * a.n_packets + 3) / 4);
     hipLaunchKernelGGL(solo_mixsh_clear_kernel, dim3((a.n_rooms + 255) / 256), dim3(256), 0, s, a.counts, a.nonspk, a.n_rooms, verdict);
     hipLaunchKernelGGL(solo_mixsh_check_kernel, rows, dim3(256), 0, s, a, verdict);
-    hipLaunchKernelGGL(solo_mix_scan_kernel, dim3(1), dim3(256), 0, s, a.counts, a.n_rooms, a.starts, a.cursor, (SxMixCount*)NULL, a.room, verdict);
-    hipLaunchKernelGGL(solo_mix_scatter_kernel, rows, dim3(256), 0, s, a.room, a.n, a.cursor, a.members, verdict);
+    sx_room_plan_finish(sx_mixsh_rooms(a), a.room, a.n, a.n_rooms, (SxMixCount*)NULL, verdict, s);
     hipLaunchKernelGGL(solo_mixsh_energy_kernel, dim3(energy_blocks), dim3(256), 0, s, a, verdict);
     hipLaunchKernelGGL(solo_mixsh_select_kernel, units, dim3(64), 0, s, a, verdict);
     hipLaunchKernelGGL(solo_mixsh_tally_kernel, rows, dim3(256), 0, s, a, verdict);
@@ -325,8 +313,7 @@ static inline hipError_t solo_mixsh_launch(SxMixShArgs a, void* scratch, SxMixSh
     return hipGetLastError();
 }
 #else
-// Host form of the launches (tests): the same passes in the same order, serially, the member lists filled from the LAST row down (any
-// order will do), in three stages that solo_mix_selected.h runs as well.
+// Host form of the launches (tests): the same passes in the same order, serially, in three stages that solo_mix_selected.h runs as well.
 // the check pass -> false: refused "on the device"
 static inline bool sx_mixsh_host_check(const SxMixShArgs& a) {
     for (int i = 0; i < a.n; i++) {
@@ -338,14 +325,9 @@ static inline bool sx_mixsh_host_check(const SxMixShArgs& a) {
 }
 // the room plan (the scratch starts zeroed): member counts and lists, spk[i] = d_keep[i], the counts rows and rooms
 static inline void sx_mixsh_host_rooms(const SxMixShArgs& a, SxMixShCount& c) {
-    const int n = a.n, R = a.n_rooms;
-    c.rows = 0; c.rooms = 0; c.speakers = 0; c.shared = 0; c.clipped = 0;
-    for (int i = 0; i < n; i++) {
-        if (a.room[i] >= 0) a.counts[a.room[i]]++;
-        a.spk[i] = (a.room[i] >= 0 && a.keep && a.keep[i]) ? 1 : 0;
-    }
-    for (int r = 0; r < R; r++) { a.starts[r] = a.cursor[r] = c.rows; c.rows += a.counts[r]; c.rooms += a.counts[r] > 0; }
-    for (int i = n - 1; i >= 0; i--) if (a.room[i] >= 0) a.members[a.cursor[a.room[i]]++] = i;
+    c.speakers = 0; c.shared = 0; c.clipped = 0;
+    for (int i = 0; i < a.n; i++) a.spk[i] = (a.room[i] >= 0 && a.keep && a.keep[i]) ? 1 : 0;
+    sx_room_plan_host(sx_mixsh_rooms(a), a.room, a.n, a.n_rooms, &c.rows, &c.rooms);
 }
 // tally, compact, source: the two lists, source[], every room's index, the counts speakers and shared
 static inline void sx_mixsh_host_lists(const SxMixShArgs& a, SxMixShCount& c) {

@@ -17,7 +17,7 @@
 // mask at or above p mod D is the front of the window, the part below it is the back, and first-empty / last-filled of either part are
 // one count-trailing / count-leading-zeros each (sx_recv_scan_chunk).  The 64-byte record is stored as four 16-byte quads by the
 // first lanes of the group.  Selection (sx_recv_select) leaves one flag per row; a second kernel compacts the selected rows in row
-// order with the wave scan of solo_send.h -- a tile's base is the number of flags in front of it, which the tile counts itself, so no
+// order with the workgroup scan of solo_wave.h -- a tile's base is the number of flags in front of it, which the tile counts itself, so no
 // launch waits for another workgroup and the output is a pure function of the inputs.
 //
 // Counting (only with solo_recv_track on) is per stream, SX_RECV_TRK_WORDS words (solo_recv.h): the insert kernel adds the verdict
@@ -29,7 +29,10 @@
 // walks the rows group by group and chunk by chunk through the very functions of the kernels, and compares it with an independent model).
 #pragma once
 #include "solo_recv.h"
-#include "solo_send.h"          // wv_scan_incl (solo_wave.h), sx_send_block_sum, SX_SEND_TILE
+#include "solo_wave.h"          // wg_sum, wg_scan_incl
+#include "solo_stream_ctl.h"
+
+#define SX_RECV_TILE 256        // rows per workgroup of the compaction = its lanes (wg_sum / wg_scan_incl are for 256)
 
 struct SxRecvReport {           // == solo_recv_report_t
     i32 play, queued, complete, ready, span, head;
@@ -152,24 +155,20 @@ __global__ void __launch_bounds__(256) solo_recv_report_kernel(const SxRecvRepor
 }
 
 // the selected rows, compacted in row order: list[k] = stream, rows[k] = row of the k-th selected row; count = {selected, n}
-__global__ void __launch_bounds__(SX_SEND_TILE) solo_recv_compact_kernel(const i32* __restrict__ sel, const i32* __restrict__ map, int n, i32* __restrict__ list,
+__global__ void __launch_bounds__(SX_RECV_TILE) solo_recv_compact_kernel(const i32* __restrict__ sel, const i32* __restrict__ map, int n, i32* __restrict__ list,
                                                                         i32* __restrict__ rows, SxRecvReportCount* count, const u32* verdict) {
-    __shared__ i32 red[4], wave_tot[4];
+    __shared__ i32 red[4], part[1][4];
     if (sx_map_refused(map, verdict)) {
         if (count && blockIdx.x == 0 && threadIdx.x == 0) count->selected = -1;
         return;
     }
-    const int tid = (int)threadIdx.x, wave = tid >> 6, t0 = (int)blockIdx.x * SX_SEND_TILE;
+    const int tid = (int)threadIdx.x, t0 = (int)blockIdx.x * SX_RECV_TILE;
     i32 before = 0;
-    for (int i = tid; i < t0; i += SX_SEND_TILE) before += sel[i];
-    before = sx_send_block_sum(before, red);
+    for (int i = tid; i < t0; i += SX_RECV_TILE) before += sel[i];
+    before = wg_sum(before, red);
     const int i = t0 + tid;
     const i32 f = i < n ? sel[i] : 0;
-    i32 inc = wv_scan_incl(f);
-    if ((tid & 63) == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    for (int w = 0; w < wave; w++) inc += wave_tot[w];
-    const i32 k = before + inc - f;                          // (k < n: there are at most n flags)
+    const i32 k = before + wg_scan_incl(f, part) - f;                         // (k < n: there are at most n flags)
     if (f) {
         if (list) list[k] = map ? map[i] : i;
         if (rows) rows[k] = i;
@@ -210,7 +209,7 @@ static inline hipError_t solo_recv_report_launch(const SxRecvReportArgs& a, i32*
     const int G = sx_recv_group(a.depth), rows_per_block = 4 * (64 / G);
     hipLaunchKernelGGL(solo_recv_report_kernel, dim3((unsigned)((a.n + rows_per_block - 1) / rows_per_block)), dim3(256), 0, s, a, G, verdict);
     if (list || rows || count)
-        hipLaunchKernelGGL(solo_recv_compact_kernel, dim3((unsigned)((a.n + SX_SEND_TILE - 1) / SX_SEND_TILE)), dim3(SX_SEND_TILE), 0, s, a.sel, a.map, a.n, list,
+        hipLaunchKernelGGL(solo_recv_compact_kernel, dim3((unsigned)((a.n + SX_RECV_TILE - 1) / SX_RECV_TILE)), dim3(SX_RECV_TILE), 0, s, a.sel, a.map, a.n, list,
                            rows, count, verdict);
     return hipGetLastError();
 }

@@ -9,8 +9,8 @@
 //     1. totals   one workgroup per tile of SX_SEND_TILE packets (one lane per packet): {datagrams, bytes, empty, refused} of the tile
 //     2. scan     ONE wavefront walks the tile totals 64 at a time (wv_scan_incl) -> every tile's first record index and byte offset,
 //                 and the call's counts
-//     3. scatter  the tile again: the same plan per packet, a scan inside the tile (wv_scan_incl + four wave totals through LDS),
-//                 records written by the packet's lane, then the bytes: a 16-lane row per packet
+//     3. scatter  the tile again: the same plan per packet, a scan inside the tile (wg_scan_incl, solo_wave.h), records written by the
+//                 packet's lane, then the bytes: a 16-lane row per packet
 //
 // The length rules are ONE function (sx_send_plan) that passes 1 and 3 both call, so they cannot disagree.  A packet's payload is already
 // contiguous in its slot, so with both descriptions sent its two datagrams are one run of `total` bytes in the pool; the run's source is
@@ -47,12 +47,18 @@ struct SxSendRecord { i32 stream, seq, desc, offset, len; };     // == solo_arri
 static_assert(sizeof(SxSendRecord) == 20, "solo_arrival_t layout");
 
 struct SxSendPlan { i32 why, len0, len1, src1, seq; };      // len0 / len1: bytes of the MD1 / MD2 || HB datagram (0: none); src1: where MD2 starts in the slot
+// a packet without a datagram, and why
+SX_HD SxSendPlan sx_send_no_plan(i32 why) {
+    SxSendPlan r;
+    r.why = why; r.len0 = 0; r.len1 = 0; r.src1 = 0; r.seq = 0;
+    return r;
+}
 
 // The length rules.  hbb: high-band bytes per packet (8; 4 with framesize_ms 20 or joint_mode 1), mask: bit 0 sends MD1, bit 1 MD2 || HB.
 // An empty packet is empty whatever else is wrong with it; a record that fails a rule yields nothing and is never dereferenced.
 SX_HD SxSendPlan sx_send_plan(i32 total, i32 n1, int slot, int hbb, int mask, long long seq) {
-    SxSendPlan r;
-    r.why = SX_SEND_OK; r.len0 = 0; r.len1 = 0; r.src1 = 0; r.seq = (i32)seq;
+    SxSendPlan r = sx_send_no_plan(SX_SEND_OK);
+    r.seq = (i32)seq;
     if (total <= 0) r.why = SX_SEND_EMPTY;
     else if (seq < 0 || seq > 0x7FFFFFFFLL) r.why = SX_SEND_SEQ;
     else if (total > slot) r.why = SX_SEND_TOO_LARGE;
@@ -87,27 +93,30 @@ SX_HD i32 sx_send_counts(const SxSendPlan& pl) {
 
 struct SxSendBase { i64 bytes; i32 records, pad; };         // where a tile's output starts
 struct SxSendRun { i64 src; i32 dst, len; };                // bytes of one packet that pass 3 copies: bits[src ..) -> payload[dst ..)
-
-// The packet's records, given the index k and the pool offset `off` of its first datagram.  Record k is written iff k < max_records and it
-// ends inside cap (<= 2^31 - 1: an offset that is written fits its int32 field).  Both sums grow along the order, so what is written is a
-// prefix -- and a packet whose MD1 record is cut loses its MD2 record as well, so the written part of a packet is always ONE run.
-SX_HD SxSendRun sx_send_emit(const SxSendPlan& pl, int stream, size_t pk, int slot, i32 k, i64 off, SxSendRecord* records, int max_records, i64 cap,
-                             int* n_written) {
+SX_HD SxSendRun sx_send_no_run() {
     SxSendRun run;
     run.src = 0; run.dst = 0; run.len = 0;
+    return run;
+}
+
+// THE record rule, of solo_send_pack and solo_send_fanout alike: record k, of description `desc`'s datagram of `len` bytes at pool offset
+// `off`, is written iff there is such a datagram (len > 0), k < max_records and the datagram ends inside cap (<= 2^31 - 1: an offset that
+// is written fits its int32 field).  -> written
+SX_HD bool sx_send_record(SxSendRecord* records, i32 k, int max_records, i64 cap, int stream, i32 seq, i32 desc, i64 off, i32 len) {
+    if (!(len > 0 && k < max_records && off + len <= cap)) return false;
+    SxSendRecord r; r.stream = stream; r.seq = seq; r.desc = desc; r.offset = (i32)off; r.len = len;
+    records[k] = r;
+    return true;
+}
+// The packet's records, given the index k and the pool offset `off` of its first datagram.  Both sums grow along the order, so what is
+// written is a prefix -- and a packet whose MD1 record is cut loses its MD2 record as well, so the written part of a packet is always ONE run.
+SX_HD SxSendRun sx_send_emit(const SxSendPlan& pl, int stream, size_t pk, int slot, i32 k, i64 off, SxSendRecord* records, int max_records, i64 cap,
+                             int* n_written) {
+    SxSendRun run = sx_send_no_run();
     *n_written = 0;
-    const bool w0 = pl.len0 > 0 && k < max_records && off + pl.len0 <= cap;
-    const i32 k1 = k + (pl.len0 > 0);
     const i64 off1 = off + pl.len0;
-    const bool w1 = pl.len1 > 0 && k1 < max_records && off1 + pl.len1 <= cap;
-    if (w0) {
-        SxSendRecord r; r.stream = stream; r.seq = pl.seq; r.desc = 0; r.offset = (i32)off; r.len = pl.len0;
-        records[k] = r;
-    }
-    if (w1) {
-        SxSendRecord r; r.stream = stream; r.seq = pl.seq; r.desc = 1; r.offset = (i32)off1; r.len = pl.len1;
-        records[k1] = r;
-    }
+    const bool w0 = sx_send_record(records, k, max_records, cap, stream, pl.seq, 0, off, pl.len0);
+    const bool w1 = sx_send_record(records, k + (pl.len0 > 0), max_records, cap, stream, pl.seq, 1, off1, pl.len1);
     if (w0 | w1) {
         run.src = (i64)(pk * (size_t)slot) + (w0 ? 0 : pl.src1);
         run.dst = (i32)(w0 ? off : off1);
@@ -152,13 +161,13 @@ SX_HD void sx_send_copy(u8* dst, const u8* src, int n, int lane, int nlanes) {
 }
 
 #if defined(__HIPCC__)
-// sum over the workgroup's four wavefronts of a per-lane value, in every lane (red: four words of LDS)
-__device__ __forceinline__ i32 sx_send_block_sum(i32 v, i32* red) {
-    v = wv_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
+// the bytes of a tile, whose runs its lanes have left in runs[] (published by a barrier): a 16-lane row per packet
+__device__ __forceinline__ void sx_send_copy_runs(const SxSendRun* runs, u8* payload, const u8* bits) {
+    const int tid = (int)threadIdx.x, lane = tid & (SX_SEND_ROW - 1);
+    for (int t = tid / SX_SEND_ROW; t < SX_SEND_TILE; t += SX_SEND_TILE / SX_SEND_ROW) {
+        const SxSendRun r = runs[t];
+        if (r.len > 0) sx_send_copy(payload + r.dst, bits + r.src, r.len, lane, SX_SEND_ROW);
+    }
 }
 
 // pass 1: totals[tile] = {counts (packed as sx_send_counts), bytes}
@@ -173,12 +182,13 @@ __global__ void __launch_bounds__(SX_SEND_TILE) solo_send_totals_kernel(const Sx
         cnt = sx_send_counts(pl);
         bytes = pl.len0 + pl.len1;
     }
-    cnt = sx_send_block_sum(cnt, red);
-    bytes = sx_send_block_sum(bytes, red);
+    cnt = wg_sum(cnt, red);
+    bytes = wg_sum(bytes, red);
     if (threadIdx.x == 0) { totals[blockIdx.x * 2 + 0] = cnt; totals[blockIdx.x * 2 + 1] = bytes; }
 }
 
-// pass 2: one wavefront; a tile holds at most 2^23 bytes, so 64 of them scan in 32 bits and the running base is carried in 64
+// pass 2, of solo_send_fanout (solo_fanout.h: its source and destination tiles in one run, map = its source rows) as well: one wavefront;
+// a tile holds at most 2^23 bytes, so 64 of them scan in 32 bits and the running base is carried in 64
 __global__ void __launch_bounds__(64) solo_send_scan_kernel(const i32* __restrict__ totals, SxSendBase* __restrict__ bases, int n_tiles, SxSendCount* count,
                                                             const i32* map, const u32* verdict) {
     if (sx_map_refused(map, verdict)) {
@@ -201,7 +211,7 @@ __global__ void __launch_bounds__(64) solo_send_scan_kernel(const i32* __restric
         empty += wv_sum((cnt >> 10) & 1023);
         refused += wv_sum((cnt >> 20) & 1023);
     }
-    if (threadIdx.x == 0) {         // (records / bytes WRITTEN: pass 3 adds what each tile wrote)
+    if (threadIdx.x == 0) {         // (records / bytes WRITTEN: the later passes add what each tile wrote)
         SxSendCount c; c.records = 0; c.records_needed = rec_base; c.bytes = 0; c.bytes_needed = byte_base; c.empty = empty; c.refused = refused;
         *count = c;
     }
@@ -211,36 +221,28 @@ __global__ void __launch_bounds__(64) solo_send_scan_kernel(const i32* __restric
 __global__ void __launch_bounds__(SX_SEND_TILE) solo_send_scatter_kernel(const SxSendArgs a, int n_pk, const SxSendBase* __restrict__ bases,
                                                                         SxSendRecord* __restrict__ records, int max_records, u8* __restrict__ payload,
                                                                         long long cap, SxSendCount* count, const u32* verdict) {
-    __shared__ i32 red[4], wave_rec[4], wave_bytes[4];
+    __shared__ i32 red[4], part[2][4];
     __shared__ SxSendRun runs[SX_SEND_TILE];
     if (sx_map_refused(a.map, verdict)) return;
-    const int tid = (int)threadIdx.x, wave = tid >> 6;
+    const int tid = (int)threadIdx.x;
     const int q = (int)blockIdx.x * SX_SEND_TILE + tid;
-    SxSendPlan pl;
-    pl.why = SX_SEND_EMPTY; pl.len0 = 0; pl.len1 = 0; pl.src1 = 0; pl.seq = 0;
+    SxSendPlan pl = sx_send_no_plan(SX_SEND_EMPTY);
     int row = 0; size_t pk = 0;
     if (q < n_pk) pl = sx_send_packet(a, q, &row, &pk);
     const i32 rec = (pl.len0 > 0) + (pl.len1 > 0), bytes = pl.len0 + pl.len1;
-    i32 irec = wv_scan_incl(rec), ibytes = wv_scan_incl(bytes);
-    if ((tid & 63) == 63) { wave_rec[wave] = irec; wave_bytes[wave] = ibytes; }
-    __syncthreads();
-    for (int w = 0; w < wave; w++) { irec += wave_rec[w]; ibytes += wave_bytes[w]; }
+    i32 incl[2] = {rec, bytes};
+    wg_scan_incl(incl, part);
     const SxSendBase base = bases[blockIdx.x];
     int n_written = 0;
-    SxSendRun run;
-    run.src = 0; run.dst = 0; run.len = 0;
-    if (rec) run = sx_send_emit(pl, a.map ? a.map[row] : row, pk, a.slot, base.records + irec - rec, base.bytes + (i64)(ibytes - bytes), records, max_records, cap, &n_written);
+    SxSendRun run = sx_send_no_run();
+    if (rec) run = sx_send_emit(pl, a.map ? a.map[row] : row, pk, a.slot, base.records + incl[0] - rec, base.bytes + (i64)(incl[1] - bytes), records, max_records, cap, &n_written);
     runs[tid] = run;
-    const i32 tile_written = sx_send_block_sum(n_written, red), tile_bytes = sx_send_block_sum(run.len, red);      // (its barriers publish runs[])
+    const i32 tile_written = wg_sum(n_written, red), tile_bytes = wg_sum(run.len, red);      // (its barriers publish runs[])
     if (tid == 0 && tile_written) {
         atomicAdd(&count->records, tile_written);
         atomicAdd((unsigned long long*)&count->bytes, (unsigned long long)tile_bytes);
     }
-    const int lane = tid & (SX_SEND_ROW - 1);
-    for (int t = tid / SX_SEND_ROW; t < SX_SEND_TILE; t += SX_SEND_TILE / SX_SEND_ROW) {
-        const SxSendRun r = runs[t];
-        if (r.len > 0) sx_send_copy(payload + r.dst, a.bits + r.src, r.len, lane, SX_SEND_ROW);
-    }
+    sx_send_copy_runs(runs, payload, a.bits);
 }
 
 // bytes of device scratch a call over n_pk packets needs: the tile totals, then the tile bases

@@ -20,7 +20,7 @@
 // what bounds it: 280 dependent steps a frame at N = 320, which no amount of lanes shortens -- only more rows in flight hide them.
 //
 // solo_vad_select: one wavefront per room, the packets in sequence, per packet one pass over the room's members (thresholds, hangover,
-// key) and max_speakers rounds of a wave-wide arg-best over the keys (the scheme of sx_mix_unit, solo_mix.h, whose room plan -- clear,
+// key) and max_speakers rounds of a wave-wide arg-best over the keys (sx_mix_select, solo_mix.h, whose room plan -- clear,
 // check, scan, scatter -- is reused as it is).
 //
 // Everything outside the kernels compiles for the host with the 1-lane forms of solo_wave.h (tests/test_vad_model.py builds
@@ -327,24 +327,14 @@ SX_HD void sx_vsel_room(const SxVselArgs& a, int room, i32* n_selected, i32* n_c
         }
         old_on = wv_sum(old_on);
         wv_sync();
-        // round k picks the first candidate that comes after pick k - 1
-        i64 pe = 0;
-        i32 pi = 0, first = -1, npick = 0, picked_old = 0;
-        for (int k = 0; k < K; k++) {
-            i64 be = -1;
-            i32 bi = 0x7FFFFFFF;
-            for (int j = SX_LANE; j < m; j += SX_NLANES) {
-                const i32 row = mem[j];
-                const i64 e = a.key[row];
-                if (e >= 0 && (k == 0 || sx_mix_before(pe, pi, e, row)) && sx_mix_before(e, row, be, bi)) { be = e; bi = row; }
-            }
-            wv_mix_best(&be, &bi);
-            if (bi == 0x7FFFFFFF) break;                    // fewer candidates than max_speakers
-            if (SX_LANE == 0) { sx_vsel_state(a, bi)[2] = 1; a.sel[(size_t)bi * P + p] = 1; }
-            if (k == 0) first = bi;
-            npick++; picked_old += (i32)(be & 1);
-            pe = be; pi = bi;
-        }
+        // round k picks the first candidate that comes after pick k - 1 (fewer candidates than max_speakers: fewer picks)
+        i32 first = -1, picked_old = 0;
+        const i32 npick = sx_mix_select(mem, m, K, [&](i32 row) { const i32 e = a.key[row]; return (i64)(e < 0 ? -2 : e); },
+                                        [&](int k, i32 row, i64 key) {
+                                            if (SX_LANE == 0) { sx_vsel_state(a, row)[2] = 1; a.sel[(size_t)row * P + p] = 1; }
+                                            if (k == 0) first = row;
+                                            picked_old += (i32)(key & 1);
+                                        });
         if (a.dominant && SX_LANE == 0) a.dominant[(size_t)room * P + p] = first;
         selected += npick;
         changes += (npick - picked_old) + (old_on - picked_old);    // newcomers, and incumbents that were not picked again
@@ -359,8 +349,8 @@ SX_HD void sx_vsel_room(const SxVselArgs& a, int room, i32* n_selected, i32* n_c
     *n_selected = selected; *n_changes = changes;
 }
 
-// bytes of device scratch of an object of n_rows rows (rooms <= n_rows): counts, starts, cursor, members, key
-static inline size_t solo_vad_scratch_bytes(int n_rows) { return 5 * (size_t)n_rows * sizeof(i32); }
+// bytes of device scratch of an object of n_rows rows (rooms <= n_rows): the room plan (solo_mix.h) | key
+static inline size_t solo_vad_scratch_bytes(int n_rows) { return sx_room_plan_bytes(n_rows) + (size_t)n_rows * sizeof(i32); }
 
 #if defined(__HIPCC__)
 // one wavefront per row of the call
@@ -414,13 +404,9 @@ static inline hipError_t solo_vad_launch(int frame, const SxVadArgs& a, SxVadCou
 template <typename ListCheck>
 static inline hipError_t solo_vad_select_launch(SxVselArgs a, const i32* room, int n, int n_rooms, int n_rows, void* scratch, SxVadCount* count, u32* verdict,
                                                 ListCheck list_check, hipStream_t s) {
-    i32* counts = (i32*)scratch, *starts = counts + n_rows, *cursor = starts + n_rows, *members = cursor + n_rows;
-    a.key = members + n_rows; a.counts = counts; a.starts = starts; a.members = members;
-    hipLaunchKernelGGL(solo_mix_clear_kernel, dim3((n_rooms + 255) / 256), dim3(256), 0, s, counts, n_rooms, verdict);
-    list_check(verdict);
-    hipLaunchKernelGGL(solo_mix_check_kernel, dim3((n + 255) / 256), dim3(256), 0, s, room, n, n_rooms, counts, verdict);
-    hipLaunchKernelGGL(solo_mix_scan_kernel, dim3(1), dim3(256), 0, s, counts, n_rooms, starts, cursor, (SxMixCount*)count, room, verdict);
-    hipLaunchKernelGGL(solo_mix_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, s, room, n, cursor, members, verdict);
+    const SxRoomPlan rp = sx_room_plan(scratch, n_rows);
+    a.key = sx_room_plan_end(rp, n_rows); a.counts = rp.counts; a.starts = rp.starts; a.members = rp.members;
+    sx_room_plan_launch(rp, room, n, n_rooms, (SxMixCount*)count, verdict, list_check, s);
     hipLaunchKernelGGL(solo_vad_select_kernel, dim3((unsigned)n_rooms), dim3(64), 0, s, a, count, room, verdict);
     return hipGetLastError();
 }
@@ -448,7 +434,7 @@ static inline bool sx_vad_host_n(const SxVadArgs& a, int n_rows, SxVadCount* cou
 static inline bool sx_vad_host(int frame, const SxVadArgs& a, int n_rows, SxVadCount* count) {
     return frame == 320 ? sx_vad_host_n<320>(a, n_rows, count) : sx_vad_host_n<160>(a, n_rows, count);
 }
-// ... of the selection: the plan of sx_mix_host (member lists filled from the LAST row down), then every room through sx_vsel_room.
+// ... of the selection: the room plan (sx_room_plan_host), then every room through sx_vsel_room.
 // -> false: a bad list or a room id outside [-1, n_rooms), nothing but count->rows = -1 is written
 static inline bool sx_vsel_host(SxVselArgs a, const i32* room, int n, int n_rooms, int n_rows, SxVadCount* count) {
     bool ok = sx_vad_map_ok(a.map, n, n_rows);
@@ -457,23 +443,19 @@ static inline bool sx_vsel_host(SxVselArgs a, const i32* room, int n, int n_room
         count->rows = -1;
         return false;
     }
-    i32* counts = new i32[(size_t)n_rooms]();
-    i32* starts = new i32[(size_t)n_rooms];
-    i32* cursor = new i32[(size_t)n_rooms];
-    i32* members = new i32[(size_t)n];
-    i32* key = new i32[(size_t)n];
-    SxVadCount c; c.rows = 0; c.rooms = 0; c.selected = 0; c.changes = 0;
-    for (int i = 0; i < n; i++) if (room[i] >= 0) counts[room[i]]++;
-    for (int r = 0; r < n_rooms; r++) { starts[r] = cursor[r] = c.rows; c.rows += counts[r]; c.rooms += counts[r] > 0; }
-    for (int i = n - 1; i >= 0; i--) if (room[i] >= 0) members[cursor[room[i]]++] = i;
-    a.counts = counts; a.starts = starts; a.members = members; a.key = key;
+    const int cap = sx_max(sx_max(n, n_rooms), n_rows);
+    i32* words = new i32[solo_vad_scratch_bytes(cap) / sizeof(i32)]();
+    const SxRoomPlan rp = sx_room_plan(words, cap);
+    SxVadCount c; c.selected = 0; c.changes = 0;
+    sx_room_plan_host(rp, room, n, n_rooms, &c.rows, &c.rooms);
+    a.counts = rp.counts; a.starts = rp.starts; a.members = rp.members; a.key = sx_room_plan_end(rp, cap);
     for (int r = 0; r < n_rooms; r++) {
         i32 s, ch;
         sx_vsel_room(a, r, &s, &ch);
         c.selected += s; c.changes += ch;
     }
     *count = c;
-    delete[] counts; delete[] starts; delete[] cursor; delete[] members; delete[] key;
+    delete[] words;
     return true;
 }
 #endif

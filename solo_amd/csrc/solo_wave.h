@@ -9,7 +9,9 @@
 //     s = wv_sum(partial);                     // wrapping int32 add => bit-exact tree reduction
 //
 // The workgroup is exactly one wavefront (blockDim.x == 64), so wv_sync() is a wave-level
-// barrier + LDS/global fence (hipcc drops the s_barrier for single-wave groups).
+// barrier + LDS/global fence (hipcc drops the s_barrier for single-wave groups).  The bridge stages around the codec work on tiles of
+// 256 lanes instead; their sum and scan over the four wavefronts of such a workgroup (wg_sum, wg_scan_incl) are at the end of the
+// lane-crossing functions below.
 //
 // Host build (SOLO_HOST_EMU): SX_NLANES == 1, the same source runs serially -- used only by the
 // CPU-side tests to check the kernel source against the reference without a GPU.  In that build every lane-crossing function of this
@@ -215,6 +217,44 @@ SX_HD void wv_argmax(i32* v, i32* idx) {
 #endif
 }
 
+#endif
+
+// The same for a WORKGROUP of 256 lanes, four wavefronts that work on one tile (the bridge stages: solo_send.h, solo_mix.h ...).  Device
+// only; every lane of the workgroup must reach the call, and the caller brings the LDS: four words per value, one per wavefront.  Checked
+// on the GPU by mode 2 of the probe (solo_debug_waveops).
+#if defined(__HIPCC__)
+// sum over the 256 lanes, in every lane.  Two barriers: the first one lets a caller hand the same `red` to one call after the other
+__device__ __forceinline__ i32 wg_sum(i32 v, i32* red) {
+    v = wv_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+// Inclusive scan over the 256 lanes of N values side by side (v[k] becomes v[k] of lane 0 + ... + v[k] of this lane, wrapping adds): a
+// wave scan each, the wave totals through part[k], ONE barrier for all N.  part[] is written once and not read back before the barrier,
+// so it needs none in front; behind the call wg_total(part[k]) is the workgroup's total of value k, for every lane.
+template <int N>
+__device__ __forceinline__ void wg_scan_incl(i32 (&v)[N], i32 (*part)[4]) {
+    const int wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+    for (int k = 0; k < N; k++) v[k] = wv_scan_incl(v[k]);
+    if ((threadIdx.x & 63) == 63) {
+#pragma unroll
+        for (int k = 0; k < N; k++) part[k][wave] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < 3; w++)                             // (the wavefronts below this one: at most three, so no loop is left)
+#pragma unroll
+        for (int k = 0; k < N; k++) v[k] += w < wave ? part[k][w] : 0;
+}
+__device__ __forceinline__ i32 wg_scan_incl(i32 v, i32 (*part)[4]) {
+    i32 a[1] = {v};
+    wg_scan_incl(a, part);
+    return a[0];
+}
+__device__ __forceinline__ i32 wg_total(const i32* part) { return part[0] + part[1] + part[2] + part[3]; }
 #endif
 
 // SX_UNI(x): x is known to be identical in all lanes of a fully active wave (wave-uniform code outside SX_PAR bodies); moving

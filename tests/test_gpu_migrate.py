@@ -5,8 +5,9 @@ mask is a 30 % Bernoulli loss of descriptions, so near a split it has isolated l
 mask made for the split -- a loss burst, an MD1-only run and an MD2-only run that straddle it -- has no fixture output and is checked
 against the compiled reference in tests of its own (test_decoder_straddling_mask_vs_compiled_reference), which are skipped where
 oracle/_ref is not present.  The encoder halves on the target handle are calls of more than one packet (k = 1, 7),
-so an imported stream encodes under the default, persistent schedule, whose per-handle words do not travel; k = 24 leaves one packet
-and with it the launch-per-chunk schedule."""
+so under the persistent schedule (opt-in: SOLO_ENC_PERSIST=1; the default is the launch-per-chunk schedule) an imported stream would
+encode with that schedule's per-handle words, which do not travel; k = 24 leaves one packet and with it the launch-per-chunk schedule
+whatever the setting."""
 import numpy as np
 import pytest
 

@@ -9,6 +9,10 @@ mode 0 applies every primitive to the raw inputs of the families A (random), B (
 other's results (the DPP read of a just-written register, straight and inside a loop of runtime trip count) on A, B and C.  Both
 with one wavefront per workgroup and with four (the front kernel's geometry).  One launch per mode / geometry / family.
 
+mode 2 is the workgroup vocabulary of the same header (wg_sum, wg_scan_incl, wg_total: the four vectors of a workgroup are its 256
+lanes) on prefixes of A, B and E whose length is a multiple of four, and once on a length of 1 modulo 4, where three wavefronts of
+the last workgroup have no vector: they contribute zeros, stay for the barriers and store nothing.
+
 Not covered: the SX_GROUP (16-lane) forms of the same functions.  No kernel calls them (the quantiser has its own RW* exchanges,
 tests/test_gpu_nsq_row.py)."""
 import numpy as np
@@ -22,15 +26,19 @@ SENTINEL = 0x5A5AA5A5
 CASES = [(0, fam) for fam in "ABCDE"] + [(1, fam) for fam in "ABC"]
 
 
-def _run(mode, fam, wpb):
+# mode 2: (family, vectors): B's first half holds every one-hot lane and every extreme once
+CASES_WG = [("A", 256), ("B", 580), ("E", 256), ("A", 257)]
+
+
+def _run(mode, fam, wpb, n=None):
     import torch
     import solo_amd
     lib = solo_amd.load_library()
-    names = M.ROWS0 if mode == 0 else M.ROWS1
+    names = (M.ROWS0, M.ROWS1, M.ROWS2)[mode]
     assert lib.solo_debug_waveops(mode, 0, wpb, None, None, None) == len(names)        # the probe's row count is the model's
     f = M.family(fam)
-    n = f["v"].shape[0]
-    d_v, d_aux = torch.from_numpy(f["v"].copy()).cuda(), torch.from_numpy(f["aux"].copy()).cuda()
+    n = f["v"].shape[0] if n is None else n
+    d_v, d_aux = torch.from_numpy(f["v"][:n].copy()).cuda(), torch.from_numpy(f["aux"][:n].copy()).cuda()
     # (one vector's worth of guard words behind the output: the probe writes its own rows and nothing else)
     d_out = torch.full(((n + 1) * len(names) * 64,), SENTINEL, dtype=torch.int32, device="cuda")
     assert lib.solo_debug_waveops(mode, n, wpb, d_v.data_ptr(), d_aux.data_ptr(), d_out.data_ptr()) == len(names)
@@ -43,11 +51,26 @@ def _run(mode, fam, wpb):
 @pytest.mark.parametrize("mode,fam", CASES)
 def test_wave_ops(mode, fam, wpb):
     names, f, got = _run(mode, fam, wpb)
-    want = M.expected(mode, fam)
+    _compare(names, f, got, M.expected(mode, fam), "mode %d, family %s, %d waves per block" % (mode, fam, wpb))
+
+
+@pytest.mark.parametrize("fam,n", CASES_WG)
+def test_workgroup_ops(fam, n):
+    assert n <= M.family(fam)["v"].shape[0] and (n % 4 == 0 or n % 4 == 1)
+    names, f, got = _run(2, fam, 4, n)
+    _compare(names, f, got, M.mode2(f["v"][:n]), "mode 2, family %s, %d vectors" % (fam, n))
+
+
+def test_workgroup_ops_need_four_waves():
+    import solo_amd
+    assert solo_amd.load_library().solo_debug_waveops(2, 0, 1, None, None, None) == -1
+
+
+def _compare(names, f, got, want, what):
     bad = got != want
     if bad.any():
         per_row = bad.any(axis=2).sum(axis=0)
-        lines = ["mode %d, family %s, %d waves per block: %d of %d vectors differ" % (mode, fam, wpb, int(bad.any(axis=(1, 2)).sum()), got.shape[0])]
+        lines = ["%s: %d of %d vectors differ" % (what, int(bad.any(axis=(1, 2)).sum()), got.shape[0])]
         for r in np.nonzero(per_row)[0]:
             k = int(np.nonzero(bad[:, r].any(axis=1))[0][0])
             lanes = np.nonzero(bad[k, r])[0]

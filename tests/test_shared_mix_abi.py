@@ -14,7 +14,7 @@ import solo_testlib as T
 
 KERNELS = ("solo_mixsh_clear_kernel", "solo_mixsh_check_kernel", "solo_mixsh_energy_kernel", "solo_mixsh_select_kernel", "solo_mixsh_tally_kernel",
            "solo_mixsh_compact_kernel", "solo_mixsh_source_kernel", "solo_mixsh_write_kernel", "solo_fan_clear_kernel", "solo_fan_mark_kernel",
-           "solo_fan_totals_kernel", "solo_fan_scan_kernel", "solo_fan_pool_kernel", "solo_fan_records_kernel")
+           "solo_fan_totals_kernel", "solo_send_scan_kernel", "solo_fan_pool_kernel", "solo_fan_records_kernel")
 
 
 @pytest.fixture(scope="module")

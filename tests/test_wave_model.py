@@ -65,6 +65,44 @@ def test_mode1_first_round_is_the_chain():
     assert np.array_equal(out[k, 9], M.wv_sum(x)[0])
 
 
+def test_mode2_known_answers():
+    # six vectors: one full workgroup and one with two vectors, whose missing half counts as zeros
+    v = np.arange(1, 6 * 64 + 1, dtype=np.int64).reshape(6, 64)
+    out = M.mode2(v)
+    assert out.shape == (6, 3, 64) and out.dtype == np.int32
+    r = {name: out[:, k] for k, name in enumerate(M.ROWS2)}
+    assert (r["wg_sum"][:4] == 256 * 257 // 2).all() and (r["wg_total"][:4] == 256 * 257 // 2).all()
+    assert r["wg_scan_incl"][:4].reshape(-1).tolist() == [l * (l + 1) // 2 for l in range(1, 257)]
+    tail = sum(range(257, 385))
+    assert (r["wg_sum"][4:] == tail).all() and (r["wg_total"][4:] == tail).all()
+    assert r["wg_scan_incl"][4:].reshape(-1).tolist() == [sum(range(257, 257 + l)) for l in range(1, 129)]
+    # lane 63 of a vector carries on into lane 0 of the next; the last lane of the workgroup holds the total
+    f = M.family("A")["v"][:257]
+    out = M.mode2(f)
+    assert np.array_equal(out[3::4, 1, 63], out[3::4, 2, 63]) and np.array_equal(out[:, 0], out[:, 2])
+    assert np.array_equal(out[1, 1, 0], M.wrap32(np.int64(out[0, 1, 63]) + f[1, 0]))
+    assert np.array_equal(out[256, 1], M.wv_scan_incl(f[256:257])[0])              # alone in its workgroup: the wave's scan
+    # wraps: 256 lanes of INT32_MAX
+    w = M.mode2(np.full((4, 64), M.I32_MAX))
+    assert (w[:, 0] == -256).all() and w[:, 1].reshape(-1).tolist() == [int(M.wrap32(np.int64(M.I32_MAX) * l)) for l in range(1, 257)]
+
+
+def test_workgroup_cases_hold_what_the_gpu_test_relies_on():
+    import test_gpu_wave_ops as G
+    assert {fam for fam, _ in G.CASES_WG} == {"A", "B", "E"}
+    assert sorted(n % 4 for _, n in G.CASES_WG) == [0, 0, 0, 1]
+    for fam, n in G.CASES_WG:
+        v = M.family(fam)["v"][:n].astype(np.int64)
+        assert n <= len(M.family(fam)["tags"])
+        if fam == "B":                                                # every hot lane, every extreme
+            hot = {int(np.nonzero(x)[0][0]) for x in v if np.count_nonzero(x) == 1}
+            assert hot == set(range(64)) and all((v == c).all(axis=1).any() for c in (M.I32_MIN, M.I32_MAX, -1, 0))
+        if fam == "E":                                                # wrapping prefixes over the workgroup, one-hot boundary lanes
+            pre = np.cumsum(np.concatenate([v, np.zeros((-n % 4, 64), np.int64)]).reshape(-1, 256), axis=1)
+            assert ((pre < M.I32_MIN) | (pre > M.I32_MAX)).any(axis=1).sum() >= 32
+            assert set(M.BOUNDARY) <= {int(np.nonzero(x)[0][0]) for x in v if np.count_nonzero(x) == 1}
+
+
 def test_family_a_sums_wrap():
     f = M.family("A")
     s = M.true_sum(f["v"])
@@ -163,7 +201,7 @@ def test_family_e_scan():
 
 
 def test_rows_and_shapes():
-    assert len(M.ROWS0) == 27 and len(M.ROWS1) == 18 and len(set(M.ROWS0)) == 27 and len(set(M.ROWS1)) == 18
+    assert len(M.ROWS0) == 27 and len(M.ROWS1) == 18 and len(set(M.ROWS0)) == 27 and len(set(M.ROWS1)) == 18 and len(M.ROWS2) == 3
     for name in "ABCDE":
         f = M.family(name)
         n = len(f["tags"])

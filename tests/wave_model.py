@@ -5,6 +5,8 @@ and wraps to 32 bits (64 for wv_sum64) only at its end.  These are the DEFINITIO
 lanes, a signed maximum, a running sum, the smallest index among the lanes that hold the extreme value ...), not a second
 implementation: nothing here knows about rows of 16 lanes except wv_row_sum / wv_col_sum, whose results are defined per row, and
 nothing restates a DPP step.  mode0 / mode1 lay the results out in the rows of the probe solo_debug_waveops (solo_api.hip).
+mode2 is the workgroup vocabulary (wg_sum, wg_scan_incl, wg_total): four consecutive vectors are the 256 lanes of one workgroup,
+vectors beyond the last one count as zeros.
 
 Used by tests/test_gpu_wave_ops.py (GPU, exact equality in every lane) and tests/test_wave_model.py (CPU: the families hold the
 cases the GPU test relies on)."""
@@ -27,6 +29,8 @@ ROWS0 = ("wv_sum", "wv_max", "wv_min", "wv_row_sum", "wv_col_sum", "wv_sum64.lo"
 _CHAIN = ("a = wv_sum(v)", "b = wv_max(v + a)", "c = wv_min(v ^ b)", "d = wv_sum(c + v)", "e = wv_scan_incl(v + d)",
           "f = wv_argmin(e ^ v, lane).value", "g = wv_argmin(e ^ v, lane).idx", "h = wv_sum64(v * g).lo", "h = wv_sum64(v * g).hi")
 ROWS1 = tuple("chain: " + s for s in _CHAIN) + tuple("loop: " + s for s in _CHAIN)
+ROWS2 = ("wg_sum", "wg_scan_incl", "wg_total")
+WG = 4                                                      # wavefronts (vectors) of a workgroup
 
 
 def wrap32(x):
@@ -183,6 +187,20 @@ def mode1(v, aux):
         last = [np.where(go, n_, l_) for n_, l_ in zip(nxt, last)]
     rows = first + last
     assert len(rows) == len(ROWS1)
+    return np.stack(rows, axis=1).astype(np.int32)
+
+
+def mode2(v):
+    """int32 [n][len(ROWS2)][64]: the sum over the workgroup's 256 lanes, the running sum along them, and the scan's total, each
+    wrapped to int32; workgroup g holds the vectors 4 g .. 4 g + 3, those at or beyond n being zeros"""
+    v = _i64(v)
+    n = v.shape[0]
+    groups = -(-n // WG)
+    flat = np.zeros((groups * WG, NL), np.int64)
+    flat[:n] = v
+    flat = flat.reshape(groups, WG * NL)
+    total = np.repeat(flat.sum(axis=1)[:, None], WG * NL, axis=1)      # |sum| <= 256 * 2^31: exact in int64
+    rows = [wrap32(x).reshape(groups * WG, NL)[:n] for x in (total, np.cumsum(flat, axis=1), total)]
     return np.stack(rows, axis=1).astype(np.int32)
 
 
