@@ -571,6 +571,97 @@ int32_t solo_vad_select(solo_vad_t *v, const int32_t *d_rows, int32_t n, const u
                         int32_t n_packets, int32_t frames, const int32_t *d_room, int32_t n_rooms,
                         const solo_vad_select_params_t *params, const int16_t *d_gain_in, uint8_t *d_sel, int16_t *d_gain_out,
                         uint8_t *d_keep, int32_t *d_dominant, solo_vad_count_t *d_count, void *hip_stream);
+/* Adaptive play-out delay control: the policy between the receive reports and the mixer -- when a stream starts, when its play-out
+ * delay grows by a packet (a 1 -> 2 stretch) or shrinks by one (a 2 -> 1 shortening) -- decided on the device with a state record per
+ * stream, and executed: after solo_playout_tick every listed stream has ONE packet of audio in the fixed row layout solo_vad / solo_mix*
+ * read.  A solo_playout_t is an object of its own; row s belongs to stream s of the handle it is ticked with.  Integers only, a total
+ * order everywhere: the output is a pure function of the arrivals.
+ *   state      SOLO_PLAYOUT_STATE_BYTES = 128 bytes per row, 32 int32 words: 0 run, 1 held, 2 cum, 3 cool, 4 age, 5 late_prev (uint32),
+ *              6 pos, 7 zero, 8 .. 23 the ring (32 int16 slots, slot j in half j & 1 of word 8 + j / 2, -32768 = none), 24 .. 31 zero; and
+ *              one packet of PCM, int16 [packet_samples], the HELD packet.  Create and the two resets leave everything zero (not running).
+ *   params     start_ready >= 1; max_span >= 0 (0 = off); window W in 1 .. 32; tolerate 0 .. 3; 0 <= lo <= hi <= 64; cooldown 0 .. 1000;
+ *              cost_gate (<= 0 = off).  They are the call's, not the object's: a tick may bring other values than the one before.
+ * The rule, per listed row and tick, from the row's solo_recv_report_t (tracking on, margin_min cleared by every tick) and depth D:
+ *   not running:  ready >= start_ready, or max_span > 0 and span >= max_span: the row STARTS -- every ring slot none, run = 1,
+ *              held = cum = cool = age = pos = 0, late_prev = late, action NORMAL.  Otherwise IDLE and the record does not move.
+ *   running, first the observation (held and cum as the tick before left them):
+ *              dl = late - late_prev (uint32), late_prev = late;
+ *              dl > 0: s = -1;  else margin_min < D: s = min(max(margin_min + held, -1), 1000);  else none
+ *              ring[pos] = s - cum (or none), pos = (pos + 1) mod 32, age = min(age + 1, W)
+ *              q = the (tolerate + 1)-th smallest VALUE among the last `age` slots, undefined with fewer values; e = q + cum
+ *   then the first of:   held: HELD, cool = max(cool - 1, 0)  |  max_span > 0 and span >= max_span: ACCEL_FORCED  |  cool > 0: NORMAL, cool -= 1
+ *              |  e defined, e < lo, ready >= 1, max_span == 0 or span + 1 < max_span: STRETCH  |  age >= W, e defined, e > hi, ready >= 2: ACCEL
+ *              |  NORMAL.
+ *   (The ring holds the arrivals' timing relative to the NETWORK, s - cum, which a move of the play-out does not change: no move clears it.
+ *   It always has 32 slots; W only says how far back the quantile looks.  |cum| saturates at 16000.)
+ *   Execution (render), gated = cost_gate > 0 and the largest entry of the row's splice costs (solo_timescale's d_cost) > cost_gate:
+ *     IDLE          L zeros, status 0                                     HELD   the held packet, held = 0, status 0
+ *     NORMAL        the packet decoded
+ *     STRETCH       1 decoded -> 2: the first is heard, the second held; held = 1, cum += 1, cool = cooldown
+ *       _GATED      the decoded packet is heard as it is, nothing else changes
+ *     ACCEL         2 decoded -> 1: heard; cum -= 1, cool = cooldown       ACCEL_FORCED  the same, never gated
+ *       _GATED      decoded packet 0 is heard, packet 1 held; held = 1
+ *   d_outcome holds SOLO_PLAYOUT_IDLE .. SOLO_PLAYOUT_ACCEL_FORCED; d_action the plan's codes 0 IDLE, 1 NORMAL, 2 HELD, 3 STRETCH, 4 ACCEL,
+ *   5 ACCEL_FORCED.  d_status is the decoder's status of rows that decoded, 0 for the others.
+ * solo_playout_plan: d_reports [n] (16-byte aligned) -> the first half of the state update, d_action [n], and three compacted lists in row
+ *   order: d_one = the streams of the NORMAL and STRETCH rows, d_two = those of the ACCEL and ACCEL_FORCED rows (both strictly increasing:
+ *   valid lists of solo_recv_decode_streams), d_stretch_pos = where each STRETCH row stands in d_one; all int32 [n], entries beyond the
+ *   counts are not written.  d_count (16-byte aligned) = {n_one, n_two, n_stretch, n}.  d_rows: a DEVICE list (strictly increasing inside
+ *   [0, n_rows), checked on the device ahead of the work: a refused list writes n_one = -1 and nothing else, no state moves), or NULL with
+ *   n = n_rows; unlisted rows keep their records bit for bit.  The object remembers where the plan put each row: the render that follows
+ *   must bring the same d_rows and n.
+ * solo_playout_gather: rows d_stretch_pos[0 .. n_stretch) of d_pcm_one [n_one][L] -> d_out [n_stretch][L], the input of solo_timescale 1 -> 2.
+ * solo_playout_render: the plan's d_action, the decode outputs of d_one (one packet: d_pcm_one [n_one][L], d_status_one) and d_two (two:
+ *   d_pcm_two [n_two][2][L], d_status_two), the scaler's outputs d_ts_stretch [n_stretch][2][L] with d_cost_stretch [n_stretch][2 L / block]
+ *   and d_ts_accel [n_two][L] with d_cost_accel [n_two][L / block] (block_samples = the scaler's block: samplerate / 200) -> d_heard
+ *   int16 [n][L] (row i = listed row i, 16-byte aligned like every PCM pointer here), d_outcome / d_status int32 [n], the held store and
+ *   held / cum / cool of the records; d_count (or NULL; 16-byte aligned) = rows per outcome, outcome[0] = -1 and nothing else for a refused
+ *   list.  Buffers of empty lists may be NULL.  A row whose action points outside the buffers brought is rendered IDLE.
+ *   plan is two short kernels (three with a list), render two (three); no allocation, no host synchronisation: each can be captured.
+ * solo_playout_tick: the receive side of a bridge tick in one call -- solo_recv_report (records, margins cleared), plan, ONE host read of
+ *   the 16-byte plan count (the tick's only synchronisation), solo_recv_decode_streams(d_one, 1) and (d_two, 2), gather, solo_timescale
+ *   1 -> 2 and 2 -> 1 with their costs, render; calls whose list is empty are skipped, the intermediates live in the object (sized at
+ *   create).  d_count = {plan, render}, 16-byte aligned.  Returns -1 with nothing enqueued: NULL po, b, params or output; a handle
+ *   without a ring, with a ring shallower than 2, with tracking off, or whose stream count or packet samples differ from the object's; a
+ *   packet that solo_timescale does not take; parameters out of range; n outside (0, n_rows]; d_streams = NULL with n != n_rows; d_heard
+ *   or d_count not 16-byte aligned.  A list refused on the device ends the tick after the plan: d_count->plan.n_one = -1, nothing else
+ *   written, no state, queue or play-out position moved.
+ * solo_playout_create: NULL unless n_rows > 0 and packet_samples is a positive multiple of 8, at most 1920.  solo_playout_reset_rows takes
+ *   a HOST list (1 .. n_rows indices inside [0, n_rows), none twice, else -1).  solo_playout_get_state / _set_state copy the listed rows'
+ *   128 + 2 x packet_samples bytes (record, then held PCM) to / from d_blob (4-byte aligned); d_rows is a DEVICE list or NULL for rows
+ *   0 .. n - 1; plain copies, an index outside [0, n_rows) moves nothing.  Calls on one object must be ordered.  INTEGRATION.md section 2. */
+#define SOLO_PLAYOUT_STATE_BYTES 128
+#define SOLO_PLAYOUT_IDLE 0
+#define SOLO_PLAYOUT_NORMAL 1
+#define SOLO_PLAYOUT_HELD 2
+#define SOLO_PLAYOUT_STRETCH 3
+#define SOLO_PLAYOUT_STRETCH_GATED 4
+#define SOLO_PLAYOUT_ACCEL 5
+#define SOLO_PLAYOUT_ACCEL_GATED 6
+#define SOLO_PLAYOUT_ACCEL_FORCED 7
+typedef struct solo_playout_obj solo_playout_t;
+typedef struct { int32_t start_ready, max_span, window, tolerate, lo, hi, cooldown, cost_gate; } solo_playout_params_t;   /* 32 bytes */
+typedef struct { int32_t n_one, n_two, n_stretch, listed; } solo_playout_plan_count_t;    /* 16 bytes; n_one = -1: list refused on the device */
+typedef struct { int32_t idle, normal, held, stretch, stretch_gated, accel, accel_gated, accel_forced; } solo_playout_render_count_t;   /* 32 bytes */
+typedef struct { solo_playout_plan_count_t plan; solo_playout_render_count_t render; } solo_playout_count_t;              /* 48 bytes */
+solo_playout_t *solo_playout_create(int32_t n_rows, int32_t packet_samples);
+void solo_playout_destroy(solo_playout_t *po);
+int32_t solo_playout_reset(solo_playout_t *po, void *hip_stream);
+int32_t solo_playout_reset_rows(solo_playout_t *po, const int32_t *h_rows, int32_t n, void *hip_stream);
+int32_t solo_playout_get_state(solo_playout_t *po, const int32_t *d_rows, int32_t n, uint8_t *d_blob, void *hip_stream);
+int32_t solo_playout_set_state(solo_playout_t *po, const int32_t *d_rows, int32_t n, const uint8_t *d_blob, void *hip_stream);
+int32_t solo_playout_plan(solo_playout_t *po, const solo_recv_report_t *d_reports, const int32_t *d_rows, int32_t n, int32_t depth,
+                          const solo_playout_params_t *params, int32_t *d_action, int32_t *d_one, int32_t *d_two, int32_t *d_stretch_pos,
+                          solo_playout_plan_count_t *d_count, void *hip_stream);
+int32_t solo_playout_gather(solo_playout_t *po, const int16_t *d_pcm_one, int32_t n_one, const int32_t *d_stretch_pos, int32_t n_stretch,
+                            int16_t *d_out, void *hip_stream);
+int32_t solo_playout_render(solo_playout_t *po, const int32_t *d_rows, int32_t n, const solo_playout_params_t *params, int32_t block_samples,
+                            const int32_t *d_action, int32_t n_one, int32_t n_two, int32_t n_stretch, const int16_t *d_pcm_one,
+                            const int32_t *d_status_one, const int16_t *d_pcm_two, const int32_t *d_status_two, const int16_t *d_ts_stretch,
+                            const int32_t *d_cost_stretch, const int16_t *d_ts_accel, const int32_t *d_cost_accel, int16_t *d_heard,
+                            int32_t *d_outcome, int32_t *d_status, solo_playout_render_count_t *d_count, void *hip_stream);
+int32_t solo_playout_tick(solo_playout_t *po, solo_batch_t *b, const int32_t *d_streams, int32_t n, const solo_playout_params_t *params,
+                          int16_t *d_heard, int32_t *d_outcome, int32_t *d_status, solo_playout_count_t *d_count, void *hip_stream);
 /* Stream migration: the state of a running call leaves a handle as a DEVICE blob and enters any slot of any handle of the same
  * geometry -- on this GPU, or on another one after the caller has moved the bytes (the blob is plain device memory: a torch.distributed
  * send, a hipMemcpyPeer).  The call goes on where it stood: no first-frame logic, no cold-start concealment, VAD / DTX / CNG / PLC and

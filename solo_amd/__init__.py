@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "solo_timescale",
     "solo_vad_create", "solo_vad_destroy", "solo_vad_reset", "solo_vad_reset_rows", "solo_vad_get_state", "solo_vad_set_state",
     "solo_vad", "solo_vad_select",
+    "solo_playout_create", "solo_playout_destroy", "solo_playout_reset", "solo_playout_reset_rows", "solo_playout_get_state",
+    "solo_playout_set_state", "solo_playout_plan", "solo_playout_gather", "solo_playout_render", "solo_playout_tick",
 ]
 
 
@@ -91,6 +93,26 @@ class solo_vad_count_t(C.Structure):
 class solo_vad_select_params_t(C.Structure):
     """the policy of a solo_vad_select call (include/solo_mi355x.h); 20 bytes"""
     _fields_ = [(n, C.c_int32) for n in ("max_speakers", "on_q8", "off_q8", "hang_packets", "stick")]
+
+
+class solo_playout_params_t(C.Structure):
+    """the policy of a solo_playout_plan / _render / _tick call (include/solo_mi355x.h); 32 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("start_ready", "max_span", "window", "tolerate", "lo", "hi", "cooldown", "cost_gate")]
+
+
+class solo_playout_plan_count_t(C.Structure):
+    """what a solo_playout_plan call decided (include/solo_mi355x.h); 16 bytes; n_one = -1: list refused on the device"""
+    _fields_ = [(n, C.c_int32) for n in ("n_one", "n_two", "n_stretch", "listed")]
+
+
+class solo_playout_render_count_t(C.Structure):
+    """rows per outcome of a solo_playout_render call (include/solo_mi355x.h); 32 bytes; idle = -1: list refused on the device"""
+    _fields_ = [(n, C.c_int32) for n in ("idle", "normal", "held", "stretch", "stretch_gated", "accel", "accel_gated", "accel_forced")]
+
+
+class solo_playout_count_t(C.Structure):
+    """what a solo_playout_tick call did: the plan's count, then the render's; 48 bytes"""
+    _fields_ = [("plan", solo_playout_plan_count_t), ("render", solo_playout_render_count_t)]
 
 
 class solo_migrate_count_t(C.Structure):
@@ -245,6 +267,26 @@ def load_library():
     lib.solo_vad_select.restype = C.c_int32
     lib.solo_vad_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.POINTER(solo_vad_select_params_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_playout_create.restype = C.c_void_p
+    lib.solo_playout_create.argtypes = [C.c_int32, C.c_int32]
+    lib.solo_playout_destroy.restype = None
+    lib.solo_playout_destroy.argtypes = [C.c_void_p]
+    lib.solo_playout_reset.restype = C.c_int32
+    lib.solo_playout_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.solo_playout_reset_rows.restype = C.c_int32
+    lib.solo_playout_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    for f in (lib.solo_playout_get_state, lib.solo_playout_set_state):
+        f.restype = C.c_int32
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    _pp = C.POINTER(solo_playout_params_t)
+    lib.solo_playout_plan.restype = C.c_int32
+    lib.solo_playout_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _pp] + [C.c_void_p] * 6
+    lib.solo_playout_gather.restype = C.c_int32
+    lib.solo_playout_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_playout_render.restype = C.c_int32
+    lib.solo_playout_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, _pp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 13
+    lib.solo_playout_tick.restype = C.c_int32
+    lib.solo_playout_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _pp] + [C.c_void_p] * 5
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1292,3 +1334,227 @@ class Vad:
         r = self.lib.solo_vad_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_vad_set_state -> %d" % r)
+
+
+PLAYOUT_STATE_BYTES = 128
+
+
+class Playout:
+    """Adaptive play-out delay control for n_rows streams on the current HIP device (solo_playout_*, include/solo_mi355x.h has the rule): per
+    stream a 128-byte state record and one held packet; row s belongs to stream s of the SoloBatch it is ticked with.  tick() is the receive
+    side of a bridge tick in one call; plan() and render() are its two stages alone."""
+
+    ACTIONS = ("IDLE", "NORMAL", "HELD", "STRETCH", "ACCEL", "ACCEL_FORCED")
+    OUTCOMES = tuple(f[0].upper() for f in solo_playout_render_count_t._fields_)
+    PARAMS = dict(start_ready=2, max_span=0, window=16, tolerate=1, lo=1, hi=3, cooldown=8, cost_gate=0)
+
+    def __init__(self, n_rows, packet_samples=PACKET_SAMPLES):
+        import torch
+        self.n_rows, self.packet_samples = int(n_rows), int(packet_samples)
+        if self.n_rows <= 0:
+            raise ValueError("n_rows must be positive")
+        if not 0 < self.packet_samples <= 1920 or self.packet_samples % 8:
+            raise ValueError("packet_samples: a positive multiple of 8, at most 1920")
+        self.h = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
+        self.torch = torch
+        self.lib = load_library()
+        self.h = self.lib.solo_playout_create(self.n_rows, self.packet_samples)
+        if not self.h:
+            raise RuntimeError("solo_playout_create failed (no GPU, or out of memory)")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.solo_playout_destroy(self.h)
+            self.h = None
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    @property
+    def state_bytes(self):
+        """bytes per row of a get_state() / set_state() blob: the record, then the held packet"""
+        return PLAYOUT_STATE_BYTES + 2 * self.packet_samples
+
+    @classmethod
+    def params(cls, **kw):
+        """the policy as a solo_playout_params_t: PARAMS overridden by kw, range-checked as the library does"""
+        unknown = set(kw) - set(cls.PARAMS)
+        if unknown:
+            raise ValueError("unknown play-out parameter(s): %s" % ", ".join(sorted(unknown)))
+        v = dict(cls.PARAMS)
+        for k, x in kw.items():
+            try:
+                v[k] = operator.index(x)
+            except TypeError:
+                raise ValueError("%s: an int" % k)
+        if any(not -2 ** 31 <= x < 2 ** 31 for x in v.values()):
+            raise ValueError("play-out parameters must fit int32")
+        if not (v["start_ready"] >= 1 and v["max_span"] >= 0 and 1 <= v["window"] <= 32 and 0 <= v["tolerate"] <= 3 and 0 <= v["lo"] <= v["hi"] <= 64 and
+                0 <= v["cooldown"] <= 1000):
+            raise ValueError("start_ready >= 1, max_span >= 0, window 1 .. 32, tolerate 0 .. 3, 0 <= lo <= hi <= 64, cooldown 0 .. 1000")
+        return solo_playout_params_t(*[v[k] for k, _ in solo_playout_params_t._fields_])
+
+    def _rows(self, rows, n=None):
+        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
+        t = self.torch
+        if rows is None:
+            return None
+        if not getattr(rows, "is_cuda", False):
+            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
+        k, = _tensor("rows", rows, t.int32, (n,))
+        if not 0 < k <= self.n_rows:
+            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
+        return rows
+
+    def _n(self, rows):
+        return self.n_rows if rows is None else int(rows.shape[0])
+
+    def tick(self, batch, streams=None, **params):
+        """The receive side of a tick (solo_playout_tick): report, plan, the two decodes, time scaling, render -> (heard int16 [n,samples],
+        outcome int32 [n], status int32 [n], count int32 [12] on the device: read it with count()).  batch: the SoloBatch whose ring is
+        played, with recv_track() on and as many streams as this object has rows.  streams: None = all, a strictly increasing sequence, or
+        an int32 CUDA tensor (checked on the device: a bad one gives plan n_one = -1 and nothing else).  params: PARAMS overridden.
+        Synchronises once (the 16-byte plan count)."""
+        t = self.torch
+        if not isinstance(batch, SoloBatch) or batch.n_streams != self.n_rows or batch.packet_samples != self.packet_samples:
+            raise ValueError("batch: a SoloBatch of %d streams and %d samples a packet" % (self.n_rows, self.packet_samples))
+        prm = self.params(**params)
+        rows = self._rows(streams)
+        n = self._n(rows)
+        heard = t.zeros((n, self.packet_samples), dtype=t.int16, device=self.device)
+        outcome = t.zeros((n,), dtype=t.int32, device=self.device)
+        status = t.zeros((n,), dtype=t.int32, device=self.device)
+        count = t.zeros((12,), dtype=t.int32, device=self.device)
+        r = self.lib.solo_playout_tick(self.h, batch.h, _ptr(rows), n, C.byref(prm), heard.data_ptr(), outcome.data_ptr(), status.data_ptr(),
+                                       count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_tick -> %d" % r)
+        return heard, outcome, status, count
+
+    def plan(self, reports, depth, rows=None, **params):
+        """reports int32 [n,16] as SoloBatch.recv_report() wrote them (tracking on, clear_margin=True), depth: the ring depth -> dict(action
+        int32 [n], one / two / stretch_pos int32 [n] (compacted; the counts say how many entries count), count int32 [4], read with
+        count()).  The first half of the state update; render() with the same rows must follow.  No synchronisation."""
+        t = self.torch
+        prm = self.params(**params)
+        rows = self._rows(rows)
+        n = self._n(rows)
+        _tensor("reports", reports, t.int32, (n, 16))
+        depth = int(depth)
+        if not 0 < depth <= 4096:
+            raise ValueError("depth: 1 .. 4096")
+        out = {k: t.zeros((n,), dtype=t.int32, device=self.device) for k in ("action", "one", "two", "stretch_pos")}
+        out["count"] = t.zeros((4,), dtype=t.int32, device=self.device)
+        r = self.lib.solo_playout_plan(self.h, reports.data_ptr(), _ptr(rows), n, depth, C.byref(prm), out["action"].data_ptr(), out["one"].data_ptr(),
+                                       out["two"].data_ptr(), out["stretch_pos"].data_ptr(), out["count"].data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_plan -> %d" % r)
+        return out
+
+    def gather(self, pcm_one, stretch_pos, n_stretch):
+        """rows stretch_pos[:n_stretch] of pcm_one int16 [n_one,samples] -> int16 [n_stretch,1,samples], what SoloBatch.timescale(., 2) takes"""
+        t = self.torch
+        n_one, _ = _tensor("pcm_one", pcm_one, t.int16, (None, self.packet_samples))
+        k, = _tensor("stretch_pos", stretch_pos, t.int32, (None,))
+        n_stretch = int(n_stretch)
+        if not 0 < n_stretch <= min(k, n_one) or n_one > self.n_rows:
+            raise ValueError("n_stretch: 1 .. min(len(stretch_pos), n_one), n_one at most %d" % self.n_rows)
+        out = t.zeros((n_stretch, 1, self.packet_samples), dtype=t.int16, device=self.device)
+        r = self.lib.solo_playout_gather(self.h, pcm_one.data_ptr(), n_one, stretch_pos.data_ptr(), n_stretch, out.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_gather -> %d" % r)
+        return out
+
+    def render(self, action, block_samples, pcm_one=None, status_one=None, pcm_two=None, status_two=None, ts_stretch=None, cost_stretch=None,
+               ts_accel=None, cost_accel=None, rows=None, **params):
+        """The second stage (solo_playout_render): action int32 [n] of the plan() before, the decode outputs of its `one` list (pcm_one int16
+        [n_one,samples], status_one int32 [n_one]) and `two` list (pcm_two [n_two,2,samples], status_two), the time scaler's outputs for
+        the STRETCH rows (ts_stretch [n_stretch,2,samples], cost_stretch int32 [n_stretch,2M]) and the ACCEL rows (ts_accel
+        [n_two,1,samples], cost_accel [n_two,M]), M = samples / block_samples; absent = an empty list -> (heard int16 [n,samples], outcome
+        int32 [n], status int32 [n], count int32 [8], read with count()).  No synchronisation."""
+        t = self.torch
+        prm = self.params(**params)
+        rows = self._rows(rows)
+        n, L = self._n(rows), self.packet_samples
+        _tensor("action", action, t.int32, (n,))
+        block_samples = int(block_samples)
+        if block_samples <= 0 or L % block_samples or L // block_samples > 16:
+            raise ValueError("block_samples: a divisor of %d, at most 16 blocks a packet" % L)
+        M = L // block_samples
+        n_one = n_two = n_stretch = 0
+        if pcm_one is not None or status_one is not None:
+            n_one, _ = _tensor("pcm_one", pcm_one, t.int16, (None, L))
+            _tensor("status_one", status_one, t.int32, (n_one,))
+        if pcm_two is not None or status_two is not None or ts_accel is not None or cost_accel is not None:
+            n_two, _, _ = _tensor("pcm_two", pcm_two, t.int16, (None, 2, L))
+            _tensor("status_two", status_two, t.int32, (n_two,))
+            _tensor("ts_accel", ts_accel, t.int16, (n_two, 1, L))
+            _tensor("cost_accel", cost_accel, t.int32, (n_two, M))
+        if ts_stretch is not None or cost_stretch is not None:
+            n_stretch, _, _ = _tensor("ts_stretch", ts_stretch, t.int16, (None, 2, L))
+            _tensor("cost_stretch", cost_stretch, t.int32, (n_stretch, 2 * M))
+        if n_stretch > n_one or n_one + n_two > n:
+            raise ValueError("n_stretch <= n_one and n_one + n_two <= n")
+        heard = t.zeros((n, L), dtype=t.int16, device=self.device)
+        outcome = t.zeros((n,), dtype=t.int32, device=self.device)
+        status = t.zeros((n,), dtype=t.int32, device=self.device)
+        count = t.zeros((8,), dtype=t.int32, device=self.device)
+
+        def p(x, k):
+            return _ptr(x) if k else None
+        r = self.lib.solo_playout_render(self.h, _ptr(rows), n, C.byref(prm), block_samples, action.data_ptr(), n_one, n_two, n_stretch, p(pcm_one, n_one),
+                                         p(status_one, n_one), p(pcm_two, n_two), p(status_two, n_two), p(ts_stretch, n_stretch), p(cost_stretch, n_stretch),
+                                         p(ts_accel, n_two), p(cost_accel, n_two), heard.data_ptr(), outcome.data_ptr(), status.data_ptr(),
+                                         count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_render -> %d" % r)
+        return heard, outcome, status, count
+
+    def count(self, count):
+        """a count tensor of plan() (4 words), render() (8) or tick() (12: dict(plan=..., render=...)) as a dict (synchronises)"""
+        k, = _tensor("count", count, self.torch.int32, (None,))
+        if k == 4:
+            return _counts(solo_playout_plan_count_t, count)
+        if k == 8:
+            return _counts(solo_playout_render_count_t, count)
+        if k != 12:
+            raise ValueError("count: 4, 8 or 12 int32")
+        return {"plan": _counts(solo_playout_plan_count_t, count[:4]), "render": _counts(solo_playout_render_count_t, count[4:])}
+
+    def reset(self):
+        """every row back to the initial state: not running, nothing held"""
+        r = self.lib.solo_playout_reset(self.h, self._stream())
+        if r:
+            raise RuntimeError("solo_playout_reset -> %d" % r)
+
+    def reset_rows(self, rows):
+        """the listed rows (a host sequence: inside [0, n_rows), none twice) back to the initial state"""
+        idx = _distinct("rows", rows, self.n_rows)
+        r = self.lib.solo_playout_reset_rows(self.h, (C.c_int32 * len(idx))(*idx), len(idx), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_reset_rows -> %d" % r)
+
+    def get_state(self, rows=None):
+        """the records and held packets of the listed rows (None: all rows) -> uint8 [n, state_bytes] on the device"""
+        t = self.torch
+        rows = self._rows(rows)
+        n = self._n(rows)
+        blob = t.empty((n, self.state_bytes), dtype=t.uint8, device=self.device)
+        r = self.lib.solo_playout_get_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_get_state -> %d" % r)
+        return blob
+
+    def set_state(self, blob, rows=None):
+        """blob uint8 [n, state_bytes] on the device -> the records and held packets of the listed rows (None: rows 0 .. n-1)"""
+        t = self.torch
+        n, _ = _tensor("blob", blob, t.uint8, (None, self.state_bytes))
+        if not 0 < n <= self.n_rows:
+            raise ValueError("blob: 1 .. %d records" % self.n_rows)
+        rows = self._rows(rows, n)
+        r = self.lib.solo_playout_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_playout_set_state -> %d" % r)

@@ -37,6 +37,7 @@
 #include "solo_resample.h"      // PCM rate conversion between handles and towards 8 / 48 kHz endpoints (solo_resample): likewise
 #include "solo_timescale.h"     // play-out time scaling by whole packets (solo_timescale): likewise
 #include "solo_vad.h"           // voice activity, audio level and speaker selection of decoded rows (solo_vad, solo_vad_select): likewise
+#include "solo_playout.h"       // adaptive play-out delay control (solo_playout_plan / _render / _tick): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -1121,6 +1122,172 @@ int32_t solo_vad_select(solo_vad_t* v, const int32_t* d_rows, int32_t n, const u
         if (d_rows) hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, n_rows, verdict, (i32*)NULL);
     }, st));
     return 0;
+}
+
+// ---- adaptive play-out delay control (solo_playout.h): an object of its own, a state record and a held packet per row ------------------
+static_assert(sizeof(solo_playout_params_t) == sizeof(SxPoParams) && sizeof(solo_playout_plan_count_t) == sizeof(SxPoPlanCount) &&
+              sizeof(solo_playout_render_count_t) == sizeof(SxPoRenderCount) && sizeof(solo_playout_count_t) == sizeof(SxPoCount) &&
+              SOLO_PLAYOUT_STATE_BYTES == SX_PO_STATE_WORDS * 4 && SOLO_PLAYOUT_ACCEL_FORCED == SX_PO_OUT_ACCEL_FORCED, "include/solo_mi355x.h and solo_playout.h agree");
+struct solo_playout_obj {
+    int32_t n_rows, L;
+    int32_t* d_state;                // [n_rows][SX_PO_STATE_WORDS]
+    int16_t* d_held;                 // [n_rows][L]
+    uint32_t* d_verdict;             // [2]: the verdict words of the plan and of the render
+    int32_t *d_slot, *d_sslot;       // [n_rows]: where the last plan put each row (solo_playout_compact_kernel)
+    // the tick's intermediates, one allocation (d_scratch) cut up at create
+    void* d_scratch;
+    uint32_t* d_reports;
+    int32_t *d_action, *d_one, *d_two, *d_spos, *d_st_one, *d_st_two, *d_cost_s, *d_cost_a;
+    int16_t *d_pcm_one, *d_pcm_two, *d_gath, *d_ts_s, *d_ts_a;
+    SxPoPlanCount* h_count;          // pinned: where the tick reads the plan count
+};
+solo_playout_t* solo_playout_create(int32_t n_rows, int32_t packet_samples) {
+    if (!sx_po_geometry_ok(n_rows, packet_samples)) return NULL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
+        return NULL;
+    }
+    solo_playout_obj* po = new (std::nothrow) solo_playout_obj();
+    if (!po) return NULL;
+    memset(po, 0, sizeof(*po));
+    po->n_rows = n_rows; po->L = packet_samples;
+    const size_t n = (size_t)n_rows, L = (size_t)packet_samples;
+    size_t off = 0;
+    auto cut = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t o_rep = cut(n * 64), o_act = cut(n * 4), o_one = cut(n * 4), o_two = cut(n * 4), o_spos = cut(n * 4), o_st1 = cut(n * 4), o_st2 = cut(n * 4),
+                 o_cs = cut(n * 2 * SX_TS_MAX_BLOCKS * 2), o_ca = cut(n * SX_TS_MAX_BLOCKS * 2), o_p1 = cut(n * L * 2), o_p2 = cut(n * L * 4), o_g = cut(n * L * 2),
+                 o_ts = cut(n * L * 4), o_ta = cut(n * L * 2);
+    if (hipMalloc((void**)&po->d_state, n * SX_PO_STATE_WORDS * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&po->d_held, n * L * sizeof(int16_t)) != hipSuccess ||
+        hipMalloc((void**)&po->d_verdict, 2 * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&po->d_slot, n * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&po->d_sslot, n * sizeof(int32_t)) != hipSuccess || hipMalloc(&po->d_scratch, off) != hipSuccess ||
+        hipHostMalloc((void**)&po->h_count, sizeof(SxPoPlanCount)) != hipSuccess || hipMemset(po->d_verdict, 0, 2 * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(po->d_slot, 0xFF, n * sizeof(int32_t)) != hipSuccess || hipMemset(po->d_sslot, 0xFF, n * sizeof(int32_t)) != hipSuccess ||
+        solo_playout_reset(po, NULL) != 0 || hipStreamSynchronize(NULL) != hipSuccess) {
+        solo_playout_destroy(po);
+        return NULL;
+    }
+    char* base = (char*)po->d_scratch;
+    po->d_reports = (uint32_t*)(base + o_rep); po->d_action = (int32_t*)(base + o_act); po->d_one = (int32_t*)(base + o_one); po->d_two = (int32_t*)(base + o_two);
+    po->d_spos = (int32_t*)(base + o_spos); po->d_st_one = (int32_t*)(base + o_st1); po->d_st_two = (int32_t*)(base + o_st2);
+    po->d_cost_s = (int32_t*)(base + o_cs); po->d_cost_a = (int32_t*)(base + o_ca); po->d_pcm_one = (int16_t*)(base + o_p1); po->d_pcm_two = (int16_t*)(base + o_p2);
+    po->d_gath = (int16_t*)(base + o_g); po->d_ts_s = (int16_t*)(base + o_ts); po->d_ts_a = (int16_t*)(base + o_ta);
+    return po;
+}
+void solo_playout_destroy(solo_playout_t* po) {
+    if (!po) return;
+    dev_free(po->d_state);
+    dev_free(po->d_held);
+    dev_free(po->d_verdict);
+    dev_free(po->d_slot);
+    dev_free(po->d_sslot);
+    dev_free(po->d_scratch);
+    if (po->h_count) (void)hipHostFree(po->h_count);
+    delete po;
+}
+int32_t solo_playout_reset(solo_playout_t* po, void* hip_stream) {
+    if (!po) return -1;
+    SOLO_CHECK(hipMemsetAsync(po->d_state, 0, (size_t)po->n_rows * SX_PO_STATE_WORDS * sizeof(int32_t), (hipStream_t)hip_stream));
+    SOLO_CHECK(hipMemsetAsync(po->d_held, 0, (size_t)po->n_rows * (size_t)po->L * sizeof(int16_t), (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_playout_reset_rows(solo_playout_t* po, const int32_t* h_rows, int32_t n, void* hip_stream) {
+    if (!po || !sx_po_list_ok(h_rows, n, po->n_rows)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<SxStreamCtl> recs((size_t)n);
+    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
+    int32_t* state = po->d_state;
+    int16_t* held = po->d_held;
+    const int L = po->L;
+    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
+        hipLaunchKernelGGL(solo_playout_reset_rows_kernel, dim3((unsigned)k), dim3(64), 0, st, state, held, L, l);
+    }));
+    return 0;
+}
+static int32_t playout_copy_state(solo_playout_obj* po, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
+    if (!po || !d_blob || n <= 0 || n > po->n_rows || ((uintptr_t)d_blob & 3)) return -1;
+    const size_t words = (size_t)n * sx_po_blob_row_words(po->L);
+    hipLaunchKernelGGL(solo_playout_copy_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, po->d_state, po->d_held, po->n_rows, po->L, d_rows, n,
+                       (i32*)d_blob, put);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+int32_t solo_playout_get_state(solo_playout_t* po, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
+    return playout_copy_state(po, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+}
+int32_t solo_playout_set_state(solo_playout_t* po, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
+    return playout_copy_state(po, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+}
+static hipError_t playout_list_check(solo_playout_obj* po, const int32_t* d_rows, int32_t n, uint32_t* verdict, hipStream_t st) {
+    if (!d_rows) return hipSuccess;
+    hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, po->n_rows, verdict, (i32*)NULL);
+    return hipGetLastError();
+}
+int32_t solo_playout_plan(solo_playout_t* po, const solo_recv_report_t* d_reports, const int32_t* d_rows, int32_t n, int32_t depth,
+                          const solo_playout_params_t* params, int32_t* d_action, int32_t* d_one, int32_t* d_two, int32_t* d_stretch_pos,
+                          solo_playout_plan_count_t* d_count, void* hip_stream) {
+    if (!po || !sx_po_plan_call_ok(po->n_rows, d_reports, d_rows, n, depth, (const SxPoParams*)params, d_action, d_one, d_two, d_stretch_pos, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(playout_list_check(po, d_rows, n, po->d_verdict, st));
+    SxPoPlanArgs a;
+    a.reports = (const uint32_t*)d_reports; a.state = po->d_state; a.map = d_rows; a.action = d_action; a.p = *(const SxPoParams*)params; a.n = n; a.depth = depth;
+    SOLO_CHECK(solo_playout_plan_launch(a, d_one, d_two, d_stretch_pos, po->d_slot, po->d_sslot, (SxPoPlanCount*)d_count, po->d_verdict, st));
+    return 0;
+}
+int32_t solo_playout_gather(solo_playout_t* po, const int16_t* d_pcm_one, int32_t n_one, const int32_t* d_stretch_pos, int32_t n_stretch, int16_t* d_out,
+                            void* hip_stream) {
+    if (!po || !sx_po_gather_call_ok(po->n_rows, d_pcm_one, n_one, d_stretch_pos, n_stretch, d_out)) return -1;
+    SOLO_CHECK(solo_playout_gather_launch(d_pcm_one, d_stretch_pos, n_one, n_stretch, po->L, d_out, (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_playout_render(solo_playout_t* po, const int32_t* d_rows, int32_t n, const solo_playout_params_t* params, int32_t block_samples,
+                            const int32_t* d_action, int32_t n_one, int32_t n_two, int32_t n_stretch, const int16_t* d_pcm_one, const int32_t* d_status_one,
+                            const int16_t* d_pcm_two, const int32_t* d_status_two, const int16_t* d_ts_stretch, const int32_t* d_cost_stretch,
+                            const int16_t* d_ts_accel, const int32_t* d_cost_accel, int16_t* d_heard, int32_t* d_outcome, int32_t* d_status,
+                            solo_playout_render_count_t* d_count, void* hip_stream) {
+    if (!po || !sx_po_render_call_ok(po->n_rows, po->L, d_rows, n, (const SxPoParams*)params, block_samples, d_action, n_one, n_two, n_stretch, d_pcm_one,
+                                     d_status_one, d_pcm_two, d_status_two, d_ts_stretch, d_cost_stretch, d_ts_accel, d_cost_accel, d_heard, d_outcome, d_status, d_count))
+        return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(playout_list_check(po, d_rows, n, po->d_verdict + 1, st));
+    SxPoRenderArgs a;
+    a.state = po->d_state; a.held = po->d_held; a.map = d_rows; a.action = d_action; a.slot = po->d_slot; a.sslot = po->d_sslot;
+    a.pcm_one = d_pcm_one; a.st_one = d_status_one; a.pcm_two = d_pcm_two; a.st_two = d_status_two; a.ts_s = d_ts_stretch; a.cost_s = d_cost_stretch;
+    a.ts_a = d_ts_accel; a.cost_a = d_cost_accel; a.heard = d_heard; a.outcome = d_outcome; a.status = d_status;
+    a.n = n; a.n_one = n_one; a.n_two = n_two; a.n_stretch = n_stretch; a.L = po->L; a.M = po->L / block_samples;
+    a.cooldown = params->cooldown; a.cost_gate = params->cost_gate;
+    SOLO_CHECK(solo_playout_render_launch(a, (SxPoRenderCount*)d_count, po->d_verdict + 1, st));
+    return 0;
+}
+int32_t solo_playout_tick(solo_playout_t* po, solo_batch_t* b, const int32_t* d_streams, int32_t n, const solo_playout_params_t* params, int16_t* d_heard,
+                          int32_t* d_outcome, int32_t* d_status, solo_playout_count_t* d_count, void* hip_stream) {
+    if (!po || !b) return -1;
+    int fs = 0;
+    const int L = handle_packet_samples(b, &fs), H = fs / 200;
+    if (!sx_po_tick_call_ok(po->n_rows, po->L, b->d_recv_ring != NULL, b->recv_track != 0, b->n_streams, b->recv_depth, L, fs, d_streams, n, (const SxPoParams*)params,
+                            d_heard, d_outcome, d_status, d_count))
+        return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    int32_t r = solo_recv_report(b, d_streams, n, NULL, 0, 0, SOLO_RECV_REPORT_CLEAR_MARGIN, (solo_recv_report_t*)po->d_reports, NULL, NULL, NULL, hip_stream);
+    if (r) return r;
+    if ((r = solo_playout_plan(po, (const solo_recv_report_t*)po->d_reports, d_streams, n, b->recv_depth, params, po->d_action, po->d_one, po->d_two, po->d_spos,
+                               &d_count->plan, hip_stream)) != 0)
+        return r;
+    // the tick's one synchronisation: how many rows each of the calls below gets
+    SOLO_CHECK(hipMemcpyAsync(po->h_count, &d_count->plan, sizeof(SxPoPlanCount), hipMemcpyDeviceToHost, st));
+    SOLO_CHECK(hipStreamSynchronize(st));
+    const SxPoPlanCount c = *po->h_count;
+    if (c.n_one < 0) return 0;                               // (the list was refused on the device: d_count->plan.n_one = -1 says so, nothing else is written)
+    if (c.n_one > n || c.n_two < 0 || c.n_two > n || c.n_stretch < 0 || c.n_stretch > c.n_one) return -1;
+    if (c.n_one && (r = solo_recv_decode_streams(b, po->d_one, c.n_one, 1, po->d_pcm_one, po->d_st_one, hip_stream)) != 0) return r;
+    if (c.n_two && (r = solo_recv_decode_streams(b, po->d_two, c.n_two, 2, po->d_pcm_two, po->d_st_two, hip_stream)) != 0) return r;
+    if (c.n_stretch) {
+        if ((r = solo_playout_gather(po, po->d_pcm_one, c.n_one, po->d_spos, c.n_stretch, po->d_gath, hip_stream)) != 0) return r;
+        if ((r = solo_timescale(b, po->d_gath, c.n_stretch, 1, 2, po->d_ts_s, NULL, po->d_cost_s, NULL, hip_stream)) != 0) return r;
+    }
+    if (c.n_two && (r = solo_timescale(b, po->d_pcm_two, c.n_two, 2, 1, po->d_ts_a, NULL, po->d_cost_a, NULL, hip_stream)) != 0) return r;
+    return solo_playout_render(po, d_streams, n, params, H, po->d_action, c.n_one, c.n_two, c.n_stretch, po->d_pcm_one, po->d_st_one, po->d_pcm_two, po->d_st_two,
+                               po->d_ts_s, po->d_cost_s, po->d_ts_a, po->d_cost_a, d_heard, d_outcome, d_status, &d_count->render, hip_stream);
 }
 
 // ---- stream migration (solo_migrate.h): encoder state, decoder state and receive queue of listed streams <-> a device blob ---------
