@@ -662,6 +662,61 @@ int32_t solo_playout_render(solo_playout_t *po, const int32_t *d_rows, int32_t n
                             int32_t *d_outcome, int32_t *d_status, solo_playout_render_count_t *d_count, void *hip_stream);
 int32_t solo_playout_tick(solo_playout_t *po, solo_batch_t *b, const int32_t *d_streams, int32_t n, const solo_playout_params_t *params,
                           int16_t *d_heard, int32_t *d_outcome, int32_t *d_status, solo_playout_count_t *d_count, void *hip_stream);
+/* Level control and peak limiter for decoded rows: the stage between solo_vad and the selection / the mix.  It brings every row's speech
+ * to target_level -dBov with a slewed gain and keeps every output sample within +-ceiling, so that a caller 20 dB below another is no
+ * longer 20 dB below in every mix and no longer loses solo_vad_select's order to the loud one.  A solo_agc_t is an object of its own,
+ * like a solo_vad_t, with the same conventions: compact rows int16 [n][P][L], 16-byte aligned; d_rows a DEVICE list, strictly
+ * increasing inside [0, n_rows), checked on the device ahead of the work, d_count then required, a refused list writes
+ * d_count->rows = -1 and nothing else and moves no state, unlisted rows keep their record bit for bit; reset_rows takes a HOST list of
+ * 1 .. n_rows indices inside [0, n_rows), none twice; get_state / set_state are plain copies of uint8 [n][64] (4-byte aligned), an
+ * index outside the object moves nothing.  AGC state is not part of a migration blob: it moves with get_state / set_state.
+ *   state      SOLO_AGC_STATE_BYTES = 64 bytes per row, 16 int32 words: 0 run, 1 spl_q8 (the smoothed speech level in -dBov, Q8),
+ *              2 gain_q8 (the gain in dB, Q8, signed), 3 g_q16 (the linear gain at the last sample of the previous packet), 4 env_q15 (the
+ *              limiter envelope at the end of the previous packet), 5 .. 15 zero (the stage never writes them).  Create and the resets
+ *              leave {0, 0, 0, 65536, 32768, 0 ...}.  Values are clamped when a call reads them: gain_q8 to +-7680, g_q16 to
+ *              [0, A[60]], env_q15 to [0, 32768], so no blob can index outside a table.
+ *   L = packet_samples   a multiple of 32 with 256 <= L <= 1920
+ *   d_level_in uint8 [n][P], what solo_vad wrote; NULL: the call computes the same RFC 6464 level from the input samples
+ *   d_sa_q8    uint8 [n][P][frames], what solo_vad wrote; NULL: activity 255 everywhere, frames is ignored
+ *   d_pcm_out  int16 [n][P][L]; d_pcm_out == d_pcm_in (in place) is allowed, any other overlap of the two ranges is refused
+ *   d_level_out (uint8 [n][P]), d_gain_q8 (int16 [n][P]) and d_count may each be NULL, except d_count with a list
+ * The rule, per row, packets in order.  All shifts are arithmetic; 64-bit products where noted.  Tables (tools/gen_agc_tables.py, exact
+ * decimal arithmetic, rounded to nearest): A[i] = round(65536 * 10^((i - 30) / 20)), i = 0 .. 60; B[r] = round(65536 * 10^(r / 5120)),
+ * r = 0 .. 255; lin(d), d in [-7680, 7680], d + 7680 = 256 i + r: (A[i] * B[r] + 32768) >> 16 in 64 bits.
+ *   1  lv = min(level_in, 127); a = max over f of sa[f]; speech = a >= sa_on_q8 and lv <= gate_level
+ *   2  only in speech packets: run == 0: spl = lv << 8, run = 1; otherwise spl += (((lv << 8) - spl) * alpha_q8) >> 8 (in 64 bits);
+ *      want = clamp(spl - (target_level << 8), -(max_cut_db << 8), max_boost_db << 8); gain += clamp(want - gain, -slew_down_q8, slew_up_q8)
+ *   3  g0 = g_q16, g1 = lin(gain), g_q16 = g1; g[s] = g0 + (((g1 - g0) * min(s + 1, 256)) >> 8);
+ *      y0[s] = (x[s] * g[s] + 32768) >> 16 in 64 bits
+ *   4  blocks of 32 samples, B = L / 32: pk_b = max |y0| over block b; a_b = 32768 if pk_b <= ceiling, else floor(ceiling * 32768 / pk_b);
+ *      a'_b = min(a_b, a_{b+1}) for b < B - 1, a'_{B-1} = a_{B-1} (one block of look-ahead inside the packet);
+ *      e_{-1} = min(env_q15, a_0); e_b = min(a'_b, e_{b-1} + release_q15); env_q15 = e_{B-1}
+ *   5  s = 32 b + t: env[s] = e_{b-1} + (((e_b - e_{b-1}) * (t + 1)) >> 5); y[s] = (y0[s] * env[s] + 16384) >> 15 in 64 bits.
+ *      Both ends of the interpolation are <= a_b, so |y[s]| <= ceiling for every sample: there is no saturation step.
+ *   6  d_level_out = the RFC 6464 level of y from its exact energy (as solo_vad's); d_gain_q8 = gain after the packet;
+ *      d_count = {rows processed, (row, packet) pairs with speech, pairs with some e_b < 32768, 0}
+ * The limiter does not see the next packet: one that opens louder than the last one closed steps the envelope down to a_0 at the
+ * boundary.  P packets in one call equal P calls of one packet.
+ * Returns -1 with nothing enqueued: NULL g, d_pcm_in, d_pcm_out or params; n outside (0, n_rows]; d_rows without d_count;
+ * n_packets <= 0; L not as above; d_sa_q8 with frames <= 0; n x P x L or n x P x frames >= 2^31; PCM not 16-byte aligned; the PCM
+ * ranges overlapping in part; target_level or gate_level outside 0 .. 127; max_boost_db or max_cut_db outside 0 .. 30; sa_on_q8 outside
+ * 0 .. 255; alpha_q8 outside 1 .. 256; slew_up_q8 or slew_down_q8 outside 0 .. 7680; ceiling outside 1 .. 32767; release_q15 outside
+ * 0 .. 32768.  No allocation, no host synchronisation, one kernel (two with a list) on hip_stream: it can sit in a captured tick.
+ * Calls on one object must be ordered (same stream, or events).  INTEGRATION.md section 2 has the tick. */
+#define SOLO_AGC_STATE_BYTES 64
+typedef struct solo_agc_obj solo_agc_t;
+typedef struct { int32_t target_level, max_boost_db, max_cut_db, sa_on_q8, gate_level, alpha_q8,
+                 slew_up_q8, slew_down_q8, ceiling, release_q15; } solo_agc_params_t;      /* 40 bytes */
+typedef struct { int32_t rows, speech, limited, zero; } solo_agc_count_t;                  /* 16 bytes; rows = -1: list refused */
+solo_agc_t *solo_agc_create(int32_t n_rows);
+void    solo_agc_destroy(solo_agc_t *g);
+int32_t solo_agc_reset(solo_agc_t *g, void *hip_stream);
+int32_t solo_agc_reset_rows(solo_agc_t *g, const int32_t *h_rows, int32_t n, void *hip_stream);
+int32_t solo_agc_get_state(solo_agc_t *g, const int32_t *d_rows, int32_t n, uint8_t *d_blob, void *hip_stream);
+int32_t solo_agc_set_state(solo_agc_t *g, const int32_t *d_rows, int32_t n, const uint8_t *d_blob, void *hip_stream);
+int32_t solo_agc(solo_agc_t *g, const int32_t *d_rows, int32_t n, const int16_t *d_pcm_in, int32_t n_packets, int32_t packet_samples,
+                 const uint8_t *d_level_in, const uint8_t *d_sa_q8, int32_t frames, const solo_agc_params_t *params,
+                 int16_t *d_pcm_out, uint8_t *d_level_out, int16_t *d_gain_q8, solo_agc_count_t *d_count, void *hip_stream);
 /* Stream migration: the state of a running call leaves a handle as a DEVICE blob and enters any slot of any handle of the same
  * geometry -- on this GPU, or on another one after the caller has moved the bytes (the blob is plain device memory: a torch.distributed
  * send, a hipMemcpyPeer).  The call goes on where it stood: no first-frame logic, no cold-start concealment, VAD / DTX / CNG / PLC and

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "solo_vad", "solo_vad_select",
     "solo_playout_create", "solo_playout_destroy", "solo_playout_reset", "solo_playout_reset_rows", "solo_playout_get_state",
     "solo_playout_set_state", "solo_playout_plan", "solo_playout_gather", "solo_playout_render", "solo_playout_tick",
+    "solo_agc_create", "solo_agc_destroy", "solo_agc_reset", "solo_agc_reset_rows", "solo_agc_get_state", "solo_agc_set_state", "solo_agc",
 ]
 
 
@@ -93,6 +94,17 @@ class solo_vad_count_t(C.Structure):
 class solo_vad_select_params_t(C.Structure):
     """the policy of a solo_vad_select call (include/solo_mi355x.h); 20 bytes"""
     _fields_ = [(n, C.c_int32) for n in ("max_speakers", "on_q8", "off_q8", "hang_packets", "stick")]
+
+
+class solo_agc_params_t(C.Structure):
+    """the policy of a solo_agc call (include/solo_mi355x.h); 40 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("target_level", "max_boost_db", "max_cut_db", "sa_on_q8", "gate_level", "alpha_q8", "slew_up_q8", "slew_down_q8",
+                                         "ceiling", "release_q15")]
+
+
+class solo_agc_count_t(C.Structure):
+    """what a solo_agc call did (include/solo_mi355x.h); 16 bytes; rows = -1: list refused on the device"""
+    _fields_ = [(n, C.c_int32) for n in ("rows", "speech", "limited", "zero")]
 
 
 class solo_playout_params_t(C.Structure):
@@ -287,6 +299,21 @@ def load_library():
     lib.solo_playout_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, _pp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 13
     lib.solo_playout_tick.restype = C.c_int32
     lib.solo_playout_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _pp] + [C.c_void_p] * 5
+    lib.solo_agc_create.restype = C.c_void_p
+    lib.solo_agc_create.argtypes = [C.c_int32]
+    lib.solo_agc_destroy.restype = None
+    lib.solo_agc_destroy.argtypes = [C.c_void_p]
+    lib.solo_agc_reset.restype = C.c_int32
+    lib.solo_agc_reset.argtypes = [C.c_void_p, C.c_void_p]
+    lib.solo_agc_reset_rows.restype = C.c_int32
+    lib.solo_agc_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_agc_get_state.restype = C.c_int32
+    lib.solo_agc_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_agc_set_state.restype = C.c_int32
+    lib.solo_agc_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_agc.restype = C.c_int32
+    lib.solo_agc.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                             C.POINTER(solo_agc_params_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1558,3 +1585,123 @@ class Playout:
         r = self.lib.solo_playout_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
         if r:
             raise RuntimeError("solo_playout_set_state -> %d" % r)
+
+
+AGC_STATE_BYTES = 64
+
+
+class Agc:
+    """n_rows independent level controls with a peak limiter on the current HIP device (solo_agc, include/solo_mi355x.h): every row's
+    speech is brought to `target` -dBov with a slewed gain, and no output sample exceeds `ceiling`.  State carries from call to call."""
+
+    COUNT = ("rows", "speech", "limited", "zero")
+
+    def __init__(self, n_rows):
+        import torch
+        self.n_rows = int(n_rows)
+        if self.n_rows <= 0:
+            raise ValueError("n_rows must be positive")
+        self.h = None
+        if not torch.cuda.is_available():
+            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
+        self.torch = torch
+        self.lib = load_library()
+        self.h = self.lib.solo_agc_create(self.n_rows)
+        if not self.h:
+            raise RuntimeError("solo_agc_create failed (no GPU, or out of memory)")
+        self.device = torch.device("cuda", torch.cuda.current_device())
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.solo_agc_destroy(self.h)
+            self.h = None
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def _rows(self, rows, n=None):
+        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
+        t = self.torch
+        if rows is None:
+            return None
+        if not getattr(rows, "is_cuda", False):
+            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
+        k, = _tensor("rows", rows, t.int32, (n,))
+        if not 0 < k <= self.n_rows:
+            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
+        return rows
+
+    def run(self, pcm, level=None, sa=None, rows=None, out=None, target=23, boost=24, cut=12, sa_on=128, gate=50, alpha=32, up=128, down=256,
+            ceiling=29204, release=256):
+        """pcm int16 [n,P,samples] (samples a multiple of 32, 256 .. 1920), level uint8 [n,P] and sa uint8 [n,P,F] as Vad.run() wrote them
+        (level=None: the level of the input samples, sa=None: activity 255) -> (pcm_out int16 [n,P,samples], level_out uint8 [n,P] in
+        -dBov, gain_q8 int16 [n,P] in dB Q8, count int32 [4] on the device, read with count()).  out=: where pcm_out goes; out=pcm works in
+        place.  target / gate: levels in -dBov; boost / cut: the gain's range in dB; sa_on: the activity a speech packet needs; alpha: the
+        level's smoothing, Q8; up / down: the gain's slew per speech packet in dB Q8; ceiling: the largest output magnitude; release: what
+        the limiter's envelope recovers per 32 samples, Q15.  rows as in Vad.run(): a bad list is refused on the device, rows == -1 in the
+        count, nothing else written.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        n, P, L = _tensor("pcm", pcm, t.int16, (None, None, None))
+        if not (0 < n <= self.n_rows and P > 0):
+            raise ValueError("pcm: 1 .. %d rows and at least one packet" % self.n_rows)
+        if L % 32 or not 256 <= L <= 1920:
+            raise ValueError("samples: a multiple of 32 inside 256 .. 1920")
+        _tensor("level", level, t.uint8, (n, P), optional=True)
+        F = _tensor("sa", sa, t.uint8, (n, P, None), optional=True)
+        F = 0 if F is None else F[2]
+        if sa is not None and F <= 0:
+            raise ValueError("sa: at least one frame")
+        _tensor("out", out, t.int16, (n, P, L), optional=True)
+        rows = self._rows(rows, n)
+        prm = solo_agc_params_t(int(target), int(boost), int(cut), int(sa_on), int(gate), int(alpha), int(up), int(down), int(ceiling), int(release))
+        if not (0 <= prm.target_level <= 127 and 0 <= prm.max_boost_db <= 30 and 0 <= prm.max_cut_db <= 30 and 0 <= prm.sa_on_q8 <= 255 and
+                0 <= prm.gate_level <= 127 and 1 <= prm.alpha_q8 <= 256 and 0 <= prm.slew_up_q8 <= 7680 and 0 <= prm.slew_down_q8 <= 7680 and
+                1 <= prm.ceiling <= 32767 and 0 <= prm.release_q15 <= 32768):
+            raise ValueError("target, gate 0 .. 127, boost, cut 0 .. 30, sa_on 0 .. 255, alpha 1 .. 256, up, down 0 .. 7680, ceiling 1 .. 32767, release 0 .. 32768")
+        if out is None:
+            out = t.empty_like(pcm)
+        level_out = t.empty((n, P), dtype=t.uint8, device=pcm.device)
+        gain = t.empty((n, P), dtype=t.int16, device=pcm.device)
+        count = (t.empty if rows is None else t.zeros)((4,), dtype=t.int32, device=pcm.device)
+        r = self.lib.solo_agc(self.h, _ptr(rows), n, pcm.data_ptr(), P, L, _ptr(level), _ptr(sa), F, C.byref(prm), out.data_ptr(), level_out.data_ptr(),
+                              gain.data_ptr(), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_agc -> %d" % r)
+        return out, level_out, gain, count
+
+    def count(self, count):
+        """a count tensor of run() as a dict (synchronises); rows == -1: the list was refused on the device"""
+        return _counts(solo_agc_count_t, count)
+
+    def reset(self, rows=None):
+        """every row, or the listed rows (a host sequence: inside [0, n_rows), none twice), back to the initial state"""
+        if rows is None:
+            r = self.lib.solo_agc_reset(self.h, self._stream())
+        else:
+            idx = _distinct("rows", rows, self.n_rows)
+            arr = (C.c_int32 * len(idx))(*idx)
+            r = self.lib.solo_agc_reset_rows(self.h, arr, len(idx), self._stream())
+        if r:
+            raise RuntimeError("solo_agc_reset -> %d" % r)
+
+    def get_state(self, rows=None):
+        """the 64-byte records of the listed rows (None: all rows) -> uint8 [n,64] on the device"""
+        t = self.torch
+        rows = self._rows(rows)
+        n = self.n_rows if rows is None else int(rows.shape[0])
+        blob = t.empty((n, AGC_STATE_BYTES), dtype=t.uint8, device=self.device)
+        r = self.lib.solo_agc_get_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_agc_get_state -> %d" % r)
+        return blob
+
+    def set_state(self, blob, rows=None):
+        """blob uint8 [n,64] on the device -> the records of the listed rows (None: rows 0 .. n-1)"""
+        t = self.torch
+        n, _ = _tensor("blob", blob, t.uint8, (None, AGC_STATE_BYTES))
+        if not 0 < n <= self.n_rows:
+            raise ValueError("blob: 1 .. %d records" % self.n_rows)
+        rows = self._rows(rows, n)
+        r = self.lib.solo_agc_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_agc_set_state -> %d" % r)

@@ -38,6 +38,7 @@
 #include "solo_timescale.h"     // play-out time scaling by whole packets (solo_timescale): likewise
 #include "solo_vad.h"           // voice activity, audio level and speaker selection of decoded rows (solo_vad, solo_vad_select): likewise
 #include "solo_playout.h"       // adaptive play-out delay control (solo_playout_plan / _render / _tick): likewise
+#include "solo_agc.h"           // level control and peak limiter of decoded rows (solo_agc): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -1084,7 +1085,7 @@ int32_t solo_vad_reset_rows(solo_vad_t* v, const int32_t* h_rows, int32_t n, voi
 static int32_t vad_copy_state(solo_vad_obj* v, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
     if (!v || !d_blob || n <= 0 || n > v->n_rows || ((uintptr_t)d_blob & 3)) return -1;
     const size_t words = (size_t)n * SX_VAD_STATE_WORDS;
-    hipLaunchKernelGGL(solo_vad_copy_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, v->d_state, v->n_rows, d_rows, n, (i32*)d_blob, put);
+    hipLaunchKernelGGL(solo_vad_copy_kernel<>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, v->d_state, v->n_rows, d_rows, n, (i32*)d_blob, put);
     SOLO_CHECK(hipGetLastError());
     return 0;
 }
@@ -1121,6 +1122,92 @@ int32_t solo_vad_select(solo_vad_t* v, const int32_t* d_rows, int32_t n, const u
     SOLO_CHECK(solo_vad_select_launch(a, d_room, n, n_rooms, n_rows, v->d_scratch, (SxVadCount*)d_count, v->d_verdict + 1, [&](u32* verdict) {
         if (d_rows) hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, n_rows, verdict, (i32*)NULL);
     }, st));
+    return 0;
+}
+
+// ---- level control and peak limiter (solo_agc.h): an object of its own, with a state record per row -----------------------------------
+static_assert(sizeof(solo_agc_count_t) == sizeof(SxAgcCount) && sizeof(solo_agc_params_t) == sizeof(SxAgcParams) &&
+              SOLO_AGC_STATE_BYTES == SX_AGC_STATE_WORDS * 4, "include/solo_mi355x.h and solo_agc.h agree");
+struct solo_agc_obj {
+    int32_t n_rows;
+    int32_t* d_state;                // [n_rows][SX_AGC_STATE_WORDS]
+    uint32_t* d_verdict;             // the verdict word of solo_agc
+    unsigned long long* d_acc;       // the counters of a call's count (solo_agc_acc_bytes; zero between calls)
+};
+solo_agc_t* solo_agc_create(int32_t n_rows) {
+    if (n_rows <= 0 || (int64_t)n_rows * SX_AGC_STATE_WORDS >= ((int64_t)1 << 31)) return NULL;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
+        return NULL;
+    }
+    solo_agc_obj* g = new (std::nothrow) solo_agc_obj();
+    if (!g) return NULL;
+    memset(g, 0, sizeof(*g));
+    g->n_rows = n_rows;
+    if (hipMalloc((void**)&g->d_state, (size_t)n_rows * SX_AGC_STATE_WORDS * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&g->d_verdict, sizeof(uint32_t)) != hipSuccess || hipMemset(g->d_verdict, 0, sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void**)&g->d_acc, solo_agc_acc_bytes(n_rows)) != hipSuccess || hipMemset(g->d_acc, 0, solo_agc_acc_bytes(n_rows)) != hipSuccess ||
+        solo_agc_reset(g, NULL) != 0 || hipStreamSynchronize(NULL) != hipSuccess) {
+        solo_agc_destroy(g);
+        return NULL;
+    }
+    return g;
+}
+void solo_agc_destroy(solo_agc_t* g) {
+    if (!g) return;
+    dev_free(g->d_state);
+    dev_free(g->d_verdict);
+    dev_free(g->d_acc);
+    delete g;
+}
+int32_t solo_agc_reset(solo_agc_t* g, void* hip_stream) {
+    if (!g) return -1;
+    const size_t words = (size_t)g->n_rows * SX_AGC_STATE_WORDS;
+    hipLaunchKernelGGL(solo_agc_reset_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, g->d_state, g->n_rows);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+int32_t solo_agc_reset_rows(solo_agc_t* g, const int32_t* h_rows, int32_t n, void* hip_stream) {
+    if (!g || !sx_vad_list_ok(h_rows, n, g->n_rows)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    std::vector<SxStreamCtl> recs((size_t)n);
+    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
+    int32_t* state = g->d_state;
+    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
+        hipLaunchKernelGGL(solo_agc_reset_rows_kernel, dim3((unsigned)k), dim3(64), 0, st, state, l);
+    }));
+    return 0;
+}
+static int32_t agc_copy_state(solo_agc_obj* g, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
+    if (!g || !d_blob || n <= 0 || n > g->n_rows || ((uintptr_t)d_blob & 3)) return -1;
+    const size_t words = (size_t)n * SX_AGC_STATE_WORDS;
+    hipLaunchKernelGGL(solo_vad_copy_kernel<SX_AGC_STATE_WORDS>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, g->d_state, g->n_rows, d_rows, n,
+                       (i32*)d_blob, put);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+int32_t solo_agc_get_state(solo_agc_t* g, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
+    return agc_copy_state(g, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+}
+int32_t solo_agc_set_state(solo_agc_t* g, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
+    return agc_copy_state(g, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+}
+int32_t solo_agc(solo_agc_t* g, const int32_t* d_rows, int32_t n, const int16_t* d_pcm_in, int32_t n_packets, int32_t packet_samples,
+                 const uint8_t* d_level_in, const uint8_t* d_sa_q8, int32_t frames, const solo_agc_params_t* params, int16_t* d_pcm_out,
+                 uint8_t* d_level_out, int16_t* d_gain_q8, solo_agc_count_t* d_count, void* hip_stream) {
+    if (!g || !sx_agc_call_ok(g->n_rows, d_rows, n, d_pcm_in, n_packets, packet_samples, d_sa_q8, frames, (const SxAgcParams*)params, d_pcm_out, d_count))
+        return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SxAgcArgs a;
+    a.in = d_pcm_in; a.out = d_pcm_out; a.state = g->d_state; a.map = d_rows; a.level_in = d_level_in; a.sa = d_sa_q8;
+    a.level_out = d_level_out; a.gain_out = d_gain_q8;
+    a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples; a.frames = d_sa_q8 ? frames : 0; a.prm = *(const SxAgcParams*)params;
+    if (d_rows) {
+        hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, g->n_rows, g->d_verdict, (i32*)NULL);
+        SOLO_CHECK(hipGetLastError());
+    }
+    SOLO_CHECK(solo_agc_launch(a, (SxAgcCount*)d_count, g->d_acc, g->d_verdict, st));
     return 0;
 }
 

@@ -374,14 +374,15 @@ __global__ void __launch_bounds__(256) solo_vad_reset_kernel(i32* state, int n_r
     if (i < (size_t)n_rows * SX_VAD_STATE_WORDS) state[i] = sx_vad_init_word((int)(i % SX_VAD_STATE_WORDS));
 }
 // plain copies of the listed rows' records (rows = NULL: rows 0 .. n - 1) to (put = 0) or from a buffer [n][128]; an index outside
-// [0, n_rows) moves nothing
+// [0, n_rows) moves nothing.  (WORDS: the record of this stage, or the 16 words of solo_agc.h)
+template <int WORDS = SX_VAD_STATE_WORDS>
 __global__ void __launch_bounds__(256) solo_vad_copy_kernel(i32* state, int n_rows, const i32* rows, int n, i32* blob, int put) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * SX_VAD_STATE_WORDS) return;
-    const int r = (int)(i / SX_VAD_STATE_WORDS), w = (int)(i % SX_VAD_STATE_WORDS);
+    if (i >= (size_t)n * WORDS) return;
+    const int r = (int)(i / WORDS), w = (int)(i % WORDS);
     const int row = rows ? rows[r] : r;
     if (row < 0 || row >= n_rows) return;
-    i32* s = state + (size_t)row * SX_VAD_STATE_WORDS + w;
+    i32* s = state + (size_t)row * WORDS + w;
     if (put) *s = blob[i];
     else blob[i] = *s;
 }
