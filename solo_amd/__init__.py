@@ -250,46 +250,24 @@ def load_library():
     for f in (lib.solo_batch_export_streams, lib.solo_batch_import_streams):
         f.restype = C.c_int32
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.solo_resample_create.restype = C.c_void_p
-    lib.solo_resample_create.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.solo_resample_destroy.restype = None
-    lib.solo_resample_destroy.argtypes = [C.c_void_p]
+    # the row-state objects: their create calls differ (the table), their lifecycle calls do not
+    for prefix, create_args, has_state in (("resample", 3, False), ("vad", 2, True), ("playout", 2, True), ("agc", 1, True)):
+        sigs = {"create": (C.c_void_p, [C.c_int32] * create_args), "destroy": (None, [C.c_void_p]), "reset": (C.c_int32, [C.c_void_p, C.c_void_p]),
+                "reset_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])}
+        if has_state:
+            sigs["get_state"] = sigs["set_state"] = (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+        for name, (restype, argtypes) in sigs.items():
+            f = getattr(lib, "solo_%s_%s" % (prefix, name))
+            f.restype, f.argtypes = restype, list(argtypes)
     lib.solo_resample_out_samples.restype = C.c_int32
     lib.solo_resample_out_samples.argtypes = [C.c_void_p, C.c_int32]
-    lib.solo_resample_reset.restype = C.c_int32
-    lib.solo_resample_reset.argtypes = [C.c_void_p, C.c_void_p]
-    lib.solo_resample_reset_rows.restype = C.c_int32
-    lib.solo_resample_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.solo_resample.restype = C.c_int32
     lib.solo_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.solo_vad_create.restype = C.c_void_p
-    lib.solo_vad_create.argtypes = [C.c_int32, C.c_int32]
-    lib.solo_vad_destroy.restype = None
-    lib.solo_vad_destroy.argtypes = [C.c_void_p]
-    lib.solo_vad_reset.restype = C.c_int32
-    lib.solo_vad_reset.argtypes = [C.c_void_p, C.c_void_p]
-    lib.solo_vad_reset_rows.restype = C.c_int32
-    lib.solo_vad_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.solo_vad_get_state.restype = C.c_int32
-    lib.solo_vad_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.solo_vad_set_state.restype = C.c_int32
-    lib.solo_vad_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.solo_vad.restype = C.c_int32
     lib.solo_vad.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_vad_select.restype = C.c_int32
     lib.solo_vad_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.POINTER(solo_vad_select_params_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.solo_playout_create.restype = C.c_void_p
-    lib.solo_playout_create.argtypes = [C.c_int32, C.c_int32]
-    lib.solo_playout_destroy.restype = None
-    lib.solo_playout_destroy.argtypes = [C.c_void_p]
-    lib.solo_playout_reset.restype = C.c_int32
-    lib.solo_playout_reset.argtypes = [C.c_void_p, C.c_void_p]
-    lib.solo_playout_reset_rows.restype = C.c_int32
-    lib.solo_playout_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    for f in (lib.solo_playout_get_state, lib.solo_playout_set_state):
-        f.restype = C.c_int32
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     _pp = C.POINTER(solo_playout_params_t)
     lib.solo_playout_plan.restype = C.c_int32
     lib.solo_playout_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _pp] + [C.c_void_p] * 6
@@ -299,18 +277,6 @@ def load_library():
     lib.solo_playout_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, _pp, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 13
     lib.solo_playout_tick.restype = C.c_int32
     lib.solo_playout_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _pp] + [C.c_void_p] * 5
-    lib.solo_agc_create.restype = C.c_void_p
-    lib.solo_agc_create.argtypes = [C.c_int32]
-    lib.solo_agc_destroy.restype = None
-    lib.solo_agc_destroy.argtypes = [C.c_void_p]
-    lib.solo_agc_reset.restype = C.c_int32
-    lib.solo_agc_reset.argtypes = [C.c_void_p, C.c_void_p]
-    lib.solo_agc_reset_rows.restype = C.c_int32
-    lib.solo_agc_reset_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.solo_agc_get_state.restype = C.c_int32
-    lib.solo_agc_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.solo_agc_set_state.restype = C.c_int32
-    lib.solo_agc_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.solo_agc.restype = C.c_int32
     lib.solo_agc.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                              C.POINTER(solo_agc_params_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1121,40 +1087,101 @@ class SoloBatch:
             pass
 
 
-RESAMPLE_PAIRS = ((48000, 16000), (48000, 32000), (32000, 16000), (16000, 8000), (16000, 32000), (8000, 16000), (16000, 48000), (32000, 48000))
+class _RowObject:
+    """What Resampler, Vad, Playout and Agc share: a library object solo_<PREFIX>_* of n_rows state records on the current HIP device,
+    carried from call to call, with its create / destroy / reset / reset_rows calls."""
 
+    PREFIX = None
 
-class Resampler:
-    """n_rows independent PCM rate converters on the current HIP device (solo_resample, include/solo_mi355x.h): the reference's
-    fixed-point resampler bit for bit, its filter memory carried from call to call.  It sits between two handles of different rates,
-    or between a handle and an 8 / 48 kHz endpoint; the pairs are RESAMPLE_PAIRS."""
-
-    COUNT = ("rows", "listed")
-
-    def __init__(self, n_rows, fs_in, fs_out):
+    def _create(self, *args):
+        """the constructor's tail: solo_<PREFIX>_create(*args), after the subclass has checked them"""
         import torch
-        self.n_rows, self.fs_in, self.fs_out = int(n_rows), int(fs_in), int(fs_out)
-        if self.n_rows <= 0:
-            raise ValueError("n_rows must be positive")
-        if (self.fs_in, self.fs_out) not in RESAMPLE_PAIRS:
-            raise ValueError("fs_in -> fs_out must be one of %s" % ", ".join("%d->%d" % p for p in RESAMPLE_PAIRS))
         self.h = None
         if not torch.cuda.is_available():
             raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
         self.torch = torch
         self.lib = load_library()
-        self.h = self.lib.solo_resample_create(self.n_rows, self.fs_in, self.fs_out)
+        self.h = getattr(self.lib, "solo_%s_create" % self.PREFIX)(*args)
         if not self.h:
-            raise RuntimeError("solo_resample_create failed (no GPU, or out of memory)")
+            raise RuntimeError("solo_%s_create failed (no GPU, or out of memory)" % self.PREFIX)
         self.device = torch.device("cuda", torch.cuda.current_device())
 
     def __del__(self):
         if getattr(self, "h", None):
-            self.lib.solo_resample_destroy(self.h)
+            getattr(self.lib, "solo_%s_destroy" % self.PREFIX)(self.h)
             self.h = None
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    def _call(self, name, *args):
+        """solo_<PREFIX>_<name>(object, *args, stream); a refusal raises"""
+        r = getattr(self.lib, "solo_%s_%s" % (self.PREFIX, name))(self.h, *args, self._stream())
+        if r:
+            raise RuntimeError("solo_%s_%s -> %d" % (self.PREFIX, name, r))
+
+    def _rows(self, rows, n=None):
+        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
+        t = self.torch
+        if rows is None:
+            return None
+        if not getattr(rows, "is_cuda", False):
+            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
+        k, = _tensor("rows", rows, t.int32, (n,))
+        if not 0 < k <= self.n_rows:
+            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
+        return rows
+
+    def _n(self, rows):
+        return self.n_rows if rows is None else int(rows.shape[0])
+
+    def reset(self, rows=None):
+        """every row, or the listed rows (a host sequence: inside [0, n_rows), none twice), back to the initial state"""
+        if rows is None:
+            return self._call("reset")
+        idx = _distinct("rows", rows, self.n_rows)
+        self._call("reset_rows", (C.c_int32 * len(idx))(*idx), len(idx))
+
+
+class _RowStateObject(_RowObject):
+    """... whose records can be read and written (solo_<PREFIX>_get_state / _set_state): state_bytes a row"""
+
+    state_bytes = None
+
+    def get_state(self, rows=None):
+        """the state of the listed rows (None: all rows) -> uint8 [n, state_bytes] on the device"""
+        rows = self._rows(rows)
+        n = self._n(rows)
+        blob = self.torch.empty((n, self.state_bytes), dtype=self.torch.uint8, device=self.device)
+        self._call("get_state", _ptr(rows), n, blob.data_ptr())
+        return blob
+
+    def set_state(self, blob, rows=None):
+        """blob uint8 [n, state_bytes] on the device -> the state of the listed rows (None: rows 0 .. n-1)"""
+        n, _ = _tensor("blob", blob, self.torch.uint8, (None, self.state_bytes))
+        if not 0 < n <= self.n_rows:
+            raise ValueError("blob: 1 .. %d records" % self.n_rows)
+        self._call("set_state", _ptr(self._rows(rows, n)), n, blob.data_ptr())
+
+
+RESAMPLE_PAIRS = ((48000, 16000), (48000, 32000), (32000, 16000), (16000, 8000), (16000, 32000), (8000, 16000), (16000, 48000), (32000, 48000))
+
+
+class Resampler(_RowObject):
+    """n_rows independent PCM rate converters on the current HIP device (solo_resample, include/solo_mi355x.h): the reference's
+    fixed-point resampler bit for bit, its filter memory carried from call to call.  It sits between two handles of different rates,
+    or between a handle and an 8 / 48 kHz endpoint; the pairs are RESAMPLE_PAIRS."""
+
+    COUNT = ("rows", "listed")
+    PREFIX = "resample"
+
+    def __init__(self, n_rows, fs_in, fs_out):
+        self.n_rows, self.fs_in, self.fs_out = int(n_rows), int(fs_in), int(fs_out)
+        if self.n_rows <= 0:
+            raise ValueError("n_rows must be positive")
+        if (self.fs_in, self.fs_out) not in RESAMPLE_PAIRS:
+            raise ValueError("fs_in -> fs_out must be one of %s" % ", ".join("%d->%d" % p for p in RESAMPLE_PAIRS))
+        self._create(self.n_rows, self.fs_in, self.fs_out)
 
     def out_samples(self, in_samples):
         """samples per output packet of in_samples per input packet: in_samples * fs_out / fs_in; in_samples must be a positive multiple
@@ -1206,64 +1233,25 @@ class Resampler:
         """the count tensor of run(rows=) as a dict (synchronises): rows converted, rows listed; rows == -1: the list was refused"""
         return _counts(solo_resample_count_t, count)
 
-    def reset(self, rows=None):
-        """zero the filter memory of every row, or of the listed rows (a host sequence: inside [0, n_rows), none twice)"""
-        if rows is None:
-            r = self.lib.solo_resample_reset(self.h, self._stream())
-        else:
-            idx = _distinct("rows", rows, self.n_rows)
-            arr = (C.c_int32 * len(idx))(*idx)
-            r = self.lib.solo_resample_reset_rows(self.h, arr, len(idx), self._stream())
-        if r:
-            raise RuntimeError("solo_resample_reset -> %d" % r)
-
 
 VAD_STATE_BYTES = 128
 
 
-class Vad:
+class Vad(_RowStateObject):
     """n_rows independent voice activity detectors on the current HIP device (solo_vad, include/solo_mi355x.h): the reference's
     fixed-point VAD bit for bit on frames of 160 or 320 samples, the RFC 6464 audio level of every packet, and a stateful speaker
     selection per room (solo_vad_select).  State carries from call to call."""
 
     COUNT = ("rows", "rooms", "selected", "changes")
+    PREFIX, state_bytes = "vad", VAD_STATE_BYTES
 
     def __init__(self, n_rows, frame_samples):
-        import torch
         self.n_rows, self.frame = int(n_rows), int(frame_samples)
         if self.n_rows <= 0:
             raise ValueError("n_rows must be positive")
         if self.frame not in (160, 320):
             raise ValueError("frame_samples must be 160 or 320")
-        self.h = None
-        if not torch.cuda.is_available():
-            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
-        self.torch = torch
-        self.lib = load_library()
-        self.h = self.lib.solo_vad_create(self.n_rows, self.frame)
-        if not self.h:
-            raise RuntimeError("solo_vad_create failed (no GPU, or out of memory)")
-        self.device = torch.device("cuda", torch.cuda.current_device())
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.lib.solo_vad_destroy(self.h)
-            self.h = None
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
-
-    def _rows(self, rows, n=None):
-        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
-        t = self.torch
-        if rows is None:
-            return None
-        if not getattr(rows, "is_cuda", False):
-            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
-        k, = _tensor("rows", rows, t.int32, (n,))
-        if not 0 < k <= self.n_rows:
-            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
-        return rows
+        self._create(self.n_rows, self.frame)
 
     def run(self, pcm, rows=None, detail=False, level=True):
         """pcm int16 [n,P,samples] (what decode() / mix() wrote; samples a multiple of frame_samples, at most 1920) -> dict(sa uint8 [n,P,F],
@@ -1329,44 +1317,11 @@ class Vad:
         """a count tensor of run(rows=) / select() as a dict (synchronises); rows == -1: the call was refused on the device"""
         return _counts(solo_vad_count_t, count)
 
-    def reset(self, rows=None):
-        """every row, or the listed rows (a host sequence: inside [0, n_rows), none twice), back to the initial state"""
-        if rows is None:
-            r = self.lib.solo_vad_reset(self.h, self._stream())
-        else:
-            idx = _distinct("rows", rows, self.n_rows)
-            arr = (C.c_int32 * len(idx))(*idx)
-            r = self.lib.solo_vad_reset_rows(self.h, arr, len(idx), self._stream())
-        if r:
-            raise RuntimeError("solo_vad_reset -> %d" % r)
-
-    def get_state(self, rows=None):
-        """the 128-byte records of the listed rows (None: all rows) -> uint8 [n,128] on the device"""
-        t = self.torch
-        rows = self._rows(rows)
-        n = self.n_rows if rows is None else int(rows.shape[0])
-        blob = t.empty((n, VAD_STATE_BYTES), dtype=t.uint8, device=self.device)
-        r = self.lib.solo_vad_get_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
-        if r:
-            raise RuntimeError("solo_vad_get_state -> %d" % r)
-        return blob
-
-    def set_state(self, blob, rows=None):
-        """blob uint8 [n,128] on the device -> the records of the listed rows (None: rows 0 .. n-1)"""
-        t = self.torch
-        n, _ = _tensor("blob", blob, t.uint8, (None, VAD_STATE_BYTES))
-        if not 0 < n <= self.n_rows:
-            raise ValueError("blob: 1 .. %d records" % self.n_rows)
-        rows = self._rows(rows, n)
-        r = self.lib.solo_vad_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
-        if r:
-            raise RuntimeError("solo_vad_set_state -> %d" % r)
-
 
 PLAYOUT_STATE_BYTES = 128
 
 
-class Playout:
+class Playout(_RowStateObject):
     """Adaptive play-out delay control for n_rows streams on the current HIP device (solo_playout_*, include/solo_mi355x.h has the rule): per
     stream a 128-byte state record and one held packet; row s belongs to stream s of the SoloBatch it is ticked with.  tick() is the receive
     side of a bridge tick in one call; plan() and render() are its two stages alone."""
@@ -1374,31 +1329,15 @@ class Playout:
     ACTIONS = ("IDLE", "NORMAL", "HELD", "STRETCH", "ACCEL", "ACCEL_FORCED")
     OUTCOMES = tuple(f[0].upper() for f in solo_playout_render_count_t._fields_)
     PARAMS = dict(start_ready=2, max_span=0, window=16, tolerate=1, lo=1, hi=3, cooldown=8, cost_gate=0)
+    PREFIX = "playout"
 
     def __init__(self, n_rows, packet_samples=PACKET_SAMPLES):
-        import torch
         self.n_rows, self.packet_samples = int(n_rows), int(packet_samples)
         if self.n_rows <= 0:
             raise ValueError("n_rows must be positive")
         if not 0 < self.packet_samples <= 1920 or self.packet_samples % 8:
             raise ValueError("packet_samples: a positive multiple of 8, at most 1920")
-        self.h = None
-        if not torch.cuda.is_available():
-            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
-        self.torch = torch
-        self.lib = load_library()
-        self.h = self.lib.solo_playout_create(self.n_rows, self.packet_samples)
-        if not self.h:
-            raise RuntimeError("solo_playout_create failed (no GPU, or out of memory)")
-        self.device = torch.device("cuda", torch.cuda.current_device())
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.lib.solo_playout_destroy(self.h)
-            self.h = None
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+        self._create(self.n_rows, self.packet_samples)
 
     @property
     def state_bytes(self):
@@ -1423,21 +1362,6 @@ class Playout:
                 0 <= v["cooldown"] <= 1000):
             raise ValueError("start_ready >= 1, max_span >= 0, window 1 .. 32, tolerate 0 .. 3, 0 <= lo <= hi <= 64, cooldown 0 .. 1000")
         return solo_playout_params_t(*[v[k] for k, _ in solo_playout_params_t._fields_])
-
-    def _rows(self, rows, n=None):
-        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
-        t = self.torch
-        if rows is None:
-            return None
-        if not getattr(rows, "is_cuda", False):
-            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
-        k, = _tensor("rows", rows, t.int32, (n,))
-        if not 0 < k <= self.n_rows:
-            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
-        return rows
-
-    def _n(self, rows):
-        return self.n_rows if rows is None else int(rows.shape[0])
 
     def tick(self, batch, streams=None, **params):
         """The receive side of a tick (solo_playout_tick): report, plan, the two decodes, time scaling, render -> (heard int16 [n,samples],
@@ -1551,85 +1475,26 @@ class Playout:
             raise ValueError("count: 4, 8 or 12 int32")
         return {"plan": _counts(solo_playout_plan_count_t, count[:4]), "render": _counts(solo_playout_render_count_t, count[4:])}
 
-    def reset(self):
-        """every row back to the initial state: not running, nothing held"""
-        r = self.lib.solo_playout_reset(self.h, self._stream())
-        if r:
-            raise RuntimeError("solo_playout_reset -> %d" % r)
-
     def reset_rows(self, rows):
-        """the listed rows (a host sequence: inside [0, n_rows), none twice) back to the initial state"""
-        idx = _distinct("rows", rows, self.n_rows)
-        r = self.lib.solo_playout_reset_rows(self.h, (C.c_int32 * len(idx))(*idx), len(idx), self._stream())
-        if r:
-            raise RuntimeError("solo_playout_reset_rows -> %d" % r)
-
-    def get_state(self, rows=None):
-        """the records and held packets of the listed rows (None: all rows) -> uint8 [n, state_bytes] on the device"""
-        t = self.torch
-        rows = self._rows(rows)
-        n = self._n(rows)
-        blob = t.empty((n, self.state_bytes), dtype=t.uint8, device=self.device)
-        r = self.lib.solo_playout_get_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
-        if r:
-            raise RuntimeError("solo_playout_get_state -> %d" % r)
-        return blob
-
-    def set_state(self, blob, rows=None):
-        """blob uint8 [n, state_bytes] on the device -> the records and held packets of the listed rows (None: rows 0 .. n-1)"""
-        t = self.torch
-        n, _ = _tensor("blob", blob, t.uint8, (None, self.state_bytes))
-        if not 0 < n <= self.n_rows:
-            raise ValueError("blob: 1 .. %d records" % self.n_rows)
-        rows = self._rows(rows, n)
-        r = self.lib.solo_playout_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
-        if r:
-            raise RuntimeError("solo_playout_set_state -> %d" % r)
+        """reset(rows): the listed rows (a host sequence: inside [0, n_rows), none twice) back to the initial state"""
+        self.reset(rows)
 
 
 AGC_STATE_BYTES = 64
 
 
-class Agc:
+class Agc(_RowStateObject):
     """n_rows independent level controls with a peak limiter on the current HIP device (solo_agc, include/solo_mi355x.h): every row's
     speech is brought to `target` -dBov with a slewed gain, and no output sample exceeds `ceiling`.  State carries from call to call."""
 
     COUNT = ("rows", "speech", "limited", "zero")
+    PREFIX, state_bytes = "agc", AGC_STATE_BYTES
 
     def __init__(self, n_rows):
-        import torch
         self.n_rows = int(n_rows)
         if self.n_rows <= 0:
             raise ValueError("n_rows must be positive")
-        self.h = None
-        if not torch.cuda.is_available():
-            raise RuntimeError("solo_amd needs a HIP device (MI355X); there is no CPU path")
-        self.torch = torch
-        self.lib = load_library()
-        self.h = self.lib.solo_agc_create(self.n_rows)
-        if not self.h:
-            raise RuntimeError("solo_agc_create failed (no GPU, or out of memory)")
-        self.device = torch.device("cuda", torch.cuda.current_device())
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.lib.solo_agc_destroy(self.h)
-            self.h = None
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
-
-    def _rows(self, rows, n=None):
-        """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
-        t = self.torch
-        if rows is None:
-            return None
-        if not getattr(rows, "is_cuda", False):
-            rows = t.tensor(_increasing("rows", rows, self.n_rows), dtype=t.int32, device=self.device)
-        k, = _tensor("rows", rows, t.int32, (n,))
-        if not 0 < k <= self.n_rows:
-            raise ValueError("rows: 1 .. %d indices" % self.n_rows)
-        return rows
+        self._create(self.n_rows)
 
     def run(self, pcm, level=None, sa=None, rows=None, out=None, target=23, boost=24, cut=12, sa_on=128, gate=50, alpha=32, up=128, down=256,
             ceiling=29204, release=256):
@@ -1672,36 +1537,3 @@ class Agc:
     def count(self, count):
         """a count tensor of run() as a dict (synchronises); rows == -1: the list was refused on the device"""
         return _counts(solo_agc_count_t, count)
-
-    def reset(self, rows=None):
-        """every row, or the listed rows (a host sequence: inside [0, n_rows), none twice), back to the initial state"""
-        if rows is None:
-            r = self.lib.solo_agc_reset(self.h, self._stream())
-        else:
-            idx = _distinct("rows", rows, self.n_rows)
-            arr = (C.c_int32 * len(idx))(*idx)
-            r = self.lib.solo_agc_reset_rows(self.h, arr, len(idx), self._stream())
-        if r:
-            raise RuntimeError("solo_agc_reset -> %d" % r)
-
-    def get_state(self, rows=None):
-        """the 64-byte records of the listed rows (None: all rows) -> uint8 [n,64] on the device"""
-        t = self.torch
-        rows = self._rows(rows)
-        n = self.n_rows if rows is None else int(rows.shape[0])
-        blob = t.empty((n, AGC_STATE_BYTES), dtype=t.uint8, device=self.device)
-        r = self.lib.solo_agc_get_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
-        if r:
-            raise RuntimeError("solo_agc_get_state -> %d" % r)
-        return blob
-
-    def set_state(self, blob, rows=None):
-        """blob uint8 [n,64] on the device -> the records of the listed rows (None: rows 0 .. n-1)"""
-        t = self.torch
-        n, _ = _tensor("blob", blob, t.uint8, (None, AGC_STATE_BYTES))
-        if not 0 < n <= self.n_rows:
-            raise ValueError("blob: 1 .. %d records" % self.n_rows)
-        rows = self._rows(rows, n)
-        r = self.lib.solo_agc_set_state(self.h, _ptr(rows), n, blob.data_ptr(), self._stream())
-        if r:
-            raise RuntimeError("solo_agc_set_state -> %d" % r)

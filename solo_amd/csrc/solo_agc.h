@@ -21,7 +21,7 @@
 // same functions are plain loops), so that the host build runs the same text (tests/agc_host.cpp).
 #pragma once
 #include <stddef.h>
-#include "solo_vad.h"           // sx_vad_level, sx_vad_list_ok, the record copy kernel
+#include "solo_vad.h"           // sx_vad_level
 #include "solo_agc_tables.inc"
 
 #define SX_AGC_STATE_WORDS 16
@@ -283,15 +283,6 @@ __global__ void __launch_bounds__(64) solo_agc_kernel(const SxAgcArgs a, SxAgcCo
         }
     }
 }
-// the listed rows' records to what the create call leaves: one wavefront per record, the list travels by value
-__global__ void __launch_bounds__(64) solo_agc_reset_rows_kernel(i32* state, const SxStreamCtlList l) {
-    const int row = l.r[blockIdx.x].stream;
-    if (threadIdx.x < SX_AGC_STATE_WORDS) state[(size_t)row * SX_AGC_STATE_WORDS + threadIdx.x] = sx_agc_init_word((int)threadIdx.x);
-}
-__global__ void __launch_bounds__(256) solo_agc_reset_kernel(i32* state, int n_rows) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (size_t)n_rows * SX_AGC_STATE_WORDS) state[i] = sx_agc_init_word((int)(i % SX_AGC_STATE_WORDS));
-}
 static inline hipError_t solo_agc_launch(const SxAgcArgs& a, SxAgcCount* count, unsigned long long* acc, const u32* verdict, hipStream_t s) {
     hipLaunchKernelGGL(solo_agc_kernel, dim3((unsigned)a.n), dim3(64), 0, s, a, count, acc, verdict);
     return hipGetLastError();
@@ -300,7 +291,7 @@ static inline hipError_t solo_agc_launch(const SxAgcArgs& a, SxAgcCount* count, 
 // Host form of the launch (tests): every row through sx_agc_row.  -> false: the list is not strictly increasing inside [0, n_rows),
 // nothing but count->rows = -1 is written
 static inline bool sx_agc_host(const SxAgcArgs& a, int n_rows, SxAgcCount* count) {
-    if (!sx_vad_map_ok(a.map, a.n, n_rows)) {
+    if (!sx_map_ok(a.map, a.n, n_rows)) {
         if (count) count->rows = -1;
         return false;
     }

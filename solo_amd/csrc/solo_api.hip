@@ -39,6 +39,7 @@
 #include "solo_vad.h"           // voice activity, audio level and speaker selection of decoded rows (solo_vad, solo_vad_select): likewise
 #include "solo_playout.h"       // adaptive play-out delay control (solo_playout_plan / _render / _tick): likewise
 #include "solo_agc.h"           // level control and peak limiter of decoded rows (solo_agc): likewise
+#include "solo_rows.h"          // the record kernels of those four objects (reset, listed reset, state copy): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -447,23 +448,20 @@ int32_t solo_batch_reset(solo_batch_t* b, void* hip_stream) {
     return 0;
 }
 
-// the listed stream indices: n in [1, N], every index in range and listed once
-static bool stream_list_ok(const solo_batch* b, const int32_t* h_streams, int32_t n) {
-    if (!h_streams || n <= 0 || n > b->n_streams) return false;
-    std::vector<char> seen((size_t)b->n_streams, 0);
-    for (int32_t i = 0; i < n; i++) {
-        const int32_t s = h_streams[i];
-        if (s < 0 || s >= b->n_streams || seen[(size_t)s]) return false;
-        seen[(size_t)s] = 1;
-    }
-    return true;
-}
-
-// Subset calls: the host checks only the count and the pointers (the list itself lives on the device: it is checked there, on the
-// caller's stream, by solo_stream_list_check_kernel, whose verdict the call's kernels read)
-static hipError_t launch_list_check(const solo_batch* b, const int32_t* d_streams, int32_t n, uint32_t* verdict, int32_t* d_status, hipStream_t s) {
-    hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, s, d_streams, n, b->n_streams, verdict, d_status);
+// Subset calls, of a handle (n_rows = its streams) or of a row-state object: the host checks only the count and the pointers (the list
+// itself lives on the device: it is checked there, on the caller's stream, by solo_stream_list_check_kernel, whose verdict the call's
+// kernels read).  No list (NULL = the identity): nothing to check, the call's kernels do not read the verdict
+static hipError_t launch_list_check(const int32_t* d_list, int32_t n, int32_t n_rows, uint32_t* verdict, int32_t* d_status, hipStream_t s) {
+    if (!d_list) return hipSuccess;
+    hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, s, d_list, n, n_rows, verdict, d_status);
     return hipGetLastError();
+}
+// every create call: this library has no CPU path
+static bool have_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return true;
+    fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
+    return false;
 }
 
 // Per-stream controls of solo_batch_reset_streams and solo_batch_update_streams: everything is validated and turned into records
@@ -472,7 +470,7 @@ static hipError_t launch_list_check(const solo_batch* b, const int32_t* d_stream
 // and must be the handle's.  false: the call is refused.
 static bool stream_ctl_records(const solo_batch* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
                                const USER_Ctrl_dec* h_dec, std::vector<SxStreamCtl>& er, std::vector<SxStreamCtl>& dr) {
-    if (!b || which < 1 || which > 3 || !stream_list_ok(b, h_streams, n)) return false;
+    if (!b || which < 1 || which > 3 || !sx_list_ok(h_streams, n, b->n_streams)) return false;
     const bool do_enc = (which & 1) != 0, do_dec = (which & 2) != 0;
     if ((do_enc && !b->have_enc) || (do_dec && !b->have_dec) || (h_enc && !do_enc) || (h_dec && !do_dec)) return false;
     if (do_enc) {
@@ -532,12 +530,7 @@ int32_t solo_batch_update_streams(solo_batch_t* b, const int32_t* h_streams, int
 }
 
 solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, const USER_Ctrl_dec* dec, int32_t slot_bytes) {
-    if (n_streams <= 0) return NULL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
-        return NULL;
-    }
+    if (n_streams <= 0 || !have_device()) return NULL;
     if (enc && !ctrl_enc_supported(enc)) return NULL;
     if (dec && !ctrl_dec_supported(dec)) return NULL;
     solo_batch* b = new (std::nothrow) solo_batch();
@@ -672,7 +665,7 @@ static int32_t solo_decode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     // the previous decode call may have been issued on ANOTHER stream than this one: it used the same states, record buffer and verdict word
     if (b->dec_done_recorded) SOLO_CHECK(hipStreamWaitEvent(st, b->evDecDone, 0));
     if (tm) (void)hipEventRecord(b->evDec[0], st);
-    hipError_t lerr = map ? launch_list_check(b, map, n, verdict, d_status, st) : hipSuccess;
+    hipError_t lerr = launch_list_check(map, n, b->n_streams, verdict, d_status, st);
     if (lerr == hipSuccess && b->dec_split)
         lerr = solo_decode_chunks(b, map, ns, verdict, d_bits, d_nbytes, d_recv, n_packets, d_pcm, d_status, st);
     else if (lerr == hipSuccess)         // single kernel: one wavefront per stream parses (two lanes) and synthesises
@@ -731,7 +724,7 @@ int32_t solo_recv_create(solo_batch_t* b, int32_t depth, int32_t slot_bytes, int
     return 0;
 }
 int32_t solo_recv_reset_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, const int32_t* h_first_seq, void* hip_stream) {
-    if (!b || !b->d_recv_ring || !h_first_seq || !stream_list_ok(b, h_streams, n)) return -1;
+    if (!b || !b->d_recv_ring || !h_first_seq || !sx_list_ok(h_streams, n, b->n_streams)) return -1;
     std::vector<SxStreamCtl> rr((size_t)n);
     for (int32_t i = 0; i < n; i++) {
         if (h_first_seq[i] < 0) return -1;
@@ -764,7 +757,7 @@ int32_t solo_recv_decode_streams(solo_batch_t* b, const int32_t* d_streams, int3
     if (!b || !b->d_recv_ring || !d_streams || n <= 0 || n > b->n_streams || !d_pcm || n_packets <= 0 || n_packets > b->recv_depth) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_RING;
-    SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, d_status, st));
+    SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, d_status, st));
     if (b->recv_track) SOLO_CHECK(solo_recv_account_launch(b->d_recv_lens, b->d_recv_play, b->d_recv_trk, n, n_packets, b->recv_depth, d_streams, verdict, st));
     SOLO_CHECK(b->dops->ring(b->d_dec_state, b->d_recv_ring, b->d_recv_lens, b->d_recv_play, n, n_packets, b->recv_depth, b->recv_slot, d_pcm, d_status,
                              d_streams, verdict, st));
@@ -799,7 +792,7 @@ int32_t solo_recv_report(solo_batch_t* b, const int32_t* d_streams, int32_t n, c
     if ((uintptr_t)d_reports & 15) return -1;               // (the records are stored 16 bytes at a time)
     hipStream_t st = (hipStream_t)hip_stream;
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_REPORT;
-    if (d_streams) SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
+    SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, NULL, st));
     SxRecvReportArgs a;
     a.lens = b->d_recv_lens; a.play = b->d_recv_play; a.trk = b->d_recv_trk; a.map = d_streams; a.min_ready_v = d_min_ready;
     a.reports = (uint32_t*)d_reports; a.sel = b->d_recv_sel;
@@ -836,7 +829,7 @@ static int32_t solo_send_impl(solo_batch_t* b, const int32_t* map, int32_t n, co
     if ((int64_t)n * (int64_t)n_packets * 2 >= ((int64_t)1 << 31)) return -1;
     SOLO_CHECK(grow_scratch(b->d_send_scratch, b->send_scratch_bytes, solo_send_scratch_bytes(n * n_packets), st));
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_SEND;
-    if (map) SOLO_CHECK(launch_list_check(b, map, n, verdict, NULL, st));
+    SOLO_CHECK(launch_list_check(map, n, b->n_streams, verdict, NULL, st));
     SxSendArgs a;
     a.bits = d_bits; a.nbytes = d_nbytes; a.send = d_send; a.seq_base = d_seq_base; a.map = map;
     a.n = n; a.n_packets = n_packets; a.slot = b->slot; a.hbb = handle_hb_bytes(b); a.first_seq = first_seq;
@@ -955,29 +948,74 @@ int32_t solo_timescale(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int3
     return 0;
 }
 
-// ---- PCM rate conversion (solo_resample.h): an object of its own, it sits between two handles of different rates ----------------------
-static_assert(sizeof(solo_resample_count_t) == sizeof(SxRsCount), "include/solo_mi355x.h and solo_resample.h agree");
-struct solo_resampler {
-    int32_t n_rows, fs_in, fs_out;
+// ---- the row-state objects: Resampler, Vad, Agc, Playout ------------------------------------------------------------------------------
+// Each sits beside a handle, holds one state record per row, carries it from call to call and derives from solo_rows; what is written
+// here once is their whole lifecycle (solo_rows.h has the kernels).  The entry points keep their own argument checks.
+struct solo_rows {
+    int32_t n_rows, words;           // rows; 32-bit words of a row's state record
+    int32_t* d_state;                // [n_rows][words]
+    uint32_t* d_verdict;             // the verdict words of the object's calls (launch_list_check)
+    int32_t* d_extra;                // [n_rows][extra_words]: a row's second segment (Playout's held packet), or NULL
+    int32_t extra_words;
+    SxRowInit init;                  // the record a reset leaves
+};
+static void rows_free(solo_rows* o) {
+    dev_free(o->d_state);
+    dev_free(o->d_verdict);
+    dev_free(o->d_extra);
+}
+static int32_t rows_reset(solo_rows* o, hipStream_t st) {
+    if (!o) return -1;
+    const size_t words = (size_t)o->n_rows * ((size_t)o->words + (size_t)o->extra_words);
+    hipLaunchKernelGGL(solo_rows_reset_all_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, o->d_state, o->words, o->init, o->d_extra, o->extra_words,
+                       o->n_rows);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+// h_rows: a HOST list (sx_list_ok); it travels by value, SX_CTL_PER_LAUNCH rows a launch
+static int32_t rows_reset_list(solo_rows* o, const int32_t* h_rows, int32_t n, hipStream_t st) {
+    if (!o || !sx_list_ok(h_rows, n, o->n_rows)) return -1;
+    std::vector<SxStreamCtl> recs((size_t)n);
+    for (int32_t i = 0; i < n; i++) recs[i] = SxStreamCtl{h_rows[i], 0, 0, 0};
+    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
+        hipLaunchKernelGGL(solo_rows_reset_kernel, dim3((unsigned)k), dim3(64), 0, st, o->d_state, o->words, o->init, o->d_extra, o->extra_words, l);
+    }));
+    return 0;
+}
+// the get_state (put = 0) and set_state calls: d_rows on the device, NULL = rows 0 .. n - 1; an index outside [0, n_rows) moves nothing
+static int32_t rows_copy_state(solo_rows* o, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
+    if (!o || !d_blob || n <= 0 || n > o->n_rows || ((uintptr_t)d_blob & 3)) return -1;
+    const size_t words = (size_t)n * ((size_t)o->words + (size_t)o->extra_words);
+    hipLaunchKernelGGL(solo_rows_copy_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, o->d_state, o->words, o->d_extra, o->extra_words, o->n_rows,
+                       d_rows, n, (i32*)d_blob, put);
+    SOLO_CHECK(hipGetLastError());
+    return 0;
+}
+// the create calls: the records (init_word(w): word w of the initial record, NULL: zeros), n_verdicts verdict words and the second
+// segment, all as a reset leaves them.  The create call's last step: it ends with the synchronisation that the caller's own memsets
+// need as well.  false: the caller's destroy call frees what there is (rows_free)
+static bool rows_alloc(solo_rows* o, int32_t n_rows, int32_t words, i32 (*init_word)(int), int32_t n_verdicts, int32_t extra_words) {
+    o->n_rows = n_rows; o->words = words; o->extra_words = extra_words;
+    for (int w = 0; w < words; w++) o->init.w[w] = init_word ? init_word(w) : 0;
+    return hipMalloc((void**)&o->d_state, (size_t)n_rows * words * sizeof(int32_t)) == hipSuccess &&
+           hipMalloc((void**)&o->d_verdict, n_verdicts * sizeof(uint32_t)) == hipSuccess && hipMemset(o->d_verdict, 0, n_verdicts * sizeof(uint32_t)) == hipSuccess &&
+           (!extra_words || hipMalloc((void**)&o->d_extra, (size_t)n_rows * extra_words * sizeof(int32_t)) == hipSuccess) && rows_reset(o, NULL) == 0 &&
+           hipStreamSynchronize(NULL) == hipSuccess;
+}
+
+// ---- PCM rate conversion (solo_resample.h): it sits between two handles of different rates; a zeroed record = SKP_Silk_resampler_init ----
+static_assert(sizeof(solo_resample_count_t) == sizeof(SxRsCount) && SX_RS_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_resample.h and solo_rows.h agree");
+struct solo_resampler : solo_rows {
+    int32_t fs_in, fs_out;
     SxRsCfg cfg;
-    int32_t* d_state;                // [n_rows][SX_RS_STATE_WORDS]
-    uint32_t* d_verdict;             // the verdict word of a solo_resample_rows call
 };
 solo_resampler_t* solo_resample_create(int32_t n_rows, int32_t fs_in, int32_t fs_out) {
     SxRsCfg cfg;
-    if (n_rows <= 0 || !sx_rs_config(fs_in, fs_out, &cfg)) return NULL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
-        return NULL;
-    }
+    if (n_rows <= 0 || !sx_rs_config(fs_in, fs_out, &cfg) || !have_device()) return NULL;
     solo_resampler* r = new (std::nothrow) solo_resampler();
     if (!r) return NULL;
-    memset(r, 0, sizeof(*r));
-    r->n_rows = n_rows; r->fs_in = fs_in; r->fs_out = fs_out; r->cfg = cfg;
-    const size_t bytes = (size_t)n_rows * SX_RS_STATE_WORDS * sizeof(int32_t);
-    if (hipMalloc((void**)&r->d_state, bytes) != hipSuccess || hipMalloc((void**)&r->d_verdict, sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(r->d_state, 0, bytes) != hipSuccess || hipMemset(r->d_verdict, 0, sizeof(uint32_t)) != hipSuccess) {
+    r->fs_in = fs_in; r->fs_out = fs_out; r->cfg = cfg;
+    if (!rows_alloc(r, n_rows, SX_RS_STATE_WORDS, NULL, 1, 0)) {
         solo_resample_destroy(r);
         return NULL;
     }
@@ -985,26 +1023,13 @@ solo_resampler_t* solo_resample_create(int32_t n_rows, int32_t fs_in, int32_t fs
 }
 void solo_resample_destroy(solo_resampler_t* r) {
     if (!r) return;
-    dev_free(r->d_state);
-    dev_free(r->d_verdict);
+    rows_free(r);
     delete r;
 }
 int32_t solo_resample_out_samples(const solo_resampler_t* r, int32_t in_samples) { return r ? sx_rs_out_samples(r->cfg, in_samples) : -1; }
-int32_t solo_resample_reset(solo_resampler_t* r, void* hip_stream) {
-    if (!r) return -1;
-    SOLO_CHECK(hipMemsetAsync(r->d_state, 0, (size_t)r->n_rows * SX_RS_STATE_WORDS * sizeof(int32_t), (hipStream_t)hip_stream));
-    return 0;
-}
+int32_t solo_resample_reset(solo_resampler_t* r, void* hip_stream) { return rows_reset(r, (hipStream_t)hip_stream); }
 int32_t solo_resample_reset_rows(solo_resampler_t* r, const int32_t* h_rows, int32_t n, void* hip_stream) {
-    if (!r || !sx_rs_list_ok(h_rows, n, r->n_rows)) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<SxStreamCtl> recs((size_t)n);
-    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
-    int32_t* state = r->d_state;
-    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
-        hipLaunchKernelGGL(solo_resample_reset_kernel, dim3((unsigned)k), dim3(64), 0, st, state, l);
-    }));
-    return 0;
+    return rows_reset_list(r, h_rows, n, (hipStream_t)hip_stream);
 }
 static int32_t resample_call(solo_resampler* r, const int32_t* d_rows, int32_t n, const int16_t* d_in, int32_t n_packets, int32_t in_samples,
                              int16_t* d_out, solo_resample_count_t* d_count, hipStream_t st) {
@@ -1012,10 +1037,7 @@ static int32_t resample_call(solo_resampler* r, const int32_t* d_rows, int32_t n
     SxRsArgs a;
     a.c = r->cfg; a.in = d_in; a.out = d_out; a.state = r->d_state; a.map = d_rows; a.n = n;
     a.batches = n_packets * (in_samples / r->cfg.n_in);
-    if (d_rows) {
-        hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, r->n_rows, r->d_verdict, (i32*)NULL);
-        SOLO_CHECK(hipGetLastError());
-    }
+    SOLO_CHECK(launch_list_check(d_rows, n, r->n_rows, r->d_verdict, NULL, st));
     SOLO_CHECK(solo_resample_launch(a, (SxRsCount*)d_count, r->d_verdict, st));
     return 0;
 }
@@ -1031,27 +1053,17 @@ int32_t solo_resample_rows(solo_resampler_t* r, const int32_t* d_rows, int32_t n
 
 // ---- voice activity, audio level, speaker selection (solo_vad.h): an object of its own, with a state record per row -------------------
 static_assert(sizeof(solo_vad_count_t) == sizeof(SxVadCount) && sizeof(solo_vad_select_params_t) == sizeof(SxVadSelectParams) &&
-              SOLO_VAD_STATE_BYTES == SX_VAD_STATE_WORDS * 4, "include/solo_mi355x.h and solo_vad.h agree");
-struct solo_vad_obj {
-    int32_t n_rows, frame;
-    int32_t* d_state;                // [n_rows][SX_VAD_STATE_WORDS]
-    uint32_t* d_verdict;             // [2]: the verdict words of solo_vad and of solo_vad_select
+              SOLO_VAD_STATE_BYTES == SX_VAD_STATE_WORDS * 4 && SX_VAD_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_vad.h and solo_rows.h agree");
+struct solo_vad_obj : solo_rows {    // d_verdict[2]: the verdict words of solo_vad and of solo_vad_select
+    int32_t frame;
     void* d_scratch;                 // the room plan and the keys of solo_vad_select (solo_vad_scratch_bytes)
 };
 solo_vad_t* solo_vad_create(int32_t n_rows, int32_t frame_samples) {
-    if (n_rows <= 0 || !sx_vad_frame_ok(frame_samples) || (int64_t)n_rows * SX_VAD_STATE_WORDS >= ((int64_t)1 << 31)) return NULL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
-        return NULL;
-    }
+    if (n_rows <= 0 || !sx_vad_frame_ok(frame_samples) || (int64_t)n_rows * SX_VAD_STATE_WORDS >= ((int64_t)1 << 31) || !have_device()) return NULL;
     solo_vad_obj* v = new (std::nothrow) solo_vad_obj();
     if (!v) return NULL;
-    memset(v, 0, sizeof(*v));
-    v->n_rows = n_rows; v->frame = frame_samples;
-    if (hipMalloc((void**)&v->d_state, (size_t)n_rows * SX_VAD_STATE_WORDS * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&v->d_verdict, 2 * sizeof(uint32_t)) != hipSuccess || hipMalloc(&v->d_scratch, solo_vad_scratch_bytes(n_rows)) != hipSuccess ||
-        hipMemset(v->d_verdict, 0, 2 * sizeof(uint32_t)) != hipSuccess || solo_vad_reset(v, NULL) != 0 || hipStreamSynchronize(NULL) != hipSuccess) {
+    v->frame = frame_samples;
+    if (hipMalloc(&v->d_scratch, solo_vad_scratch_bytes(n_rows)) != hipSuccess || !rows_alloc(v, n_rows, SX_VAD_STATE_WORDS, sx_vad_init_word, 2, 0)) {
         solo_vad_destroy(v);
         return NULL;
     }
@@ -1059,41 +1071,17 @@ solo_vad_t* solo_vad_create(int32_t n_rows, int32_t frame_samples) {
 }
 void solo_vad_destroy(solo_vad_t* v) {
     if (!v) return;
-    dev_free(v->d_state);
-    dev_free(v->d_verdict);
+    rows_free(v);
     dev_free(v->d_scratch);
     delete v;
 }
-int32_t solo_vad_reset(solo_vad_t* v, void* hip_stream) {
-    if (!v) return -1;
-    const size_t words = (size_t)v->n_rows * SX_VAD_STATE_WORDS;
-    hipLaunchKernelGGL(solo_vad_reset_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, v->d_state, v->n_rows);
-    SOLO_CHECK(hipGetLastError());
-    return 0;
-}
-int32_t solo_vad_reset_rows(solo_vad_t* v, const int32_t* h_rows, int32_t n, void* hip_stream) {
-    if (!v || !sx_vad_list_ok(h_rows, n, v->n_rows)) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<SxStreamCtl> recs((size_t)n);
-    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
-    int32_t* state = v->d_state;
-    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
-        hipLaunchKernelGGL(solo_vad_reset_rows_kernel, dim3((unsigned)k), dim3(64), 0, st, state, l);
-    }));
-    return 0;
-}
-static int32_t vad_copy_state(solo_vad_obj* v, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
-    if (!v || !d_blob || n <= 0 || n > v->n_rows || ((uintptr_t)d_blob & 3)) return -1;
-    const size_t words = (size_t)n * SX_VAD_STATE_WORDS;
-    hipLaunchKernelGGL(solo_vad_copy_kernel<>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, v->d_state, v->n_rows, d_rows, n, (i32*)d_blob, put);
-    SOLO_CHECK(hipGetLastError());
-    return 0;
-}
+int32_t solo_vad_reset(solo_vad_t* v, void* hip_stream) { return rows_reset(v, (hipStream_t)hip_stream); }
+int32_t solo_vad_reset_rows(solo_vad_t* v, const int32_t* h_rows, int32_t n, void* hip_stream) { return rows_reset_list(v, h_rows, n, (hipStream_t)hip_stream); }
 int32_t solo_vad_get_state(solo_vad_t* v, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
-    return vad_copy_state(v, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+    return rows_copy_state(v, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
 }
 int32_t solo_vad_set_state(solo_vad_t* v, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
-    return vad_copy_state(v, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+    return rows_copy_state(v, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
 }
 int32_t solo_vad(solo_vad_t* v, const int32_t* d_rows, int32_t n, const int16_t* d_pcm, int32_t n_packets, int32_t packet_samples, uint8_t* d_sa_q8,
                  int32_t* d_detail, uint8_t* d_level, solo_vad_count_t* d_count, void* hip_stream) {
@@ -1102,10 +1090,7 @@ int32_t solo_vad(solo_vad_t* v, const int32_t* d_rows, int32_t n, const int16_t*
     SxVadArgs a;
     a.pcm = d_pcm; a.state = v->d_state; a.map = d_rows; a.sa = d_sa_q8; a.detail = d_detail; a.level = d_level;
     a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples;
-    if (d_rows) {
-        hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, v->n_rows, v->d_verdict, (i32*)NULL);
-        SOLO_CHECK(hipGetLastError());
-    }
+    SOLO_CHECK(launch_list_check(d_rows, n, v->n_rows, v->d_verdict, NULL, st));
     SOLO_CHECK(solo_vad_launch(v->frame, a, (SxVadCount*)d_count, v->d_verdict, st));
     return 0;
 }
@@ -1119,36 +1104,26 @@ int32_t solo_vad_select(solo_vad_t* v, const int32_t* d_rows, int32_t n, const u
     a.sel = d_sel; a.gain_out = d_gain_out; a.keep = d_keep; a.dominant = d_dominant; a.state = v->d_state;
     a.n_packets = n_packets; a.frames = frames; a.prm = *(const SxVadSelectParams*)params;
     const int32_t n_rows = v->n_rows;
+    hipError_t lerr = hipSuccess;
     SOLO_CHECK(solo_vad_select_launch(a, d_room, n, n_rooms, n_rows, v->d_scratch, (SxVadCount*)d_count, v->d_verdict + 1, [&](u32* verdict) {
-        if (d_rows) hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, n_rows, verdict, (i32*)NULL);
+        lerr = launch_list_check(d_rows, n, n_rows, verdict, NULL, st);
     }, st));
+    SOLO_CHECK(lerr);
     return 0;
 }
 
 // ---- level control and peak limiter (solo_agc.h): an object of its own, with a state record per row -----------------------------------
 static_assert(sizeof(solo_agc_count_t) == sizeof(SxAgcCount) && sizeof(solo_agc_params_t) == sizeof(SxAgcParams) &&
-              SOLO_AGC_STATE_BYTES == SX_AGC_STATE_WORDS * 4, "include/solo_mi355x.h and solo_agc.h agree");
-struct solo_agc_obj {
-    int32_t n_rows;
-    int32_t* d_state;                // [n_rows][SX_AGC_STATE_WORDS]
-    uint32_t* d_verdict;             // the verdict word of solo_agc
+              SOLO_AGC_STATE_BYTES == SX_AGC_STATE_WORDS * 4 && SX_AGC_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_agc.h and solo_rows.h agree");
+struct solo_agc_obj : solo_rows {
     unsigned long long* d_acc;       // the counters of a call's count (solo_agc_acc_bytes; zero between calls)
 };
 solo_agc_t* solo_agc_create(int32_t n_rows) {
-    if (n_rows <= 0 || (int64_t)n_rows * SX_AGC_STATE_WORDS >= ((int64_t)1 << 31)) return NULL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
-        return NULL;
-    }
+    if (n_rows <= 0 || (int64_t)n_rows * SX_AGC_STATE_WORDS >= ((int64_t)1 << 31) || !have_device()) return NULL;
     solo_agc_obj* g = new (std::nothrow) solo_agc_obj();
     if (!g) return NULL;
-    memset(g, 0, sizeof(*g));
-    g->n_rows = n_rows;
-    if (hipMalloc((void**)&g->d_state, (size_t)n_rows * SX_AGC_STATE_WORDS * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&g->d_verdict, sizeof(uint32_t)) != hipSuccess || hipMemset(g->d_verdict, 0, sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void**)&g->d_acc, solo_agc_acc_bytes(n_rows)) != hipSuccess || hipMemset(g->d_acc, 0, solo_agc_acc_bytes(n_rows)) != hipSuccess ||
-        solo_agc_reset(g, NULL) != 0 || hipStreamSynchronize(NULL) != hipSuccess) {
+    if (hipMalloc((void**)&g->d_acc, solo_agc_acc_bytes(n_rows)) != hipSuccess || hipMemset(g->d_acc, 0, solo_agc_acc_bytes(n_rows)) != hipSuccess ||
+        !rows_alloc(g, n_rows, SX_AGC_STATE_WORDS, sx_agc_init_word, 1, 0)) {
         solo_agc_destroy(g);
         return NULL;
     }
@@ -1156,42 +1131,17 @@ solo_agc_t* solo_agc_create(int32_t n_rows) {
 }
 void solo_agc_destroy(solo_agc_t* g) {
     if (!g) return;
-    dev_free(g->d_state);
-    dev_free(g->d_verdict);
+    rows_free(g);
     dev_free(g->d_acc);
     delete g;
 }
-int32_t solo_agc_reset(solo_agc_t* g, void* hip_stream) {
-    if (!g) return -1;
-    const size_t words = (size_t)g->n_rows * SX_AGC_STATE_WORDS;
-    hipLaunchKernelGGL(solo_agc_reset_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, g->d_state, g->n_rows);
-    SOLO_CHECK(hipGetLastError());
-    return 0;
-}
-int32_t solo_agc_reset_rows(solo_agc_t* g, const int32_t* h_rows, int32_t n, void* hip_stream) {
-    if (!g || !sx_vad_list_ok(h_rows, n, g->n_rows)) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<SxStreamCtl> recs((size_t)n);
-    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
-    int32_t* state = g->d_state;
-    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
-        hipLaunchKernelGGL(solo_agc_reset_rows_kernel, dim3((unsigned)k), dim3(64), 0, st, state, l);
-    }));
-    return 0;
-}
-static int32_t agc_copy_state(solo_agc_obj* g, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
-    if (!g || !d_blob || n <= 0 || n > g->n_rows || ((uintptr_t)d_blob & 3)) return -1;
-    const size_t words = (size_t)n * SX_AGC_STATE_WORDS;
-    hipLaunchKernelGGL(solo_vad_copy_kernel<SX_AGC_STATE_WORDS>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, g->d_state, g->n_rows, d_rows, n,
-                       (i32*)d_blob, put);
-    SOLO_CHECK(hipGetLastError());
-    return 0;
-}
+int32_t solo_agc_reset(solo_agc_t* g, void* hip_stream) { return rows_reset(g, (hipStream_t)hip_stream); }
+int32_t solo_agc_reset_rows(solo_agc_t* g, const int32_t* h_rows, int32_t n, void* hip_stream) { return rows_reset_list(g, h_rows, n, (hipStream_t)hip_stream); }
 int32_t solo_agc_get_state(solo_agc_t* g, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
-    return agc_copy_state(g, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+    return rows_copy_state(g, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
 }
 int32_t solo_agc_set_state(solo_agc_t* g, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
-    return agc_copy_state(g, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+    return rows_copy_state(g, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
 }
 int32_t solo_agc(solo_agc_t* g, const int32_t* d_rows, int32_t n, const int16_t* d_pcm_in, int32_t n_packets, int32_t packet_samples,
                  const uint8_t* d_level_in, const uint8_t* d_sa_q8, int32_t frames, const solo_agc_params_t* params, int16_t* d_pcm_out,
@@ -1203,10 +1153,7 @@ int32_t solo_agc(solo_agc_t* g, const int32_t* d_rows, int32_t n, const int16_t*
     a.in = d_pcm_in; a.out = d_pcm_out; a.state = g->d_state; a.map = d_rows; a.level_in = d_level_in; a.sa = d_sa_q8;
     a.level_out = d_level_out; a.gain_out = d_gain_q8;
     a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples; a.frames = d_sa_q8 ? frames : 0; a.prm = *(const SxAgcParams*)params;
-    if (d_rows) {
-        hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, g->n_rows, g->d_verdict, (i32*)NULL);
-        SOLO_CHECK(hipGetLastError());
-    }
+    SOLO_CHECK(launch_list_check(d_rows, n, g->n_rows, g->d_verdict, NULL, st));
     SOLO_CHECK(solo_agc_launch(a, (SxAgcCount*)d_count, g->d_acc, g->d_verdict, st));
     return 0;
 }
@@ -1214,12 +1161,10 @@ int32_t solo_agc(solo_agc_t* g, const int32_t* d_rows, int32_t n, const int16_t*
 // ---- adaptive play-out delay control (solo_playout.h): an object of its own, a state record and a held packet per row ------------------
 static_assert(sizeof(solo_playout_params_t) == sizeof(SxPoParams) && sizeof(solo_playout_plan_count_t) == sizeof(SxPoPlanCount) &&
               sizeof(solo_playout_render_count_t) == sizeof(SxPoRenderCount) && sizeof(solo_playout_count_t) == sizeof(SxPoCount) &&
-              SOLO_PLAYOUT_STATE_BYTES == SX_PO_STATE_WORDS * 4 && SOLO_PLAYOUT_ACCEL_FORCED == SX_PO_OUT_ACCEL_FORCED, "include/solo_mi355x.h and solo_playout.h agree");
-struct solo_playout_obj {
-    int32_t n_rows, L;
-    int32_t* d_state;                // [n_rows][SX_PO_STATE_WORDS]
-    int16_t* d_held;                 // [n_rows][L]
-    uint32_t* d_verdict;             // [2]: the verdict words of the plan and of the render
+              SOLO_PLAYOUT_STATE_BYTES == SX_PO_STATE_WORDS * 4 && SOLO_PLAYOUT_ACCEL_FORCED == SX_PO_OUT_ACCEL_FORCED && SX_PO_STATE_WORDS <= SX_ROWS_MAX_WORDS,
+              "include/solo_mi355x.h, solo_playout.h and solo_rows.h agree");
+struct solo_playout_obj : solo_rows {    // d_verdict[2]: the verdict words of the plan and of the render; d_extra: the held packets, int16 [n_rows][L]
+    int32_t L;
     int32_t *d_slot, *d_sslot;       // [n_rows]: where the last plan put each row (solo_playout_compact_kernel)
     // the tick's intermediates, one allocation (d_scratch) cut up at create
     void* d_scratch;
@@ -1229,28 +1174,20 @@ struct solo_playout_obj {
     SxPoPlanCount* h_count;          // pinned: where the tick reads the plan count
 };
 solo_playout_t* solo_playout_create(int32_t n_rows, int32_t packet_samples) {
-    if (!sx_po_geometry_ok(n_rows, packet_samples)) return NULL;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        fprintf(stderr, "solo_mi355x: no HIP device available -- this library has no CPU path\n");
-        return NULL;
-    }
+    if (!sx_po_geometry_ok(n_rows, packet_samples) || !have_device()) return NULL;
     solo_playout_obj* po = new (std::nothrow) solo_playout_obj();
     if (!po) return NULL;
-    memset(po, 0, sizeof(*po));
-    po->n_rows = n_rows; po->L = packet_samples;
+    po->L = packet_samples;
     const size_t n = (size_t)n_rows, L = (size_t)packet_samples;
     size_t off = 0;
     auto cut = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_rep = cut(n * 64), o_act = cut(n * 4), o_one = cut(n * 4), o_two = cut(n * 4), o_spos = cut(n * 4), o_st1 = cut(n * 4), o_st2 = cut(n * 4),
                  o_cs = cut(n * 2 * SX_TS_MAX_BLOCKS * 2), o_ca = cut(n * SX_TS_MAX_BLOCKS * 2), o_p1 = cut(n * L * 2), o_p2 = cut(n * L * 4), o_g = cut(n * L * 2),
                  o_ts = cut(n * L * 4), o_ta = cut(n * L * 2);
-    if (hipMalloc((void**)&po->d_state, n * SX_PO_STATE_WORDS * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&po->d_held, n * L * sizeof(int16_t)) != hipSuccess ||
-        hipMalloc((void**)&po->d_verdict, 2 * sizeof(uint32_t)) != hipSuccess || hipMalloc((void**)&po->d_slot, n * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&po->d_sslot, n * sizeof(int32_t)) != hipSuccess || hipMalloc(&po->d_scratch, off) != hipSuccess ||
-        hipHostMalloc((void**)&po->h_count, sizeof(SxPoPlanCount)) != hipSuccess || hipMemset(po->d_verdict, 0, 2 * sizeof(uint32_t)) != hipSuccess ||
+    if (hipMalloc((void**)&po->d_slot, n * sizeof(int32_t)) != hipSuccess || hipMalloc((void**)&po->d_sslot, n * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc(&po->d_scratch, off) != hipSuccess || hipHostMalloc((void**)&po->h_count, sizeof(SxPoPlanCount)) != hipSuccess ||
         hipMemset(po->d_slot, 0xFF, n * sizeof(int32_t)) != hipSuccess || hipMemset(po->d_sslot, 0xFF, n * sizeof(int32_t)) != hipSuccess ||
-        solo_playout_reset(po, NULL) != 0 || hipStreamSynchronize(NULL) != hipSuccess) {
+        !rows_alloc(po, n_rows, SX_PO_STATE_WORDS, NULL, 2, packet_samples / 2)) {
         solo_playout_destroy(po);
         return NULL;
     }
@@ -1263,59 +1200,29 @@ solo_playout_t* solo_playout_create(int32_t n_rows, int32_t packet_samples) {
 }
 void solo_playout_destroy(solo_playout_t* po) {
     if (!po) return;
-    dev_free(po->d_state);
-    dev_free(po->d_held);
-    dev_free(po->d_verdict);
+    rows_free(po);
     dev_free(po->d_slot);
     dev_free(po->d_sslot);
     dev_free(po->d_scratch);
     if (po->h_count) (void)hipHostFree(po->h_count);
     delete po;
 }
-int32_t solo_playout_reset(solo_playout_t* po, void* hip_stream) {
-    if (!po) return -1;
-    SOLO_CHECK(hipMemsetAsync(po->d_state, 0, (size_t)po->n_rows * SX_PO_STATE_WORDS * sizeof(int32_t), (hipStream_t)hip_stream));
-    SOLO_CHECK(hipMemsetAsync(po->d_held, 0, (size_t)po->n_rows * (size_t)po->L * sizeof(int16_t), (hipStream_t)hip_stream));
-    return 0;
-}
+int32_t solo_playout_reset(solo_playout_t* po, void* hip_stream) { return rows_reset(po, (hipStream_t)hip_stream); }
 int32_t solo_playout_reset_rows(solo_playout_t* po, const int32_t* h_rows, int32_t n, void* hip_stream) {
-    if (!po || !sx_po_list_ok(h_rows, n, po->n_rows)) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
-    std::vector<SxStreamCtl> recs((size_t)n);
-    for (int32_t i = 0; i < n; i++) { recs[i].stream = h_rows[i]; recs[i].a = recs[i].b = recs[i].c = 0; }
-    int32_t* state = po->d_state;
-    int16_t* held = po->d_held;
-    const int L = po->L;
-    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
-        hipLaunchKernelGGL(solo_playout_reset_rows_kernel, dim3((unsigned)k), dim3(64), 0, st, state, held, L, l);
-    }));
-    return 0;
-}
-static int32_t playout_copy_state(solo_playout_obj* po, const int32_t* d_rows, int32_t n, uint8_t* d_blob, int put, hipStream_t st) {
-    if (!po || !d_blob || n <= 0 || n > po->n_rows || ((uintptr_t)d_blob & 3)) return -1;
-    const size_t words = (size_t)n * sx_po_blob_row_words(po->L);
-    hipLaunchKernelGGL(solo_playout_copy_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, po->d_state, po->d_held, po->n_rows, po->L, d_rows, n,
-                       (i32*)d_blob, put);
-    SOLO_CHECK(hipGetLastError());
-    return 0;
+    return rows_reset_list(po, h_rows, n, (hipStream_t)hip_stream);
 }
 int32_t solo_playout_get_state(solo_playout_t* po, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
-    return playout_copy_state(po, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+    return rows_copy_state(po, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
 }
 int32_t solo_playout_set_state(solo_playout_t* po, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
-    return playout_copy_state(po, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
-}
-static hipError_t playout_list_check(solo_playout_obj* po, const int32_t* d_rows, int32_t n, uint32_t* verdict, hipStream_t st) {
-    if (!d_rows) return hipSuccess;
-    hipLaunchKernelGGL(solo_stream_list_check_kernel, dim3(1), dim3(256), 0, st, d_rows, n, po->n_rows, verdict, (i32*)NULL);
-    return hipGetLastError();
+    return rows_copy_state(po, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
 }
 int32_t solo_playout_plan(solo_playout_t* po, const solo_recv_report_t* d_reports, const int32_t* d_rows, int32_t n, int32_t depth,
                           const solo_playout_params_t* params, int32_t* d_action, int32_t* d_one, int32_t* d_two, int32_t* d_stretch_pos,
                           solo_playout_plan_count_t* d_count, void* hip_stream) {
     if (!po || !sx_po_plan_call_ok(po->n_rows, d_reports, d_rows, n, depth, (const SxPoParams*)params, d_action, d_one, d_two, d_stretch_pos, d_count)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
-    SOLO_CHECK(playout_list_check(po, d_rows, n, po->d_verdict, st));
+    SOLO_CHECK(launch_list_check(d_rows, n, po->n_rows, po->d_verdict, NULL, st));
     SxPoPlanArgs a;
     a.reports = (const uint32_t*)d_reports; a.state = po->d_state; a.map = d_rows; a.action = d_action; a.p = *(const SxPoParams*)params; a.n = n; a.depth = depth;
     SOLO_CHECK(solo_playout_plan_launch(a, d_one, d_two, d_stretch_pos, po->d_slot, po->d_sslot, (SxPoPlanCount*)d_count, po->d_verdict, st));
@@ -1336,9 +1243,9 @@ int32_t solo_playout_render(solo_playout_t* po, const int32_t* d_rows, int32_t n
                                      d_status_one, d_pcm_two, d_status_two, d_ts_stretch, d_cost_stretch, d_ts_accel, d_cost_accel, d_heard, d_outcome, d_status, d_count))
         return -1;
     hipStream_t st = (hipStream_t)hip_stream;
-    SOLO_CHECK(playout_list_check(po, d_rows, n, po->d_verdict + 1, st));
+    SOLO_CHECK(launch_list_check(d_rows, n, po->n_rows, po->d_verdict + 1, NULL, st));
     SxPoRenderArgs a;
-    a.state = po->d_state; a.held = po->d_held; a.map = d_rows; a.action = d_action; a.slot = po->d_slot; a.sslot = po->d_sslot;
+    a.state = po->d_state; a.held = (int16_t*)po->d_extra; a.map = d_rows; a.action = d_action; a.slot = po->d_slot; a.sslot = po->d_sslot;
     a.pcm_one = d_pcm_one; a.st_one = d_status_one; a.pcm_two = d_pcm_two; a.st_two = d_status_two; a.ts_s = d_ts_stretch; a.cost_s = d_cost_stretch;
     a.ts_a = d_ts_accel; a.cost_a = d_cost_accel; a.heard = d_heard; a.outcome = d_outcome; a.status = d_status;
     a.n = n; a.n_one = n_one; a.n_two = n_two; a.n_stretch = n_stretch; a.L = po->L; a.M = po->L / block_samples;
@@ -1425,7 +1332,7 @@ int32_t solo_batch_export_streams(solo_batch_t* b, const int32_t* d_streams, int
         if (r) return r;
     }
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_EXPORT;
-    SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
+    SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, NULL, st));
     SOLO_CHECK(solo_migrate_export_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
     return 0;
 }
@@ -1438,7 +1345,7 @@ int32_t solo_batch_import_streams(solo_batch_t* b, const int32_t* d_streams, int
         if (r) return r;
     }
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_IMPORT;
-    SOLO_CHECK(launch_list_check(b, d_streams, n, verdict, NULL, st));
+    SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, NULL, st));
     SOLO_CHECK(solo_migrate_import_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
     return 0;
 }
@@ -1645,7 +1552,7 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
             SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinA[b->enc_seq & 1u], 0));
             SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinC[b->enc_seq & 1u], 0));
         }
-        SOLO_CHECK(launch_list_check(b, map, n, verdict, d_status, st));
+        SOLO_CHECK(launch_list_check(map, n, b->n_streams, verdict, d_status, st));
     }
     if (b->enc_seq > 0 && (b->last_np != n_packets || b->last_cp != cp || b->evC_valid == 0)) {
         // the previous call laid its hand-over records out differently (or ran the persistent schedule): no chunk-wise reuse, wait for all of it

@@ -75,16 +75,8 @@ static inline bool sx_po_params_ok(const SxPoParams* p) {
 static inline bool sx_po_geometry_ok(i32 n_rows, i32 L) {
     return n_rows > 0 && L > 0 && L <= SX_PO_MAX_L && L % 8 == 0 && (i64)n_rows * (2 * (i64)L) < ((i64)1 << 31);
 }
-// a HOST list of rows for the reset: 1 .. n_rows indices inside [0, n_rows), none twice
-static inline bool sx_po_list_ok(const i32* rows, i32 n, i32 n_rows) {
-    if (!rows || n <= 0 || n > n_rows) return false;
-    for (i32 i = 0; i < n; i++) {
-        if (rows[i] < 0 || rows[i] >= n_rows) return false;
-        for (i32 j = 0; j < i; j++)
-            if (rows[j] == rows[i]) return false;
-    }
-    return true;
-}
+// (the name the host build of tests/playout_host.cpp asks the host-list rule by)
+static inline bool sx_po_list_ok(const i32* rows, i32 n, i32 n_rows) { return sx_list_ok(rows, n, n_rows); }
 
 // what the host checks of a call before it enqueues anything (solo_api.hip; the host build of the tests asks the same functions)
 static inline bool sx_po_rows_ok(i32 n_rows, const void* rows, i32 n) { return n > 0 && n <= n_rows && (rows || n == n_rows); }
@@ -357,26 +349,6 @@ __global__ void __launch_bounds__(SX_PO_TILE) solo_playout_count_kernel(const i3
     }
 }
 
-// the listed rows back to the initial state (all zero: not running, nothing held); one wavefront per record, the list travels by value
-__global__ void __launch_bounds__(64) solo_playout_reset_rows_kernel(i32* state, i16* held, int L, const SxStreamCtlList l) {
-    const int row = l.r[blockIdx.x].stream;
-    if (threadIdx.x < SX_PO_STATE_WORDS) state[(size_t)row * SX_PO_STATE_WORDS + threadIdx.x] = 0;
-    i32* h = (i32*)(held + (size_t)row * L);
-    SX_PAR(w, L >> 1) h[w] = 0;
-}
-// plain copies of the listed rows' records and held packets (rows = NULL: rows 0 .. n - 1) to (put = 0) or from a blob of
-// sx_po_blob_row_words(L) words a row; an index outside [0, n_rows) moves nothing
-__global__ void __launch_bounds__(256) solo_playout_copy_kernel(i32* state, i16* held, int n_rows, int L, const i32* rows, int n, i32* blob, int put) {
-    const size_t rw = sx_po_blob_row_words(L), i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * rw) return;
-    const int r = (int)(i / rw), w = (int)(i % rw);
-    const int row = rows ? rows[r] : r;
-    if (row < 0 || row >= n_rows) return;
-    i32* s = w < SX_PO_STATE_WORDS ? state + (size_t)row * SX_PO_STATE_WORDS + w : (i32*)(held + (size_t)row * L) + (w - SX_PO_STATE_WORDS);
-    if (put) *s = blob[i];
-    else blob[i] = *s;
-}
-
 static inline hipError_t solo_playout_plan_launch(const SxPoPlanArgs& a, i32* one, i32* two, i32* spos, i32* slot, i32* sslot, SxPoPlanCount* count,
                                                   const u32* verdict, hipStream_t s) {
     const unsigned tiles = (unsigned)((a.n + SX_PO_TILE - 1) / SX_PO_TILE);
@@ -394,16 +366,10 @@ static inline hipError_t solo_playout_render_launch(const SxPoRenderArgs& a, SxP
     return hipGetLastError();
 }
 #else
-static inline bool sx_po_map_ok(const i32* map, int n, int n_rows) {
-    if (map)
-        for (int i = 0; i < n; i++)
-            if (map[i] < 0 || map[i] >= n_rows || (i > 0 && map[i - 1] >= map[i])) return false;
-    return true;
-}
 // Host form of the plan (tests): the rows one by one through sx_po_plan_row, then the lists as the compaction leaves them.
 // -> false: the list is not strictly increasing inside [0, n_rows), nothing but count->n_one = -1 is written
 static inline bool sx_po_plan_host(const SxPoPlanArgs& a, int n_rows, i32* one, i32* two, i32* spos, i32* slot, i32* sslot, SxPoPlanCount* count) {
-    if (!sx_po_map_ok(a.map, a.n, n_rows)) { count->n_one = -1; return false; }
+    if (!sx_map_ok(a.map, a.n, n_rows)) { count->n_one = -1; return false; }
     i32 k1 = 0, k2 = 0, k3 = 0;
     for (int i = 0; i < a.n; i++) {
         const int s = a.map ? a.map[i] : i;
@@ -432,7 +398,7 @@ static inline void sx_po_gather_host(const i16* pcm_one, const i32* spos, int n_
 }
 // ... of the render and its count
 static inline bool sx_po_render_host(const SxPoRenderArgs& a, int n_rows, SxPoRenderCount* count) {
-    if (!sx_po_map_ok(a.map, a.n, n_rows)) { if (count) count->outcome[0] = -1; return false; }
+    if (!sx_map_ok(a.map, a.n, n_rows)) { if (count) count->outcome[0] = -1; return false; }
     for (int i = 0; i < a.n; i++) sx_po_render_row(a, i);
     if (count) {
         for (int o = 0; o < SX_PO_N_OUTCOMES; o++) count->outcome[o] = 0;

@@ -99,15 +99,8 @@ static inline bool sx_rs_call_ok(const SxRsCfg& c, i32 n_rows, i32 n, i32 n_pack
     if ((a & 15) || (b & 15)) return false;
     return !(a < b + (uintptr_t)e_out * 2 && b < a + (uintptr_t)e_in * 2);
 }
-// a HOST list of rows to reset: 1 .. n_rows of them, inside [0, n_rows), none twice
-static inline bool sx_rs_list_ok(const i32* rows, i32 n, i32 n_rows) {
-    if (!rows || n <= 0 || n > n_rows) return false;
-    for (i32 i = 0; i < n; i++) {
-        if (rows[i] < 0 || rows[i] >= n_rows) return false;
-        for (i32 j = 0; j < i; j++) if (rows[j] == rows[i]) return false;
-    }
-    return true;
-}
+// (the name the host build of tests/resample_host.cpp asks the host-list rule by)
+static inline bool sx_rs_list_ok(const i32* rows, i32 n, i32 n_rows) { return sx_list_ok(rows, n, n_rows); }
 
 struct alignas(16) SxRsX8 { u32 w[4]; };                    // what one lane loads and stores: 8 samples
 
@@ -367,11 +360,6 @@ __global__ void __launch_bounds__(64) solo_resample_kernel(const SxRsArgs a, SxR
     if (blockIdx.x == 0 && threadIdx.x == 0 && count) { count->rows = a.n; count->listed = a.n; }
     sx_rs_group(a, (int)blockIdx.x * SX_RS_ROWS, sx_rs_lds);
 }
-// the listed rows' state records zeroed (= SKP_Silk_resampler_init): one wavefront per record, the list travels by value
-__global__ void __launch_bounds__(64) solo_resample_reset_kernel(i32* state, const SxStreamCtlList l) {
-    const int row = l.r[blockIdx.x].stream;
-    if (threadIdx.x < SX_RS_STATE_WORDS) state[(size_t)row * SX_RS_STATE_WORDS + threadIdx.x] = 0;
-}
 static inline hipError_t solo_resample_launch(const SxRsArgs& a, SxRsCount* count, const u32* verdict, hipStream_t s) {
     const unsigned groups = (unsigned)((a.n + SX_RS_ROWS - 1) / SX_RS_ROWS);
     const size_t lds = (size_t)SX_RS_ROWS * (size_t)a.c.row_words * sizeof(u32);
@@ -382,12 +370,10 @@ static inline hipError_t solo_resample_launch(const SxRsArgs& a, SxRsCount* coun
 // Host form of the launch (tests): every group through sx_rs_group.  -> false: the list is not strictly increasing inside [0, n_rows),
 // nothing but count->rows = -1 is written
 static inline bool sx_rs_host(const SxRsArgs& a, int n_rows, SxRsCount* count) {
-    if (a.map)
-        for (int i = 0; i < a.n; i++)
-            if (a.map[i] < 0 || a.map[i] >= n_rows || (i > 0 && a.map[i - 1] >= a.map[i])) {
-                if (count) count->rows = -1;
-                return false;
-            }
+    if (!sx_map_ok(a.map, a.n, n_rows)) {
+        if (count) count->rows = -1;
+        return false;
+    }
     u32* lds = new u32[(size_t)SX_RS_ROWS * (size_t)a.c.row_words]();
     for (int row0 = 0; row0 < a.n; row0 += SX_RS_ROWS) sx_rs_group(a, row0, lds);
     if (count) { count->rows = a.n; count->listed = a.n; }

@@ -45,7 +45,7 @@ struct SxVadCount { i32 rows, rooms, selected, changes; };  // == solo_vad_count
 static_assert(sizeof(SxVadCount) == sizeof(SxMixCount), "the room plan's scan kernel writes {rows, rooms, 0, 0} through a SxMixCount");
 struct SxVadSelectParams { i32 max_speakers, on_q8, off_q8, hang_packets, stick; };     // == solo_vad_select_params_t
 
-// word w of the record SKP_Silk_VAD_Init leaves (VAD.c:39-67), selection state zero
+// word w of the record SKP_Silk_VAD_Init leaves (VAD.c:39-67), selection state zero: what the create and reset calls write
 SX_HD i32 sx_vad_init_word(int w) {
     if (w >= 10 && w < 14) return 100 * 256;                                    // NrgRatioSmth_Q8: 20 dB
     if (w >= 15 && w < 27) {
@@ -78,15 +78,8 @@ static inline bool sx_vsel_call_ok(i32 n_rows, i32 n, const void* sa, const void
     if (n <= 0 || n > n_rows || n_packets <= 0 || frames <= 0 || n_rooms <= 0 || n_rooms > n_rows) return false;
     return (i64)n * (i64)n_packets * (i64)frames < ((i64)1 << 31) && (i64)n_rooms * (i64)n_packets < ((i64)1 << 31);
 }
-// a HOST list of rows to reset: 1 .. n_rows of them, inside [0, n_rows), none twice
-static inline bool sx_vad_list_ok(const i32* rows, i32 n, i32 n_rows) {
-    if (!rows || n <= 0 || n > n_rows) return false;
-    for (i32 i = 0; i < n; i++) {
-        if (rows[i] < 0 || rows[i] >= n_rows) return false;
-        for (i32 j = 0; j < i; j++) if (rows[j] == rows[i]) return false;
-    }
-    return true;
-}
+// (the name the host builds of tests/vad_host.cpp and tests/agc_host.cpp ask the host-list rule by)
+static inline bool sx_vad_list_ok(const i32* rows, i32 n, i32 n_rows) { return sx_list_ok(rows, n, n_rows); }
 
 // ---- one frame of N samples ---------------------------------------------------------------------------------------------------------
 // LDS of a row (the host form: plain memory).  X holds the bands, highest first: X3 (N / 2 samples), X2 (N / 4), X1 (N / 8), X0 (N / 8,
@@ -364,28 +357,6 @@ __global__ void __launch_bounds__(64) solo_vad_kernel(const SxVadArgs a, SxVadCo
     if (blockIdx.x == 0 && threadIdx.x == 0 && count) { SxVadCount c; c.rows = a.n; c.rooms = 0; c.selected = 0; c.changes = 0; *count = c; }
     sx_vadf_row<N>(a, (int)blockIdx.x, &lds);
 }
-// the listed rows' records to what SKP_Silk_VAD_Init leaves: one wavefront per record, the list travels by value
-__global__ void __launch_bounds__(64) solo_vad_reset_rows_kernel(i32* state, const SxStreamCtlList l) {
-    const int row = l.r[blockIdx.x].stream;
-    if (threadIdx.x < SX_VAD_STATE_WORDS) state[(size_t)row * SX_VAD_STATE_WORDS + threadIdx.x] = sx_vad_init_word((int)threadIdx.x);
-}
-__global__ void __launch_bounds__(256) solo_vad_reset_kernel(i32* state, int n_rows) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < (size_t)n_rows * SX_VAD_STATE_WORDS) state[i] = sx_vad_init_word((int)(i % SX_VAD_STATE_WORDS));
-}
-// plain copies of the listed rows' records (rows = NULL: rows 0 .. n - 1) to (put = 0) or from a buffer [n][128]; an index outside
-// [0, n_rows) moves nothing.  (WORDS: the record of this stage, or the 16 words of solo_agc.h)
-template <int WORDS = SX_VAD_STATE_WORDS>
-__global__ void __launch_bounds__(256) solo_vad_copy_kernel(i32* state, int n_rows, const i32* rows, int n, i32* blob, int put) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * WORDS) return;
-    const int r = (int)(i / WORDS), w = (int)(i % WORDS);
-    const int row = rows ? rows[r] : r;
-    if (row < 0 || row >= n_rows) return;
-    i32* s = state + (size_t)row * WORDS + w;
-    if (put) *s = blob[i];
-    else blob[i] = *s;
-}
 // one wavefront per room
 __global__ void __launch_bounds__(64) solo_vad_select_kernel(const SxVselArgs a, SxVadCount* count, const i32* room_ids, const u32* verdict) {
     if (sx_map_refused(room_ids, verdict)) return;
@@ -412,17 +383,11 @@ static inline hipError_t solo_vad_select_launch(SxVselArgs a, const i32* room, i
     return hipGetLastError();
 }
 #else
-static inline bool sx_vad_map_ok(const i32* map, int n, int n_rows) {
-    if (map)
-        for (int i = 0; i < n; i++)
-            if (map[i] < 0 || map[i] >= n_rows || (i > 0 && map[i - 1] >= map[i])) return false;
-    return true;
-}
 // Host form of the launch (tests): every row through sx_vadf_row.  -> false: the list is not strictly increasing inside [0, n_rows),
 // nothing but count->rows = -1 is written
 template <int N>
 static inline bool sx_vad_host_n(const SxVadArgs& a, int n_rows, SxVadCount* count) {
-    if (!sx_vad_map_ok(a.map, a.n, n_rows)) {
+    if (!sx_map_ok(a.map, a.n, n_rows)) {
         if (count) count->rows = -1;
         return false;
     }
@@ -438,7 +403,7 @@ static inline bool sx_vad_host(int frame, const SxVadArgs& a, int n_rows, SxVadC
 // ... of the selection: the room plan (sx_room_plan_host), then every room through sx_vsel_room.
 // -> false: a bad list or a room id outside [-1, n_rooms), nothing but count->rows = -1 is written
 static inline bool sx_vsel_host(SxVselArgs a, const i32* room, int n, int n_rooms, int n_rows, SxVadCount* count) {
-    bool ok = sx_vad_map_ok(a.map, n, n_rows);
+    bool ok = sx_map_ok(a.map, n, n_rows);
     for (int i = 0; ok && i < n; i++) ok = room[i] >= -1 && room[i] < n_rooms;
     if (!ok) {
         count->rows = -1;

@@ -17,7 +17,7 @@ import solo_testlib as T
 SYMBOLS = ("solo_playout_create", "solo_playout_destroy", "solo_playout_reset", "solo_playout_reset_rows", "solo_playout_get_state",
            "solo_playout_set_state", "solo_playout_plan", "solo_playout_gather", "solo_playout_render", "solo_playout_tick")
 KERNELS = ("solo_playout_plan_kernel", "solo_playout_compact_kernel", "solo_playout_gather_kernel", "solo_playout_render_kernel",
-           "solo_playout_count_kernel", "solo_playout_reset_rows_kernel", "solo_playout_copy_kernel")
+           "solo_playout_count_kernel", "solo_rows_reset_kernel", "solo_rows_reset_all_kernel", "solo_rows_copy_kernel")
 
 
 @pytest.fixture(scope="module")
