@@ -143,6 +143,31 @@ int32_t solo_batch_reset_streams(solo_batch_t *b, const int32_t *h_streams, int3
  * files a desc = -1 arrival follows the stream's decoder useMDIndex when solo_recv_insert runs. */
 int32_t solo_batch_update_streams(solo_batch_t *b, const int32_t *h_streams, int32_t n, int32_t which,
                                   const USER_Ctrl_enc *h_enc, const USER_Ctrl_dec *h_dec, void *hip_stream);
+/* Graph capture.  solo_batch_encode, solo_batch_decode, solo_batch_decode_split, the subset calls, solo_batch_wait_encode,
+ * solo_recv_insert, solo_recv_decode and the calls below that say so can be recorded into a graph (hipStreamBeginCapture on hip_stream,
+ * torch.cuda.graph) and replayed; tests/test_gpu_graph_replay.py captures every one of them.  What holds for all of them:
+ *   Set-up comes first.  A handle's FIRST encode call, its first decode call and solo_recv_create / solo_recv_track allocate, create
+ *     streams and events and read the environment: they cannot run inside a capture.  The same goes for scratch: make one call of the
+ *     same geometry (or of the largest the graph's life will see) before capturing.  A graph holds the ADDRESSES of the handle's scratch
+ *     (hand-over records, extraction records, the mix / send scratch): any later call, captured or not, that is larger than every one
+ *     before re-allocates it, and a graph captured earlier must then be captured again -- replaying it would write to freed memory.
+ *   Frozen into the graph: every host argument -- n, n_packets, n_arrivals, payload_bytes, n_rooms, max_speakers, first_seq, min_ready,
+ *     max_span, flags, the caps, the counts solo_playout_render takes, the parameter structs (they travel as kernel arguments) -- and
+ *     the pointers.  A replay numbers its packets with the SAME first_seq: a tick that moves on brings d_seq_base and advances it on
+ *     the device.  What a replay varies is the CONTENTS of device buffers: PCM, payloads, arrivals (pad a tick that brought fewer than
+ *     n_arrivals with records of stream -1: they are counted `bad` and nothing else), the d_streams / d_rows lists, rooms, gains.
+ *   Order.  The events by which one encode call of a handle waits for the one before (also across streams) are waited for only between
+ *     calls of ONE context: both issued on running streams, or both inside the same capture; and the event a decode call leaves orders
+ *     nothing outside the graph it was recorded in.  Across the boundary the stream is the order: a graph launch runs as a whole where it
+ *     stands in its stream, so launch the replays and issue the eager calls of a handle on one stream, or order the streams yourself.  With asynchronous joins the solo_batch_wait_encode of a captured encode call
+ *     belongs into the same capture.
+ *   Schedules.  SOLO_ENC_PERSIST=1 does not survive a replay (its tickets are host counters passed by value: the second replay would
+ *     find the first one's flags raised): such an encode call is refused inside a capture (-hipErrorStreamCaptureUnsupported).
+ *     SOLO_ENC_GATE=1 replays correctly but stops gating: its targets are frozen while the device counters run on, so from the second
+ *     replay on -- and for eager calls afterwards -- every gate opens at once (never the 20 ms bail-out).  solo_batch_set_timing
+ *     brackets do not belong into a capture.
+ *   Hardware queues.  An encode call of n_packets > 1 is a graph with parallel branches (three internal streams).  Operators report
+ *     that the HIP runtime can crash replaying such a graph with fewer than 4 hardware queues (GPU_MAX_HW_QUEUES; not measured here). */
 int32_t solo_batch_encode(solo_batch_t *b, const int16_t *d_pcm, int32_t n_packets, uint8_t *d_bits,
                           int16_t *d_nbytes, int32_t *d_status, void *hip_stream);
 int32_t solo_batch_decode(solo_batch_t *b, const uint8_t *d_bits, const int16_t *d_nbytes,
@@ -168,7 +193,9 @@ int32_t solo_batch_decode_split(solo_batch_t *b, const uint8_t *d_descA, const i
  * mapping of solo_batch_decode_split; nothing arrived = concealment), frees those entries and advances the play-out positions.
  * Like solo_batch_decode_split it refuses a packet whose descriptions together exceed 252 bytes: not decoded, d_status -11.
  * d_pcm int16 [N][n_packets][packet samples], d_status int32 [N] or NULL.  Calls on one handle must be ordered (same stream, or
- * events).  solo_recv_stats copies {inserted, late, ahead, duplicate, bad, 0, 0, 0} to HOST memory (synchronises the stream). */
+ * events).  solo_recv_stats copies {inserted, late, ahead, duplicate, bad, 0, 0, 0} to HOST memory (synchronises the stream).
+ * solo_recv_insert and solo_recv_decode enqueue kernels on hip_stream only and can be captured (n_arrivals, payload_bytes and n_packets are
+ * frozen); solo_recv_create and solo_recv_stats cannot. */
 typedef struct { int32_t stream, seq, desc, offset, len; } solo_arrival_t;
 int32_t solo_recv_create(solo_batch_t *b, int32_t depth, int32_t slot_bytes, int32_t first_seq, void *hip_stream);
 int32_t solo_recv_insert(solo_batch_t *b, const solo_arrival_t *d_arrivals, int32_t n_arrivals, const uint8_t *d_payload,
@@ -183,7 +210,8 @@ int32_t solo_recv_reset_streams(solo_batch_t *b, const int32_t *h_streams, int32
                                 void *hip_stream);
 /* Subset calls: encode, decode or play out only the n streams listed in d_streams, so that idle slots of a handle cost nothing.
  *   d_streams  int32 [n]  DEVICE array, strictly increasing, every index in [0, N).  Being on the device, a per-tick list needs no
- *                         host copy and the call can be captured in a graph.
+ *                         host copy and the call can be captured in a graph (n itself is frozen: a replay brings other contents,
+ *                         not another length).
  *   I/O is COMPACT: row i of d_pcm, d_bits, d_nbytes, d_recv and d_status belongs to stream d_streams[i] (shapes as in the
  *   calls above with n in place of N).  The codec state, the decoder state, the receiver queue and the play-out position are
  *   those of stream d_streams[i].  A listed stream moves on exactly as if it had been called alone; an UNLISTED stream keeps its
@@ -437,8 +465,8 @@ int32_t solo_mix_selected(solo_batch_t *b, const int16_t *d_pcm_in, int32_t n, i
  * n_packets <= 0; a negative cap; n_dst x n_packets x 2 >= 2^31 or n_src x n_packets x 2 >= 2^31.  A d_source entry outside [-1, n_src) is
  * found on the device, ahead of the other kernels: nothing is written except d_count->records = -1.
  * Any handle will do (slot_bytes and the packet geometry are used, and the scratch of solo_send_pack: 8 bytes per source packet, 4 per source
- * row and 24 per 256 packets, grown as there).  Six short kernels on hip_stream only, no host synchronisation; the call does not wait for the handle's
- * internal streams, and calls on one handle must be ordered. */
+ * row and 24 per 256 packets, grown as there).  Six short kernels on hip_stream only, no host synchronisation, so the call can be captured like
+ * solo_send_pack; the call does not wait for the handle's internal streams, and calls on one handle must be ordered. */
 int32_t solo_send_fanout(solo_batch_t *b, const uint8_t *d_bits, const int16_t *d_nbytes, int32_t n_src,
                          const int32_t *d_source, const int32_t *d_dst_stream, int32_t n_dst,
                          const uint8_t *d_send, int32_t n_packets, const int32_t *d_seq_base, int32_t first_seq,
@@ -765,7 +793,8 @@ int32_t solo_batch_import_streams(solo_batch_t *b, const int32_t *d_streams, int
  * solo_batch_wait_encode(b, stream, which): which = 0 the most recent encode call, 1 the one before; the INPUT buffers of a
  * call must stay valid and unmodified until then as well (a stream-ordered allocator does not know the handle's internal
  * streams).  Default: off (every
- * call is complete on its stream when the next operation of that stream runs). */
+ * call is complete on its stream when the next operation of that stream runs).  solo_batch_wait_encode can be captured, and for an encode
+ * call inside a capture it must be (see "Graph capture"); solo_batch_set_async_join is a host switch, read when a call is issued. */
 int32_t solo_batch_set_async_join(solo_batch_t *b, int32_t on);
 int32_t solo_batch_wait_encode(solo_batch_t *b, void *hip_stream, int32_t which);
 /* Geometry / introspection */

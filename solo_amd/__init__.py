@@ -435,11 +435,16 @@ class SoloBatch:
     def _subset(self, streams):
         """streams= of encode / decode / recv_decode: a sequence or an int32 CUDA tensor of stream indices, strictly increasing ->
         (int32 tensor on the device, n).  Checked here (the library checks the device list once more and refuses
-        a bad one with status -1, but by then the call is enqueued)."""
+        a bad one with status -1, but by then the call is enqueued).  While the current stream is capturing a graph a CUDA tensor
+        is taken as it is -- reading it would synchronise, and a replay brings other contents anyway: the device check is the check."""
         t = self.torch
         on_dev = getattr(streams, "is_cuda", False)
         if on_dev and (streams.dtype != t.int32 or len(streams.shape) != 1):     # (need not be contiguous: it is made so below)
             raise ValueError("streams: a sequence or a 1-D int32 CUDA tensor")
+        if on_dev and t.cuda.is_initialized() and t.cuda.is_current_stream_capturing():
+            if not streams.is_contiguous() or not 0 < streams.shape[0] <= self.n_streams:
+                raise ValueError("streams: in a graph capture a contiguous int32 CUDA tensor of 1 .. %d indices" % self.n_streams)
+            return streams, int(streams.shape[0])
         idx = _increasing("streams", streams, self.n_streams)
         if on_dev:
             return streams.contiguous(), len(idx)

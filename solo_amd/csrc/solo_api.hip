@@ -238,6 +238,7 @@ struct solo_batch {
     hipEvent_t evFork, evJoinA[2], evJoinC[2], evA[SOLO_MAX_CHUNKS], evB[SOLO_MAX_CHUNKS], evC[SOLO_MAX_CHUNKS];
     int async_join;                  // solo_batch_set_async_join: encode returns without joining its streams into the caller's
     unsigned int enc_seq;            // encode calls so far (selects the join-event set)
+    unsigned long long join_cap[2];  // the graph capture each join-event set (and with it evC[]) was last recorded in, 0 = on running streams
     int evC_valid;                   // chunks of the previous call whose coding-done events are recorded
     int last_np, last_cp;            // packets / packets per chunk of the previous call (layout of the hand-over records)
     hipEvent_t tev[3][SOLO_MAX_CHUNKS][2];   // timing brackets per kernel type / launch (created with set_timing)
@@ -331,6 +332,20 @@ static hipError_t grow_scratch(void*& p, size_t& bytes, size_t need, hipStream_t
     return e;
 }
 
+// The graph capture `st` is recording into, 0 when it is not capturing.  The events that order one encode call of a handle against the
+// next (evJoinA / evJoinC / evC) mean something only inside the context they were recorded in: recorded in a capture they are nodes of
+// that graph and order nothing outside it, and the runtime refuses (hipErrorStreamCaptureIsolation) an internal stream that has joined a
+// capture and waits for an event it recorded before.  So an encode call waits for the previous call's events only when both were issued
+// in ONE context -- both on running streams, or both in the same capture.  Across the boundary the caller's stream is the order: a graph
+// launch runs as a whole where it stands in its stream (include/solo_mi355x.h, "Graph capture").  (evDecDone needs none of this: a
+// decode call runs on the caller's stream alone, and the runtime takes its wait for an event of a running stream into a capture.)
+static unsigned long long stream_capture(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    unsigned long long id = 0;
+    if (hipStreamGetCaptureInfo(st, &cs, &id) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return cs == hipStreamCaptureStatusActive ? (id ? id : ~0ull) : 0;
+}
+
 #ifdef SOLO_WITH_ENCODER
 static int enc_hb_joint(const solo_batch* b) { return ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode); }
 static int enc_frames_per_packet(const solo_batch* b) { return ctrl_frames_per_packet(b->enc_ctrl.framesize_ms); }
@@ -407,6 +422,7 @@ int32_t solo_batch_set_async_join(solo_batch_t* b, int32_t on) {
 int32_t solo_batch_wait_encode(solo_batch_t* b, void* hip_stream, int32_t which) {
     if (!b || !b->pipe_ready || which < 0 || which > 1 || b->enc_seq <= (unsigned int)which) return b ? 0 : -1;
     const int js = (int)((b->enc_seq - 1u - (unsigned int)which) & 1u);
+    if (b->join_cap[js] != stream_capture((hipStream_t)hip_stream)) return 0;      // (the other side of a capture: stream order, see stream_capture)
     SOLO_CHECK(hipStreamWaitEvent((hipStream_t)hip_stream, b->evJoinA[js], 0));
     SOLO_CHECK(hipStreamWaitEvent((hipStream_t)hip_stream, b->evJoinC[js], 0));
     return 0;
@@ -416,12 +432,14 @@ int32_t solo_batch_last_encode_chunks(const solo_batch_t* b) { return b ? b->las
 // Makes `s` wait for the handle's encode work still in flight on its internal streams and for its most recent decode call (before
 // init kernels overwrite states).
 static int32_t solo_wait_in_flight(solo_batch_t* b, hipStream_t s) {
+    const unsigned long long cap = stream_capture(s);
     if (b->pipe_ready && b->enc_seq > 0) {
         // kernels of the most recent encode calls may still run on the internal streams (always so with async joins, and when
         // reset is issued on another stream than the encode was): the init kernels must not overtake them
         for (int i = 0; i < 2; i++) {
             if (b->enc_seq <= (unsigned int)i) break;
             const int js = (int)((b->enc_seq - 1u - (unsigned int)i) & 1u);
+            if (b->join_cap[js] != cap) continue;
             SOLO_CHECK(hipStreamWaitEvent(s, b->evJoinA[js], 0));
             SOLO_CHECK(hipStreamWaitEvent(s, b->evJoinC[js], 0));
         }
@@ -1424,6 +1442,8 @@ static int32_t solo_enc_pipe_setup(solo_batch* b) {
 static int32_t solo_encode_persist(solo_batch* b, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes, int32_t* d_status,
                                    hipStream_t st, void* nin, void* nout, void* cin) {
     const solo_enc_ops* ops = b->eops;
+    // not in a graph: the tickets are host counters passed by value, a replay would find the flags of the replay before it already raised
+    if (stream_capture(st) != 0) return -(int32_t)hipErrorStreamCaptureUnsupported;
     const int G = b->persist_group, ngroups = (b->n_streams + G - 1) / G;
     const bool tm = b->timing && b->tev_ready && ngroups <= SOLO_MAX_CHUNKS;
     unsigned int* ana = b->d_flags;
@@ -1436,7 +1456,7 @@ static int32_t solo_encode_persist(solo_batch* b, const int16_t* d_pcm, int32_t 
     SOLO_CHECK(hipEventRecord(b->evFork, st));
     SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evFork, 0));
     SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evFork, 0));
-    if (b->enc_seq > 0) {          // the previous call (of either schedule) has read its hand-over records to the end
+    if (b->enc_seq > 0 && b->join_cap[(b->enc_seq - 1u) & 1u] == 0) {          // the previous call (of either schedule) has read its hand-over records to the end
         const int jp = (int)((b->enc_seq - 1u) & 1u);
         SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evJoinC[jp], 0));
         SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evJoinC[jp], 0));
@@ -1483,6 +1503,7 @@ static int32_t solo_encode_persist(solo_batch* b, const int16_t* d_pcm, int32_t 
     // join (also after a refused launch: whatever was enqueued still runs, nothing of this call stays forked)
     const int js = (int)(b->enc_seq & 1u);
     b->enc_seq++;
+    b->join_cap[js] = 0;
     (void)hipEventRecord(b->evJoinA[js], b->sA);
     (void)hipEventRecord(b->evJoinC[js], b->sB);
     if (!b->async_join || lerr != hipSuccess) {
@@ -1542,19 +1563,24 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         SOLO_CHECK(grow_scratch(b->d_rc_scratch, b->rc_scratch_bytes, ops->rc_scratch_bytes(gs, cp), b->sC));
     }
     const bool tm_req = b->timing && b->tev_ready;
+    // the previous call's events are waited for only inside one context (stream_capture); on the other side of a capture this call
+    // starts behind everything of it through the fork from `st`
+    const unsigned long long cap = stream_capture(st);
+    if (b->enc_seq > 0 && b->join_cap[(b->enc_seq - 1u) & 1u] != cap) b->evC_valid = -1;
     uint32_t* verdict = NULL;
     if (map) {
         // the layout of the hand-over records depends on the list: no chunk-wise reuse across a subset call, either side
-        b->evC_valid = 0;
+        if (b->evC_valid > 0) b->evC_valid = 0;
         // the verdict word of this call; the call two before used the same one: its kernels must be through
         verdict = b->d_verdict + SOLO_VERDICT_ENC + (b->enc_seq & 1u);
-        if (b->enc_seq >= 2) {
+        if (b->enc_seq >= 2 && b->join_cap[b->enc_seq & 1u] == cap) {
             SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinA[b->enc_seq & 1u], 0));
             SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinC[b->enc_seq & 1u], 0));
         }
         SOLO_CHECK(launch_list_check(map, n, b->n_streams, verdict, d_status, st));
     }
-    if (b->enc_seq > 0 && (b->last_np != n_packets || b->last_cp != cp || b->evC_valid == 0)) {
+    if (b->evC_valid < 0) b->evC_valid = 0;          // (the previous call was issued on the other side of a capture: nothing to wait for)
+    else if (b->enc_seq > 0 && (b->last_np != n_packets || b->last_cp != cp || b->evC_valid == 0)) {
         // the previous call laid its hand-over records out differently (or ran the persistent schedule): no chunk-wise reuse, wait for all of it
         SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evJoinC[(b->enc_seq - 1u) & 1u], 0));
         SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evJoinA[(b->enc_seq - 1u) & 1u], 0));
@@ -1625,6 +1651,7 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     b->evC_valid = (ok && ngroups == 1 && !map) ? nchunks : 0;       // chunk-wise hand-over guards only for single-group calls of every stream
     const int js = (int)(b->enc_seq & 1u);
     b->enc_seq++;
+    b->join_cap[js] = cap;
     (void)hipEventRecord(b->evJoinA[js], b->sA);
     (void)hipEventRecord(b->evJoinC[js], b->sC);      // (sC's last launch waits for sB's)
     if (!b->async_join || !ok) {
