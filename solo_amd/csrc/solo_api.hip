@@ -185,6 +185,7 @@ extern "C" const solo_dec_ops* solo_wb_dec_ops();          // the same decoder c
 #ifdef SOLO_WITH_ENCODER
 #include "solo_enc_ops.h"
 extern "C" int solo_launch_gate(const unsigned int* flag, unsigned int target, void* hip_stream);      // solo_nsq_row.hip
+extern "C" int solo_launch_gate_for(const unsigned int* flag, unsigned int target, int max_iters, void* hip_stream);
 extern "C" const solo_enc_ops* solo_nb_enc_ops();                                                      // solo_enc_k.hip
 extern "C" const solo_enc_ops* solo_wb_enc_ops();                                                      // solo_enc_k_wb.hip
 #endif
@@ -193,6 +194,8 @@ extern "C" const solo_enc_ops* solo_wb_enc_ops();                               
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
 #define SOLO_MAX_CHUNKS 64
+#define SOLO_ENC_RC_BATCH_DEFAULT 5
+#define SOLO_HB_GATE_ITERS 500           // bound of the high band's wait for the next quantiser launch, ~1 us each
 // verdict words of subset calls (solo_stream_list_check_kernel), one per kind of call so that calls of different kinds in flight on
 // different streams do not share one
 enum {
@@ -234,6 +237,7 @@ struct solo_batch {
     int ev_ready, ev_enc, ev_dec;
     // encoder: three internal streams (analysis / front kernel: sA, quantiser: sB, third stage of the launch-per-chunk schedule: sC)
     int pipe_ready, chunk_packets;   // chunk_packets: packets per chunk of the launch-per-chunk schedule (env SOLO_ENC_CHUNK, default 1; 0 = one chunk)
+    int rc_batch;                    // packets per range-coder launch of the launch-per-chunk schedule (env SOLO_ENC_RC_BATCH; 1 = one launch per chunk)
     hipStream_t sA, sB, sC;
     hipEvent_t evFork, evJoinA[2], evJoinC[2], evA[SOLO_MAX_CHUNKS], evB[SOLO_MAX_CHUNKS], evC[SOLO_MAX_CHUNKS];
     int async_join;                  // solo_batch_set_async_join: encode returns without joining its streams into the caller's
@@ -1397,6 +1401,13 @@ static int32_t solo_enc_pipe_setup(solo_batch* b) {
     b->persist = env_int("SOLO_ENC_PERSIST", 0) != 0;
     b->chunk_packets = env_int("SOLO_ENC_CHUNK", 1);
     if (b->chunk_packets < 0) b->chunk_packets = 1;
+    // SOLO_ENC_RC_BATCH: packets per range-coder launch.  The coder is latency bound: one launch over k chunks takes about as long as
+    // one chunk's.  What its launch per chunk did for the schedule -- hold the next high band back until the quantiser launch that
+    // starts at the same moment is resident -- a bounded gate in front of the high band does directly (- 5 %).
+    // 1 = a coder launch behind every chunk's high band, no gate.
+    b->rc_batch = env_int("SOLO_ENC_RC_BATCH", SOLO_ENC_RC_BATCH_DEFAULT);
+    if (b->rc_batch < 1) b->rc_batch = 1;
+    if (b->rc_batch > ops->rc_batch_max) b->rc_batch = ops->rc_batch_max;
     // launch per chunk: the residency gate (hold analysis chunk c + 1 until the quantiser launch of chunk c is resident) costs 3 % with 256
     // quantiser workgroups per chunk: off unless asked for.  Persistent: ONE gate per launch group, in front of the front kernel -- the
     // quantiser's wavefronts have to be resident before 4096 front workgroups take every register of the device: on unless turned off.
@@ -1557,15 +1568,19 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     int cp = b->chunk_packets > 0 ? b->chunk_packets : n_packets;
     int nchunks = (n_packets + cp - 1) / cp;
     if (nchunks > SOLO_MAX_CHUNKS) { cp = (n_packets + SOLO_MAX_CHUNKS - 1) / SOLO_MAX_CHUNKS; nchunks = (n_packets + cp - 1) / cp; }
-    {   // scratch of one coding launch: the byte buffers of its descriptions
-        const int gs = (b->group_streams > 0 && b->group_streams < b->n_streams) ? b->group_streams : b->n_streams;
-        // (sC: a coding launch of the previous call may still read the old one)
-        SOLO_CHECK(grow_scratch(b->d_rc_scratch, b->rc_scratch_bytes, ops->rc_scratch_bytes(gs, cp), b->sC));
-    }
-    const bool tm_req = b->timing && b->tev_ready;
     // the previous call's events are waited for only inside one context (stream_capture); on the other side of a capture this call
     // starts behind everything of it through the fork from `st`
     const unsigned long long cap = stream_capture(st);
+    // chunks per range-coder launch: whole chunks, SOLO_ENC_RC_BATCH packets at the most; 1 (a call of one chunk, and a call that is
+    // captured into a graph: the gate's target is a running count passed by value): ops->coding per chunk
+    const int kc = nchunks > 1 && !cap && b->rc_batch / cp > 1 ? (b->rc_batch / cp < nchunks ? b->rc_batch / cp : nchunks) : 1;
+    const int kb_cap = kc * cp;
+    {   // scratch of one coding launch: the byte buffers of its descriptions
+        const int gs = (b->group_streams > 0 && b->group_streams < b->n_streams) ? b->group_streams : b->n_streams;
+        // (sC: a coding launch of the previous call may still read the old one)
+        SOLO_CHECK(grow_scratch(b->d_rc_scratch, b->rc_scratch_bytes, ops->rc_scratch_bytes(gs, kb_cap), b->sC));
+    }
+    const bool tm_req = b->timing && b->tev_ready;
     if (b->enc_seq > 0 && b->join_cap[(b->enc_seq - 1u) & 1u] != cap) b->evC_valid = -1;
     uint32_t* verdict = NULL;
     if (map) {
@@ -1602,6 +1617,11 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     const size_t frame_samples = (size_t)enc_packet_samples(b);
     int idx = 0;
     hipError_t lerr = hipSuccess;
+#ifdef SX_EXPERIMENTS     // builds for the section tools only (tools/build_stops.sh): SOLO_EXP_SKIP bit 0 = no quantiser, bit 1 = no third stage, bit 2 = no range coder -- wrong output
+    static const int exp_skip = env_int("SOLO_EXP_SKIP", 0);
+#else
+    constexpr int exp_skip = 0;
+#endif
     for (int g = 0; g < ngroups && lerr == hipSuccess; g++) {
         const int s0 = g * G, ns = (s0 + G <= nall) ? G : nall - s0;
         const size_t pk0 = (size_t)s0 * (size_t)n_packets;                               // first packet record of the group
@@ -1614,6 +1634,25 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
         uint8_t* g_bits = d_bits + pk0 * (size_t)b->slot;
         int16_t* g_nbytes = d_nbytes + pk0 * 2;
         int32_t* g_status = d_status ? d_status + s0 : NULL;
+        int pb = 0, hb_end = 0, idx_b = idx;         // the open batch of the coder: its first packet, the end of its chunks with a high-band launch, its first event slot
+        int pend = -1, pend_idx = 0;
+        auto third = [&](int tcc, int tidx) -> hipError_t {
+            const int tc = tidx % SOLO_MAX_CHUNKS, tp0 = tcc * cp, tpc = (tp0 + cp <= n_packets) ? cp : n_packets - tp0;
+            const bool last = (tcc + 1) % kc == 0 || tcc + 1 == nchunks;
+            hipError_t e;
+            if (tm) (void)hipEventRecord(b->tev[2][tc][0], b->sC);
+            if (!(exp_skip & 2) && (e = ops->hb(g_states, g_cin, g_nout, ns, n_packets, tp0, tpc, pb, kb_cap, cp, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) return e;
+            hb_end = tp0 + tpc;
+            if (last && !(exp_skip & 6) &&
+                (e = ops->rc_batch(g_states, g_cin, g_nout, ns, n_packets, pb, hb_end - pb, kb_cap, cp, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) return e;
+            if (tm) (void)hipEventRecord(b->tev[2][tc][1], b->sC);
+            if (last) {
+                for (int i = idx_b; i <= tidx; i++) if ((e = hipEventRecord(b->evC[i % SOLO_MAX_CHUNKS], b->sC)) != hipSuccess) return e;
+                pb = hb_end;
+                idx_b = tidx + 1;
+            }
+            return hipSuccess;
+        };
         for (int cc = 0; cc < nchunks; cc++, idx++) {
             const int c = idx % SOLO_MAX_CHUNKS, cprev = (idx + SOLO_MAX_CHUNKS - 1) % SOLO_MAX_CHUNKS;     // event / counter slot
             const int p0 = cc * cp, pc = (p0 + cp <= n_packets) ? cp : n_packets - p0;
@@ -1626,17 +1665,31 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
             SOLO_CHECK(hipEventRecord(b->evA[c], b->sA));
             SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evA[c], 0));
             if (tm) (void)hipEventRecord(b->tev[1][c][0], b->sB);
-#ifdef SX_EXPERIMENTS     // builds for the section tools only (tools/build_stops.sh): SOLO_EXP_SKIP bit 0 = no quantiser, bit 1 = no third stage -- wrong output
-            static const int exp_skip = env_int("SOLO_EXP_SKIP", 0);
-#else
-            constexpr int exp_skip = 0;
-#endif
             if (!(exp_skip & 1)) {
             if ((lerr = (hipError_t)ops->nsq(g_states, g_nin, g_nout, ns, n_packets, p0, pc, &b->d_started[c], b->d_nsq_ring, g_map, verdict, b->sB)) != hipSuccess) break;
             b->started_target[c] += (unsigned int)ops->nsq_workgroups(ns);     // workgroups of this launch, counted once it is enqueued
             }
             if (tm) (void)hipEventRecord(b->tev[1][c][1], b->sB);
             SOLO_CHECK(hipEventRecord(b->evB[c], b->sB));
+            if (kc > 1 || (exp_skip & 4)) {
+                // the high band of a chunk; behind the batch's (the call's) last chunk the range coder of all of its packets.  evC[] of the
+                // batch's chunks only then: the coder reads their hand-over records
+                if (kc <= 1 || (exp_skip & 1)) {          // (timing builds)
+                    SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[c], 0));
+                    if ((lerr = third(cc, idx)) != hipSuccess) break;
+                } else {
+                    // the third stage of the chunk BEFORE, behind its quantiser launch and a gate that holds it until this chunk's quantiser
+                    // launch -- which starts when that one ends -- is resident: the high band's 4096 workgroups would take the register
+                    // holes its wavefronts need.  The gate gives up after ~0.5 ms (sC has that much slack per chunk).
+                    if (pend >= 0) {
+                        SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[cprev], 0));
+                        (void)solo_launch_gate_for(&b->d_started[c], b->started_target[c], SOLO_HB_GATE_ITERS, b->sC);
+                        if ((lerr = third(pend, pend_idx)) != hipSuccess) break;
+                    }
+                    pend = cc; pend_idx = idx;
+                }
+                continue;
+            }
             SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[c], 0));
             if (tm) (void)hipEventRecord(b->tev[2][c][0], b->sC);
             if (!(exp_skip & 2))
@@ -1644,6 +1697,13 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
             if (tm) (void)hipEventRecord(b->tev[2][c][1], b->sC);
             SOLO_CHECK(hipEventRecord(b->evC[c], b->sC));
         }
+        if (pend >= 0) {
+            (void)hipStreamWaitEvent(b->sC, b->evB[pend_idx % SOLO_MAX_CHUNKS], 0);
+            const hipError_t e = third(pend, pend_idx);
+            if (lerr == hipSuccess) lerr = e;
+        }
+        if (lerr != hipSuccess && kc > 1 && hb_end > pb)       // a refused launch: the chunks whose high band is enqueued are still coded
+            (void)ops->rc_batch(g_states, g_cin, g_nout, ns, n_packets, pb, hb_end - pb, kb_cap, cp, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC);
     }
     // join the internal streams back into the caller's.  After a refused launch too: whatever was enqueued so far still runs, nothing of
     // this call is left forked (sB as well, which sC's last launch may not have waited for), the chunk-wise guards are dropped

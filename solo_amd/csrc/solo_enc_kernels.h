@@ -36,6 +36,8 @@ __global__ void __launch_bounds__(64) SX_K(solo_enc_ctl_list_kernel)(SxEncStream
 //      B  solo_nsq_kernel           four streams per wavefront (solo_nsq_row.hip): the delayed-decision quantiser
 //      C  solo_enc_coding_kernel    one wavefront per stream: high-band encoder (8 bytes per packet into the launch's scratch)
 //      D  solo_enc_rc_kernel        one LANE per description: range coding, then the payload assembly by the two lanes of a packet
+//         (SOLO_ENC_RC_BATCH = k > 1, the default: C per chunk behind a gate on the next chunk's launch of B, D once per k packets as
+//         solo_enc_rc_batch_kernel, one LANE per (stream, packet of the batch, description): solo_api.hip)
 //  * persistent (SOLO_ENC_PERSIST=1, calls of two or more packets): ONE launch of solo_enc_front_kernel (one wavefront per stream:
 //    analysis of every packet, and -- as soon as the quantiser has published a packet -- its high band, range coding and payload) beside
 //    ONE launch of solo_nsq_persist_kernel (solo_nsq_row.hip); the two hand packets to each other through per-stream flags in HBM while
@@ -182,6 +184,48 @@ __global__ void __launch_bounds__(64) SX_K(solo_enc_rc_kernel)(const SxEncStream
     if (status && md == 0) {               // first error of the call (the chunks of a call run in order)
         if (p0 == 0) status[s] = first_err;
         else if (first_err != 0 && status[s] == 0) status[s] = first_err;
+    }
+}
+
+// The same coder over a BATCH of chunks: ONE launch for packets [pb, pb + kb) of every stream, behind the high-band launches of the
+// batch's chunks (solo_api.hip, SOLO_ENC_RC_BATCH).  The coder is latency bound (62 % of its wave cycles wait), so kb times the lanes
+// take about as long as one chunk's, and the HIP stream that carries the high band is held by the coder once per batch, not once per
+// chunk.  Lane = (stream, packet of the batch, description): the 2 kb lanes of a stream are neighbours inside ONE wavefront
+// (2 kb <= 64; 64 / (2 kb) streams per wavefront), the two descriptions of a packet in lanes l, l ^ 1 as the assembly's exchange needs.
+// So a stream's first error in packet order is one ballot, and status[s] has one writer.  rcbuf / rcinfo: [(stream * kb_cap + j) * 2 +
+// md]; hbout: where the batch's high-band launches left their bytes, chunk after chunk (chunk i of cp packets, the call's last one
+// shorter: [i * n_streams * cp + stream * pc_i + packet of the chunk] * 8).
+__global__ void __launch_bounds__(64) SX_K(solo_enc_rc_batch_kernel)(const SxEncStream* states, const SxCodeIn* __restrict__ code_in,
+                                                                     const SxNsqOut* __restrict__ nsq_out, int n_streams, int n_packets, int pb, int kb,
+                                                                     int kb_cap, int cp, u8* __restrict__ rcbuf, SxRcInfo* __restrict__ rcinfo,
+                                                                     const u8* __restrict__ hbout, int slot_bytes, u8* __restrict__ bits,
+                                                                     i16* __restrict__ nbytes, i32* status, const i32* __restrict__ map, const u32* verdict) {
+    __shared__ SxRcWork w;
+    if (sx_map_refused(map, verdict)) return;
+    SX_K(sx_cdf_stage)(&w.cdf);
+    const int lane = threadIdx.x, per = 2 * kb, spw = 64 / per;          // lanes per stream, streams per wavefront
+    const int sl = lane / per, r = lane - sl * per, j = r >> 1, md = r & 1;
+    const int s = blockIdx.x * spw + sl;
+    const bool on = sl < spw && s < n_streams;
+    i32 ret = 0;
+    if (on) {
+        const SxEncState* st = &states[map ? map[s] : s].core;
+        const int useDTX = st->useDTX, useMDIndex = st->useMDIndex, fpp = st->fpp;
+        const int hb_bytes = st->hb_joint ? 4 : 4 * fpp;
+        const int ci = j / cp, pin = j - ci * cp, left = n_packets - (pb + ci * cp), pcc = left < cp ? left : cp;      // the packet's chunk, its place and the chunk's length
+        const size_t pk = (size_t)s * n_packets + (size_t)(pb + j);
+        const size_t slot = ((size_t)s * kb_cap + (size_t)j) * 2 + (size_t)md;
+        ret = SX_K(sx_rc_code_and_assemble)(code_in[pk].idx, nsq_out + pk * 2, md, useDTX, useMDIndex, fpp, hb_bytes, &w.cdf, (u8*)&w.pw[lane][0],
+                                            rcbuf + slot * SX_RC_BUF_STRIDE, hbout + ((size_t)ci * n_streams * cp + (size_t)s * pcc + (size_t)pin) * 8, slot_bytes,
+                                            bits + pk * (size_t)slot_bytes, nbytes + pk * 2, &rcinfo[slot]);
+    }
+    // first error of the stream in packet order (both lanes of a packet hold its return value): the lowest failing lane of the stream's
+    const unsigned long long bad = __builtin_amdgcn_ballot_w64(on && ret < 0) >> (sl < spw ? sl * per : 0);
+    const unsigned long long mine = per < 64 ? (bad & ((1ull << per) - 1ull)) : bad;
+    const i32 first_err = __shfl(ret, sl * per + (mine ? (int)__builtin_ctzll(mine) : 0));
+    if (status && on && r == 0) {          // first error of the call (the batches of a call run in order)
+        if (pb == 0) status[s] = mine ? first_err : 0;
+        else if (mine && status[s] == 0) status[s] = first_err;
     }
 }
 
@@ -430,6 +474,26 @@ static hipError_t SX_K(solo_enc_launch_coding)(void* states, const void* code_in
                        (const u8*)SX_K(solo_enc_hbout_of)(rcbuf, n_streams, pc), slot, bits, nbytes, status, map, verdict);
     return hipGetLastError();
 }
+// The third stage with the coder batched over chunks (rc_scratch: of kb_cap packets per stream).  hb: the high band of ONE chunk, packets
+// [p0, p0 + pc) of the batch that starts at packet pb in chunks of cp; rc_batch: coder + assembly of the batch's kb packets, behind them.
+static hipError_t SX_K(solo_enc_launch_hb)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int p0, int pc, int pb, int kb_cap,
+                                           int cp, void* rc_scratch, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
+    u8* hbout = SX_K(solo_enc_hbout_of)((u8*)rc_scratch, n_streams, kb_cap) + (size_t)((p0 - pb) / cp) * (size_t)n_streams * (size_t)cp * 8;
+    hipLaunchKernelGGL(SX_K(solo_enc_coding_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, (const SxCodeIn*)code_in,
+                       (const SxNsqOut*)nsq_out, n_streams, n_packets, p0, pc, hbout, map, verdict);
+    return hipGetLastError();
+}
+static hipError_t SX_K(solo_enc_launch_rc_batch)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int pb, int kb, int kb_cap,
+                                                 int cp, int slot, uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, const int32_t* map,
+                                                 const uint32_t* verdict, hipStream_t s) {
+    if (kb < 1 || kb > SX_RC_LANES / 2 || kb > kb_cap || cp < 1) return hipErrorInvalidValue;
+    u8* rcbuf = (u8*)rc_scratch;
+    const int spw = SX_RC_LANES / (2 * kb);
+    hipLaunchKernelGGL(SX_K(solo_enc_rc_batch_kernel), dim3((n_streams + spw - 1) / spw), dim3(64), 0, s, (const SxEncStream*)states, (const SxCodeIn*)code_in,
+                       (const SxNsqOut*)nsq_out, n_streams, n_packets, pb, kb, kb_cap, cp, rcbuf, SX_K(solo_enc_rcinfo_of)(rcbuf, n_streams, kb_cap),
+                       (const u8*)SX_K(solo_enc_hbout_of)(rcbuf, n_streams, kb_cap), slot, bits, nbytes, status, map, verdict);
+    return hipGetLastError();
+}
 #endif
 #ifdef SX_TU_FRONT
 // persistent pipeline: scratch of the in-wave coder (2 SX_FRONT_RB byte buffers per stream) and the front kernel's launch
@@ -459,6 +523,6 @@ static const solo_enc_ops SX_K(solo_enc_ops_table) = {
     sizeof(SxEncStream), sizeof(SxNsqIn), sizeof(SxNsqOut), sizeof(SxCodeIn), SX_PACKET,
     SX_K(solo_enc_launch_init), SX_K(solo_enc_launch_init_list), SX_K(solo_enc_launch_ctl_list), SX_K(solo_enc_launch_analysis), SX_K(solo_launch_nsq), SX_K(solo_enc_launch_coding), SX_K(solo_enc_rc_scratch_bytes),
     SX_K(solo_nsq_workgroups), SX_K(solo_nsq_ring_bytes), SX_K(solo_enc_launch_front), SX_K(solo_launch_nsq_persist), SX_K(solo_enc_front_scratch_bytes), SX_K(solo_nsq_persist_workgroups), SX_K(solo_nsq_stage_bytes),
-    SX_FRONT_WAVES, SX_FRONT_PER_CU};
+    SX_FRONT_WAVES, SX_FRONT_PER_CU, SX_K(solo_enc_launch_hb), SX_K(solo_enc_launch_rc_batch), SX_RC_LANES / 2};
 
 #endif

@@ -38,5 +38,13 @@ struct solo_enc_ops {
     size_t (*nsq_stage_bytes)(int n_streams);                            // the persistent quantiser's private copies of the records it works on
     int front_waves;                                                     // streams (= wavefronts) per front workgroup
     int front_per_cu;                                                    // front wavefronts that a compute unit holds beside the quantiser's
+    // ---- launch per chunk, the range coder batched over chunks (SOLO_ENC_RC_BATCH; solo_enc_kernels.h: solo_enc_rc_batch_kernel) ----
+    // rc_scratch: of rc_scratch_bytes(n_streams, kb_cap).  hb: the high band of one chunk, packets [p0, p0 + pc) of the batch that starts
+    // at packet pb (chunks of cp packets); rc_batch: range coder + payload assembly of the batch's kb packets, behind its chunks' hb
+    hipError_t (*hb)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int p0, int pc, int pb, int kb_cap, int cp,
+                     void* rc_scratch, const int32_t* map, const uint32_t* verdict, hipStream_t s);
+    hipError_t (*rc_batch)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int pb, int kb, int kb_cap, int cp, int slot,
+                           uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, const int32_t* map, const uint32_t* verdict, hipStream_t s);
+    int rc_batch_max;                                                    // packets one rc_batch launch takes at most (a stream's lanes share a wavefront)
 };
 #endif

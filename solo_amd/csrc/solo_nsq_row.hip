@@ -184,19 +184,21 @@ extern "C" __global__ void SX_NSQ_CAP_ATTR __launch_bounds__(64 * SX_NSQ_PERSIST
 
 #if SX_FS_KHZ == 8
 // gate: holds a stream until `*flag` has reached `target` (modulo 2^32), i.e. until all workgroups of the quantiser launch that
-// counts into it are resident; gives up after ~20 ms so that a runtime that serialises the streams cannot hang
-extern "C" __global__ void __launch_bounds__(64) solo_gate_kernel(const unsigned int* flag, unsigned int target) {
+// counts into it are resident; gives up after max_iters looks (~1 us each; solo_launch_gate: ~20 ms) so that a runtime that serialises
+// the streams cannot hang
+extern "C" __global__ void __launch_bounds__(64) solo_gate_kernel(const unsigned int* flag, unsigned int target, int max_iters) {
     if (threadIdx.x == 0) {
-        for (int it = 0; it < 20000; it++) {
+        for (int it = 0; it < max_iters; it++) {
             if (__atomic_load_n(flag, __ATOMIC_RELAXED) - target < 0x80000000u) break;
             __builtin_amdgcn_s_sleep(32);
         }
     }
 }
-extern "C" int solo_launch_gate(const unsigned int* flag, unsigned int target, void* hip_stream) {
-    hipLaunchKernelGGL(solo_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, flag, target);
+extern "C" int solo_launch_gate_for(const unsigned int* flag, unsigned int target, int max_iters, void* hip_stream) {
+    hipLaunchKernelGGL(solo_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, flag, target, max_iters);
     return (int)hipGetLastError();
 }
+extern "C" int solo_launch_gate(const unsigned int* flag, unsigned int target, void* hip_stream) { return solo_launch_gate_for(flag, target, 20000, hip_stream); }
 
 // Unit check of the row exchanges (tests/test_gpu_nsq_row.py): out[0..7][lane] = the primitives applied to in[lane]
 extern "C" __global__ void __launch_bounds__(64) solo_debug_rowops_kernel(const i32* in, const i32* idx, i32* out) {
