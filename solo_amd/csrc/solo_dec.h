@@ -351,7 +351,9 @@ SX_HD i32 sx_decode_pulses(RC* rc, int sigtype, int QuantOffsetType, QT* q, cons
                     abs_q = sx_shl(abs_q, 1);
                     abs_q += sx_rc_dec_bin(rc, p_lsb);
                 }
-                if (sizeof(QT) == 1 && abs_q > 127) *narrow = 1;
+                // (stored as 127, not cut to its low byte: a value that came out <= 0 would skip its sign bit below, and the symbols
+                // behind the pulses would be read from the wrong place -- the record then said `coder error`, not `narrow`)
+                if (sizeof(QT) == 1 && abs_q > 127) { *narrow = 1; abs_q = 127; }
                 q[i * 16 + k] = (QT)abs_q;
             }
         }

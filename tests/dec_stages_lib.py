@@ -146,6 +146,43 @@ def map_record(n0, n1, recv, hbb):
     return r
 
 
+def desc_spans(a0, a1, lostflag, hbb):
+    """sx_desc_span (solo_dec.h): where the description slots of a record handed over as (nBytes0, nBytes1, lostflag) lie inside the bytes handed
+    over -> [(offset, length)] per slot in use"""
+    if lostflag < 2:
+        return []
+    nb0 = a0 if lostflag == 2 else a0 - hbb
+    nb1 = a1 - hbb if a1 else 0
+    return [(0, nb0 - nb1), (nb0 - nb1, nb1)][:2 if lostflag == 4 else 1]
+
+
+def writer(lib):
+    """the description writer of the host emulation (tests/emu/solo_emu.cpp: emu_write_desc, emu_min_planes) with its argument types set"""
+    import ctypes as C
+    lib.emu_write_desc.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.emu_min_planes.argtypes = [C.c_void_p]
+    return lib
+
+
+def min_planes(lib, pulses):
+    """pulses [..., F] of any width -> the fewest LSB planes the encoder gives every block of 16 [..., F / 16]"""
+    q = np.ascontiguousarray(pulses, np.int32).reshape(-1, 16)
+    out = np.array([lib.emu_min_planes(q[i].ctypes.data) for i in range(len(q))], np.int32)
+    return out.reshape(np.shape(pulses)[:-1] + (np.shape(pulses)[-1] // 16,))
+
+
+def write_desc(lib, use_md_index, syms, pulses, planes, term):
+    """syms [n] of dtypes()["syms"], pulses [n][F], planes [n][F / 16], term [n] -> the description's bytes, or None where the writer refuses"""
+    import ctypes as C
+    n = len(term)
+    syms, pulses = np.ascontiguousarray(syms[:n]), np.ascontiguousarray(pulses[:n], np.int32)
+    planes, term = np.ascontiguousarray(planes[:n], np.int32), np.ascontiguousarray(term, np.int32)
+    assert len(syms) == n and pulses.shape == (n, planes.shape[1] * 16)
+    out, err = np.zeros(1100, np.uint8), C.c_int(0)
+    nb = lib.emu_write_desc(n, use_md_index, syms.ctypes.data, pulses.ctypes.data, planes.ctypes.data, term.ctypes.data, out.ctypes.data, out.size, C.byref(err))
+    return bytes(out[:nb]) if nb > 0 else None
+
+
 def usable_rule(fpp, more_before, lostflag, e0, e1):
     """sx_extracted_usable on the packet's two records -> 0 (the records are taken) or the reason they are not (a description's own, or STRUCTURE);
     None: the packet has no description at all (lost)"""

@@ -179,6 +179,114 @@ int emu_encode_pulses(int sigtype, int QuantOffsetType, const int8_t* q, uint8_t
     *error = rc.error;
     return nb;
 }
+// ---- description writer (tests/test_dec_constructed.py, tests/golden/make_dec_constructed.py): codes CHOSEN symbols, so that the decoder's
+// rarely taken branches get well-formed inputs.  A second statement of the bitstream layout next to sx_code_description: it shares the range
+// encoder, the shell coder's split and the tables with the product and nothing else, and nothing under solo_amd/ calls it. ----
+// the fewest LSB planes SKP_Silk_encode_pulses would give a block of 16 magnitudes of any width (combine_and_check, encode_pulses.c:86-110)
+int emu_min_planes(const int32_t* q16) {
+    const i32 maxp0 = T_max_pulses[0], maxp1 = T_max_pulses[1], maxp2 = T_max_pulses[2], maxp3 = T_max_pulses[3];
+    for (int nrs = 0; nrs < 31; nrs++) {
+        i32 c1[8], c2[4], c3[2];
+        int bad = 0;
+        for (int k = 0; k < 8; k++) { c1[k] = (abs(q16[2 * k]) >> nrs) + (abs(q16[2 * k + 1]) >> nrs); bad |= c1[k] > maxp0; }
+        for (int k = 0; k < 4; k++) { c2[k] = c1[2 * k] + c1[2 * k + 1]; bad |= c2[k] > maxp1; }
+        for (int k = 0; k < 2; k++) { c3[k] = c2[2 * k] + c2[2 * k + 1]; bad |= c3[k] > maxp2; }
+        bad |= c3[0] + c3[1] > maxp3;
+        if (!bad) return nrs;
+    }
+    return -1;
+}
+// pulses of one frame: q[SX_FRAME] of any width, planes[SX_FRAME / 16] = the LSB planes of every block as the CALLER chooses them (at least
+// emu_min_planes of the block, or the shell coder has no code for it: returns -1), the rate level given
+static int emu_write_pulses(SxRangeEnc* rc, int sigtype, int QuantOffsetType, int RateLevelIndex, const int32_t* q, const int32_t* planes, const SxCdf* cdf) {
+    const int iter = SX_FRAME / 16;
+    u8 top[SX_FRAME];                                        // the magnitudes without their LSB planes: what the shell coder codes
+    i32 sum[SX_FRAME / 16];
+    for (int i = 0; i < iter; i++) {
+        if (planes[i] < emu_min_planes(&q[i * 16]) || planes[i] > 30) return -1;
+        sum[i] = 0;
+        for (int k = 0; k < 16; k++) { top[i * 16 + k] = (u8)(abs(q[i * 16 + k]) >> planes[i]); sum[i] += top[i * 16 + k]; }
+    }
+    sx_rc_enc(rc, RateLevelIndex, &cdf->cdf_rate_levels[sigtype * 10]);
+    const u16* first = &cdf->cdf_pulses_per_block[RateLevelIndex * 21];
+    const u16* more = &cdf->cdf_pulses_per_block[9 * 21];
+    for (int i = 0; i < iter; i++) {
+        const u16* t = first;
+        for (int k = 0; k < planes[i]; k++) { sx_rc_enc(rc, 18 + 1, t); t = more; }
+        sx_rc_enc(rc, sum[i], t);
+    }
+    for (int i = 0; i < iter; i++)
+        if (sum[i] > 0) sx_shell_encoder(rc, &top[i * 16], 0, cdf);
+    const u32 p_lsb = cdf->cdf_lsb[1];
+    for (int i = 0; i < iter; i++)
+        for (int k = 0; k < 16 && planes[i] > 0; k++)
+            for (int j = planes[i] - 1; j >= 0; j--) sx_rc_enc_bin(rc, (abs(q[i * 16 + k]) >> j) & 1, p_lsb);
+    const u32 p_sign = cdf->cdf_sign[sx_smulbb(10 - 1, (sigtype << 1) + QuantOffsetType) + RateLevelIndex];
+    for (int i = 0; i < SX_FRAME; i++)
+        if (q[i] != 0) sx_rc_enc_bin(rc, q[i] > 0, p_sign);
+    return 0;
+}
+// ONE description of nframes (1..3) frames: syms = SxFrameSyms[nframes] (the symbols in coding order; fs_bad, NLSF_Q15 and the fields after
+// vadFlag are not looked at), pulses[nframes][SX_FRAME], planes[nframes][SX_FRAME / 16], term[nframes] = the frame-termination symbol 0..3
+// coded after each frame, whatever it is.  -> the number of bytes written to out (SKP_Silk_range_coder_get_length before the wrap-up, as the
+// encoder counts them), or -1; *error = the range encoder's
+int emu_write_desc(int nframes, int useMDIndex, const void* syms, const int32_t* pulses, const int32_t* planes, const int32_t* term, uint8_t* out, int cap, int* error) {
+    static SxCdf cdf;
+    sx_cdf_load(&cdf);
+    static u8 buf[SX_RC_BUF_STRIDE];
+    memset(buf, 0, sizeof(buf));
+    *error = 0;
+    if (nframes < 1 || nframes > 3) return -1;
+    SxRangeEnc rc;
+    sx_rc_enc_init(&rc, buf);
+    int prev = 0;
+    for (int f = 0; f < nframes; f++) {
+        const SxFrameSyms* y = (const SxFrameSyms*)syms + f;
+        const int sigtype = y->typeOffset >> 1, QuantOffsetType = y->typeOffset & 1;
+        if (f == 0) {
+            if (useMDIndex == 1) sx_rc_enc(&rc, y->MDIndex, cdf.cdf_mdindex);
+            sx_rc_enc(&rc, SX_FS_KHZ == 8 ? 0 : 2, cdf.cdf_fs);
+            sx_rc_enc(&rc, y->typeOffset, cdf.cdf_type_offset);
+            sx_rc_enc(&rc, y->GainsIndices[0], &cdf.cdf_gain[sigtype * 65]);
+        } else {
+            sx_rc_enc(&rc, y->typeOffset, &cdf.cdf_type_offset_joint[prev * 5]);
+            sx_rc_enc(&rc, y->GainsIndices[0], cdf.cdf_delta_gain);
+        }
+        prev = y->typeOffset;
+        for (int i = 1; i < SX_NB_SUBFR; i++) sx_rc_enc(&rc, y->GainsIndices[i], cdf.cdf_delta_gain);
+        if (f == 0) sx_rc_enc(&rc, y->DeltaGainIndices, cdf.cdf_md_delta_gain);
+        {
+            const i32 nvec0[SX_NLSF_STAGES] = T_NLSF_CB0_NVEC, nvec1[SX_NLSF_STAGES] = T_NLSF_CB1_NVEC;
+            const u16* ncdf = sigtype == 0 ? cdf.nlsf_cb0_cdf : cdf.nlsf_cb1_cdf;
+            int off = 0;
+            for (int s = 0; s < SX_NLSF_STAGES; s++) {
+                sx_rc_enc(&rc, y->NLSFIndices[s], ncdf + off);
+                off += (sigtype == 0 ? nvec0[s] : nvec1[s]) + 1;
+            }
+        }
+        sx_rc_enc(&rc, y->NLSFInterpCoef_Q2, cdf.cdf_nlsf_interp);
+        if (sigtype == 0) {
+            sx_rc_enc(&rc, y->lagIx, cdf.cdf_pitch_lag);
+            sx_rc_enc(&rc, y->conIx, cdf.cdf_pitch_contour);
+            sx_rc_enc(&rc, y->PERIndex, cdf.cdf_ltp_per);
+            const u16* gcdf = y->PERIndex == 0 ? cdf.cdf_ltp_gain0 : (y->PERIndex == 1 ? cdf.cdf_ltp_gain1 : cdf.cdf_ltp_gain2);
+            for (int k = 0; k < SX_NB_SUBFR; k++) sx_rc_enc(&rc, y->LTPIx[k], gcdf);
+            sx_rc_enc(&rc, y->LTPscaleIx, cdf.cdf_ltpscale);
+        }
+        sx_rc_enc(&rc, y->Seed, cdf.cdf_seed);
+        if (emu_write_pulses(&rc, sigtype, QuantOffsetType, y->RateLevelIndex, pulses + f * SX_FRAME, planes + f * (SX_FRAME / 16), &cdf) < 0) return -1;
+        sx_rc_enc(&rc, y->vadFlag, cdf.cdf_vadflag);
+        if (term[f] < 0 || term[f] > 3) return -1;
+        sx_rc_enc(&rc, term[f], cdf.cdf_frame_term);
+    }
+    i32 nb;
+    sx_rc_length_bits(rc.bufferIx, rc.range_Q16, &nb);
+    sx_rc_enc_wrap_up(&rc);
+    *error = rc.error;
+    if (rc.error || nb <= 0 || nb > cap || nb > (i32)sizeof(buf)) return -1;
+    memcpy(out, buf, (size_t)nb);
+    return nb;
+}
 int emu_frame_samples() { return SX_FRAME; }
 int emu_sizeof_nsq_in() { return (int)sizeof(SxNsqIn); }
 int emu_sizeof_enc_state() { return (int)sizeof(SxEncStream); }

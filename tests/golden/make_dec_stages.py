@@ -58,7 +58,7 @@ def hb_bytes(joint, ms):
     return 4 if (joint or ms == 20) else 8
 
 
-def decode(recs, recv, md=0, joint=0, samplerate=16000, ms=40, **_):
+def decode(recs, recv, md=0, joint=0, samplerate=16000, ms=40, wide=False, **_):
     """the reference decoder, one packet per tap run -> pcm, ret, ext, meta, state of every packet"""
     wb = samplerate == 32000
     dt = L.dtypes(wb)
@@ -86,10 +86,14 @@ def decode(recs, recv, md=0, joint=0, samplerate=16000, ms=40, **_):
             more = int(state[p]["moreInternalDecoderFrames"])
         ndesc = 2 if lostflag == 4 else (1 if lostflag >= 2 else 0)
         # an ordinary two-frame packet: the calls come as (frame 0, description 0), [(0, 1)], (1, 0), [(1, 1)]
-        if fpp == 2 and ndesc and meta[p, 1] == 0 and n == 2 * ndesc and r[:, 4].all() and ret[p] == 0:
+        if (fpp == 2 and ndesc and meta[p, 1] == 0 and n == 2 * ndesc and r[:, 4].all() and ret[p] == 0
+                and (not wide or [tuple(v) for v in r[:, :2]] == [(f, k) for f in range(2) for k in range(ndesc)])):
             assert [tuple(v) for v in r[:, :2]] == [(f, k) for f in range(2) for k in range(ndesc)]
             for k in range(ndesc):
                 e = ext[p, k]
+                if wide and max(np.abs(r[f * ndesc + k][L.DREC_PULSES:L.DREC_PULSES + F]).max() for f in range(2)) > 127:
+                    e["pad_"][0] = L.NARROW     # (make_dec_constructed.py: SxExtracted::pulses cannot hold them -- no record of this description)
+                    continue
                 for f in range(2):
                     q = r[f * ndesc + k]
                     e["y"][f] = L.unflatten(q[L.DREC_SYMS:], dt["syms"])[0]

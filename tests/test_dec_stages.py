@@ -21,6 +21,10 @@ fit stands in for them: these two branches stay without a known probing input, a
 the corrupted sampling-rate symbol names another rate the reference supports, the reference switches to it and returns 0; the build decodes one
 internal rate and returns -12 (tools/debug/fuzz_decoder_gen.py: "other_rate"): the status is asserted, PCM and state of that last packet are not.
 
+Constructed inputs for those two branches -- and for the continuation of a call in the previous packet's coder buffers on clean data -- are in
+tests/test_dec_constructed.py (fixtures of their own, dec_constructed*.npz: descriptions written symbol by symbol by the host emulation's
+description writer, expected values from the compiled reference); the searched fixtures here and NOT_FOUND stay as they are.
+
 What is left out of the comparison, and nothing else.  Records (`_ext_mask`):
  1. struct padding (the tail of SxExtracted up to its 16-byte alignment) and pad_[1..2];
  2. ctl[1].MDIndex: the reference assigns MDIndex in a packet's first frame alone (SKP_Silk_decode_parameters.c:54-57), its control block is an
@@ -68,8 +72,9 @@ NOT_FOUND = "narrow, structure"
 
 
 @functools.lru_cache(None)
-def _load(rate):
-    name, samplerate = FILES[rate]
+def _load(rate, files=None):
+    """files: another pair of fixture files in the same layout (tests/test_dec_constructed.py), as a tuple of FILES' items"""
+    name, samplerate = dict(files or FILES.items())[rate]
     wb = rate == "wb"
     dt = L.dtypes(wb)
     z = np.load(os.path.join(T.GOLDEN, name))
