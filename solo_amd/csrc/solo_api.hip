@@ -182,20 +182,10 @@ __global__ void __launch_bounds__(256) solo_stream_list_check_kernel(const i32* 
 extern "C" const solo_dec_ops* solo_nb_dec_ops() { return &solo_dec_ops_table; }
 extern "C" const solo_dec_ops* solo_wb_dec_ops();          // the same decoder compiled for the 32 kHz API rate (SILK wide band, 16 kHz bands): solo_api_wb.hip
 
-#ifdef SOLO_WITH_ENCODER
-#include "solo_enc_ops.h"
-extern "C" int solo_launch_gate(const unsigned int* flag, unsigned int target, void* hip_stream);      // solo_nsq_row.hip
-extern "C" int solo_launch_gate_for(const unsigned int* flag, unsigned int target, int max_iters, void* hip_stream);
-extern "C" const solo_enc_ops* solo_nb_enc_ops();                                                      // solo_enc_k.hip
-extern "C" const solo_enc_ops* solo_wb_enc_ops();                                                      // solo_enc_k_wb.hip
-#endif
 
 // ---------------------------------------------------------------------------------------------------
 // host side: handle + C ABI
 // ---------------------------------------------------------------------------------------------------
-#define SOLO_MAX_CHUNKS 64
-#define SOLO_ENC_RC_BATCH_DEFAULT 5
-#define SOLO_HB_GATE_ITERS 500           // bound of the high band's wait for the next quantiser launch, ~1 us each
 // verdict words of subset calls (solo_stream_list_check_kernel), one per kind of call so that calls of different kinds in flight on
 // different streams do not share one
 enum {
@@ -209,6 +199,39 @@ enum {
     SOLO_VERDICT_IMPORT,             // [8, 9] solo_batch_import_streams (its list, its records)
     SOLO_N_VERDICTS = SOLO_VERDICT_IMPORT + 2
 };
+// an environment knob (INTEGRATION.md section 5) that is a number
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+template <typename T>
+static void dev_free(T*& p) {
+    if (p) (void)hipFree(p);
+    p = NULL;
+}
+// Grows a device scratch of the handle to `need` bytes (it never shrinks).  `s` is the stream whose kernels may still use the old
+// buffer: growing synchronises it, steady-state calls do not.
+static hipError_t grow_scratch(void*& p, size_t& bytes, size_t need, hipStream_t s) {
+    if (need <= bytes) return hipSuccess;
+    if (p) {
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return e;
+        dev_free(p);
+        bytes = 0;
+    }
+    const hipError_t e = hipMalloc(&p, need);
+    if (e == hipSuccess) bytes = need;
+    return e;
+}
+#ifdef SOLO_WITH_ENCODER
+#include "solo_enc_ops.h"
+extern "C" int solo_launch_gate(const unsigned int* flag, unsigned int target, void* hip_stream);      // solo_nsq_row.hip
+extern "C" int solo_launch_gate_for(const unsigned int* flag, unsigned int target, int max_iters, void* hip_stream);
+extern "C" const solo_enc_ops* solo_nb_enc_ops();                                                      // solo_enc_k.hip
+extern "C" const solo_enc_ops* solo_wb_enc_ops();                                                      // solo_enc_k_wb.hip
+#include "solo_enc_pipe.h"                                                                            // the encoder's launch schedule and what a handle owns for it
+#endif
+
 struct solo_batch {
     int32_t n_streams;
     int32_t slot;
@@ -218,8 +241,8 @@ struct solo_batch {
     void* d_enc_state;
 #ifdef SOLO_WITH_ENCODER
     const solo_enc_ops* eops;        // launch table of the build that matches the encoder's rate (solo_enc_kernels.h)
+    solo_enc_pipe enc;               // the encoder's streams, events, knobs, scratch and schedule state (solo_enc_pipe.h)
 #endif
-    void* d_nsq_ring;                // emission-ring scratch of the quantiser launches (one launch group of streams; frame-local data)
     // decoder: every kernel of a decode call runs on the caller's stream; two-kernel path: per chunk of packets the symbol extraction,
     // then the decoder proper
     hipEvent_t evDecDone;            // end of the most recent decode call, on whichever stream it was issued
@@ -228,38 +251,9 @@ struct solo_batch {
     size_t parsed_bytes;
     int dec_pipe_ready, dec_split, dec_chunk, dec_first;
     size_t dec_scratch_cap;          // env SOLO_DEC_SCRATCH_CAP, read when the handle's decode pipeline is set up
-    void* d_rc_scratch;              // range-coder byte buffers of one coding launch (the launches of a call run in order on sC)
-    size_t rc_scratch_bytes;
-    void* d_enc_work;                // hand-over records of one launch: SxNsqIn[N][P][2] | SxNsqOut[N][P][2] | SxCodeIn[N][P]
-    int32_t enc_work_packets;        // P the hand-over area is sized for
     int timing;                      // solo_batch_set_timing: bracket every kernel with HIP events on its launch stream
-    hipEvent_t evDec[2];             // brackets of a decode call on the caller's stream (the encoder's: tev)
-    int ev_ready, ev_enc, ev_dec;
-    // encoder: three internal streams (analysis / front kernel: sA, quantiser: sB, third stage of the launch-per-chunk schedule: sC)
-    int pipe_ready, chunk_packets;   // chunk_packets: packets per chunk of the launch-per-chunk schedule (env SOLO_ENC_CHUNK, default 1; 0 = one chunk)
-    int rc_batch;                    // packets per range-coder launch of the launch-per-chunk schedule (env SOLO_ENC_RC_BATCH; 1 = one launch per chunk)
-    hipStream_t sA, sB, sC;
-    hipEvent_t evFork, evJoinA[2], evJoinC[2], evA[SOLO_MAX_CHUNKS], evB[SOLO_MAX_CHUNKS], evC[SOLO_MAX_CHUNKS];
-    int async_join;                  // solo_batch_set_async_join: encode returns without joining its streams into the caller's
-    unsigned int enc_seq;            // encode calls so far (selects the join-event set)
-    unsigned long long join_cap[2];  // the graph capture each join-event set (and with it evC[]) was last recorded in, 0 = on running streams
-    int evC_valid;                   // chunks of the previous call whose coding-done events are recorded
-    int last_np, last_cp;            // packets / packets per chunk of the previous call (layout of the hand-over records)
-    hipEvent_t tev[3][SOLO_MAX_CHUNKS][2];   // timing brackets per kernel type / launch (created with set_timing)
-    int tev_ready, last_chunks;
-    unsigned int* d_started;         // per launch slot: workgroups of the quantiser launches that have started (running count)
-    unsigned int started_target[SOLO_MAX_CHUNKS];
-    int group_streams;               // streams per launch group (env SOLO_ENC_GROUP; default: launch per chunk 8192, persistent = what is resident at once)
-    int gate;                        // env SOLO_ENC_GATE: the front / next analysis launch starts once the quantiser's workgroups are resident
-    // persistent schedule (calls of two or more packets; off unless env SOLO_ENC_PERSIST=1 turns it on): per-stream hand-over flags, tickets
-    int persist;
-    int persist_group;               // streams per launch group: all of a group's front workgroups are resident beside its quantiser's
-    unsigned int* d_flags;           // ana[n_streams] | nsq[n_streams / 4 + 1] | prog[n_streams] | err[4]
-    unsigned int ticket;             // packets encoded by persistent calls so far (mod 2^32): the flag words are never reset
-    unsigned int final_wait_ticks;   // env SOLO_ENC_FINAL_WAIT_US: bound of the front kernel's wait for the quantiser's last packets (100 MHz ticks)
-    int front_defer;                 // SOLO_ENC_FINAL_WAIT_US=-1
-    void* d_nsq_stage;               // the persistent quantiser's staging records (one launch group)
-    void* d_front_scratch;           // byte buffers of the front kernel's in-wave range coder (one launch group)
+    hipEvent_t evDec[2];             // brackets of a decode call on the caller's stream (the encoder's: solo_enc_pipe::tev)
+    int ev_ready, ev_dec;
     const solo_dec_ops* dops;        // launch table of the build that matches the decoder's rate (solo_dec_kernels.h)
     void* d_dec_state;               // SxDecStream[n_streams] of that build
     // receiver staging ring (solo_recv.h): payload [N][D][2][slot] | length words [N][D] | play-out positions [N] | statistics
@@ -311,45 +305,6 @@ static int dec_packet_samples(const solo_batch* b) { return ctrl_packet_samples(
 // the decoder's hb_mode argument of sx_dec_state_init: bit 0 = joint_mode 1, bit 1 = one frame per packet
 static int dec_hb_mode(const solo_batch* b) { return ctrl_hb_joint(b->dec_ctrl.joint_enable, b->dec_ctrl.joint_mode) | (ctrl_frames_per_packet(b->dec_ctrl.framesize_ms) == 1 ? 2 : 0); }
 
-// an environment knob (INTEGRATION.md section 5) that is a number
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-template <typename T>
-static void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = NULL;
-}
-// Grows a device scratch of the handle to `need` bytes (it never shrinks).  `s` is the stream whose kernels may still use the old
-// buffer: growing synchronises it, steady-state calls do not.
-static hipError_t grow_scratch(void*& p, size_t& bytes, size_t need, hipStream_t s) {
-    if (need <= bytes) return hipSuccess;
-    if (p) {
-        const hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return e;
-        dev_free(p);
-        bytes = 0;
-    }
-    const hipError_t e = hipMalloc(&p, need);
-    if (e == hipSuccess) bytes = need;
-    return e;
-}
-
-// The graph capture `st` is recording into, 0 when it is not capturing.  The events that order one encode call of a handle against the
-// next (evJoinA / evJoinC / evC) mean something only inside the context they were recorded in: recorded in a capture they are nodes of
-// that graph and order nothing outside it, and the runtime refuses (hipErrorStreamCaptureIsolation) an internal stream that has joined a
-// capture and waits for an event it recorded before.  So an encode call waits for the previous call's events only when both were issued
-// in ONE context -- both on running streams, or both in the same capture.  Across the boundary the caller's stream is the order: a graph
-// launch runs as a whole where it stands in its stream (include/solo_mi355x.h, "Graph capture").  (evDecDone needs none of this: a
-// decode call runs on the caller's stream alone, and the runtime takes its wait for an event of a running stream into a capture.)
-static unsigned long long stream_capture(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    unsigned long long id = 0;
-    if (hipStreamGetCaptureInfo(st, &cs, &id) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return cs == hipStreamCaptureStatusActive ? (id ? id : ~0ull) : 0;
-}
-
 #ifdef SOLO_WITH_ENCODER
 static int enc_hb_joint(const solo_batch* b) { return ctrl_hb_joint(b->enc_ctrl.joint_enable, b->enc_ctrl.joint_mode); }
 static int enc_frames_per_packet(const solo_batch* b) { return ctrl_frames_per_packet(b->enc_ctrl.framesize_ms); }
@@ -358,15 +313,6 @@ static int32_t solo_enc_reset(solo_batch* b, hipStream_t s) {
     SOLO_CHECK(b->eops->init(b->d_enc_state, b->n_streams, ctrl_silk_rate(&b->enc_ctrl), b->enc_ctrl.useMDIndex, enc_hb_joint(b),
                              b->enc_ctrl.dtx_enable ? 1 : 0, enc_frames_per_packet(b), s));
     return 0;
-}
-static void solo_enc_free(solo_batch* b) {
-    dev_free(b->d_enc_state);
-    dev_free(b->d_enc_work);
-    dev_free(b->d_nsq_ring);
-    dev_free(b->d_rc_scratch);
-    dev_free(b->d_flags);
-    dev_free(b->d_front_scratch);
-    dev_free(b->d_nsq_stage);
 }
 #endif
 
@@ -386,27 +332,31 @@ int32_t solo_batch_set_timing(solo_batch_t* b, int32_t on) {
     if (on && !b->ev_ready) {
         for (int i = 0; i < 2; i++) SOLO_CHECK(hipEventCreate(&b->evDec[i]));
         b->ev_ready = 1;
-        for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) SOLO_CHECK(hipEventCreate(&b->tev[k][c][e]));
-        b->tev_ready = 1;
     }
+#ifdef SOLO_WITH_ENCODER
+    if (on) { SOLO_CHECK(enc_events_create(&b->enc.tev[0][0][0], 3 * SOLO_MAX_CHUNKS * 2, hipEventDefault)); b->enc.tev_ready = 1; }      // (those that are missing)
+#endif
     b->timing = on ? 1 : 0;
     return 0;
 }
 int32_t solo_batch_last_kernel_ms(solo_batch_t* b, float* ms4) {
     if (!b || !ms4 || !b->ev_ready) return -1;
     for (int i = 0; i < 4; i++) ms4[i] = -1.0f;
-    if (b->ev_enc && b->tev_ready) {               // sum over the chunks (the three kernel types overlap in time)
+#ifdef SOLO_WITH_ENCODER
+    const solo_enc_pipe* p = &b->enc;
+    if (p->ev_enc && p->tev_ready) {               // sum over the chunks (the three kernel types overlap in time)
         for (int k = 0; k < 3; k++) {
             float tot = 0.0f;
-            for (int c = 0; c < b->last_chunks; c++) {
+            for (int c = 0; c < p->last_chunks; c++) {
                 float t = 0.0f;
-                SOLO_CHECK(hipEventSynchronize(b->tev[k][c][1]));
-                SOLO_CHECK(hipEventElapsedTime(&t, b->tev[k][c][0], b->tev[k][c][1]));
+                SOLO_CHECK(hipEventSynchronize(p->tev[k][c][1]));
+                SOLO_CHECK(hipEventElapsedTime(&t, p->tev[k][c][0], p->tev[k][c][1]));
                 tot += t;
             }
             ms4[k] = tot;
         }
     }
+#endif
     if (b->ev_dec) {
         SOLO_CHECK(hipEventSynchronize(b->evDec[1]));
         SOLO_CHECK(hipEventElapsedTime(&ms4[3], b->evDec[0], b->evDec[1]));
@@ -414,40 +364,14 @@ int32_t solo_batch_last_kernel_ms(solo_batch_t* b, float* ms4) {
     return 0;
 }
 int32_t solo_batch_slot_bytes(const solo_batch_t* b) { return b ? b->slot : 0; }
-// Asynchronous joins: with on = 1 solo_batch_encode returns without making the caller's stream wait for its internal streams, so
-// that the next encode call can start (its first analysis chunk) while the last quantiser / coding chunks of this one still run.
-// Whoever consumes the outputs then calls solo_batch_wait_encode(b, stream, which) first: which = 0 the most recent encode call,
-// 1 the one before.  The hand-over records are guarded inside the library; the OUTPUT buffers of two calls in flight must differ.
-int32_t solo_batch_set_async_join(solo_batch_t* b, int32_t on) {
-    if (!b) return -1;
-    b->async_join = on ? 1 : 0;
-    return 0;
-}
-int32_t solo_batch_wait_encode(solo_batch_t* b, void* hip_stream, int32_t which) {
-    if (!b || !b->pipe_ready || which < 0 || which > 1 || b->enc_seq <= (unsigned int)which) return b ? 0 : -1;
-    const int js = (int)((b->enc_seq - 1u - (unsigned int)which) & 1u);
-    if (b->join_cap[js] != stream_capture((hipStream_t)hip_stream)) return 0;      // (the other side of a capture: stream order, see stream_capture)
-    SOLO_CHECK(hipStreamWaitEvent((hipStream_t)hip_stream, b->evJoinA[js], 0));
-    SOLO_CHECK(hipStreamWaitEvent((hipStream_t)hip_stream, b->evJoinC[js], 0));
-    return 0;
-}
-int32_t solo_batch_last_encode_chunks(const solo_batch_t* b) { return b ? b->last_chunks : 0; }
-
 // Makes `s` wait for the handle's encode work still in flight on its internal streams and for its most recent decode call (before
 // init kernels overwrite states).
 static int32_t solo_wait_in_flight(solo_batch_t* b, hipStream_t s) {
-    const unsigned long long cap = stream_capture(s);
-    if (b->pipe_ready && b->enc_seq > 0) {
-        // kernels of the most recent encode calls may still run on the internal streams (always so with async joins, and when
-        // reset is issued on another stream than the encode was): the init kernels must not overtake them
-        for (int i = 0; i < 2; i++) {
-            if (b->enc_seq <= (unsigned int)i) break;
-            const int js = (int)((b->enc_seq - 1u - (unsigned int)i) & 1u);
-            if (b->join_cap[js] != cap) continue;
-            SOLO_CHECK(hipStreamWaitEvent(s, b->evJoinA[js], 0));
-            SOLO_CHECK(hipStreamWaitEvent(s, b->evJoinC[js], 0));
-        }
-    }
+#ifdef SOLO_WITH_ENCODER
+    // kernels of the most recent encode calls may still run on the internal streams (always so with async joins, and when
+    // reset is issued on another stream than the encode was): the init kernels must not overtake them
+    for (int which = 0; which < 2; which++) SOLO_CHECK(enc_pipe_wait(&b->enc, s, stream_capture(s), which, ENC_END));
+#endif
     // (the most recent decode call may have been issued on another stream than `s`)
     if (b->dec_done_recorded) SOLO_CHECK(hipStreamWaitEvent(s, b->evDecDone, 0));
     return 0;
@@ -599,18 +523,9 @@ void solo_batch_destroy(solo_batch_t* b) {
     dev_free(b->d_send_scratch);
     dev_free(b->d_mix_scratch);
     if (b->ev_ready) for (int i = 0; i < 2; i++) (void)hipEventDestroy(b->evDec[i]);
-    if (b->tev_ready) for (int k = 0; k < 3; k++) for (int c = 0; c < SOLO_MAX_CHUNKS; c++) for (int e = 0; e < 2; e++) (void)hipEventDestroy(b->tev[k][c][e]);
-    if (b->pipe_ready) {
-        (void)hipStreamSynchronize(b->sA); (void)hipStreamSynchronize(b->sB); (void)hipStreamSynchronize(b->sC);
-        (void)hipStreamDestroy(b->sA); (void)hipStreamDestroy(b->sB); (void)hipStreamDestroy(b->sC);
-        dev_free(b->d_started);
-        (void)hipEventDestroy(b->evFork);
-        for (int i = 0; i < 2; i++) { (void)hipEventDestroy(b->evJoinA[i]); (void)hipEventDestroy(b->evJoinC[i]); }
-        for (int c = 0; c < SOLO_MAX_CHUNKS; c++) (void)hipEventDestroy(b->evC[c]);
-        for (int c = 0; c < SOLO_MAX_CHUNKS; c++) { (void)hipEventDestroy(b->evA[c]); (void)hipEventDestroy(b->evB[c]); }
-    }
 #ifdef SOLO_WITH_ENCODER
-    solo_enc_free(b);
+    enc_pipe_destroy(&b->enc);
+    dev_free(b->d_enc_state);
 #endif
     delete b;
 }
@@ -1373,167 +1288,13 @@ int32_t solo_batch_import_streams(solo_batch_t* b, const int32_t* d_streams, int
 }
 
 #ifdef SOLO_WITH_ENCODER
-// one-time set-up of a handle's encoder pipeline: internal streams, events, knobs (documented in INTEGRATION.md section 5), scratch
-static int32_t solo_enc_pipe_setup(solo_batch* b) {
-    const solo_enc_ops* ops = b->eops;
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);            // hi = numerically lowest = greatest priority
-    SOLO_CHECK(hipStreamCreateWithPriority(&b->sA, hipStreamNonBlocking, lo));
-    SOLO_CHECK(hipStreamCreateWithPriority(&b->sB, hipStreamNonBlocking, hi));
-    SOLO_CHECK(hipStreamCreateWithPriority(&b->sC, hipStreamNonBlocking, lo));
-    SOLO_CHECK(hipEventCreateWithFlags(&b->evFork, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) {
-        SOLO_CHECK(hipEventCreateWithFlags(&b->evJoinA[i], hipEventDisableTiming));
-        SOLO_CHECK(hipEventCreateWithFlags(&b->evJoinC[i], hipEventDisableTiming));
-    }
-    for (int c = 0; c < SOLO_MAX_CHUNKS; c++) {
-        SOLO_CHECK(hipEventCreateWithFlags(&b->evA[c], hipEventDisableTiming));
-        SOLO_CHECK(hipEventCreateWithFlags(&b->evB[c], hipEventDisableTiming));
-        SOLO_CHECK(hipEventCreateWithFlags(&b->evC[c], hipEventDisableTiming));
-    }
-    int dev = 0, ncu = 0;
-    SOLO_CHECK(hipGetDevice(&dev));
-    SOLO_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    // SOLO_ENC_PERSIST=1: the persistent schedule (two kernels per call that hand packets over through flags) instead of one launch per
-    // chunk and stage.  Bit-exact and deadlock-free by construction, but measured SLOWER (54 - 60 against 50.5 ms per 4096 x 50 packets:
-    // DESIGN.md section 9 has the trace): it removes the launch tails, but it also fixes the SIMD's population at five dependent
-    // chains, where the launch-per-chunk schedule reaches nine.  Off unless asked for.
-    b->persist = env_int("SOLO_ENC_PERSIST", 0) != 0;
-    b->chunk_packets = env_int("SOLO_ENC_CHUNK", 1);
-    if (b->chunk_packets < 0) b->chunk_packets = 1;
-    // SOLO_ENC_RC_BATCH: packets per range-coder launch.  The coder is latency bound: one launch over k chunks takes about as long as
-    // one chunk's.  What its launch per chunk did for the schedule -- hold the next high band back until the quantiser launch that
-    // starts at the same moment is resident -- a bounded gate in front of the high band does directly (- 5 %).
-    // 1 = a coder launch behind every chunk's high band, no gate.
-    b->rc_batch = env_int("SOLO_ENC_RC_BATCH", SOLO_ENC_RC_BATCH_DEFAULT);
-    if (b->rc_batch < 1) b->rc_batch = 1;
-    if (b->rc_batch > ops->rc_batch_max) b->rc_batch = ops->rc_batch_max;
-    // launch per chunk: the residency gate (hold analysis chunk c + 1 until the quantiser launch of chunk c is resident) costs 3 % with 256
-    // quantiser workgroups per chunk: off unless asked for.  Persistent: ONE gate per launch group, in front of the front kernel -- the
-    // quantiser's wavefronts have to be resident before 4096 front workgroups take every register of the device: on unless turned off.
-    b->gate = getenv("SOLO_ENC_GATE") ? (env_int("SOLO_ENC_GATE", 0) != 0) : -1;      // (-1: the schedule's default)
-    // streams per launch group.  Launch per chunk: 8192 (one group of 8192 takes 120 ms per 50 packets, two of 4096 take 134).  Persistent:
-    // what is resident at once -- front workgroups per compute unit (LDS-bound: 16 at the 16 kHz rate, 9 at 32 kHz) x compute units, a
-    // multiple of the quantiser's four streams per wavefront: a larger group's last workgroups would only start when the first ones have
-    // finished ALL their packets, while their quantiser wavefronts held registers from the start
-    const int g_env = env_int("SOLO_ENC_GROUP", -1);
-    b->group_streams = g_env >= 0 ? g_env : 8192;
-    b->persist_group = g_env > 0 ? ((g_env + 3) & ~3) : ((ops->front_per_cu * (ncu > 0 ? ncu : 256)) & ~3);
-    if (b->persist_group < 4) b->persist_group = 4;
-    {
-        // (-1, tests: the front launch codes nothing -- no look at the quantiser's flags at all --, the second launch every packet)
-        const long us = env_int("SOLO_ENC_FINAL_WAIT_US", 20000);
-        b->front_defer = us < 0;
-        b->final_wait_ticks = (unsigned int)((us < 0 ? 0 : (us > 10000000 ? 10000000 : us)) * 100);
-    }
-    {   // the quantiser launches of a call run one after the other on sB: one ring, sized for the largest launch group
-        int gs = (b->group_streams > 0 && b->group_streams < b->n_streams) ? b->group_streams : b->n_streams;
-        if (b->persist && b->persist_group > gs) gs = b->persist_group < b->n_streams ? b->persist_group : b->n_streams;
-        SOLO_CHECK(hipMalloc(&b->d_nsq_ring, ops->nsq_ring_bytes(gs)));
-    }
-    SOLO_CHECK(hipMalloc((void**)&b->d_started, SOLO_MAX_CHUNKS * sizeof(unsigned int)));
-    SOLO_CHECK(hipMemset(b->d_started, 0, SOLO_MAX_CHUNKS * sizeof(unsigned int)));
-    memset(b->started_target, 0, sizeof(b->started_target));
-    if (b->persist) {
-        const size_t nflags = (size_t)b->n_streams * 2 + (size_t)b->n_streams / 4 + 1 + 4;
-        SOLO_CHECK(hipMalloc((void**)&b->d_flags, nflags * sizeof(unsigned int)));
-        SOLO_CHECK(hipMemset(b->d_flags, 0, nflags * sizeof(unsigned int)));
-        const int gs = b->persist_group < b->n_streams ? b->persist_group : b->n_streams;
-        SOLO_CHECK(hipMalloc(&b->d_front_scratch, ops->front_scratch_bytes(gs)));
-        SOLO_CHECK(hipMalloc(&b->d_nsq_stage, ops->nsq_stage_bytes(gs)));
-    }
-    b->ticket = 0;
-    b->pipe_ready = 1;
-    return 0;
-}
-
-// Persistent schedule of one call: per launch group ONE quantiser launch (sB) and ONE front launch (sA) that hand packets to each other
-// through flags while they run (solo_enc_kernels.h), then the front kernel once more behind the quantiser (mode 1: what a bounded wait
-// left undone -- nothing, normally).
-static int32_t solo_encode_persist(solo_batch* b, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes, int32_t* d_status,
-                                   hipStream_t st, void* nin, void* nout, void* cin) {
-    const solo_enc_ops* ops = b->eops;
-    // not in a graph: the tickets are host counters passed by value, a replay would find the flags of the replay before it already raised
-    if (stream_capture(st) != 0) return -(int32_t)hipErrorStreamCaptureUnsupported;
-    const int G = b->persist_group, ngroups = (b->n_streams + G - 1) / G;
-    const bool tm = b->timing && b->tev_ready && ngroups <= SOLO_MAX_CHUNKS;
-    unsigned int* ana = b->d_flags;
-    unsigned int* nsqf = ana + b->n_streams;
-    unsigned int* prog = nsqf + (size_t)b->n_streams / 4 + 1;
-    unsigned int* err = prog + b->n_streams;
-    const unsigned int ticket0 = b->ticket;
-    b->ticket += (unsigned int)n_packets;
-    const size_t frame_samples = (size_t)enc_packet_samples(b);
-    SOLO_CHECK(hipEventRecord(b->evFork, st));
-    SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evFork, 0));
-    SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evFork, 0));
-    if (b->enc_seq > 0 && b->join_cap[(b->enc_seq - 1u) & 1u] == 0) {          // the previous call (of either schedule) has read its hand-over records to the end
-        const int jp = (int)((b->enc_seq - 1u) & 1u);
-        SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evJoinC[jp], 0));
-        SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evJoinC[jp], 0));
-        SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evJoinA[jp], 0));
-    }
-    b->evC_valid = 0;
-    b->last_np = n_packets;
-    b->last_cp = 0;
-    hipError_t lerr = hipSuccess;
-    for (int g = 0; g < ngroups && lerr == hipSuccess; g++) {
-        const int s0 = g * G, ns = (s0 + G <= b->n_streams) ? G : b->n_streams - s0, c = g % SOLO_MAX_CHUNKS;
-        const size_t pk0 = (size_t)s0 * (size_t)n_packets;
-        void* g_states = (char*)b->d_enc_state + (size_t)s0 * ops->state_bytes;
-        void* g_nin = (char*)nin + pk0 * 2 * ops->nsq_in_bytes;
-        void* g_nout = (char*)nout + pk0 * 2 * ops->nsq_out_bytes;
-        void* g_cin = (char*)cin + pk0 * ops->code_in_bytes;
-        const int16_t* g_pcm = d_pcm + pk0 * frame_samples;
-        uint8_t* g_bits = d_bits + pk0 * (size_t)b->slot;
-        int16_t* g_nbytes = d_nbytes + pk0 * 2;
-        int32_t* g_status = d_status ? d_status + s0 : NULL;
-        // the front kernel first; the quantiser's launch is held until the front workgroups have started (they fill every compute unit
-        // up to one 128-register hole per SIMD, which is where the quantiser's wavefronts then go: solo_nsq_row.hip, "Residency")
-        // (sB comes up to where sA stands -- behind the previous group's last launch -- before it starts counting)
-        if ((lerr = hipEventRecord(b->evA[c], b->sA)) != hipSuccess) break;
-        if ((lerr = hipStreamWaitEvent(b->sB, b->evA[c], 0)) != hipSuccess) break;
-        if (tm) (void)hipEventRecord(b->tev[0][c][0], b->sA);
-        lerr = ops->front(g_states, g_pcm, ns, n_packets, g_nin, g_cin, g_nout, ana + s0, nsqf + s0 / 4, prog + s0, ticket0, b->front_defer ? 2 : 0, b->final_wait_ticks, b->slot,
-                          g_bits, g_nbytes, g_status, b->d_front_scratch, &b->d_started[c], b->sA);
-        if (lerr != hipSuccess) break;
-        b->started_target[c] += (unsigned int)((ns + ops->front_waves - 1) / ops->front_waves);
-        if (tm) (void)hipEventRecord(b->tev[0][c][1], b->sA);
-        if (b->gate != 0) (void)solo_launch_gate(&b->d_started[c], b->started_target[c], b->sB);
-        if (tm) (void)hipEventRecord(b->tev[1][c][0], b->sB);
-        lerr = (hipError_t)ops->nsq_persist(g_states, g_nin, g_nout, ns, n_packets, NULL, b->d_nsq_ring, ana + s0, nsqf + s0 / 4, ticket0, err, b->d_nsq_stage, b->sB);
-        if (lerr != hipSuccess) break;
-        if (tm) (void)hipEventRecord(b->tev[1][c][1], b->sB);
-        if ((lerr = hipEventRecord(b->evB[c], b->sB)) != hipSuccess) break;
-        if ((lerr = hipStreamWaitEvent(b->sA, b->evB[c], 0)) != hipSuccess) break;
-        if (tm) (void)hipEventRecord(b->tev[2][c][0], b->sA);
-        lerr = ops->front(g_states, g_pcm, ns, n_packets, g_nin, g_cin, g_nout, ana + s0, nsqf + s0 / 4, prog + s0, ticket0, 1, 0u, b->slot, g_bits, g_nbytes,
-                          g_status, b->d_front_scratch, NULL, b->sA);
-        if (tm) (void)hipEventRecord(b->tev[2][c][1], b->sA);
-    }
-    // join (also after a refused launch: whatever was enqueued still runs, nothing of this call stays forked)
-    const int js = (int)(b->enc_seq & 1u);
-    b->enc_seq++;
-    b->join_cap[js] = 0;
-    (void)hipEventRecord(b->evJoinA[js], b->sA);
-    (void)hipEventRecord(b->evJoinC[js], b->sB);
-    if (!b->async_join || lerr != hipSuccess) {
-        (void)hipStreamWaitEvent(st, b->evJoinA[js], 0);
-        (void)hipStreamWaitEvent(st, b->evJoinC[js], 0);
-    }
-    b->last_chunks = (lerr == hipSuccess && (tm || ngroups <= SOLO_MAX_CHUNKS)) ? ngroups : 0;
-    if (tm && lerr == hipSuccess) b->ev_enc = 1;
-    SOLO_CHECK(lerr);
-    SOLO_CHECK(hipGetLastError());
-    return 0;
-}
-
 // map = NULL: every stream (solo_batch_encode); else the n listed streams of solo_batch_encode_streams: PCM, payloads, status and the
-// hand-over records at the compact position, the stream state through the map (solo_stream_ctl.h)
+// hand-over records at the compact position, the stream state through the map (solo_stream_ctl.h).  The schedules: solo_enc_pipe.h
 static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes,
                                 int32_t* d_status, hipStream_t st) {
     const size_t np = (size_t)b->n_streams * (size_t)n_packets;
     const solo_enc_ops* ops = b->eops;
+    solo_enc_pipe* p = &b->enc;
     // a subset call's quantiser addresses the states of its rows with 32-bit offsets from the handle's first state (solo_nsq_row.hip)
     if (map && (unsigned long long)b->n_streams * (unsigned long long)ops->state_bytes >= (1ull << 32)) return -1;
     // the quantiser addresses the hand-over records of its wavefront's four streams with 32-bit offsets from a wave-uniform base
@@ -1541,193 +1302,46 @@ static int32_t solo_encode_impl(solo_batch_t* b, const int32_t* map, int32_t n, 
     // below 4 GiB (~700 k packets per call at the 16 kHz API rate)
     const unsigned long long per_wave = 64ull / (unsigned long long)ops->nsq_workgroups(64);
     if (((per_wave - 1ull) * 2ull * (unsigned long long)n_packets + 1ull) * (unsigned long long)ops->nsq_out_bytes >= (1ull << 32)) return -1;
+    int32_t r;
+    if (!p->ready && (r = enc_pipe_setup(p, ops, b->n_streams, b->slot, enc_packet_samples(b))) != 0) return r;
     const size_t sz_in = np * 2 * ops->nsq_in_bytes, sz_out = np * 2 * ops->nsq_out_bytes, sz_code = np * ops->code_in_bytes;
-    if (n_packets > b->enc_work_packets) {          // grow the hand-over area (synchronises; steady-state launches do not)
-        SOLO_CHECK(hipStreamSynchronize(st));
-        if (b->pipe_ready) { (void)hipStreamSynchronize(b->sA); (void)hipStreamSynchronize(b->sB); (void)hipStreamSynchronize(b->sC); }
-        dev_free(b->d_enc_work);
-        SOLO_CHECK(hipMalloc(&b->d_enc_work, sz_in + sz_out + sz_code + 256));
-        b->enc_work_packets = n_packets;
+    if (sz_in + sz_out + sz_code + 256 > p->enc_work_bytes) {          // the hand-over area grows (synchronises; steady-state calls do not)
+        (void)hipStreamSynchronize(p->sA); (void)hipStreamSynchronize(p->sB); (void)hipStreamSynchronize(p->sC);
     }
-    void* nin = b->d_enc_work;
-    void* nout = (char*)b->d_enc_work + ((sz_in + 63) & ~(size_t)63);
-    void* cin = (char*)nout + ((sz_out + 63) & ~(size_t)63);
-    void* states = b->d_enc_state;
-    if (!b->pipe_ready) {
-        const int32_t r = solo_enc_pipe_setup(b);
-        if (r) return r;
-    }
+    SOLO_CHECK(grow_scratch(p->d_enc_work, p->enc_work_bytes, sz_in + sz_out + sz_code + 256, st));
+    enc_rows call = {0, map ? n : b->n_streams, b->d_enc_state, map, d_pcm, NULL, NULL, NULL, d_bits, d_nbytes, d_status};
+    call.nin = p->d_enc_work;
+    call.nout = (char*)call.nin + ((sz_in + 63) & ~(size_t)63);
+    call.cin = (char*)call.nout + ((sz_out + 63) & ~(size_t)63);
     // SOLO_ENC_PERSIST=1: calls of two or more packets run the persistent schedule (a single packet has nothing to pipeline inside the call);
     // a subset call always runs the launch-per-chunk schedule
-    if (!map && b->persist && n_packets >= 2) return solo_encode_persist(b, d_pcm, n_packets, d_bits, d_nbytes, d_status, st, nin, nout, cin);
-
-    // Launch per chunk: chunk c of the call's packets goes analysis (stream sA) -> quantiser (sB) -> high band, range coder (sC).  A_c
-    // follows A_{c-1}, B_c follows A_c and B_{c-1}, C_c follows B_c and C_{c-1}; so the quantiser of chunk c (one wave per SIMD, latency
-    // bound) runs next to the analysis of chunk c + 1 and the coding of chunk c - 1 (instruction bound): they share the SIMDs.  The
-    // kernels of different types touch disjoint parts of the stream records.  The caller's stream is forked / joined by events.
-    int cp = b->chunk_packets > 0 ? b->chunk_packets : n_packets;
-    int nchunks = (n_packets + cp - 1) / cp;
-    if (nchunks > SOLO_MAX_CHUNKS) { cp = (n_packets + SOLO_MAX_CHUNKS - 1) / SOLO_MAX_CHUNKS; nchunks = (n_packets + cp - 1) / cp; }
-    // the previous call's events are waited for only inside one context (stream_capture); on the other side of a capture this call
-    // starts behind everything of it through the fork from `st`
-    const unsigned long long cap = stream_capture(st);
-    // chunks per range-coder launch: whole chunks, SOLO_ENC_RC_BATCH packets at the most; 1 (a call of one chunk, and a call that is
-    // captured into a graph: the gate's target is a running count passed by value): ops->coding per chunk
-    const int kc = nchunks > 1 && !cap && b->rc_batch / cp > 1 ? (b->rc_batch / cp < nchunks ? b->rc_batch / cp : nchunks) : 1;
-    const int kb_cap = kc * cp;
-    {   // scratch of one coding launch: the byte buffers of its descriptions
-        const int gs = (b->group_streams > 0 && b->group_streams < b->n_streams) ? b->group_streams : b->n_streams;
-        // (sC: a coding launch of the previous call may still read the old one)
-        SOLO_CHECK(grow_scratch(b->d_rc_scratch, b->rc_scratch_bytes, ops->rc_scratch_bytes(gs, kb_cap), b->sC));
-    }
-    const bool tm_req = b->timing && b->tev_ready;
-    if (b->enc_seq > 0 && b->join_cap[(b->enc_seq - 1u) & 1u] != cap) b->evC_valid = -1;
+    if (!map && p->persist && n_packets >= 2) return enc_pipe_run_persist(p, call, n_packets, b->timing != 0, st);
     uint32_t* verdict = NULL;
     if (map) {
-        // the layout of the hand-over records depends on the list: no chunk-wise reuse across a subset call, either side
-        if (b->evC_valid > 0) b->evC_valid = 0;
         // the verdict word of this call; the call two before used the same one: its kernels must be through
-        verdict = b->d_verdict + SOLO_VERDICT_ENC + (b->enc_seq & 1u);
-        if (b->enc_seq >= 2 && b->join_cap[b->enc_seq & 1u] == cap) {
-            SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinA[b->enc_seq & 1u], 0));
-            SOLO_CHECK(hipStreamWaitEvent(st, b->evJoinC[b->enc_seq & 1u], 0));
-        }
+        const unsigned long long cap = stream_capture(st);
+        verdict = b->d_verdict + SOLO_VERDICT_ENC + enc_pipe_call_set(p, -1, cap);
+        SOLO_CHECK(enc_pipe_wait(p, st, cap, 1, ENC_END));
         SOLO_CHECK(launch_list_check(map, n, b->n_streams, verdict, d_status, st));
     }
-    if (b->evC_valid < 0) b->evC_valid = 0;          // (the previous call was issued on the other side of a capture: nothing to wait for)
-    else if (b->enc_seq > 0 && (b->last_np != n_packets || b->last_cp != cp || b->evC_valid == 0)) {
-        // the previous call laid its hand-over records out differently (or ran the persistent schedule): no chunk-wise reuse, wait for all of it
-        SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evJoinC[(b->enc_seq - 1u) & 1u], 0));
-        SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evJoinA[(b->enc_seq - 1u) & 1u], 0));
-        b->evC_valid = 0;
-    }
-    b->last_np = n_packets;
-    b->last_cp = cp;
-    SOLO_CHECK(hipEventRecord(b->evFork, st));
-    SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evFork, 0));
-    SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evFork, 0));
-    SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evFork, 0));
-    // Streams beyond the launch group (SOLO_ENC_GROUP) are processed group after group; all per-stream arrays are stream-major, so a
-    // group is the same launch on offset pointers.
-    // (a subset call: groups of compact positions, group g works on the streams map[s0 .. s0 + ns))
-    const int nall = map ? n : b->n_streams;
-    const int G = b->group_streams > 0 ? b->group_streams : nall;
-    const int ngroups = (nall + G - 1) / G;
-    const bool tm = tm_req && (size_t)ngroups * (size_t)nchunks <= SOLO_MAX_CHUNKS;     // (per-launch timing brackets: one per event slot)
-    const size_t frame_samples = (size_t)enc_packet_samples(b);
-    int idx = 0;
-    hipError_t lerr = hipSuccess;
-#ifdef SX_EXPERIMENTS     // builds for the section tools only (tools/build_stops.sh): SOLO_EXP_SKIP bit 0 = no quantiser, bit 1 = no third stage, bit 2 = no range coder -- wrong output
-    static const int exp_skip = env_int("SOLO_EXP_SKIP", 0);
-#else
-    constexpr int exp_skip = 0;
-#endif
-    for (int g = 0; g < ngroups && lerr == hipSuccess; g++) {
-        const int s0 = g * G, ns = (s0 + G <= nall) ? G : nall - s0;
-        const size_t pk0 = (size_t)s0 * (size_t)n_packets;                               // first packet record of the group
-        void* g_states = map ? states : (char*)states + (size_t)s0 * ops->state_bytes;
-        const int32_t* g_map = map ? map + s0 : NULL;
-        const int16_t* g_pcm = d_pcm + pk0 * frame_samples;
-        void* g_nin = (char*)nin + pk0 * 2 * ops->nsq_in_bytes;
-        void* g_nout = (char*)nout + pk0 * 2 * ops->nsq_out_bytes;
-        void* g_cin = (char*)cin + pk0 * ops->code_in_bytes;
-        uint8_t* g_bits = d_bits + pk0 * (size_t)b->slot;
-        int16_t* g_nbytes = d_nbytes + pk0 * 2;
-        int32_t* g_status = d_status ? d_status + s0 : NULL;
-        int pb = 0, hb_end = 0, idx_b = idx;         // the open batch of the coder: its first packet, the end of its chunks with a high-band launch, its first event slot
-        int pend = -1, pend_idx = 0;
-        auto third = [&](int tcc, int tidx) -> hipError_t {
-            const int tc = tidx % SOLO_MAX_CHUNKS, tp0 = tcc * cp, tpc = (tp0 + cp <= n_packets) ? cp : n_packets - tp0;
-            const bool last = (tcc + 1) % kc == 0 || tcc + 1 == nchunks;
-            hipError_t e;
-            if (tm) (void)hipEventRecord(b->tev[2][tc][0], b->sC);
-            if (!(exp_skip & 2) && (e = ops->hb(g_states, g_cin, g_nout, ns, n_packets, tp0, tpc, pb, kb_cap, cp, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) return e;
-            hb_end = tp0 + tpc;
-            if (last && !(exp_skip & 6) &&
-                (e = ops->rc_batch(g_states, g_cin, g_nout, ns, n_packets, pb, hb_end - pb, kb_cap, cp, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) return e;
-            if (tm) (void)hipEventRecord(b->tev[2][tc][1], b->sC);
-            if (last) {
-                for (int i = idx_b; i <= tidx; i++) if ((e = hipEventRecord(b->evC[i % SOLO_MAX_CHUNKS], b->sC)) != hipSuccess) return e;
-                pb = hb_end;
-                idx_b = tidx + 1;
-            }
-            return hipSuccess;
-        };
-        for (int cc = 0; cc < nchunks; cc++, idx++) {
-            const int c = idx % SOLO_MAX_CHUNKS, cprev = (idx + SOLO_MAX_CHUNKS - 1) % SOLO_MAX_CHUNKS;     // event / counter slot
-            const int p0 = cc * cp, pc = (p0 + cp <= n_packets) ? cp : n_packets - p0;
-            if (ngroups == 1 && cc < b->evC_valid) SOLO_CHECK(hipStreamWaitEvent(b->sA, b->evC[c], 0));      // (previous call: its coding of this chunk's records is done)
-            if (idx > 0 && b->gate > 0) (void)solo_launch_gate(&b->d_started[cprev], b->started_target[cprev], b->sA);
-            if (tm) (void)hipEventRecord(b->tev[0][c][0], b->sA);
-            // (a refused launch leaves both loops for the join block below)
-            if ((lerr = ops->analysis(g_states, g_pcm, ns, n_packets, p0, pc, g_nin, g_cin, g_map, verdict, b->sA)) != hipSuccess) break;
-            if (tm) (void)hipEventRecord(b->tev[0][c][1], b->sA);
-            SOLO_CHECK(hipEventRecord(b->evA[c], b->sA));
-            SOLO_CHECK(hipStreamWaitEvent(b->sB, b->evA[c], 0));
-            if (tm) (void)hipEventRecord(b->tev[1][c][0], b->sB);
-            if (!(exp_skip & 1)) {
-            if ((lerr = (hipError_t)ops->nsq(g_states, g_nin, g_nout, ns, n_packets, p0, pc, &b->d_started[c], b->d_nsq_ring, g_map, verdict, b->sB)) != hipSuccess) break;
-            b->started_target[c] += (unsigned int)ops->nsq_workgroups(ns);     // workgroups of this launch, counted once it is enqueued
-            }
-            if (tm) (void)hipEventRecord(b->tev[1][c][1], b->sB);
-            SOLO_CHECK(hipEventRecord(b->evB[c], b->sB));
-            if (kc > 1 || (exp_skip & 4)) {
-                // the high band of a chunk; behind the batch's (the call's) last chunk the range coder of all of its packets.  evC[] of the
-                // batch's chunks only then: the coder reads their hand-over records
-                if (kc <= 1 || (exp_skip & 1)) {          // (timing builds)
-                    SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[c], 0));
-                    if ((lerr = third(cc, idx)) != hipSuccess) break;
-                } else {
-                    // the third stage of the chunk BEFORE, behind its quantiser launch and a gate that holds it until this chunk's quantiser
-                    // launch -- which starts when that one ends -- is resident: the high band's 4096 workgroups would take the register
-                    // holes its wavefronts need.  The gate gives up after ~0.5 ms (sC has that much slack per chunk).
-                    if (pend >= 0) {
-                        SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[cprev], 0));
-                        (void)solo_launch_gate_for(&b->d_started[c], b->started_target[c], SOLO_HB_GATE_ITERS, b->sC);
-                        if ((lerr = third(pend, pend_idx)) != hipSuccess) break;
-                    }
-                    pend = cc; pend_idx = idx;
-                }
-                continue;
-            }
-            SOLO_CHECK(hipStreamWaitEvent(b->sC, b->evB[c], 0));
-            if (tm) (void)hipEventRecord(b->tev[2][c][0], b->sC);
-            if (!(exp_skip & 2))
-            if ((lerr = ops->coding(g_states, g_cin, g_nout, ns, n_packets, p0, pc, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC)) != hipSuccess) break;
-            if (tm) (void)hipEventRecord(b->tev[2][c][1], b->sC);
-            SOLO_CHECK(hipEventRecord(b->evC[c], b->sC));
-        }
-        if (pend >= 0) {
-            (void)hipStreamWaitEvent(b->sC, b->evB[pend_idx % SOLO_MAX_CHUNKS], 0);
-            const hipError_t e = third(pend, pend_idx);
-            if (lerr == hipSuccess) lerr = e;
-        }
-        if (lerr != hipSuccess && kc > 1 && hb_end > pb)       // a refused launch: the chunks whose high band is enqueued are still coded
-            (void)ops->rc_batch(g_states, g_cin, g_nout, ns, n_packets, pb, hb_end - pb, kb_cap, cp, b->slot, g_bits, g_nbytes, g_status, b->d_rc_scratch, g_map, verdict, b->sC);
-    }
-    // join the internal streams back into the caller's.  After a refused launch too: whatever was enqueued so far still runs, nothing of
-    // this call is left forked (sB as well, which sC's last launch may not have waited for), the chunk-wise guards are dropped
-    const bool ok = lerr == hipSuccess;
-    b->evC_valid = (ok && ngroups == 1 && !map) ? nchunks : 0;       // chunk-wise hand-over guards only for single-group calls of every stream
-    const int js = (int)(b->enc_seq & 1u);
-    b->enc_seq++;
-    b->join_cap[js] = cap;
-    (void)hipEventRecord(b->evJoinA[js], b->sA);
-    (void)hipEventRecord(b->evJoinC[js], b->sC);      // (sC's last launch waits for sB's)
-    if (!b->async_join || !ok) {
-        (void)hipStreamWaitEvent(st, b->evJoinA[js], 0);
-        (void)hipStreamWaitEvent(st, b->evJoinC[js], 0);
-    }
-    if (!ok) {
-        (void)hipEventRecord(b->evFork, b->sB);
-        (void)hipStreamWaitEvent(st, b->evFork, 0);
-    }
-    b->last_chunks = !ok ? 0 : (tm ? ngroups * nchunks : (ngroups == 1 ? nchunks : 0));
-    if (tm && ok) b->ev_enc = 1;
-    SOLO_CHECK(lerr);
-    SOLO_CHECK(hipGetLastError());
+    return enc_pipe_run_chunks(p, call, n_packets, verdict, b->timing != 0, st);
+}
+// Asynchronous joins: with on = 1 solo_batch_encode returns without making the caller's stream wait for its internal streams, so
+// that the next encode call can start (its first analysis chunk) while the last quantiser / coding chunks of this one still run.
+// Whoever consumes the outputs then calls solo_batch_wait_encode(b, stream, which) first: which = 0 the most recent encode call,
+// 1 the one before.  The hand-over records are guarded inside the library; the OUTPUT buffers of two calls in flight must differ.
+int32_t solo_batch_set_async_join(solo_batch_t* b, int32_t on) {
+    if (!b) return -1;
+    b->enc.async_join = on ? 1 : 0;
     return 0;
 }
+int32_t solo_batch_wait_encode(solo_batch_t* b, void* hip_stream, int32_t which) {
+    if (!b || which < 0 || which > 1) return b ? 0 : -1;
+    // (a call issued on the other side of a capture is not waited for: stream order, see stream_capture)
+    SOLO_CHECK(enc_pipe_wait(&b->enc, (hipStream_t)hip_stream, stream_capture((hipStream_t)hip_stream), which, ENC_END));
+    return 0;
+}
+int32_t solo_batch_last_encode_chunks(const solo_batch_t* b) { return b ? b->enc.last_chunks : 0; }
 int32_t solo_batch_encode(solo_batch_t* b, const int16_t* d_pcm, int32_t n_packets, uint8_t* d_bits, int16_t* d_nbytes,
                           int32_t* d_status, void* hip_stream) {
     if (!b || !b->have_enc || !d_pcm || !d_bits || !d_nbytes || n_packets <= 0) return -1;
@@ -1741,6 +1355,9 @@ int32_t solo_batch_encode_streams(solo_batch_t* b, const int32_t* d_streams, int
 #else
 int32_t solo_batch_encode(solo_batch_t*, const int16_t*, int32_t, uint8_t*, int16_t*, int32_t*, void*) { return -1; }
 int32_t solo_batch_encode_streams(solo_batch_t*, const int32_t*, int32_t, const int16_t*, int32_t, uint8_t*, int16_t*, int32_t*, void*) { return -1; }
+int32_t solo_batch_set_async_join(solo_batch_t* b, int32_t) { return b ? 0 : -1; }
+int32_t solo_batch_wait_encode(solo_batch_t* b, void*, int32_t) { return b ? 0 : -1; }
+int32_t solo_batch_last_encode_chunks(const solo_batch_t*) { return 0; }
 #endif
 
 // ---- the reference's six entry points: a batch of one stream, staged through device buffers ----------

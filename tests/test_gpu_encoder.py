@@ -284,14 +284,13 @@ def test_stream_groups_of_the_pipeline(torch_cuda, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("order", ["1", "0", "2"])
-def test_payload_larger_than_its_slot_is_reported_not_written(torch_cuda, monkeypatch, order):
+def test_payload_larger_than_its_slot_is_reported_not_written(torch_cuda):
     """A payload that does not fit the caller's slot (AGR_Sate_Encoder_Encode's nBytesOut / buffer check, AGR_BWE_SDK_API.c:129 ->
     sx_enc_stage_c_out): both byte counts of the packet are 0, the stream's status carries the first error of the call, every other
-    packet of the batch is unaffected -- under each launch order of the third stage (the assembly lives in a different kernel in each)."""
+    packet of the batch is unaffected.  (The default schedule: the payloads are assembled by the batched range coder; the coder of one
+    launch per chunk takes the same case in tests/test_gpu_rc_batch.py, "slot".)"""
     import solo_amd
     torch = torch_cuda
-    monkeypatch.setenv("SOLO_ENC_CORDER", order)
     z = np.load(T.GOLDEN + "/synth8x25.npz")
     P, S = 12, 80                                              # golden payloads of these packets: 56 .. 114 bytes
     b = solo_amd.SoloBatch(8, encoder=True, decoder=False, slot_bytes=S)
