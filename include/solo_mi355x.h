@@ -787,6 +787,90 @@ int32_t solo_batch_export_streams(solo_batch_t *b, const int32_t *d_streams, int
                                   uint8_t *d_blob, int64_t blob_stride, solo_migrate_count_t *d_count, void *hip_stream);
 int32_t solo_batch_import_streams(solo_batch_t *b, const int32_t *d_streams, int32_t n, int32_t which,
                                   const uint8_t *d_blob, int64_t blob_stride, solo_migrate_count_t *d_count, void *hip_stream);
+/* RTP at both ends of the bridge: solo_rtp_pack puts an RTP header (RFC 3550 section 5.1) in front of every datagram solo_send_pack /
+ * solo_send_fanout recorded, so that what leaves the device is what the socket sends; solo_rtp_parse turns received datagrams into the
+ * arrivals solo_recv_insert takes, in place (no payload byte moves twice).  The RFC 6464 audio level of solo_vad / solo_agc travels in a
+ * one-byte header extension (RFC 8285 section 4.2) and is read back without decoding.  A solo_rtp_t is an object of its own beside a
+ * handle: the per-stream configuration and a sorted (SSRC, stream) table on the device, a mirror of both on the host.  The device code
+ * never writes them: with the configuration held fixed, both calls are pure functions of their inputs.
+ *   packet_samples   timestamp ticks per packet: 320, 640 or 1280 (the handle's packet samples)
+ * Control plane -- HOST arrays, as for solo_batch_reset_streams.  solo_rtp_bind gives the listed streams their SSRC, timestamp offset,
+ * sequence offset (the random starts of RFC 3550) and the payload types of MD1 and of MD2 || HB (0 .. 127; equal types: the receiver reads
+ * the description from the payload, which takes useMDIndex = 1) and marks them bound; level_id, the RFC 8285 element id of the audio
+ * level (1 .. 14; 0: parse looks for none, pack takes no levels), belongs to the session: the latest bind wins.  solo_rtp_unbind takes
+ * the binding away (a stream that has none stays so).  Both rebuild the table from the mirror, are ordered on hip_stream, return when
+ * the table is on the device and are not capturable; a captured pack or parse reads the configuration of the moment it runs.  -1, and
+ * nothing changes: NULL r or array; n <= 0; an index outside [0, n_streams) or listed twice; a payload type above 127; level_id outside
+ * 0 .. 14; an SSRC that two bound streams would share after the call.  The host mirror moves only after the device holds the call's
+ * records and table: a call whose launches or copy fail is judged afterwards against what the session held before it.
+ * Wire format: 12 bytes, V = 2, P = 0, CC = 0, M = 0; PT = pt_md1 for description 0, pt_md2 for description 1; sequence number =
+ * seq_offset + 2 seq + desc mod 2^16 (a description that is not sent shows as a gap); timestamp = ts_offset + seq x packet_samples mod
+ * 2^32; the stream's SSRC.  With levels X = 1 and 8 more bytes: 0xBE 0xDE 0x00 0x01, level_id << 4, the level byte as it is (V << 7 |
+ * level), two zero bytes.  Header and payload are contiguous; every datagram starts at a multiple of 4 of d_wire and the 0 .. 3 bytes
+ * behind it are written as zero.
+ * solo_rtp_pack
+ *   d_records, d_send_count   what solo_send_pack / solo_send_fanout wrote; the records of the call are min(d_send_count->records,
+ *                    max_records), READ ON THE DEVICE: the call can sit behind solo_send_pack in one captured graph.
+ *                    d_send_count->records < 0 (a refused list): d_count->dgrams = -1 and nothing else is written
+ *   d_payload        the pool the records point into, payload_bytes long; offsets may repeat (fanout)
+ *   d_level          uint8 [n_streams][level_depth] or NULL (no extension): the byte of packet seq of stream s is
+ *                    d_level[s x level_depth + seq % level_depth]
+ *   d_dgrams         solo_dgram_t [max_records]: entry k belongs to record k (packet-major order is kept): where its datagram lies in d_wire,
+ *                    header included; {0, 0} for a record that is refused or cut by the cap.  Entries behind the call's records stay
+ *   d_wire           uint8 [wire_capacity]: the offsets are the running sum of roundup4(H + len) over the valid records, H = 12 or 20
+ *   d_count          one solo_rtp_pack_count_t (8-byte aligned): written and needed datagrams and bytes (pad bytes included), refused records
+ * Record k is refused -- and its payload never read -- when its stream is outside [0, n_streams) or not bound, desc is not 0 or 1, seq < 0,
+ * len <= 0, len > 32767 or [offset, offset + len) is not inside the pool.  A datagram is written iff it and its pad bytes end inside
+ * min(wire_capacity, 2^31 - 1): what is written is a prefix, nothing is written at or beyond the cap, wire_capacity = 0 only counts;
+ * d_count->bytes_needed is the capacity that never overflows.
+ * -1 with nothing enqueued: a NULL pointer other than d_level; max_records <= 0; a negative payload_bytes or wire_capacity; d_level with
+ * level_depth <= 0 or while the session's level_id is 0; d_records, d_send_count, d_dgrams or d_wire not 4-byte, d_count not 8-byte
+ * aligned.  Three short kernels on hip_stream only, no host synchronisation; the session's scratch for the scan (16 bytes per 256
+ * records) grows, with a stream synchronisation, when max_records is larger than in every call before.
+ * solo_rtp_parse
+ *   b                the receiving handle: it must have a receiver ring, the session's stream count and packet samples (-1 otherwise)
+ *   d_dgrams, d_wire n_dgrams datagrams inside d_wire (wire_bytes long), at any byte alignment
+ *   d_arrivals       solo_arrival_t [n_dgrams]: arrival i belongs to datagram i, its offset points at the payload inside d_wire -- then
+ *                    solo_recv_insert(b, d_arrivals, n_dgrams, d_wire, wire_bytes, hip_stream).  A rejected datagram yields
+ *                    {stream = -1, 0, 0, 0, 0}, WHICH THE RING COUNTS AS `bad`: d_count, not the ring's statistics, says why
+ *   d_level_out      uint8 [n_dgrams] or NULL: the level byte of an accepted datagram with X set, profile 0xBEDE and level_id > 0 -- the
+ *                    first one-byte element with id level_id and one data byte (id 0: a pad byte; id 15, or an element that reaches over
+ *                    the block's end: the walk stops); 255: none, any other profile (the two-byte form included) and rejected datagrams
+ *                    (a sender's byte 255, "voice at -127 dBov", therefore reads as none)
+ *   d_rtp_seq_out    uint16 [n_dgrams] or NULL: the raw 16-bit sequence number (0 for a rejected datagram), for transport statistics
+ *   d_count          one solo_rtp_parse_count_t: a counter per verdict
+ * The verdict is the FIRST rule that fails: malformed (len < 12 or a range outside [0, min(wire_bytes, 2^31 - 1)); 12 + 4 CC or the
+ * extension block, 4 + 4 x length with X set, reaches past the datagram; P set with a pad count of 0 or larger than what is left; no
+ * payload byte left; more than 32767 payload bytes), version (V != 2), unknown_ssrc (binary search of the bound table), unknown_pt
+ * (neither of the stream's two; equal types give desc = -1), timestamp.  The packet number comes from the TIMESTAMP, not from the
+ * sequence number, so any sender that stamps both descriptions with the packet's sampling instant interoperates; it is unwrapped against
+ * the stream's play-out position p (the ring's, read on the device): delta = (int32)(ts - ts_offset - (uint32)p x L) must be a multiple
+ * of L, seq = p + delta / L must lie in 0 .. 2^31 - 1.  No state, no dependence on arrival order, a window of about +-3.3 M packets at
+ * L = 640; late and ahead stay the ring's decision.
+ * -1 with nothing enqueued: NULL r, b or d_count; b as above; n_dgrams < 0 or wire_bytes < 0; with n_dgrams > 0 a NULL d_dgrams, d_wire or
+ * d_arrivals; d_dgrams, d_arrivals or d_count not 4-byte, d_rtp_seq_out not 2-byte aligned.  Two kernels (the clear of the count, then a lane per
+ * datagram) on hip_stream, no allocation, no host synchronisation: capturable with n_dgrams frozen.  Calls on a handle must be ordered
+ * with the rest of the ring (same stream, or events).  INTEGRATION.md section 2 has the tick. */
+typedef struct solo_rtp_obj solo_rtp_t;
+typedef struct { int32_t offset, len; } solo_dgram_t;      /* 8 bytes: one datagram inside a wire buffer */
+typedef struct {
+    int32_t dgrams, dgrams_needed;     /* written / what the call would have written without the cap; dgrams = -1: refused list */
+    int64_t bytes, bytes_needed;       /* the same for wire bytes, pad bytes included */
+    int32_t refused, reserved;         /* records that yield no datagram; 0 */
+} solo_rtp_pack_count_t;               /* 32 bytes */
+typedef struct { int32_t accepted, with_level, malformed, version, unknown_ssrc, unknown_pt, timestamp, reserved; } solo_rtp_parse_count_t;   /* 32 bytes */
+/* The session's lifecycle and control plane, then its two device calls. */
+solo_rtp_t *solo_rtp_create(int32_t n_streams, int32_t packet_samples);
+void    solo_rtp_destroy(solo_rtp_t *r);
+int32_t solo_rtp_bind(solo_rtp_t *r, const int32_t *h_streams, int32_t n, const uint32_t *h_ssrc, const uint32_t *h_ts_offset,
+                      const uint16_t *h_seq_offset, const uint8_t *h_pt_md1, const uint8_t *h_pt_md2, int32_t level_id, void *hip_stream);
+int32_t solo_rtp_unbind(solo_rtp_t *r, const int32_t *h_streams, int32_t n, void *hip_stream);
+int32_t solo_rtp_pack(solo_rtp_t *r, const solo_arrival_t *d_records, const solo_send_count_t *d_send_count, int32_t max_records,
+                      const uint8_t *d_payload, int64_t payload_bytes, const uint8_t *d_level, int32_t level_depth,
+                      solo_dgram_t *d_dgrams, uint8_t *d_wire, int64_t wire_capacity, solo_rtp_pack_count_t *d_count, void *hip_stream);
+int32_t solo_rtp_parse(solo_rtp_t *r, solo_batch_t *b, const solo_dgram_t *d_dgrams, int32_t n_dgrams, const uint8_t *d_wire, int64_t wire_bytes,
+                       solo_arrival_t *d_arrivals, uint8_t *d_level_out, uint16_t *d_rtp_seq_out, solo_rtp_parse_count_t *d_count,
+                       void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "solo_playout_create", "solo_playout_destroy", "solo_playout_reset", "solo_playout_reset_rows", "solo_playout_get_state",
     "solo_playout_set_state", "solo_playout_plan", "solo_playout_gather", "solo_playout_render", "solo_playout_tick",
     "solo_agc_create", "solo_agc_destroy", "solo_agc_reset", "solo_agc_reset_rows", "solo_agc_get_state", "solo_agc_set_state", "solo_agc",
+    "solo_rtp_create", "solo_rtp_destroy", "solo_rtp_bind", "solo_rtp_unbind", "solo_rtp_pack", "solo_rtp_parse",
 ]
 
 
@@ -142,6 +143,22 @@ class solo_recv_report_t(C.Structure):
 class solo_recv_report_count_t(C.Structure):
     """how many rows a solo_recv_report call selected, of how many listed; 8 bytes; selected = -1: list refused on the device"""
     _fields_ = [("selected", C.c_int32), ("listed", C.c_int32)]
+
+
+class solo_dgram_t(C.Structure):
+    """one datagram inside a wire buffer (include/solo_mi355x.h); 8 bytes"""
+    _fields_ = [("offset", C.c_int32), ("len", C.c_int32)]
+
+
+class solo_rtp_pack_count_t(C.Structure):
+    """what a solo_rtp_pack call wrote and what it needed (include/solo_mi355x.h); 32 bytes; dgrams = -1: the list behind the records was refused"""
+    _fields_ = [("dgrams", C.c_int32), ("dgrams_needed", C.c_int32), ("bytes", C.c_int64), ("bytes_needed", C.c_int64),
+                ("refused", C.c_int32), ("reserved", C.c_int32)]
+
+
+class solo_rtp_parse_count_t(C.Structure):
+    """datagrams per verdict of a solo_rtp_parse call (include/solo_mi355x.h); 32 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("accepted", "with_level", "malformed", "version", "unknown_ssrc", "unknown_pt", "timestamp", "reserved")]
 
 
 RECV_REPORT_CLEAR_MARGIN = 1
@@ -280,6 +297,19 @@ def load_library():
     lib.solo_agc.restype = C.c_int32
     lib.solo_agc.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                              C.POINTER(solo_agc_params_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_rtp_create.restype = C.c_void_p
+    lib.solo_rtp_create.argtypes = [C.c_int32, C.c_int32]
+    lib.solo_rtp_destroy.restype = None
+    lib.solo_rtp_destroy.argtypes = [C.c_void_p]
+    lib.solo_rtp_bind.restype = C.c_int32
+    lib.solo_rtp_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_rtp_unbind.restype = C.c_int32
+    lib.solo_rtp_unbind.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_rtp_pack.restype = C.c_int32
+    lib.solo_rtp_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p]
+    lib.solo_rtp_parse.restype = C.c_int32
+    lib.solo_rtp_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1542,3 +1572,136 @@ class Agc(_RowStateObject):
     def count(self, count):
         """a count tensor of run() as a dict (synchronises); rows == -1: the list was refused on the device"""
         return _counts(solo_agc_count_t, count)
+
+
+class Rtp(_RowObject):
+    """An RTP session beside a handle (solo_rtp_*, include/solo_mi355x.h): per stream an SSRC, the random timestamp and sequence
+    offsets of RFC 3550 and two payload types; pack() frames the records of send_pack() / send_fanout() for the socket, parse() turns
+    received datagrams into the arrivals recv_insert() takes, in place.  The device code has no mutable state."""
+
+    PACK_COUNT = ("dgrams", "dgrams_needed", "bytes", "bytes_needed", "refused")
+    PARSE_COUNT = ("accepted", "with_level", "malformed", "version", "unknown_ssrc", "unknown_pt", "timestamp")
+    PREFIX = "rtp"
+
+    def __init__(self, n_streams, packet_samples=PACKET_SAMPLES):
+        self.n_rows = self.n_streams = int(n_streams)
+        self.packet_samples = int(packet_samples)
+        self.level_id = 0
+        if self.n_streams <= 0 or self.packet_samples not in (320, 640, 1280):
+            raise ValueError("n_streams must be positive, packet_samples 320, 640 or 1280")
+        self._create(self.n_streams, self.packet_samples)
+
+    @staticmethod
+    def _per_stream(v, n, name, top):
+        """a scalar or one value per listed stream, each inside [0, top] -> list"""
+        try:
+            vals = [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)] if hasattr(v, "__len__") else [int(v)] * n
+        except (TypeError, ValueError):
+            vals = None
+        if vals is None or len(vals) != n or any(not 0 <= x <= top for x in vals):
+            raise ValueError("%s: a scalar or %d values inside [0, %d]" % (name, n, top))
+        return vals
+
+    def bind(self, streams, ssrc, ts_offset=0, seq_offset=0, pt=(96, 97), level_id=0):
+        """Bind the listed streams (a host sequence inside [0, n_streams), none twice): ssrc (32 bits), ts_offset (32 bits) and seq_offset
+        (16 bits) a scalar or one value per listed stream; pt = (MD1's, MD2 || HB's) payload type, 0 .. 127, one pair or one per listed
+        stream (equal types: the receiver reads the description from the payload); level_id 0 .. 14, the RFC 8285 id of the audio level
+        (0: none), for the whole session: the latest bind wins.  An SSRC that two bound streams would share is refused (RuntimeError), and
+        nothing changes.  Ordered on the current stream; synchronises; not capturable."""
+        idx = _distinct("streams", streams, self.n_streams)
+        n = len(idx)
+        ssrc = self._per_stream(ssrc, n, "ssrc", 2 ** 32 - 1)
+        ts = self._per_stream(ts_offset, n, "ts_offset", 2 ** 32 - 1)
+        sq = self._per_stream(seq_offset, n, "seq_offset", 2 ** 16 - 1)
+        try:
+            pairs = [tuple(int(x) for x in q) for q in pt] if hasattr(pt[0], "__len__") else [tuple(int(x) for x in pt)] * n
+        except (TypeError, ValueError, IndexError):
+            pairs = None
+        if pairs is None or len(pairs) != n or any(len(q) != 2 or not (0 <= q[0] <= 127 and 0 <= q[1] <= 127) for q in pairs):
+            raise ValueError("pt: a pair of payload types inside 0 .. 127, or %d pairs" % n)
+        level_id = int(level_id)
+        if not 0 <= level_id <= 14:
+            raise ValueError("level_id: 0 .. 14")
+        self._call("bind", (C.c_int32 * n)(*idx), n, (C.c_uint32 * n)(*ssrc), (C.c_uint32 * n)(*ts), (C.c_uint16 * n)(*sq),
+                   (C.c_uint8 * n)(*[q[0] for q in pairs]), (C.c_uint8 * n)(*[q[1] for q in pairs]), level_id)
+        self.level_id = level_id
+
+    def unbind(self, streams):
+        """Take the binding of the listed streams away: their records are refused by pack(), their datagrams are unknown_ssrc to parse()"""
+        idx = _distinct("streams", streams, self.n_streams)
+        self._call("unbind", (C.c_int32 * len(idx))(*idx), len(idx))
+
+    def reset(self, rows=None):
+        """unbind the listed streams (None: all of them)"""
+        self.unbind(range(self.n_streams) if rows is None else rows)
+
+    def pack(self, records, send_count, payload, level=None, dgrams=None, wire=None):
+        """records int32 [max,5], send_count int32 [8] and payload uint8 [bytes] as send_pack() / send_fanout() returned them, level uint8
+        [n_streams, depth] or None (the byte of packet seq of stream s is level[s, seq % depth]; it needs a level_id) -> (dgrams int32
+        [max,2] = (offset, len) of datagram k = record k inside wire, (0, 0) where it is refused or cut; wire uint8 [cap]: 12 (20 with
+        levels) header bytes, then the payload, every datagram at a multiple of 4; count int32 [8] on the device, read with pack_count()).
+        The number of records is min(send_count's records, max), read on the device.  dgrams / wire: the caller's buffers; the default
+        wire, bytes + 23 x max, is never too small for the records of send_pack() (for those of send_fanout(), whose offsets repeat,
+        bring one: bytes_needed of the count says how large).  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        m, _ = _tensor("records", records, t.int32, (None, 5))
+        _tensor("send_count", send_count, t.int32, (8,))
+        nbytes, = _tensor("payload", payload, t.uint8, (None,))
+        depth = _tensor("level", level, t.uint8, (self.n_streams, None), optional=True)
+        depth = 0 if depth is None else depth[1]
+        if m < 1 or (level is not None and (depth < 1 or not self.level_id)):
+            raise ValueError("records: at least one; level: a depth of at least 1 and a session with a level_id")
+        _tensor("dgrams", dgrams, t.int32, (m, 2), optional=True)
+        _tensor("wire", wire, t.uint8, (None,), optional=True)
+        if dgrams is None:
+            dgrams = t.zeros((m, 2), dtype=t.int32, device=records.device)
+        if wire is None:
+            wire = t.zeros((nbytes + 23 * m,), dtype=t.uint8, device=records.device)
+        count = t.zeros((8,), dtype=t.int32, device=records.device)
+        # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
+        self._call("pack", records.data_ptr(), send_count.data_ptr(), m, payload.data_ptr() or count.data_ptr(), nbytes, _ptr(level), depth,
+                   dgrams.data_ptr(), wire.data_ptr() or count.data_ptr(), wire.shape[0], count.data_ptr())
+        return dgrams, wire, count
+
+    def parse(self, batch, dgrams, wire, arrivals=None, level=False, rtp_seq=False):
+        """dgrams int32 [n,2] = (offset, len) of the received datagrams inside wire uint8 [bytes]; batch: the receiving SoloBatch (with a
+        ring, the session's stream count and packet samples) -> (arrivals int32 [n,5] for batch.recv_insert(arrivals, wire): the offsets
+        point at the payloads inside wire, a rejected datagram is (-1, 0, 0, 0, 0), which the ring counts as bad; level uint8 [n] or None;
+        rtp_seq int16 [n] (the raw 16 bits) or None; count int32 [8] on the device, read with parse_count()).  level / rtp_seq: True = wanted,
+        or the caller's tensor.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        n, _ = _tensor("dgrams", dgrams, t.int32, (None, 2))
+        nbytes, = _tensor("wire", wire, t.uint8, (None,))
+        _tensor("arrivals", arrivals, t.int32, (n, 5), optional=True)
+        if not isinstance(batch, SoloBatch) or batch.n_streams != self.n_streams or batch.packet_samples != self.packet_samples:
+            raise ValueError("batch: a SoloBatch of %d streams and %d samples a packet" % (self.n_streams, self.packet_samples))
+        outs = []
+        for name, x, dtype in (("level", level, t.uint8), ("rtp_seq", rtp_seq, t.int16)):
+            if x is True:
+                x = t.zeros((n,), dtype=dtype, device=dgrams.device)
+            elif x is False or x is None:
+                x = None
+            else:
+                _tensor(name, x, dtype, (n,))
+            outs.append(x)
+        if arrivals is None:
+            arrivals = t.zeros((n, 5), dtype=t.int32, device=dgrams.device)
+        count = t.zeros((8,), dtype=t.int32, device=dgrams.device)
+        r = self.lib.solo_rtp_parse(self.h, batch.h, dgrams.data_ptr() or count.data_ptr(), n, wire.data_ptr() or count.data_ptr(), nbytes,
+                                    arrivals.data_ptr() or count.data_ptr(), _ptr(outs[0]), _ptr(outs[1]), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_rtp_parse -> %d" % r)
+        return arrivals, outs[0], outs[1], count
+
+    def pack_count(self, count):
+        """the count tensor of pack() as a dict (synchronises); dgrams == -1: the list behind the records was refused on the device"""
+        return _counts(solo_rtp_pack_count_t, count)
+
+    def parse_count(self, count):
+        """the count tensor of parse() as a dict (synchronises): datagrams per verdict"""
+        return _counts(solo_rtp_parse_count_t, count)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.solo_rtp_destroy(self.h)
+            self.h = None

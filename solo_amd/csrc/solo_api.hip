@@ -40,6 +40,7 @@
 #include "solo_playout.h"       // adaptive play-out delay control (solo_playout_plan / _render / _tick): likewise
 #include "solo_agc.h"           // level control and peak limiter of decoded rows (solo_agc): likewise
 #include "solo_rows.h"          // the record kernels of those four objects (reset, listed reset, state copy): likewise
+#include "solo_rtp.h"           // RTP framing of the sender's records and parsing of received datagrams (solo_rtp_pack / _parse): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -1219,6 +1220,97 @@ int32_t solo_playout_tick(solo_playout_t* po, solo_batch_t* b, const int32_t* d_
     if (c.n_two && (r = solo_timescale(b, po->d_pcm_two, c.n_two, 2, 1, po->d_ts_a, NULL, po->d_cost_a, NULL, hip_stream)) != 0) return r;
     return solo_playout_render(po, d_streams, n, params, H, po->d_action, c.n_one, c.n_two, c.n_stretch, po->d_pcm_one, po->d_st_one, po->d_pcm_two, po->d_st_two,
                                po->d_ts_s, po->d_cost_s, po->d_ts_a, po->d_cost_a, d_heard, d_outcome, d_status, &d_count->render, hip_stream);
+}
+
+// ---- RTP at both ends (solo_rtp.h): records + pool -> datagrams for the socket; received datagrams -> arrivals, in place -------------
+// A session is a row object whose record is a stream's configuration (a zeroed record = not bound: unbind is the listed reset), plus
+// the sorted SSRC table and the host mirror both are rebuilt from.  The device code reads the configuration and never writes it.
+static_assert(sizeof(solo_dgram_t) == sizeof(SxRtpDgram) && sizeof(solo_rtp_pack_count_t) == sizeof(SxRtpPackCount) &&
+              sizeof(solo_rtp_parse_count_t) == sizeof(SxRtpParseCount) && SX_RTP_CFG_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_rtp.h and solo_rows.h agree");
+struct solo_rtp_obj : solo_rows {    // d_state: SxRtpStream [n_rows]
+    int32_t L;                       // timestamp ticks per packet
+    SxRtpMirror mirror;
+    uint32_t* d_table;               // SX_RTP_TABLE_HEAD + 2 x n_rows words
+    void* d_scratch;                 // tile bases and tile totals of a solo_rtp_pack call, grown on demand
+    size_t scratch_bytes;
+};
+solo_rtp_t* solo_rtp_create(int32_t n_streams, int32_t packet_samples) {
+    if (n_streams <= 0 || (packet_samples != 320 && packet_samples != 640 && packet_samples != 1280) || !have_device()) return NULL;
+    solo_rtp_obj* r = new (std::nothrow) solo_rtp_obj();
+    if (!r) return NULL;
+    r->L = packet_samples;
+    r->mirror.cfg.assign((size_t)n_streams, SxRtpStream{0, 0, 0, 0});
+    r->mirror.level_id = 0;
+    const size_t table_bytes = (SX_RTP_TABLE_HEAD + 2 * (size_t)n_streams) * sizeof(uint32_t);
+    if (hipMalloc((void**)&r->d_table, table_bytes) != hipSuccess || hipMemset(r->d_table, 0, table_bytes) != hipSuccess ||
+        !rows_alloc(r, n_streams, SX_RTP_CFG_WORDS, NULL, 1, 0)) {
+        solo_rtp_destroy(r);
+        return NULL;
+    }
+    return r;
+}
+void solo_rtp_destroy(solo_rtp_t* r) {
+    if (!r) return;
+    rows_free(r);
+    dev_free(r->d_table);
+    dev_free(r->d_scratch);
+    delete r;
+}
+// the new table, behind the kernels that changed the records; the call returns when it is there (the vector it came from goes)
+static int32_t rtp_upload_table(solo_rtp_obj* r, const std::vector<u32>& table, hipStream_t st) {
+    SOLO_CHECK(hipMemcpyAsync(r->d_table, table.data(), table.size() * sizeof(u32), hipMemcpyHostToDevice, st));
+    SOLO_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+int32_t solo_rtp_bind(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint32_t* h_ssrc, const uint32_t* h_ts_offset, const uint16_t* h_seq_offset,
+                      const uint8_t* h_pt_md1, const uint8_t* h_pt_md2, int32_t level_id, void* hip_stream) {
+    std::vector<SxStreamCtl> recs;
+    std::vector<u32> table;
+    SxRtpMirror next;
+    if (!r || !sx_rtp_bind_plan(r->mirror, h_streams, n, h_ssrc, h_ts_offset, h_seq_offset, h_pt_md1, h_pt_md2, level_id, next, recs, table)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(sx_launch_ctl_batches(recs.data(), n, [&](const SxStreamCtlList& l, int k) {
+        hipLaunchKernelGGL(solo_rtp_bind_kernel, dim3((unsigned)k), dim3(64), 0, st, (u32*)r->d_state, l);
+    }));
+    const int32_t e = rtp_upload_table(r, table, st);
+    if (e == 0) r->mirror.cfg.swap(next.cfg), r->mirror.level_id = next.level_id;      // (only what the device now holds)
+    return e;
+}
+int32_t solo_rtp_unbind(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
+    std::vector<u32> table;
+    SxRtpMirror next;
+    if (!r || !sx_rtp_unbind_plan(r->mirror, h_streams, n, next, table)) return -1;
+    int32_t e = rows_reset_list(r, h_streams, n, (hipStream_t)hip_stream);
+    if (e == 0) e = rtp_upload_table(r, table, (hipStream_t)hip_stream);
+    if (e == 0) r->mirror.cfg.swap(next.cfg);
+    return e;
+}
+int32_t solo_rtp_pack(solo_rtp_t* r, const solo_arrival_t* d_records, const solo_send_count_t* d_send_count, int32_t max_records, const uint8_t* d_payload,
+                      int64_t payload_bytes, const uint8_t* d_level, int32_t level_depth, solo_dgram_t* d_dgrams, uint8_t* d_wire, int64_t wire_capacity,
+                      solo_rtp_pack_count_t* d_count, void* hip_stream) {
+    if (!r || !d_records || !d_send_count || !d_payload || !d_dgrams || !d_wire || !d_count || max_records <= 0 || payload_bytes < 0 || wire_capacity < 0) return -1;
+    if (d_level && (level_depth <= 0 || r->mirror.level_id == 0)) return -1;       // (levels need the id the latest bind gave)
+    if ((((uintptr_t)d_records | (uintptr_t)d_send_count | (uintptr_t)d_dgrams | (uintptr_t)d_wire) & 3) || ((uintptr_t)d_count & 7)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(r->d_scratch, r->scratch_bytes, solo_rtp_scratch_bytes(max_records), st));
+    SxRtpPackArgs a;
+    a.records = (const SxSendRecord*)d_records; a.send_count = (const SxSendCount*)d_send_count; a.payload = d_payload; a.level = d_level;
+    a.cfg = (const SxRtpStream*)r->d_state; a.table = r->d_table; a.payload_bytes = payload_bytes;
+    a.max_records = max_records; a.n_streams = r->n_rows; a.level_depth = level_depth; a.packet_samples = r->L;
+    SOLO_CHECK(solo_rtp_pack_launch(a, r->d_scratch, (SxRtpDgram*)d_dgrams, d_wire, (long long)wire_capacity, (SxRtpPackCount*)d_count, st));
+    return 0;
+}
+int32_t solo_rtp_parse(solo_rtp_t* r, solo_batch_t* b, const solo_dgram_t* d_dgrams, int32_t n_dgrams, const uint8_t* d_wire, int64_t wire_bytes,
+                       solo_arrival_t* d_arrivals, uint8_t* d_level_out, uint16_t* d_rtp_seq_out, solo_rtp_parse_count_t* d_count, void* hip_stream) {
+    if (!r || !b || !b->d_recv_ring || b->n_streams != r->n_rows || handle_packet_samples(b) != r->L) return -1;
+    if (n_dgrams < 0 || wire_bytes < 0 || !d_count || (n_dgrams > 0 && (!d_dgrams || !d_wire || !d_arrivals))) return -1;
+    if ((((uintptr_t)d_dgrams | (uintptr_t)d_arrivals | (uintptr_t)d_count) & 3) || ((uintptr_t)d_rtp_seq_out & 1)) return -1;
+    SxRtpParseArgs a;
+    a.dgrams = (const SxRtpDgram*)d_dgrams; a.wire = d_wire; a.cfg = (const SxRtpStream*)r->d_state; a.table = r->d_table; a.play = b->d_recv_play;
+    a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
+    a.n_dgrams = n_dgrams; a.n_streams = r->n_rows; a.packet_samples = r->L;
+    SOLO_CHECK(solo_rtp_parse_launch(a, (SxSendRecord*)d_arrivals, d_level_out, d_rtp_seq_out, (SxRtpParseCount*)d_count, (hipStream_t)hip_stream));
+    return 0;
 }
 
 // ---- stream migration (solo_migrate.h): encoder state, decoder state and receive queue of listed streams <-> a device blob ---------
