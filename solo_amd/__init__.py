@@ -776,7 +776,7 @@ class SoloBatch:
         return _counts(solo_recv_report_count_t, count)
 
     # ---- sender back end (solo_send_pack): slots + length records -> datagram records + a dense payload pool ----
-    SEND_COUNT = ("records", "records_needed", "bytes", "bytes_needed", "empty", "refused")
+    SEND_COUNT = tuple(n for n, _ in solo_send_count_t._fields_)
 
     def send_pack(self, bits, nbytes, send=None, first_seq=0, seq_base=None, records=None, payload=None, streams=None):
         """What encode() wrote -> the datagrams to send: bits uint8 [n,P,slot], nbytes int16 [n,P,2], send uint8 [n,P] (bit 0: MD1, bit 1:
@@ -832,7 +832,7 @@ class SoloBatch:
         return _counts(solo_send_count_t, count)
 
     # ---- mixing bridge (solo_mix): decoded rows -> what every participant of a room hears ----
-    MIX_COUNT = ("rows", "rooms", "clipped")
+    MIX_COUNT = tuple(n for n, _ in solo_mix_count_t._fields_)
 
     def mix(self, pcm, room, gain=None, max_speakers=0, out=None, energy=None, mixed=None):
         """Mix-minus on the device: pcm int16 [n,P,samples] (what decode() / recv_decode() wrote, compact rows included), room int32 [n]
@@ -875,7 +875,7 @@ class SoloBatch:
         return _counts(solo_mix_count_t, count)
 
     # ---- play-out time scaling (solo_timescale): a decoded packets of a row -> b packets of audio ----
-    TIMESCALE_COUNT = ("rows", "blocks", "cost")
+    TIMESCALE_COUNT = tuple(n for n, _ in solo_timescale_count_t._fields_)
 
     def timescale(self, pcm, out_packets, out=None, shift=None, cost=None):
         """Shorten or stretch play-out by whole packets on the device: pcm int16 [n,a,samples] (what recv_decode() wrote, compact rows
@@ -910,7 +910,7 @@ class SoloBatch:
         return _counts(solo_timescale_count_t, count)
 
     # ---- shared listener mixes (solo_mix_shared, solo_send_fanout): a personal mix per speaker, one mix per room for everybody else ----
-    MIX_SHARED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped")
+    MIX_SHARED_COUNT = tuple(n for n, _ in solo_mix_shared_count_t._fields_)
 
     def _shared_mix_args(self, pcm, room, gain, keep, slots, n_rooms, energy, pcm_spk, pcm_room):
         """the checks of the arguments mix_shared() and mix_selected() both take -> (n, P, samples, n_rooms)"""
@@ -976,7 +976,7 @@ class SoloBatch:
         return _counts(solo_mix_shared_count_t, count)
 
     # ---- shared listener mixes from a given selection (solo_mix_selected): the end of a tick that ran Vad.select ----
-    MIX_SELECTED_COUNT = ("rows", "rooms", "speakers", "shared", "clipped", "selected", "silent")
+    MIX_SELECTED_COUNT = tuple(n for n, _ in solo_mix_selected_count_t._fields_)
 
     def mix_selected(self, pcm, room, sel, gain=None, keep=None, slots=None, n_rooms=None, energy=None, room_nsel=None, pcm_spk=None,
                      pcm_room=None):
@@ -1040,7 +1040,7 @@ class SoloBatch:
         return records, payload, count
 
     # ---- stream migration (solo_batch_export_streams / solo_batch_import_streams): a running call moves between handles ----
-    MIGRATE_COUNT = ("streams", "refused", "bytes")
+    MIGRATE_COUNT = tuple(n for n, _ in solo_migrate_count_t._fields_)
     _MIGRATE = {"enc": 1, "encoder": 1, "dec": 2, "decoder": 2, "recv": 4, "ring": 4}
 
     def _migrate_which(self, which):

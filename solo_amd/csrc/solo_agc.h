@@ -32,9 +32,9 @@
 #define SX_AGC_MAX_GAIN_Q8 7680                                         // 30 dB
 #define SX_AGC_ONE_Q15 32768
 
-struct SxAgcParams { i32 target_level, max_boost_db, max_cut_db, sa_on_q8, gate_level, alpha_q8, slew_up_q8, slew_down_q8, ceiling, release_q15; };
-struct SxAgcCount { i32 rows, speech, limited, zero; };     // == solo_agc_count_t
-static_assert(sizeof(SxAgcParams) == 40 && sizeof(SxAgcCount) == 16, "== solo_agc_params_t, solo_agc_count_t");
+typedef solo_agc_params_t SxAgcParams;
+typedef solo_agc_count_t SxAgcCount;
+static_assert(sizeof(SxAgcParams) == 40 && sizeof(SxAgcCount) == 16, "solo_agc_params_t, solo_agc_count_t layout");
 
 // word w of the record the create and reset calls leave
 SX_HD i32 sx_agc_init_word(int w) { return w == 3 ? 65536 : (w == 4 ? SX_AGC_ONE_Q15 : 0); }

@@ -709,8 +709,6 @@ int32_t solo_recv_stats(solo_batch_t* b, uint32_t* out8, void* hip_stream) {
 }
 
 // ---- read side of the ring (solo_recv_report.h): per-stream counters, queue report, play-out list ----------------------------------
-static_assert(sizeof(solo_recv_report_t) == sizeof(SxRecvReport) && sizeof(solo_recv_report_count_t) == sizeof(SxRecvReportCount) &&
-              SOLO_RECV_REPORT_CLEAR_MARGIN == SX_RECV_REPORT_CLEAR_MARGIN, "include/solo_mi355x.h and solo_recv_report.h agree");
 int32_t solo_recv_track(solo_batch_t* b, int32_t on, void* hip_stream) {
     if (!b || !b->d_recv_ring) return -1;
     if (!on) { b->recv_track = 0; return 0; }               // (the values stay; solo_recv_report goes on showing them)
@@ -735,7 +733,7 @@ int32_t solo_recv_report(solo_batch_t* b, const int32_t* d_streams, int32_t n, c
     a.lens = b->d_recv_lens; a.play = b->d_recv_play; a.trk = b->d_recv_trk; a.map = d_streams; a.min_ready_v = d_min_ready;
     a.reports = (uint32_t*)d_reports; a.sel = b->d_recv_sel;
     a.n = n; a.depth = b->recv_depth; a.min_ready = min_ready; a.max_span = max_span; a.clear_margin = (flags & SOLO_RECV_REPORT_CLEAR_MARGIN) != 0;
-    SOLO_CHECK(solo_recv_report_launch(a, d_play_list, d_play_rows, (SxRecvReportCount*)d_count, verdict, st));
+    SOLO_CHECK(solo_recv_report_launch(a, d_play_list, d_play_rows, d_count, verdict, st));
     return 0;
 }
 
@@ -758,7 +756,6 @@ static int handle_hb_bytes(const solo_batch* b) {
 }
 
 // ---- sender back end (solo_send.h): slots + length records -> datagram records + a dense payload pool ----------------------------
-static_assert(sizeof(solo_send_count_t) == sizeof(SxSendCount) && sizeof(solo_arrival_t) == sizeof(SxSendRecord), "include/solo_mi355x.h and solo_send.h agree");
 // map = NULL: the rows are the handle's streams 0 .. n - 1; else row i is stream map[i] (checked on the device, ahead of the passes)
 static int32_t solo_send_impl(solo_batch_t* b, const int32_t* map, int32_t n, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_send,
                               int32_t n_packets, const int32_t* d_seq_base, int32_t first_seq, solo_arrival_t* d_records, int32_t max_records,
@@ -771,8 +768,7 @@ static int32_t solo_send_impl(solo_batch_t* b, const int32_t* map, int32_t n, co
     SxSendArgs a;
     a.bits = d_bits; a.nbytes = d_nbytes; a.send = d_send; a.seq_base = d_seq_base; a.map = map;
     a.n = n; a.n_packets = n_packets; a.slot = b->slot; a.hbb = handle_hb_bytes(b); a.first_seq = first_seq;
-    SOLO_CHECK(solo_send_launch(a, b->d_send_scratch, (SxSendRecord*)d_records, max_records, d_payload, (long long)payload_capacity, (SxSendCount*)d_count,
-                                verdict, st));
+    SOLO_CHECK(solo_send_launch(a, b->d_send_scratch, d_records, max_records, d_payload, (long long)payload_capacity, d_count, verdict, st));
     return 0;
 }
 int32_t solo_send_pack(solo_batch_t* b, const uint8_t* d_bits, const int16_t* d_nbytes, const uint8_t* d_send, int32_t n_packets,
@@ -802,13 +798,11 @@ int32_t solo_send_fanout(solo_batch_t* b, const uint8_t* d_bits, const int16_t* 
     a.named = NULL; a.pool_off = NULL;
     a.n_src = n_src; a.n_dst = n_dst; a.n_packets = n_packets; a.slot = b->slot; a.first_seq = first_seq;
     a.hbb = handle_hb_bytes(b);
-    SOLO_CHECK(solo_fan_launch(a, b->d_send_scratch, (SxSendRecord*)d_records, max_records, d_payload, (long long)payload_capacity, (SxSendCount*)d_count,
-                               b->d_verdict + SOLO_VERDICT_SEND, st));
+    SOLO_CHECK(solo_fan_launch(a, b->d_send_scratch, d_records, max_records, d_payload, (long long)payload_capacity, d_count, b->d_verdict + SOLO_VERDICT_SEND, st));
     return 0;
 }
 
 // ---- mixing bridge (solo_mix.h): decoded rows -> mix-minus rows, room by room ------------------------------------------------------
-static_assert(sizeof(solo_mix_count_t) == sizeof(SxMixCount), "include/solo_mi355x.h and solo_mix.h agree");
 int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
                  const int16_t* d_gain_q12, int32_t max_speakers, int16_t* d_pcm_out, int64_t* d_energy, uint8_t* d_mixed, solo_mix_count_t* d_count,
                  void* hip_stream) {
@@ -826,12 +820,11 @@ int32_t solo_mix(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_
     a.pcm_in = d_pcm_in; a.gain = d_gain_q12; a.pcm_out = d_pcm_out; a.energy = d_energy; a.mixed = d_mixed;
     a.counts = NULL; a.starts = NULL; a.members = NULL;
     a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
-    SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, (SxMixCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
+    SOLO_CHECK(solo_mix_launch(a, d_room, n, n_rooms, b->d_mix_scratch, d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
     return 0;
 }
 
 // ... with shared listener mixes (solo_mix_shared.h): a personal row per speaker, one row per room for everybody else
-static_assert(sizeof(solo_mix_shared_count_t) == sizeof(SxMixShCount), "include/solo_mi355x.h and solo_mix_shared.h agree");
 int32_t solo_mix_shared(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
                         const int16_t* d_gain_q12, int32_t max_speakers, const uint8_t* d_keep, const int32_t* d_slots, int16_t* d_pcm_spk,
                         int32_t* d_spk_list, int32_t* d_spk_rows, int16_t* d_pcm_room, int32_t* d_room_list, int32_t* d_source, int64_t* d_energy,
@@ -846,12 +839,11 @@ int32_t solo_mix_shared(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int
     a.pcm_spk = d_pcm_spk; a.spk_list = d_spk_list; a.spk_rows = d_spk_rows; a.pcm_room = d_pcm_room; a.room_list = d_room_list; a.source = d_source;
     a.energy = d_energy; a.mixed = d_mixed;
     a.n = n; a.n_rooms = n_rooms; a.n_packets = n_packets; a.L = L; a.max_speakers = max_speakers;
-    SOLO_CHECK(solo_mixsh_launch(a, b->d_mix_scratch, (SxMixShCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
+    SOLO_CHECK(solo_mixsh_launch(a, b->d_mix_scratch, d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
     return 0;
 }
 
 // ... from a selection the caller brings (solo_mix_selected.h): no energies, no select pass
-static_assert(sizeof(solo_mix_selected_count_t) == sizeof(SxMixSelCount), "include/solo_mi355x.h and solo_mix_selected.h agree");
 int32_t solo_mix_selected(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t n_packets, const int32_t* d_room, int32_t n_rooms,
                           const int16_t* d_gain_q12, const uint8_t* d_sel, const uint8_t* d_keep, const int32_t* d_slots, int16_t* d_pcm_spk,
                           int32_t* d_spk_list, int32_t* d_spk_rows, int16_t* d_pcm_room, int32_t* d_room_list, int32_t* d_source,
@@ -867,12 +859,11 @@ int32_t solo_mix_selected(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, i
     a.sh.source = d_source; a.sh.energy = d_energy; a.sh.mixed = const_cast<uint8_t*>(d_sel);       // (read only on this path)
     a.sh.n = n; a.sh.n_rooms = n_rooms; a.sh.n_packets = n_packets; a.sh.L = L; a.sh.max_speakers = SX_MIX_MAX_SPEAKERS;
     a.room_nsel = d_room_nsel;
-    SOLO_CHECK(solo_mixsel_launch(a, b->d_mix_scratch, (SxMixSelCount*)d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
+    SOLO_CHECK(solo_mixsel_launch(a, b->d_mix_scratch, d_count, b->d_verdict + SOLO_VERDICT_MIX, st));
     return 0;
 }
 
 // ---- play-out time scaling (solo_timescale.h): in_packets decoded packets of a row -> out_packets packets of audio ---------------------
-static_assert(sizeof(solo_timescale_count_t) == sizeof(SxTsCount), "include/solo_mi355x.h and solo_timescale.h agree");
 int32_t solo_timescale(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int32_t in_packets, int32_t out_packets, int16_t* d_pcm_out,
                        int32_t* d_shift, int32_t* d_cost, solo_timescale_count_t* d_count, void* hip_stream) {
     if (!b) return -1;
@@ -882,7 +873,7 @@ int32_t solo_timescale(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int3
     SxTsArgs a;
     a.pcm_in = d_pcm_in; a.pcm_out = d_pcm_out; a.shift = d_shift; a.cost = d_cost;
     a.Li = in_packets * L; a.Lo = out_packets * L; a.H = fs / 200;
-    SOLO_CHECK(solo_timescale_launch(a, n, (SxTsCount*)d_count, (hipStream_t)hip_stream));
+    SOLO_CHECK(solo_timescale_launch(a, n, d_count, (hipStream_t)hip_stream));
     return 0;
 }
 
@@ -942,7 +933,7 @@ static bool rows_alloc(solo_rows* o, int32_t n_rows, int32_t words, i32 (*init_w
 }
 
 // ---- PCM rate conversion (solo_resample.h): it sits between two handles of different rates; a zeroed record = SKP_Silk_resampler_init ----
-static_assert(sizeof(solo_resample_count_t) == sizeof(SxRsCount) && SX_RS_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_resample.h and solo_rows.h agree");
+static_assert(SX_RS_STATE_WORDS <= SX_ROWS_MAX_WORDS, "solo_resample.h and solo_rows.h agree");
 struct solo_resampler : solo_rows {
     int32_t fs_in, fs_out;
     SxRsCfg cfg;
@@ -976,7 +967,7 @@ static int32_t resample_call(solo_resampler* r, const int32_t* d_rows, int32_t n
     a.c = r->cfg; a.in = d_in; a.out = d_out; a.state = r->d_state; a.map = d_rows; a.n = n;
     a.batches = n_packets * (in_samples / r->cfg.n_in);
     SOLO_CHECK(launch_list_check(d_rows, n, r->n_rows, r->d_verdict, NULL, st));
-    SOLO_CHECK(solo_resample_launch(a, (SxRsCount*)d_count, r->d_verdict, st));
+    SOLO_CHECK(solo_resample_launch(a, d_count, r->d_verdict, st));
     return 0;
 }
 int32_t solo_resample(solo_resampler_t* r, const int16_t* d_in, int32_t n_packets, int32_t in_samples, int16_t* d_out, void* hip_stream) {
@@ -990,8 +981,7 @@ int32_t solo_resample_rows(solo_resampler_t* r, const int32_t* d_rows, int32_t n
 }
 
 // ---- voice activity, audio level, speaker selection (solo_vad.h): an object of its own, with a state record per row -------------------
-static_assert(sizeof(solo_vad_count_t) == sizeof(SxVadCount) && sizeof(solo_vad_select_params_t) == sizeof(SxVadSelectParams) &&
-              SOLO_VAD_STATE_BYTES == SX_VAD_STATE_WORDS * 4 && SX_VAD_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_vad.h and solo_rows.h agree");
+static_assert(SOLO_VAD_STATE_BYTES == SX_VAD_STATE_WORDS * 4 && SX_VAD_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_vad.h and solo_rows.h agree");
 struct solo_vad_obj : solo_rows {    // d_verdict[2]: the verdict words of solo_vad and of solo_vad_select
     int32_t frame;
     void* d_scratch;                 // the room plan and the keys of solo_vad_select (solo_vad_scratch_bytes)
@@ -1029,21 +1019,21 @@ int32_t solo_vad(solo_vad_t* v, const int32_t* d_rows, int32_t n, const int16_t*
     a.pcm = d_pcm; a.state = v->d_state; a.map = d_rows; a.sa = d_sa_q8; a.detail = d_detail; a.level = d_level;
     a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples;
     SOLO_CHECK(launch_list_check(d_rows, n, v->n_rows, v->d_verdict, NULL, st));
-    SOLO_CHECK(solo_vad_launch(v->frame, a, (SxVadCount*)d_count, v->d_verdict, st));
+    SOLO_CHECK(solo_vad_launch(v->frame, a, d_count, v->d_verdict, st));
     return 0;
 }
 int32_t solo_vad_select(solo_vad_t* v, const int32_t* d_rows, int32_t n, const uint8_t* d_sa_q8, const uint8_t* d_level, int32_t n_packets, int32_t frames,
                         const int32_t* d_room, int32_t n_rooms, const solo_vad_select_params_t* params, const int16_t* d_gain_in, uint8_t* d_sel,
                         int16_t* d_gain_out, uint8_t* d_keep, int32_t* d_dominant, solo_vad_count_t* d_count, void* hip_stream) {
-    if (!v || !sx_vsel_call_ok(v->n_rows, n, d_sa_q8, d_level, n_packets, frames, d_room, n_rooms, (const SxVadSelectParams*)params, d_sel, d_count)) return -1;
+    if (!v || !sx_vsel_call_ok(v->n_rows, n, d_sa_q8, d_level, n_packets, frames, d_room, n_rooms, params, d_sel, d_count)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     SxVselArgs a = {};
     a.sa = d_sa_q8; a.level = d_level; a.gain_in = d_gain_in; a.map = d_rows;
     a.sel = d_sel; a.gain_out = d_gain_out; a.keep = d_keep; a.dominant = d_dominant; a.state = v->d_state;
-    a.n_packets = n_packets; a.frames = frames; a.prm = *(const SxVadSelectParams*)params;
+    a.n_packets = n_packets; a.frames = frames; a.prm = *params;
     const int32_t n_rows = v->n_rows;
     hipError_t lerr = hipSuccess;
-    SOLO_CHECK(solo_vad_select_launch(a, d_room, n, n_rooms, n_rows, v->d_scratch, (SxVadCount*)d_count, v->d_verdict + 1, [&](u32* verdict) {
+    SOLO_CHECK(solo_vad_select_launch(a, d_room, n, n_rooms, n_rows, v->d_scratch, d_count, v->d_verdict + 1, [&](u32* verdict) {
         lerr = launch_list_check(d_rows, n, n_rows, verdict, NULL, st);
     }, st));
     SOLO_CHECK(lerr);
@@ -1051,8 +1041,7 @@ int32_t solo_vad_select(solo_vad_t* v, const int32_t* d_rows, int32_t n, const u
 }
 
 // ---- level control and peak limiter (solo_agc.h): an object of its own, with a state record per row -----------------------------------
-static_assert(sizeof(solo_agc_count_t) == sizeof(SxAgcCount) && sizeof(solo_agc_params_t) == sizeof(SxAgcParams) &&
-              SOLO_AGC_STATE_BYTES == SX_AGC_STATE_WORDS * 4 && SX_AGC_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_agc.h and solo_rows.h agree");
+static_assert(SOLO_AGC_STATE_BYTES == SX_AGC_STATE_WORDS * 4 && SX_AGC_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_agc.h and solo_rows.h agree");
 struct solo_agc_obj : solo_rows {
     unsigned long long* d_acc;       // the counters of a call's count (solo_agc_acc_bytes; zero between calls)
 };
@@ -1084,23 +1073,20 @@ int32_t solo_agc_set_state(solo_agc_t* g, const int32_t* d_rows, int32_t n, cons
 int32_t solo_agc(solo_agc_t* g, const int32_t* d_rows, int32_t n, const int16_t* d_pcm_in, int32_t n_packets, int32_t packet_samples,
                  const uint8_t* d_level_in, const uint8_t* d_sa_q8, int32_t frames, const solo_agc_params_t* params, int16_t* d_pcm_out,
                  uint8_t* d_level_out, int16_t* d_gain_q8, solo_agc_count_t* d_count, void* hip_stream) {
-    if (!g || !sx_agc_call_ok(g->n_rows, d_rows, n, d_pcm_in, n_packets, packet_samples, d_sa_q8, frames, (const SxAgcParams*)params, d_pcm_out, d_count))
+    if (!g || !sx_agc_call_ok(g->n_rows, d_rows, n, d_pcm_in, n_packets, packet_samples, d_sa_q8, frames, params, d_pcm_out, d_count))
         return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     SxAgcArgs a;
     a.in = d_pcm_in; a.out = d_pcm_out; a.state = g->d_state; a.map = d_rows; a.level_in = d_level_in; a.sa = d_sa_q8;
     a.level_out = d_level_out; a.gain_out = d_gain_q8;
-    a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples; a.frames = d_sa_q8 ? frames : 0; a.prm = *(const SxAgcParams*)params;
+    a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples; a.frames = d_sa_q8 ? frames : 0; a.prm = *params;
     SOLO_CHECK(launch_list_check(d_rows, n, g->n_rows, g->d_verdict, NULL, st));
-    SOLO_CHECK(solo_agc_launch(a, (SxAgcCount*)d_count, g->d_acc, g->d_verdict, st));
+    SOLO_CHECK(solo_agc_launch(a, d_count, g->d_acc, g->d_verdict, st));
     return 0;
 }
 
 // ---- adaptive play-out delay control (solo_playout.h): an object of its own, a state record and a held packet per row ------------------
-static_assert(sizeof(solo_playout_params_t) == sizeof(SxPoParams) && sizeof(solo_playout_plan_count_t) == sizeof(SxPoPlanCount) &&
-              sizeof(solo_playout_render_count_t) == sizeof(SxPoRenderCount) && sizeof(solo_playout_count_t) == sizeof(SxPoCount) &&
-              SOLO_PLAYOUT_STATE_BYTES == SX_PO_STATE_WORDS * 4 && SOLO_PLAYOUT_ACCEL_FORCED == SX_PO_OUT_ACCEL_FORCED && SX_PO_STATE_WORDS <= SX_ROWS_MAX_WORDS,
-              "include/solo_mi355x.h, solo_playout.h and solo_rows.h agree");
+static_assert(SOLO_PLAYOUT_STATE_BYTES == SX_PO_STATE_WORDS * 4 && SX_PO_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_playout.h and solo_rows.h agree");
 struct solo_playout_obj : solo_rows {    // d_verdict[2]: the verdict words of the plan and of the render; d_extra: the held packets, int16 [n_rows][L]
     int32_t L;
     int32_t *d_slot, *d_sslot;       // [n_rows]: where the last plan put each row (solo_playout_compact_kernel)
@@ -1158,11 +1144,11 @@ int32_t solo_playout_set_state(solo_playout_t* po, const int32_t* d_rows, int32_
 int32_t solo_playout_plan(solo_playout_t* po, const solo_recv_report_t* d_reports, const int32_t* d_rows, int32_t n, int32_t depth,
                           const solo_playout_params_t* params, int32_t* d_action, int32_t* d_one, int32_t* d_two, int32_t* d_stretch_pos,
                           solo_playout_plan_count_t* d_count, void* hip_stream) {
-    if (!po || !sx_po_plan_call_ok(po->n_rows, d_reports, d_rows, n, depth, (const SxPoParams*)params, d_action, d_one, d_two, d_stretch_pos, d_count)) return -1;
+    if (!po || !sx_po_plan_call_ok(po->n_rows, d_reports, d_rows, n, depth, params, d_action, d_one, d_two, d_stretch_pos, d_count)) return -1;
     hipStream_t st = (hipStream_t)hip_stream;
     SOLO_CHECK(launch_list_check(d_rows, n, po->n_rows, po->d_verdict, NULL, st));
     SxPoPlanArgs a;
-    a.reports = (const uint32_t*)d_reports; a.state = po->d_state; a.map = d_rows; a.action = d_action; a.p = *(const SxPoParams*)params; a.n = n; a.depth = depth;
+    a.reports = (const uint32_t*)d_reports; a.state = po->d_state; a.map = d_rows; a.action = d_action; a.p = *params; a.n = n; a.depth = depth;
     SOLO_CHECK(solo_playout_plan_launch(a, d_one, d_two, d_stretch_pos, po->d_slot, po->d_sslot, (SxPoPlanCount*)d_count, po->d_verdict, st));
     return 0;
 }
@@ -1177,7 +1163,7 @@ int32_t solo_playout_render(solo_playout_t* po, const int32_t* d_rows, int32_t n
                             const int16_t* d_pcm_two, const int32_t* d_status_two, const int16_t* d_ts_stretch, const int32_t* d_cost_stretch,
                             const int16_t* d_ts_accel, const int32_t* d_cost_accel, int16_t* d_heard, int32_t* d_outcome, int32_t* d_status,
                             solo_playout_render_count_t* d_count, void* hip_stream) {
-    if (!po || !sx_po_render_call_ok(po->n_rows, po->L, d_rows, n, (const SxPoParams*)params, block_samples, d_action, n_one, n_two, n_stretch, d_pcm_one,
+    if (!po || !sx_po_render_call_ok(po->n_rows, po->L, d_rows, n, params, block_samples, d_action, n_one, n_two, n_stretch, d_pcm_one,
                                      d_status_one, d_pcm_two, d_status_two, d_ts_stretch, d_cost_stretch, d_ts_accel, d_cost_accel, d_heard, d_outcome, d_status, d_count))
         return -1;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -1196,7 +1182,7 @@ int32_t solo_playout_tick(solo_playout_t* po, solo_batch_t* b, const int32_t* d_
     if (!po || !b) return -1;
     int fs = 0;
     const int L = handle_packet_samples(b, &fs), H = fs / 200;
-    if (!sx_po_tick_call_ok(po->n_rows, po->L, b->d_recv_ring != NULL, b->recv_track != 0, b->n_streams, b->recv_depth, L, fs, d_streams, n, (const SxPoParams*)params,
+    if (!sx_po_tick_call_ok(po->n_rows, po->L, b->d_recv_ring != NULL, b->recv_track != 0, b->n_streams, b->recv_depth, L, fs, d_streams, n, params,
                             d_heard, d_outcome, d_status, d_count))
         return -1;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -1225,8 +1211,7 @@ int32_t solo_playout_tick(solo_playout_t* po, solo_batch_t* b, const int32_t* d_
 // ---- RTP at both ends (solo_rtp.h): records + pool -> datagrams for the socket; received datagrams -> arrivals, in place -------------
 // A session is a row object whose record is a stream's configuration (a zeroed record = not bound: unbind is the listed reset), plus
 // the sorted SSRC table and the host mirror both are rebuilt from.  The device code reads the configuration and never writes it.
-static_assert(sizeof(solo_dgram_t) == sizeof(SxRtpDgram) && sizeof(solo_rtp_pack_count_t) == sizeof(SxRtpPackCount) &&
-              sizeof(solo_rtp_parse_count_t) == sizeof(SxRtpParseCount) && SX_RTP_CFG_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_rtp.h and solo_rows.h agree");
+static_assert(SX_RTP_CFG_WORDS <= SX_ROWS_MAX_WORDS, "solo_rtp.h and solo_rows.h agree");
 struct solo_rtp_obj : solo_rows {    // d_state: SxRtpStream [n_rows]
     int32_t L;                       // timestamp ticks per packet
     SxRtpMirror mirror;
@@ -1294,10 +1279,10 @@ int32_t solo_rtp_pack(solo_rtp_t* r, const solo_arrival_t* d_records, const solo
     hipStream_t st = (hipStream_t)hip_stream;
     SOLO_CHECK(grow_scratch(r->d_scratch, r->scratch_bytes, solo_rtp_scratch_bytes(max_records), st));
     SxRtpPackArgs a;
-    a.records = (const SxSendRecord*)d_records; a.send_count = (const SxSendCount*)d_send_count; a.payload = d_payload; a.level = d_level;
+    a.records = d_records; a.send_count = d_send_count; a.payload = d_payload; a.level = d_level;
     a.cfg = (const SxRtpStream*)r->d_state; a.table = r->d_table; a.payload_bytes = payload_bytes;
     a.max_records = max_records; a.n_streams = r->n_rows; a.level_depth = level_depth; a.packet_samples = r->L;
-    SOLO_CHECK(solo_rtp_pack_launch(a, r->d_scratch, (SxRtpDgram*)d_dgrams, d_wire, (long long)wire_capacity, (SxRtpPackCount*)d_count, st));
+    SOLO_CHECK(solo_rtp_pack_launch(a, r->d_scratch, d_dgrams, d_wire, (long long)wire_capacity, d_count, st));
     return 0;
 }
 int32_t solo_rtp_parse(solo_rtp_t* r, solo_batch_t* b, const solo_dgram_t* d_dgrams, int32_t n_dgrams, const uint8_t* d_wire, int64_t wire_bytes,
@@ -1306,15 +1291,14 @@ int32_t solo_rtp_parse(solo_rtp_t* r, solo_batch_t* b, const solo_dgram_t* d_dgr
     if (n_dgrams < 0 || wire_bytes < 0 || !d_count || (n_dgrams > 0 && (!d_dgrams || !d_wire || !d_arrivals))) return -1;
     if ((((uintptr_t)d_dgrams | (uintptr_t)d_arrivals | (uintptr_t)d_count) & 3) || ((uintptr_t)d_rtp_seq_out & 1)) return -1;
     SxRtpParseArgs a;
-    a.dgrams = (const SxRtpDgram*)d_dgrams; a.wire = d_wire; a.cfg = (const SxRtpStream*)r->d_state; a.table = r->d_table; a.play = b->d_recv_play;
+    a.dgrams = d_dgrams; a.wire = d_wire; a.cfg = (const SxRtpStream*)r->d_state; a.table = r->d_table; a.play = b->d_recv_play;
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n_dgrams = n_dgrams; a.n_streams = r->n_rows; a.packet_samples = r->L;
-    SOLO_CHECK(solo_rtp_parse_launch(a, (SxSendRecord*)d_arrivals, d_level_out, d_rtp_seq_out, (SxRtpParseCount*)d_count, (hipStream_t)hip_stream));
+    SOLO_CHECK(solo_rtp_parse_launch(a, d_arrivals, d_level_out, d_rtp_seq_out, d_count, (hipStream_t)hip_stream));
     return 0;
 }
 
 // ---- stream migration (solo_migrate.h): encoder state, decoder state and receive queue of listed streams <-> a device blob ---------
-static_assert(sizeof(solo_migrate_count_t) == sizeof(SxMigCount), "include/solo_mi355x.h and solo_migrate.h agree");
 // which: a non-empty subset of {1 encoder, 2 decoder, 4 receive queue} that the handle has
 static bool migrate_which_ok(const solo_batch* b, int32_t which) {
     return b && which > 0 && which <= SX_MIG_ALL && !((which & SX_MIG_ENC) && !b->have_enc) && !((which & SX_MIG_DEC) && !b->have_dec) &&
@@ -1362,7 +1346,7 @@ int32_t solo_batch_export_streams(solo_batch_t* b, const int32_t* d_streams, int
     }
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_EXPORT;
     SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, NULL, st));
-    SOLO_CHECK(solo_migrate_export_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
+    SOLO_CHECK(solo_migrate_export_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, d_count, verdict, st));
     return 0;
 }
 int32_t solo_batch_import_streams(solo_batch_t* b, const int32_t* d_streams, int32_t n, int32_t which, const uint8_t* d_blob, int64_t blob_stride,
@@ -1375,7 +1359,7 @@ int32_t solo_batch_import_streams(solo_batch_t* b, const int32_t* d_streams, int
     }
     uint32_t* verdict = b->d_verdict + SOLO_VERDICT_IMPORT;
     SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, NULL, st));
-    SOLO_CHECK(solo_migrate_import_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, (SxMigCount*)d_count, verdict, st));
+    SOLO_CHECK(solo_migrate_import_launch(migrate_handle(b), d_streams, n, which, d_blob, (long long)blob_stride, d_count, verdict, st));
     return 0;
 }
 

@@ -70,7 +70,7 @@
 #define SX_MIG_BAD_SUM 7
 #define SX_MIG_BAD_QUEUE 8      // a play-out position below 0 or a length above slot_bytes (a ring must never hold one)
 
-struct SxMigCount { i32 streams, refused; i64 bytes; };      // == solo_migrate_count_t
+typedef solo_migrate_count_t SxMigCount;
 static_assert(sizeof(SxMigCount) == 16, "solo_migrate_count_t layout");
 
 struct SxMigGeom {              // header words 4 .. 11: what a section's bytes mean; of a handle, or of a blob

@@ -35,6 +35,7 @@
 #pragma once
 #include "solo_wave.h"
 #include "solo_stream_ctl.h"
+#include "../../include/solo_mi355x.h"
 
 #define SX_MIX_MAX_SPEAKERS 64
 #define SX_MIX_MAX_L 1280                                   // samples of the longest packet (40 ms at 32 kHz)
@@ -42,10 +43,7 @@
 #define SX_MIX_ITERS ((SX_MIX_MAX_L / 8 + SX_NLANES - 1) / SX_NLANES)       // chunks per lane and row: 3 (160 in the 1-lane host form)
 #define SX_MIX_MAX_ALL_ROWS 8191                            // rows of a call that may mix every member: 8191 x 2^18 < 2^31
 
-struct SxMixCount {             // == solo_mix_count_t
-    i32 rows, rooms;
-    i64 clipped;
-};
+typedef solo_mix_count_t SxMixCount;
 static_assert(sizeof(SxMixCount) == 16, "solo_mix_count_t layout");
 
 struct alignas(16) SxMixX8 { i16 s[8]; };                   // what one lane loads and stores

@@ -29,11 +29,7 @@
 #pragma once
 #include "solo_mix_shared.h"
 
-struct SxMixSelCount {          // == solo_mix_selected_count_t
-    i32 rows, rooms, speakers, shared;
-    i64 clipped;
-    i32 selected, silent;
-};
+typedef solo_mix_selected_count_t SxMixSelCount;
 static_assert(sizeof(SxMixSelCount) == 32, "solo_mix_selected_count_t layout");
 
 struct SxMixSelArgs {

@@ -34,10 +34,7 @@
 #pragma once
 #include "solo_mix.h"
 
-struct SxMixShCount {           // == solo_mix_shared_count_t
-    i32 rows, rooms, speakers, shared;
-    i64 clipped;
-};
+typedef solo_mix_shared_count_t SxMixShCount;
 static_assert(sizeof(SxMixShCount) == 24, "solo_mix_shared_count_t layout");
 
 struct SxMixShArgs {

@@ -24,6 +24,7 @@
 // Everything outside the kernels compiles for the host as well (tests/playout_host.cpp walks the rows through the very functions of the
 // kernels; tests/test_playout_model.py compares them with the independent model of tests/playout_model.py).
 #pragma once
+#include <stddef.h>
 #include <string.h>
 #include "solo_wave.h"          // wg_sum, wg_scan_incl
 #include "solo_stream_ctl.h"    // sx_map_refused, the list launches
@@ -48,21 +49,38 @@
 #define SX_PO_ACT_ACCEL 4
 #define SX_PO_ACT_ACCEL_FORCED 5
 
-#define SX_PO_OUT_IDLE 0
-#define SX_PO_OUT_NORMAL 1
-#define SX_PO_OUT_HELD 2
-#define SX_PO_OUT_STRETCH 3
-#define SX_PO_OUT_STRETCH_GATED 4
-#define SX_PO_OUT_ACCEL 5
-#define SX_PO_OUT_ACCEL_GATED 6
-#define SX_PO_OUT_ACCEL_FORCED 7
+#define SX_PO_OUT_IDLE SOLO_PLAYOUT_IDLE
+#define SX_PO_OUT_NORMAL SOLO_PLAYOUT_NORMAL
+#define SX_PO_OUT_HELD SOLO_PLAYOUT_HELD
+#define SX_PO_OUT_STRETCH SOLO_PLAYOUT_STRETCH
+#define SX_PO_OUT_STRETCH_GATED SOLO_PLAYOUT_STRETCH_GATED
+#define SX_PO_OUT_ACCEL SOLO_PLAYOUT_ACCEL
+#define SX_PO_OUT_ACCEL_GATED SOLO_PLAYOUT_ACCEL_GATED
+#define SX_PO_OUT_ACCEL_FORCED SOLO_PLAYOUT_ACCEL_FORCED
 #define SX_PO_N_OUTCOMES 8
 
-struct SxPoParams { i32 start_ready, max_span, window, tolerate, lo, hi, cooldown, cost_gate; };       // == solo_playout_params_t
-struct alignas(16) SxPoPlanCount { i32 n_one, n_two, n_stretch, listed; };                              // == solo_playout_plan_count_t
-struct alignas(16) SxPoRenderCount { i32 outcome[SX_PO_N_OUTCOMES]; };                                  // == solo_playout_render_count_t
-struct SxPoCount { SxPoPlanCount plan; SxPoRenderCount render; };                                       // == solo_playout_count_t
+typedef solo_playout_params_t SxPoParams;
+// The three counts are the public records with what those do not say: the 16-byte alignment the interface asks of the caller (the kernels
+// store whole records), and the outcomes as an array indexed by the SOLO_PLAYOUT_* code.
+struct alignas(16) SxPoPlanCount { i32 n_one, n_two, n_stretch, listed; };
+struct alignas(16) SxPoRenderCount { i32 outcome[SX_PO_N_OUTCOMES]; };
+struct SxPoCount { SxPoPlanCount plan; SxPoRenderCount render; };
 static_assert(sizeof(SxPoParams) == 32 && sizeof(SxPoPlanCount) == 16 && sizeof(SxPoRenderCount) == 32 && sizeof(SxPoCount) == 48, "solo_playout_* layout");
+// ... and agree with them field by field: every public field at the twin's word, every outcome's field at the index of its code
+#define SX_PO_SAME(pub, twin, f) (offsetof(pub, f) == offsetof(twin, f) && sizeof(((pub*)0)->f) == sizeof(((twin*)0)->f))
+#define SX_PO_OUTCOME(f, code) (offsetof(solo_playout_render_count_t, f) == offsetof(SxPoRenderCount, outcome) + sizeof(i32) * (code))
+static_assert(SX_PO_SAME(solo_playout_plan_count_t, SxPoPlanCount, n_one) && SX_PO_SAME(solo_playout_plan_count_t, SxPoPlanCount, n_two) &&
+              SX_PO_SAME(solo_playout_plan_count_t, SxPoPlanCount, n_stretch) && SX_PO_SAME(solo_playout_plan_count_t, SxPoPlanCount, listed) &&
+              sizeof(solo_playout_plan_count_t) == sizeof(SxPoPlanCount) && alignof(SxPoPlanCount) == 16, "solo_playout_plan_count_t, field by field");
+static_assert(SX_PO_OUTCOME(idle, SOLO_PLAYOUT_IDLE) && SX_PO_OUTCOME(normal, SOLO_PLAYOUT_NORMAL) && SX_PO_OUTCOME(held, SOLO_PLAYOUT_HELD) &&
+              SX_PO_OUTCOME(stretch, SOLO_PLAYOUT_STRETCH) && SX_PO_OUTCOME(stretch_gated, SOLO_PLAYOUT_STRETCH_GATED) &&
+              SX_PO_OUTCOME(accel, SOLO_PLAYOUT_ACCEL) && SX_PO_OUTCOME(accel_gated, SOLO_PLAYOUT_ACCEL_GATED) &&
+              SX_PO_OUTCOME(accel_forced, SOLO_PLAYOUT_ACCEL_FORCED) && SOLO_PLAYOUT_ACCEL_FORCED + 1 == SX_PO_N_OUTCOMES &&
+              sizeof(solo_playout_render_count_t) == sizeof(SxPoRenderCount) && alignof(SxPoRenderCount) == 16, "solo_playout_render_count_t, field by field");
+static_assert(SX_PO_SAME(solo_playout_count_t, SxPoCount, plan) && SX_PO_SAME(solo_playout_count_t, SxPoCount, render) &&
+              sizeof(solo_playout_count_t) == sizeof(SxPoCount) && alignof(SxPoCount) == 16, "solo_playout_count_t, field by field");
+#undef SX_PO_SAME
+#undef SX_PO_OUTCOME
 
 struct SxPoCtl { i32 run, held, cum, cool, age; u32 late_prev; i32 pos, zero; };
 struct SxPoRow { SxPoCtl c; u32 ring[SX_PO_RING / 2]; };    // words 0 .. 23 of a record, in registers

@@ -24,8 +24,9 @@
 // solo_recv_report (solo_recv_report.h).
 #pragma once
 #include "solo_rc.h"
+#include "../../include/solo_mi355x.h"
 
-struct SxRecvArrival { i32 stream, seq, desc, offset, len; };      // == solo_arrival_t (include/solo_mi355x.h)
+typedef solo_arrival_t SxRecvArrival;
 static_assert(sizeof(SxRecvArrival) == 20, "solo_arrival_t layout");
 
 // what became of an arrival (index into the handle's statistics)

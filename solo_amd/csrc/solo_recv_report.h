@@ -34,17 +34,12 @@
 
 #define SX_RECV_TILE 256        // rows per workgroup of the compaction = its lanes (wg_sum / wg_scan_incl are for 256)
 
-struct SxRecvReport {           // == solo_recv_report_t
-    i32 play, queued, complete, ready, span, head;
-    u32 inserted, late, ahead, duplicate, bad;
-    u32 played_both, played_md1, played_md2, played_none;
-    i32 margin_min;
-};
+typedef solo_recv_report_t SxRecvReport;
 static_assert(sizeof(SxRecvReport) == 64, "solo_recv_report_t layout");
-struct SxRecvReportCount { i32 selected, listed; };          // == solo_recv_report_count_t
+typedef solo_recv_report_count_t SxRecvReportCount;
 static_assert(sizeof(SxRecvReportCount) == 8, "solo_recv_report_count_t layout");
 
-#define SX_RECV_REPORT_CLEAR_MARGIN 1
+#define SX_RECV_REPORT_CLEAR_MARGIN SOLO_RECV_REPORT_CLEAR_MARGIN
 
 // lanes that read one stream: the power of two at or above min(depth, 64)
 SX_HD int sx_recv_group(int depth) {

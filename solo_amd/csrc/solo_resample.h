@@ -33,6 +33,7 @@
 #pragma once
 #include "solo_wave.h"
 #include "solo_stream_ctl.h"
+#include "../../include/solo_mi355x.h"
 
 #if !defined(SOLO_TAB)
 #if defined(__HIPCC__)
@@ -57,7 +58,7 @@ struct SxRsCfg {
     i32 coefs;                  // kind 0: 0 = 1:3, 1 = 2:3, 2 = 1:2
     i32 mid_words, row_words;   // LDS words of a row's mid buffer (history included), and of the whole row (odd)
 };
-struct SxRsCount { i32 rows, listed; };                     // == solo_resample_count_t
+typedef solo_resample_count_t SxRsCount;
 
 static inline bool sx_rs_rate_ok(i32 fs) { return fs == 8000 || fs == 16000 || fs == 32000 || fs == 48000; }
 // The conversions of this library -> false for every other pair.  invRatio_Q16 as SKP_Silk_resampler_init computes it

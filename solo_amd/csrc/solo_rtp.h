@@ -43,15 +43,11 @@
 #define SX_RTP_UNKNOWN_PT 4
 #define SX_RTP_TIMESTAMP 5
 
-struct SxRtpDgram { i32 offset, len; };                      // == solo_dgram_t
+typedef solo_dgram_t SxRtpDgram;
 static_assert(sizeof(SxRtpDgram) == 8, "solo_dgram_t layout");
-struct SxRtpPackCount {                                      // == solo_rtp_pack_count_t
-    i32 dgrams, dgrams_needed;
-    i64 bytes, bytes_needed;
-    i32 refused, reserved;
-};
+typedef solo_rtp_pack_count_t SxRtpPackCount;
 static_assert(sizeof(SxRtpPackCount) == 32, "solo_rtp_pack_count_t layout");
-struct SxRtpParseCount { i32 accepted, with_level, malformed, version, unknown_ssrc, unknown_pt, timestamp, reserved; };     // == solo_rtp_parse_count_t
+typedef solo_rtp_parse_count_t SxRtpParseCount;
 static_assert(sizeof(SxRtpParseCount) == 32, "solo_rtp_parse_count_t layout");
 
 struct SxRtpStream { u32 ssrc, ts_offset, seq_pt, bound; };  // a stream's record; seq_pt: sequence offset | pt_md1 << 16 | pt_md2 << 24

@@ -23,6 +23,7 @@
 #pragma once
 #include "solo_wave.h"
 #include "solo_stream_ctl.h"
+#include "../../include/solo_mi355x.h"
 
 #define SX_SEND_TILE 256        // packets per tile = lanes per workgroup of passes 1 and 3
 #define SX_SEND_ROW 16          // lanes that copy one packet's run (four packets per wavefront: a 78-byte packet is 20 dwords)
@@ -36,14 +37,10 @@
 #define SX_SEND_N1_SHORT 5      // a second description shorter than the high-band bytes it ends with
 #define SX_SEND_SEQ 6           // the sequence number is negative or does not fit int32
 
-struct SxSendCount {            // == solo_send_count_t
-    i32 records, records_needed;
-    i64 bytes, bytes_needed;
-    i32 empty, refused;
-};
+typedef solo_send_count_t SxSendCount;
 static_assert(sizeof(SxSendCount) == 32, "solo_send_count_t layout");
 
-struct SxSendRecord { i32 stream, seq, desc, offset, len; };     // == solo_arrival_t, SxRecvArrival (solo_recv.h): what solo_recv_insert takes
+typedef solo_arrival_t SxSendRecord;                        // what solo_recv_insert takes: SxRecvArrival of solo_recv.h
 static_assert(sizeof(SxSendRecord) == 20, "solo_arrival_t layout");
 
 struct SxSendPlan { i32 why, len0, len1, src1, seq; };      // len0 / len1: bytes of the MD1 / MD2 || HB datagram (0: none); src1: where MD2 starts in the slot

@@ -24,6 +24,7 @@
 // very functions of the kernel, with the 1-lane forms of solo_wave.h, and are compared with an independent model).
 #pragma once
 #include "solo_wave.h"
+#include "../../include/solo_mi355x.h"
 
 #define SX_TS_MAX_PACKETS 4
 #define SX_TS_MAX_L 1280                                    // samples of the longest packet (40 ms at 32 kHz)
@@ -31,10 +32,7 @@
                                                             // candidate, and the template's pairing, read up to R + 1 samples past the row
 #define SX_TS_MAX_BLOCKS 32                                 // 4 packets of 8 blocks
 
-struct SxTsCount {              // == solo_timescale_count_t
-    i32 rows, blocks;
-    i64 cost;
-};
+typedef solo_timescale_count_t SxTsCount;
 static_assert(sizeof(SxTsCount) == 16, "solo_timescale_count_t layout");
 
 struct alignas(16) SxTsX8 { u32 d[4]; };                    // what one lane loads and stores: 8 samples

@@ -41,9 +41,9 @@
 
 struct SxVadRow { SxVAD v; i32 talking, hang, picked, zero; };
 static_assert(sizeof(SxVAD) == SX_VAD_REF_WORDS * 4 && sizeof(SxVadRow) == SX_VAD_STATE_WORDS * 4, "the state record of a row");
-struct SxVadCount { i32 rows, rooms, selected, changes; };  // == solo_vad_count_t
+typedef solo_vad_count_t SxVadCount;
 static_assert(sizeof(SxVadCount) == sizeof(SxMixCount), "the room plan's scan kernel writes {rows, rooms, 0, 0} through a SxMixCount");
-struct SxVadSelectParams { i32 max_speakers, on_q8, off_q8, hang_packets, stick; };     // == solo_vad_select_params_t
+typedef solo_vad_select_params_t SxVadSelectParams;
 
 // word w of the record SKP_Silk_VAD_Init leaves (VAD.c:39-67), selection state zero: what the create and reset calls write
 SX_HD i32 sx_vad_init_word(int w) {

@@ -1,5 +1,5 @@
 // Host build of the level control stage (solo_amd/csrc/solo_agc.h) for tests/test_agc_model.py and tests/test_agc_abi.py, which compile
-// this file into a temporary directory with the flags of tests/test_vad_model.py.
+// this file into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_agc.h"
 

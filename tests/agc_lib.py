@@ -7,18 +7,15 @@ rows list or None, inplace bool, prm dict of parameters that differ from the def
 (the host build here, the C ABI and solo_amd.Agc in the GPU tests) and through tests/agc_model.py, and compares PCM, level_out, gain_q8,
 count and the whole state after every call, byte for byte."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import agc_model as M
-from vad_lib import ROOT, SEED, speech
+from host_build import host_lib
+from vad_lib import SEED, speech
 
 STATE_BYTES = 64
 SHAPES = [(L, n, P) for L in (320, 640, 1920) for n in (1, 5, 67) for P in (1, 3)]
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------------------
@@ -182,10 +179,8 @@ def check_case(engine, case, tag):
 
 
 # ---- the host build of solo_agc.h ------------------------------------------------------------------------------------------------------------
-def build_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("agc") / "libagc_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(ROOT, "tests", "agc_host.cpp"), "-o", out])
-    lib, V, I = C.CDLL(out), C.c_void_p, C.c_int
+def build_host():
+    lib, V, I = host_lib("agc"), C.c_void_p, C.c_int
     lib.emu_agc_init.argtypes = [V, I]
     lib.emu_agc_prefix_min_steps.argtypes = [V]
     lib.emu_agc_list_ok.argtypes = [V, I, I]

@@ -1,5 +1,5 @@
 // Host build of the stream migration (solo_amd/csrc/solo_migrate.h: export, check and import in their host forms) for
-// tests/test_migrate_model.py, which compiles this file into a temporary directory with the flags of tests/emu/Makefile.
+// tests/test_migrate_model.py, which compiles this file into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_dec.h"          // (the tables solo_recv.h reads)
 #include "../solo_amd/csrc/solo_migrate.h"

@@ -1,5 +1,5 @@
 // Host build of the mixing bridge (solo_amd/csrc/solo_mix.h) for tests/test_mix_model.py, which compiles this file into a temporary
-// directory with the flags of tests/emu/Makefile.
+// directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_mix.h"
 

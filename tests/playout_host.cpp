@@ -1,5 +1,5 @@
 // Host build of the play-out delay control (solo_amd/csrc/solo_playout.h) for tests/test_playout_model.py and tests/test_playout_abi.py,
-// which compile this file into a temporary directory with the flags of tests/test_timescale_model.py.  An "object" here is the caller's
+// which compile this file into a temporary directory through tests/host_build.py.  An "object" here is the caller's
 // memory: state int32 [n_rows][32], held int16 [n_rows][L], slot / sslot int32 [n_rows].
 #include <string.h>
 #include "../solo_amd/csrc/solo_playout.h"

@@ -2,16 +2,12 @@
 library, a back end that keeps an object's memory in numpy arrays, and drive(): the tick-by-tick comparison of a back end with the
 independent model of tests/playout_model.py -- every action, list, count, output sample and state byte after every tick."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import playout_model as PM
-import solo_testlib as T
+from host_build import host_lib
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 GUARD = 3                                                         # entries / rows behind the call's
 FILL_A, FILL_L, FILL_N, FILL_H, FILL_O, FILL_S = -7, -77, 0x5A5A5A5A, 0x1234, -5, -99
 
@@ -24,10 +20,8 @@ def c_params(p):
     return Params(*[int(p[k]) for k in PM.PARAMS])
 
 
-def build_host(tmpdir):
-    out = os.path.join(str(tmpdir), "libplayout_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "playout_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def build_host():
+    lib = host_lib("playout")
     P, V, I = C.POINTER(Params), C.c_void_p, C.c_int
     lib.emu_po_params_ok.argtypes = [P]
     lib.emu_po_list_ok.argtypes = [V, I, I]

@@ -1,5 +1,5 @@
 // Host build of the read side of the receiver ring (solo_amd/csrc/solo_recv_report.h) for tests/test_recv_report_model.py, which
-// compiles this file into a temporary directory with the flags of tests/emu/Makefile.
+// compiles this file into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_dec.h"
 #include "../solo_amd/csrc/solo_recv_report.h"

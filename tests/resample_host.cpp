@@ -1,5 +1,5 @@
 // Host build of the PCM resampler (solo_amd/csrc/solo_resample.h) for tests/test_resample_model.py, which compiles this file into a
-// temporary directory with the flags of tests/test_mix_model.py.
+// temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_resample.h"
 

@@ -1,5 +1,5 @@
 // Host build of the RTP stage (solo_amd/csrc/solo_rtp.h) for tests/test_rtp_model.py, which compiles this file into a temporary
-// directory with the flags of tests/emu/Makefile.  The session is the host mirror of solo_api.hip's object: the same bind / unbind
+// directory through tests/host_build.py.  The session is the host mirror of solo_api.hip's object: the same bind / unbind
 // functions, with the "device" records and table kept in vectors.
 #include <string.h>
 #include "../solo_amd/csrc/solo_dec.h"

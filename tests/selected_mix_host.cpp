@@ -1,5 +1,5 @@
 // Host build of the shared mixing bridge with a given selection (solo_amd/csrc/solo_mix_selected.h) for tests/test_selected_mix_model.py,
-// which compiles this file into a temporary directory with the flags of tests/test_mix_model.py -- and, with -DSELECTED_MIX_MAIN, as a
+// which compiles this file into a temporary directory through tests/host_build.py -- and, with -DSELECTED_MIX_MAIN, as a
 // stand-alone program (the sanitiser build): it reads one case from a file, runs the host form and writes every output to a second file.
 // The host forms of solo_mix and solo_mix_shared are exported as well: the identities of the test run against them.
 #include <stdio.h>

@@ -1,5 +1,5 @@
 // Host build of the sender back end (solo_amd/csrc/solo_send.h) and of the wave scan's host form (solo_wave.h) for
-// tests/test_send_pack_model.py, which compiles this file into a temporary directory with the flags of tests/emu/Makefile.
+// tests/test_send_pack_model.py, which compiles this file into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_send.h"
 

@@ -1,5 +1,5 @@
 // Host build of the shared mixing bridge and the fan-out sender (solo_amd/csrc/solo_mix_shared.h, solo_fanout.h) for
-// tests/test_shared_mix_model.py, which compiles this file into a temporary directory with the flags of tests/test_mix_model.py.
+// tests/test_shared_mix_model.py, which compiles this file into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_mix_shared.h"
 #include "../solo_amd/csrc/solo_fanout.h"

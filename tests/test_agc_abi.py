@@ -16,8 +16,8 @@ SYMBOLS = ("solo_agc_create", "solo_agc_destroy", "solo_agc_reset", "solo_agc_re
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    return L.build_host(tmp_path_factory)
+def host():
+    return L.build_host()
 
 
 def test_symbols_and_layouts(host):

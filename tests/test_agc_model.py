@@ -10,8 +10,8 @@ import vad_lib as VL
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    return L.build_host(tmp_path_factory)
+def host():
+    return L.build_host()
 
 
 def test_tables_and_lin(host):

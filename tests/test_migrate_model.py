@@ -1,28 +1,22 @@
 """Stream migration (solo_batch_export_streams / solo_batch_import_streams, solo_amd/csrc/solo_migrate.h) without a GPU: the host
-forms of the export, the record check and the import are compiled by this test (tests/migrate_host.cpp, the flags of
-tests/emu/Makefile) and run on numpy-made handles -- random bytes as stream records, a small ring with random lengths -- against the
+forms of the export, the record check and the import are compiled by this test (tests/migrate_host.cpp, through
+tests/host_build.py) and run on numpy-made handles -- random bytes as stream records, a small ring with random lengths -- against the
 independent numpy model of tests/migrate_model.py: header fields, both checksums, play-relative order of the queue at every wrap
 offset, zero fill beyond `len`, every refusal rule, and a refused import that leaves the target as it was."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import solo_testlib as T
 import migrate_model as M
+from host_build import host_lib
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 ENC_BYTES, DEC_BYTES = 1072, 604          # a multiple of 16 and one that is only a multiple of 4, like the real records
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("migrate") / "libmigrate_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "migrate_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("migrate")
     lib.emu_mig_state_bytes.restype = C.c_longlong
     lib.emu_mig_state_bytes.argtypes = [C.c_void_p, C.c_int]
     common = [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]

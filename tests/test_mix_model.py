@@ -1,27 +1,21 @@
 """Mixing bridge (solo_mix, solo_amd/csrc/solo_mix.h) without a GPU: the room plan and the per-(room, packet) walk are compiled for the
-host by this test (tests/mix_host.cpp, the flags of tests/test_send_pack_model.py) and compared with the independent numpy model of
+host by this test (tests/mix_host.cpp, through tests/host_build.py) and compared with the independent numpy model of
 tests/mix_model.py -- every output sample, the energies, the flags and the count."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import solo_testlib as T
+from host_build import host_lib
 from mix_model import GAINS, mix_case, model_mix, ties_decide
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 FILL_O, FILL_E, FILL_M = 0x1234, -77, 0xA5
 GUARD = 3                                                         # rows behind the call's
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("mix") / "libmix_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "mix_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("mix")
     lib.emu_mix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emu_mix_before.argtypes = [C.c_longlong, C.c_int, C.c_longlong, C.c_int]
     lib.emu_mix_contrib.argtypes = [C.c_int, C.c_int]

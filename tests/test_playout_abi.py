@@ -21,8 +21,8 @@ KERNELS = ("solo_playout_plan_kernel", "solo_playout_compact_kernel", "solo_play
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    return PL.build_host(tmp_path_factory.mktemp("playout_abi"))
+def host():
+    return PL.build_host()
 
 
 def _struct_fields(name):

@@ -17,8 +17,8 @@ LISTED = sorted(np.random.RandomState(77).choice(N, 77, replace=False).tolist())
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    return PL.build_host(tmp_path_factory.mktemp("playout"))
+def host():
+    return PL.build_host()
 
 
 @pytest.fixture(scope="module")

@@ -1,29 +1,25 @@
 """Read side of the receiver ring (solo_recv_report, solo_amd/csrc/solo_recv_report.h) without a GPU: the per-stream queue scan, the
 selection rule, the record layout and the play-out classification are compiled for the host by this test (tests/recv_report_host.cpp,
-the flags of tests/emu/Makefile) and compared with the independent model of tests/recv_report_model.py on random rings -- every depth
+through tests/host_build.py) and compared with the independent model of tests/recv_report_model.py on random rings -- every depth
 around the group sizes of the kernel, play-out positions that make the window wrap the ring, empty / full / head-missing /
 only-last-entry queues, every branch of the selection; the built library's new kernels use no scratch."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import solo_testlib as T
+from host_build import host_lib
 from recv_report_model import FIELDS, RingModel, lens_words, queue_fields, selected
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 DEPTHS = [1, 2, 5, 8, 63, 64, 65, 4096]
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("recv_report") / "librecv_report_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "recv_report_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("recv_report")
     lib.emu_recv_report.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p] * 4
     lib.emu_recv_play_class.argtypes = [C.c_uint]
     return lib

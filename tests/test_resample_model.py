@@ -1,9 +1,8 @@
 """PCM resampler (solo_resample, solo_amd/csrc/solo_resample.h) without a GPU: the fixture recorded from the compiled reference
 (tests/golden/resample.npz), the independent model of tests/resample_model.py and the host form of the kernel source (compiled by this
-test from tests/resample_host.cpp) must agree sample for sample and state byte for state byte.  No tolerance anywhere."""
+test from tests/resample_host.cpp, through tests/host_build.py) must agree sample for sample and state byte for state byte.  No tolerance anywhere."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,19 +10,16 @@ import pytest
 import resample_lib as L
 import resample_model as M
 import solo_testlib as T
+from host_build import host_lib
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 REF_LIB = os.path.join(T.ROOT, "oracle", "_ref", "libsolo_ref_fix.so")
 CASES = [(fi, fo, 40) for fi, fo in L.PAIRS] + [(fi, fo, 20) for fi, fo in L.PAIRS_20MS]
 ids = lambda c: "%d-%d-%dms" % (c[0] // 1000, c[1] // 1000, c[2])
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("resample") / "libresample_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "resample_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("resample")
     lib.emu_rs_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.emu_rs_call_ok.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_void_p]
     lib.emu_rs_list_ok.argtypes = [C.c_void_p, C.c_int, C.c_int]

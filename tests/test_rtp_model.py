@@ -1,11 +1,10 @@
 """RTP framing and parsing (solo_rtp_pack / solo_rtp_parse, solo_amd/csrc/solo_rtp.h) without a GPU: the per-record and per-datagram
-functions, the three pack passes and the control plane are compiled for the host by this test (tests/rtp_host.cpp, the flags of
-tests/emu/Makefile) and compared with the independent model of tests/rtp_model.py: the parse verdicts in rule order, the timestamp
+functions, the three pack passes and the control plane are compiled for the host by this test (tests/rtp_host.cpp, through
+tests/host_build.py) and compared with the independent model of tests/rtp_model.py: the parse verdicts in rule order, the timestamp
 unwrap at its edges, random records with every refusal reason under both caps, the loopback parse(pack(x)) == x, the binding rules;
 then the ABI and the built library's new kernels (no scratch)."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,18 +12,15 @@ import pytest
 
 import solo_testlib as T
 import rtp_model as M
+from host_build import host_lib
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 RTP_SYMBOLS = ("solo_rtp_create", "solo_rtp_destroy", "solo_rtp_bind", "solo_rtp_unbind", "solo_rtp_pack", "solo_rtp_parse")
 FILL = 0xA5
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("rtp") / "librtp_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "rtp_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("rtp")
     lib.emu_rtp_create.restype = C.c_void_p
     lib.emu_rtp_create.argtypes = [C.c_int, C.c_int]
     lib.emu_rtp_destroy.argtypes = [C.c_void_p]

@@ -1,5 +1,5 @@
 """Shared listener mixes from a given selection without a GPU (solo_mix_selected): the passes of solo_amd/csrc/solo_mix_selected.h are
-compiled for the host by this test (tests/selected_mix_host.cpp, the flags of tests/test_mix_model.py) and compared bit for bit with the
+compiled for the host by this test (tests/selected_mix_host.cpp, through tests/host_build.py) and compared bit for bit with the
 independent model of tests/selected_mix_model.py -- PCM, lists, source table, room_nsel, energies, counts, and the fill behind the counts.
 Two identities tie the call to the host forms of solo_mix_shared and solo_mix, and one family runs through a stand-alone build of the
 same file under the address and undefined-behaviour sanitisers."""
@@ -10,26 +10,22 @@ import subprocess
 import numpy as np
 import pytest
 
-import solo_testlib as T
+from host_build import FLAGS, host_lib, source
 from selected_mix_model import heard, model_mix_selected, selected_case
 from shared_mix_model import shared_case
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 FILL = dict(pcm_spk=0x1234, spk_list=-7001, spk_rows=-7002, pcm_room=0x4321, room_list=-7003, source=-7004, room_nsel=0xA5, energy=-77)
 DTYPE = dict(pcm_spk=np.int16, spk_list=np.int32, spk_rows=np.int32, pcm_room=np.int16, room_list=np.int32, source=np.int32, room_nsel=np.uint8,
              energy=np.int64)
 OPTIONAL = ("spk_rows", "room_nsel", "energy")
 FILL_C = 0x5A5A5A5A
 COUNT = ("rows", "rooms", "speakers", "shared", "clipped", "selected", "silent")
-SRC = os.path.join(T.ROOT, "tests", "selected_mix_host.cpp")
+SRC = source("selected_mix")
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("selected_mix") / "libselected_mix_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [SRC, "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("selected_mix")
     V, I = C.c_void_p, C.c_int
     lib.emu_mix_selected.argtypes = [V, I, I, I, V, I] + [V] * 13
     lib.emu_mix_shared.argtypes = [V, I, I, I, V, I, V, I, V, V, V, V, V, V, V, V, V, V, V]

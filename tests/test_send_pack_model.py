@@ -1,27 +1,22 @@
 """Sender back end (solo_send_pack, solo_amd/csrc/solo_send.h) without a GPU: the length rules, the three passes and the byte copy are
-compiled for the host by this test (tests/send_pack_host.cpp, the flags of tests/emu/Makefile) and compared with the independent numpy
+compiled for the host by this test (tests/send_pack_host.cpp, through tests/host_build.py) and compared with the independent numpy
 model of tests/send_pack_model.py on random length records; the wave scan's host form against a running sum; the built library's new
 kernels use no scratch."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import solo_testlib as T
+from host_build import host_lib
 from send_pack_model import INT32_MAX, REASONS, model_pack
-
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("send_pack") / "libsend_pack_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "send_pack_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("send_pack")
     lib.emu_send_plan.argtypes = [C.c_int] * 5 + [C.c_longlong, C.c_void_p]
     lib.emu_send_pack.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
     lib.emu_send_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int]

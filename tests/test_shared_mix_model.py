@@ -1,20 +1,16 @@
 """Shared listener mixes without a GPU (solo_mix_shared, solo_send_fanout): the passes of solo_amd/csrc/solo_mix_shared.h and
-solo_fanout.h are compiled for the host by this test (tests/shared_mix_host.cpp, the flags of tests/test_mix_model.py) and compared bit
+solo_fanout.h are compiled for the host by this test (tests/shared_mix_host.cpp, through tests/host_build.py) and compared bit
 for bit with the independent model of tests/shared_mix_model.py -- PCM, lists, source table, counts, records, pool bytes, and the fill
 behind the counts."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import solo_testlib as T
+from host_build import host_lib
 from mix_model import model_mix, ties_decide
 from shared_mix_model import fanout_case, heard, model_fanout, model_mix_shared, shared_case
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 FILL = dict(pcm_spk=0x1234, spk_list=-7001, spk_rows=-7002, pcm_room=0x4321, room_list=-7003, source=-7004, energy=-77, mixed=0xA5)
 DTYPE = dict(pcm_spk=np.int16, spk_list=np.int32, spk_rows=np.int32, pcm_room=np.int16, room_list=np.int32, source=np.int32, energy=np.int64,
              mixed=np.uint8)
@@ -24,10 +20,8 @@ SEND_COUNT = ("records", "records_needed", "bytes", "bytes_needed", "empty", "re
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("shared_mix") / "libshared_mix_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "shared_mix_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("shared_mix")
     V, I = C.c_void_p, C.c_int
     lib.emu_mix_shared.argtypes = [V, I, I, I, V, I, V, I, V, V, V, V, V, V, V, V, V, V, V]
     lib.emu_send_fanout.argtypes = [V, V, I, V, V, I, V, I, I, I, V, I, V, I, V, C.c_longlong, V]

@@ -1,21 +1,17 @@
 """Play-out time scaling (solo_timescale, solo_amd/csrc/solo_timescale.h) without a GPU: the row walk is compiled for the host by this test
-(tests/timescale_host.cpp, the flags of tests/test_mix_model.py) and compared with the independent numpy model of tests/timescale_model.py
+(tests/timescale_host.cpp, through tests/host_build.py) and compared with the independent numpy model of tests/timescale_model.py
 -- every output sample, shift, cost and the count, for every (in_packets, out_packets) in 1..4 x 1..4 at the four packet geometries -- and
 with what the interface promises whatever the model says; then the model alone: the search must earn its keep on speech, and the
 look-ahead term of the block before the last must lower the cost of the pinned last splice."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-import solo_testlib as T
+from host_build import host_lib
 from timescale_model import (FAMILIES, GEOMETRIES, PERIODS, geometry, lag_range, model_timescale, narrowest_window, nominal, speech_segments,
                              timescale_rows)
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 FILL_O, FILL_S, FILL_C, FILL_N = 0x1234, -77, -99, 0x5A5A5A5A
 GUARD = 3                                                         # rows behind the call's
 N = 67
@@ -23,10 +19,8 @@ RATIOS = ((2, 1), (3, 2), (1, 2), (2, 3))
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("timescale") / "libtimescale_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "timescale_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def host():
+    lib = host_lib("timescale")
     lib.emu_timescale.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emu_ts_sad.restype = lib.emu_ts_straddle.restype = C.c_uint
     lib.emu_ts_sad.argtypes = [C.c_uint] * 3

@@ -16,8 +16,8 @@ SYMBOLS = ("solo_vad_create", "solo_vad_destroy", "solo_vad_reset", "solo_vad_re
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    return build_host(tmp_path_factory)
+def host():
+    return build_host()
 
 
 def test_symbols_and_layouts(host):

@@ -1,6 +1,6 @@
 """VAD stage (solo_vad / solo_vad_select, solo_amd/csrc/solo_vad.h) without a GPU: the fixture recorded from the compiled reference
 (tests/golden/vad.npz), the independent model of tests/vad_model.py and the host form of the kernel source (compiled by this test from
-tests/vad_host.cpp) must agree sample for sample and state byte for state byte.  No tolerance anywhere.
+tests/vad_host.cpp, through tests/host_build.py) must agree sample for sample and state byte for state byte.  No tolerance anywhere.
 
 The issue's condition "row 2 reaches NL == 0x00FFFFFF in every band" is asserted at frames of 160 samples.  At frames of 320 samples no
 input can meet it within 16 packets: from the initial state the inverse noise level falls by at most min_coef / 65536 of itself per
@@ -10,7 +10,6 @@ period 16 after 32 frames: 10631107, 7642290, 4598466, 3645982).  There it is as
 falls below 1 kHz and band 0 stops at NL 16393004 at frames of 160 (the family was tuned, the condition stands)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,17 +17,14 @@ import pytest
 import solo_testlib as T
 import vad_lib as L
 import vad_model as M
+from host_build import host_lib
 
-FLAGS = ["-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-fwrapv", "-fno-strict-aliasing", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-         "-DSOLO_HOST_EMU"]
 REF_LIB = os.path.join(T.ROOT, "oracle", "_ref", "libsolo_ref_fix.so")
 P32 = C.POINTER(C.c_int32)
 
 
-def build_host(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("vad") / "libvad_host.so")
-    subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [os.path.join(T.ROOT, "tests", "vad_host.cpp"), "-o", out])
-    lib = C.CDLL(out)
+def build_host():
+    lib = host_lib("vad")
     lib.emu_vad_threshold.restype = C.c_uint64
     lib.emu_vad_level.argtypes = [C.c_int64, C.c_int]
     lib.emu_vad_init.argtypes = [C.c_void_p, C.c_int]
@@ -42,8 +38,8 @@ def build_host(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
-def host(tmp_path_factory):
-    return build_host(tmp_path_factory)
+def host():
+    return build_host()
 
 
 def host_state(lib, n_rows):

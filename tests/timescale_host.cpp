@@ -1,5 +1,5 @@
 // Host build of the play-out time scaler (solo_amd/csrc/solo_timescale.h) for tests/test_timescale_model.py, which compiles this file
-// into a temporary directory with the flags of tests/emu/Makefile.
+// into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_timescale.h"
 

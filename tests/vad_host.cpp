@@ -1,5 +1,5 @@
 // Host build of the VAD stage (solo_amd/csrc/solo_vad.h) for tests/test_vad_model.py and tests/test_vad_abi.py, which compile this file
-// into a temporary directory with the flags of tests/test_resample_model.py.
+// into a temporary directory through tests/host_build.py.
 #include <string.h>
 #include "../solo_amd/csrc/solo_vad.h"
 
