@@ -871,6 +871,68 @@ int32_t solo_rtp_pack(solo_rtp_t *r, const solo_arrival_t *d_records, const solo
 int32_t solo_rtp_parse(solo_rtp_t *r, solo_batch_t *b, const solo_dgram_t *d_dgrams, int32_t n_dgrams, const uint8_t *d_wire, int64_t wire_bytes,
                        solo_arrival_t *d_arrivals, uint8_t *d_level_out, uint16_t *d_rtp_seq_out, solo_rtp_parse_count_t *d_count,
                        void *hip_stream);
+/* SRTP at both ends (RFC 3711, the mandatory default transforms): solo_srtp_protect stands behind solo_rtp_pack and turns the packed
+ * datagrams into SRTP in place, solo_srtp_unprotect stands in front of solo_rtp_parse and turns received SRTP datagrams back into RTP in
+ * place, so that a secured deployment walks no datagram on the host either.  Cipher AES-128 in counter mode (AES_CM_128) over everything
+ * behind the RTP header (12 + 4 CC bytes and the extension block: the RFC 6464 level stays readable for a forwarding server),
+ * authentication HMAC-SHA1 over header, ciphertext and rollover counter with an 80- or 32-bit tag (HMAC_SHA1_80 / _32), key derivation
+ * of section 4.3 with rate 0.  The keys belong to the solo_rtp_t session, which already has the SSRC table and the sequence offsets.
+ * solo_rtp_set_trailer -- a host switch, 0 .. 16, default 0, read when a pack call is issued: with a trailer T solo_rtp_pack plans every
+ *   valid record as roundup4(H + len + T), writes the T bytes behind the datagram as zero together with the pad bytes, leaves
+ *   d_dgrams[k].len = H + len, counts the trailer in bytes and bytes_needed, and writes a datagram iff all of it fits the cap.  T = 0:
+ *   every byte and count as without the call.  -1: NULL r, a value outside 0 .. 16, or one below the tag of a stream's tx key.
+ * Control plane -- HOST arrays, as for solo_rtp_bind; ordered on hip_stream, the calls return when the device holds the records, not
+ * capturable.  The device holds per stream and direction a 256-byte record: the expanded AES round keys, the salt at its place in the
+ * IV, the SHA-1 states behind the HMAC's ipad and opad blocks, the tag length and a "has key" word, derived ON THE HOST from one
+ * direction's SDES / DTLS-SRTP keying material (master key || master salt) with labels 0, 1, 2 and index 0; and per stream a receive
+ * record, the highest authenticated packet index.  The records are a device allocation made by the first solo_srtp_set_keys: a session
+ * without SRTP pays nothing.  The host keeps per stream "has tx / has rx / tag bytes" and never the keys; it moves after the device does.
+ *   solo_srtp_set_keys    h_tx_master / h_rx_master: [n][30] or NULL = that direction keeps what it had; h_rx_roc: [n] initial rollover
+ *                    counters or NULL = 0; a call that sets a stream's rx key resets its receive record to "none yet" with that counter.
+ *                    -1, nothing changed: NULL r or list; n <= 0, an index outside [0, n_streams) or listed twice; tag_bytes other
+ *                    than 4 or 10; both masters NULL; a tx key while the session's trailer is smaller than tag_bytes
+ *   solo_srtp_clear_keys  both keys and the receive record of the listed streams go (zeroed on the device).  solo_rtp_unbind does the
+ *                    same for its streams: a slot taken by the next call never inherits them; solo_rtp_destroy zeroes all records
+ *   solo_srtp_get_rx_index  h_index[i] = the highest authenticated index (ROC << 16 | SEQ) of listed stream i, -1: none yet.  With
+ *                    solo_srtp_set_keys' h_rx_roc this is the hand-over of a receiver to another session
+ * solo_srtp_protect -- datagram k belongs to record k; the records of the call are min(d_send_count->records, max_records), read on the
+ *   device as in pack; d_send_count->records < 0: d_count->ok = -1, no datagram is touched.  d_dgrams[k].len == 0 (refused by pack, or
+ *   cut): skipped.  The stream has no tx key: d_dgrams[k] becomes {0, 0}, counted no_key -- NOTHING OF A SESSION'S LEAVES IN THE CLEAR
+ *   THROUGH THIS CALL.  Otherwise the packet index is i = seq_offset + 2 seq + desc, the unreduced integer behind pack's sequence number,
+ *   ROC = (i >> 16) mod 2^32 (the sender keeps no state: protect is a pure function like pack); IV = (k_s << 16) ^ (SSRC << 64) ^
+ *   (i << 16); keystream block j = AES(k_e, IV + j), XORed over the bytes behind the header; tag = the first tag_bytes of
+ *   HMAC-SHA1(k_a, header || ciphertext || ROC as 4 big-endian bytes), written at [len, len + tag_bytes): pack's trailer is its room;
+ *   d_dgrams[k].len += tag_bytes.  malformed, voided like no_key: a datagram whose range or tag reaches past wire_bytes, shorter than 12
+ *   bytes or whose header reaches past its end, or a record whose stream, seq or desc pack would refuse.
+ *   -1 with nothing enqueued: a NULL pointer; max_records <= 0; wire_bytes < 0; d_records, d_send_count, d_dgrams or d_count not 4-byte
+ *   aligned.  Two kernels (the clear of the count, a workgroup per 256 datagrams) on hip_stream, no allocation, no host synchronisation:
+ *   capturable with max_records frozen.
+ * solo_srtp_unprotect -- n_dgrams datagrams inside d_wire at any byte alignment, their ranges disjoint.  The verdict is the FIRST rule that
+ *   fails: malformed (a range outside [0, min(wire_bytes, 2^31 - 1)); len < 12 + tag; 12 + 4 CC or the extension block reaching past
+ *   len - tag; tag = that of the stream's rx key, and 4 where the SSRC or the key is not known), unknown_ssrc (the table search of
+ *   parse), no_key, auth_failed.  AUTHENTICATE FIRST: only an accepted datagram is decrypted, d_dgrams_out[i] = {offset, len - tag},
+ *   ready for solo_rtp_parse (d_dgrams_out may be d_dgrams); a rejected datagram leaves every wire byte as it was and yields {0, 0},
+ *   which parse counts as malformed and the ring as bad.  The rollover counter is estimated by RFC 3711 section 3.3.1 / appendix A
+ *   against the stream's receive record as it stood when the call began (none yet: the initial counter; s_l < 32768: ROC - 1 when
+ *   SEQ - s_l > 32768; s_l >= 32768: ROC + 1 when s_l - 32768 > SEQ), index = v << 16 | SEQ; behind the verdicts a second short kernel
+ *   raises each stream's record to the highest index the call accepted.  The result does not depend on the order inside the call and
+ *   equals the RFC's packet-by-packet receiver unless one call holds datagrams of a stream more than 2^15 sequence numbers apart.
+ *   THERE IS NO REPLAY LIST: a replayed datagram reaches the ring, which drops it as duplicate or late.
+ *   -1 with nothing enqueued: NULL r or d_count; n_dgrams < 0 or wire_bytes < 0; with n_dgrams > 0 a NULL d_dgrams, d_wire or
+ *   d_dgrams_out; d_dgrams, d_dgrams_out or d_count not 4-byte aligned.  Three kernels on hip_stream, no allocation, no host
+ *   synchronisation: capturable with n_dgrams frozen.  Not built: SRTCP, MKI, RFC 6904, AES-GCM, AES-256. */
+#define SOLO_SRTP_MASTER_BYTES 30   /* master key (16) || master salt (14): one direction's SDES / DTLS-SRTP keying material */
+typedef struct { int32_t ok, skipped, malformed, unknown_ssrc, no_key, auth_failed, reserved[2]; } solo_srtp_count_t;   /* 32 bytes */
+/* The trailer switch and the key calls of the session, then its two SRTP device calls. */
+int32_t solo_rtp_set_trailer(solo_rtp_t *r, int32_t trailer_bytes);
+int32_t solo_srtp_set_keys(solo_rtp_t *r, const int32_t *h_streams, int32_t n, const uint8_t *h_tx_master, const uint8_t *h_rx_master,
+                           const uint32_t *h_rx_roc, int32_t tag_bytes, void *hip_stream);
+int32_t solo_srtp_clear_keys(solo_rtp_t *r, const int32_t *h_streams, int32_t n, void *hip_stream);
+int32_t solo_srtp_get_rx_index(solo_rtp_t *r, const int32_t *h_streams, int32_t n, int64_t *h_index, void *hip_stream);
+int32_t solo_srtp_protect(solo_rtp_t *r, const solo_arrival_t *d_records, const solo_send_count_t *d_send_count, int32_t max_records,
+                          solo_dgram_t *d_dgrams, uint8_t *d_wire, int64_t wire_bytes, solo_srtp_count_t *d_count, void *hip_stream);
+int32_t solo_srtp_unprotect(solo_rtp_t *r, const solo_dgram_t *d_dgrams, int32_t n_dgrams, uint8_t *d_wire, int64_t wire_bytes,
+                            solo_dgram_t *d_dgrams_out, solo_srtp_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "solo_playout_set_state", "solo_playout_plan", "solo_playout_gather", "solo_playout_render", "solo_playout_tick",
     "solo_agc_create", "solo_agc_destroy", "solo_agc_reset", "solo_agc_reset_rows", "solo_agc_get_state", "solo_agc_set_state", "solo_agc",
     "solo_rtp_create", "solo_rtp_destroy", "solo_rtp_bind", "solo_rtp_unbind", "solo_rtp_pack", "solo_rtp_parse",
+    "solo_rtp_set_trailer", "solo_srtp_set_keys", "solo_srtp_clear_keys", "solo_srtp_get_rx_index", "solo_srtp_protect", "solo_srtp_unprotect",
 ]
 
 
@@ -161,6 +162,13 @@ class solo_rtp_parse_count_t(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("accepted", "with_level", "malformed", "version", "unknown_ssrc", "unknown_pt", "timestamp", "reserved")]
 
 
+class solo_srtp_count_t(C.Structure):
+    """datagrams per verdict of a solo_srtp_protect / solo_srtp_unprotect call (include/solo_mi355x.h); 32 bytes; ok = -1: the list behind
+    protect's records was refused"""
+    _fields_ = [(n, C.c_int32) for n in ("ok", "skipped", "malformed", "unknown_ssrc", "no_key", "auth_failed", "reserved0", "reserved1")]
+
+
+SRTP_MASTER_BYTES = 30
 RECV_REPORT_CLEAR_MARGIN = 1
 
 _lib = None
@@ -310,6 +318,18 @@ def load_library():
                                   C.c_void_p, C.c_void_p]
     lib.solo_rtp_parse.restype = C.c_int32
     lib.solo_rtp_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_rtp_set_trailer.restype = C.c_int32
+    lib.solo_rtp_set_trailer.argtypes = [C.c_void_p, C.c_int32]
+    lib.solo_srtp_set_keys.restype = C.c_int32
+    lib.solo_srtp_set_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_srtp_clear_keys.restype = C.c_int32
+    lib.solo_srtp_clear_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_srtp_get_rx_index.restype = C.c_int32
+    lib.solo_srtp_get_rx_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.solo_srtp_protect.restype = C.c_int32
+    lib.solo_srtp_protect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.solo_srtp_unprotect.restype = C.c_int32
+    lib.solo_srtp_unprotect.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1149,11 +1169,12 @@ class _RowObject:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
 
-    def _call(self, name, *args):
+    def _call(self, name, *args, prefix=None):
         """solo_<PREFIX>_<name>(object, *args, stream); a refusal raises"""
-        r = getattr(self.lib, "solo_%s_%s" % (self.PREFIX, name))(self.h, *args, self._stream())
+        prefix = prefix or self.PREFIX
+        r = getattr(self.lib, "solo_%s_%s" % (prefix, name))(self.h, *args, self._stream())
         if r:
-            raise RuntimeError("solo_%s_%s -> %d" % (self.PREFIX, name, r))
+            raise RuntimeError("solo_%s_%s -> %d" % (prefix, name, r))
 
     def _rows(self, rows, n=None):
         """None, or the list as a contiguous int32 CUDA tensor (a host sequence is checked here and copied)"""
@@ -1587,6 +1608,7 @@ class Rtp(_RowObject):
         self.n_rows = self.n_streams = int(n_streams)
         self.packet_samples = int(packet_samples)
         self.level_id = 0
+        self.trailer = 0
         if self.n_streams <= 0 or self.packet_samples not in (320, 640, 1280):
             raise ValueError("n_streams must be positive, packet_samples 320, 640 or 1280")
         self._create(self.n_streams, self.packet_samples)
@@ -1656,7 +1678,7 @@ class Rtp(_RowObject):
         if dgrams is None:
             dgrams = t.zeros((m, 2), dtype=t.int32, device=records.device)
         if wire is None:
-            wire = t.zeros((nbytes + 23 * m,), dtype=t.uint8, device=records.device)
+            wire = t.zeros((nbytes + (23 + getattr(self, "trailer", 0)) * m,), dtype=t.uint8, device=records.device)
         count = t.zeros((8,), dtype=t.int32, device=records.device)
         # (an empty tensor has no address: a cap of 0 only counts, the pointer is never used -- the library still wants one)
         self._call("pack", records.data_ptr(), send_count.data_ptr(), m, payload.data_ptr() or count.data_ptr(), nbytes, _ptr(level), depth,
@@ -1692,6 +1714,95 @@ class Rtp(_RowObject):
         if r:
             raise RuntimeError("solo_rtp_parse -> %d" % r)
         return arrivals, outs[0], outs[1], count
+
+    # ---- SRTP (solo_srtp_*): keys per stream, protect() behind pack(), unprotect() in front of parse() ----
+    def set_trailer(self, trailer_bytes):
+        """bytes pack() keeps free (and zero) behind every datagram: the room of the SRTP tag, 0 .. 16; dgrams[k].len stays the RTP
+        packet's, the offsets and byte counts include the trailer.  Read by the next pack()."""
+        trailer_bytes = int(trailer_bytes)
+        if not 0 <= trailer_bytes <= 16:
+            raise ValueError("trailer_bytes: 0 .. 16")
+        r = self.lib.solo_rtp_set_trailer(self.h, trailer_bytes)
+        if r:
+            raise RuntimeError("solo_rtp_set_trailer -> %d" % r)
+        self.trailer = trailer_bytes
+
+    @staticmethod
+    def _masters(name, v, n):
+        """None, or n x 30 bytes of keying material (bytes, a sequence of bytes objects, or a uint8 array [n,30]) -> ctypes array"""
+        if v is None:
+            return None
+        try:
+            raw = bytes(v) if isinstance(v, (bytes, bytearray)) else v.tobytes() if hasattr(v, "tobytes") else b"".join(bytes(x) for x in v)
+        except (TypeError, ValueError):
+            raw = b""
+        if len(raw) != SRTP_MASTER_BYTES * n:
+            raise ValueError("%s: %d x %d bytes (master key || master salt per listed stream) or None" % (name, n, SRTP_MASTER_BYTES))
+        return (C.c_uint8 * len(raw)).from_buffer_copy(raw)
+
+    def set_keys(self, streams, tx=None, rx=None, rx_roc=None, tag_bytes=10):
+        """SRTP keys of the listed streams (a host sequence inside [0, n_streams), none twice): tx / rx = 30 bytes of keying material per
+        listed stream (master key || master salt, as SDES or DTLS-SRTP give them) or None = that direction keeps what it had; rx_roc: the
+        receiver's initial rollover counter, a scalar or one per listed stream; tag_bytes 10 or 4.  A tx key needs a trailer of at least
+        tag_bytes (set_trailer).  Setting an rx key resets the stream's receive index.  Ordered on the current stream; synchronises; not
+        capturable."""
+        idx = _distinct("streams", streams, self.n_streams)
+        n = len(idx)
+        txa, rxa = self._masters("tx", tx, n), self._masters("rx", rx, n)
+        tag_bytes = int(tag_bytes)
+        if tag_bytes not in (4, 10) or (txa is None and rxa is None):
+            raise ValueError("tag_bytes: 10 or 4; at least one of tx and rx")
+        if txa is not None and self.trailer < tag_bytes:
+            raise ValueError("a tx key needs set_trailer(%d) or more first" % tag_bytes)
+        roc = None if rx_roc is None else (C.c_uint32 * n)(*self._per_stream(rx_roc, n, "rx_roc", 2 ** 32 - 1))
+        self._call("set_keys", (C.c_int32 * n)(*idx), n, txa, rxa, roc, tag_bytes, prefix="srtp")
+
+    def clear_keys(self, streams):
+        """both keys and the receive index of the listed streams go; unbind() does the same"""
+        idx = _distinct("streams", streams, self.n_streams)
+        self._call("clear_keys", (C.c_int32 * len(idx))(*idx), len(idx), prefix="srtp")
+
+    def rx_index(self, streams=None):
+        """the highest authenticated packet index (ROC << 16 | SEQ) of the listed streams (None: all), -1 = none yet (synchronises)"""
+        idx = list(range(self.n_streams)) if streams is None else _distinct("streams", streams, self.n_streams)
+        out = (C.c_int64 * len(idx))()
+        self._call("get_rx_index", (C.c_int32 * len(idx))(*idx), len(idx), out, prefix="srtp")
+        return list(out)
+
+    def protect(self, records, send_count, dgrams, wire):
+        """behind pack(records, send_count, ...) -> (dgrams, wire, count): the datagrams of pack() become SRTP in place (the payload
+        encrypted, the tag in the trailer, dgrams[k].len grown by the tag); a datagram of a stream without a tx key becomes (0, 0) and is
+        counted no_key -> count int32 [8] on the device, read with srtp_count().  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        m, _ = _tensor("records", records, t.int32, (None, 5))
+        _tensor("send_count", send_count, t.int32, (8,))
+        _tensor("dgrams", dgrams, t.int32, (m, 2))
+        nbytes, = _tensor("wire", wire, t.uint8, (None,))
+        if m < 1:
+            raise ValueError("records: at least one")
+        count = t.zeros((8,), dtype=t.int32, device=records.device)
+        self._call("protect", records.data_ptr(), send_count.data_ptr(), m, dgrams.data_ptr(), wire.data_ptr() or count.data_ptr(), nbytes, count.data_ptr(),
+                   prefix="srtp")
+        return count
+
+    def unprotect(self, dgrams, wire, dgrams_out=None):
+        """in front of parse(): dgrams int32 [n,2] of received SRTP datagrams inside wire -> (dgrams_out int32 [n,2] for parse(): the RTP
+        packet of an accepted datagram, decrypted in place, (0, 0) for a rejected one, whose bytes stay as they were; count int32 [8] on
+        the device, read with srtp_count()).  dgrams_out may be dgrams.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        n, _ = _tensor("dgrams", dgrams, t.int32, (None, 2))
+        nbytes, = _tensor("wire", wire, t.uint8, (None,))
+        _tensor("dgrams_out", dgrams_out, t.int32, (n, 2), optional=True)
+        if dgrams_out is None:
+            dgrams_out = t.zeros((n, 2), dtype=t.int32, device=dgrams.device)
+        count = t.zeros((8,), dtype=t.int32, device=dgrams.device)
+        self._call("unprotect", dgrams.data_ptr() or count.data_ptr(), n, wire.data_ptr() or count.data_ptr(), nbytes,
+                   dgrams_out.data_ptr() or count.data_ptr(), count.data_ptr(), prefix="srtp")
+        return dgrams_out, count
+
+    def srtp_count(self, count):
+        """the count tensor of protect() / unprotect() as a dict (synchronises); ok == -1: the list behind protect's records was refused"""
+        return _counts(solo_srtp_count_t, count)
 
     def pack_count(self, count):
         """the count tensor of pack() as a dict (synchronises); dgrams == -1: the list behind the records was refused on the device"""

@@ -40,6 +40,7 @@
 #include "solo_playout.h"       // adaptive play-out delay control (solo_playout_plan / _render / _tick): likewise
 #include "solo_agc.h"           // level control and peak limiter of decoded rows (solo_agc): likewise
 #include "solo_rows.h"          // the record kernels of those four objects (reset, listed reset, state copy): likewise
+#include "solo_srtp.h"          // SRTP protection of the datagrams of solo_rtp.h (solo_srtp_protect / _unprotect): likewise
 #include "solo_rtp.h"           // RTP framing of the sender's records and parsing of received datagrams (solo_rtp_pack / _parse): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
@@ -1218,6 +1219,11 @@ struct solo_rtp_obj : solo_rows {    // d_state: SxRtpStream [n_rows]
     uint32_t* d_table;               // SX_RTP_TABLE_HEAD + 2 x n_rows words
     void* d_scratch;                 // tile bases and tile totals of a solo_rtp_pack call, grown on demand
     size_t scratch_bytes;
+    int32_t trailer;                 // solo_rtp_set_trailer
+    // SRTP (solo_srtp.h): allocated by the first solo_srtp_set_keys.  The mirror holds tag lengths, never keys
+    SxSrtpKey* d_keys;               // [n_rows][2]: tx, rx
+    SxSrtpRx* d_rx;                  // [n_rows]
+    SxSrtpMirror srtp;
 };
 solo_rtp_t* solo_rtp_create(int32_t n_streams, int32_t packet_samples) {
     if (n_streams <= 0 || (packet_samples != 320 && packet_samples != 640 && packet_samples != 1280) || !have_device()) return NULL;
@@ -1236,6 +1242,12 @@ solo_rtp_t* solo_rtp_create(int32_t n_streams, int32_t packet_samples) {
 }
 void solo_rtp_destroy(solo_rtp_t* r) {
     if (!r) return;
+    if (r->d_keys) {                 // no key outlives the session in freed memory
+        (void)hipMemset(r->d_keys, 0, 2 * (size_t)r->n_rows * sizeof(SxSrtpKey));
+        (void)hipDeviceSynchronize();
+    }
+    dev_free(r->d_keys);
+    dev_free(r->d_rx);
     rows_free(r);
     dev_free(r->d_table);
     dev_free(r->d_scratch);
@@ -1261,11 +1273,23 @@ int32_t solo_rtp_bind(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const 
     if (e == 0) r->mirror.cfg.swap(next.cfg), r->mirror.level_id = next.level_id;      // (only what the device now holds)
     return e;
 }
+// keys and receive records of the listed (validated) streams -> none; enqueued, the caller synchronises
+static int32_t srtp_clear(solo_rtp_obj* r, const int32_t* h_streams, int32_t n, hipStream_t st) {
+    if (!r->d_keys) return 0;
+    for (int32_t i = 0; i < n; i++) {
+        SOLO_CHECK(hipMemsetAsync(r->d_keys + 2 * (size_t)h_streams[i], 0, 2 * sizeof(SxSrtpKey), st));
+        SOLO_CHECK(hipMemsetAsync(r->d_rx + h_streams[i], 0xFF, sizeof(i64), st));                                  // index = -1
+        SOLO_CHECK(hipMemsetAsync((uint8_t*)(r->d_rx + h_streams[i]) + sizeof(i64), 0, sizeof(SxSrtpRx) - sizeof(i64), st));
+        r->srtp.tx_tag[(size_t)h_streams[i]] = 0; r->srtp.rx_tag[(size_t)h_streams[i]] = 0;
+    }
+    return 0;
+}
 int32_t solo_rtp_unbind(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
     std::vector<u32> table;
     SxRtpMirror next;
     if (!r || !sx_rtp_unbind_plan(r->mirror, h_streams, n, next, table)) return -1;
     int32_t e = rows_reset_list(r, h_streams, n, (hipStream_t)hip_stream);
+    if (e == 0) e = srtp_clear(r, h_streams, n, (hipStream_t)hip_stream);             // (a slot taken by the next bind inherits no key)
     if (e == 0) e = rtp_upload_table(r, table, (hipStream_t)hip_stream);
     if (e == 0) r->mirror.cfg.swap(next.cfg);
     return e;
@@ -1281,7 +1305,7 @@ int32_t solo_rtp_pack(solo_rtp_t* r, const solo_arrival_t* d_records, const solo
     SxRtpPackArgs a;
     a.records = d_records; a.send_count = d_send_count; a.payload = d_payload; a.level = d_level;
     a.cfg = (const SxRtpStream*)r->d_state; a.table = r->d_table; a.payload_bytes = payload_bytes;
-    a.max_records = max_records; a.n_streams = r->n_rows; a.level_depth = level_depth; a.packet_samples = r->L;
+    a.max_records = max_records; a.n_streams = r->n_rows; a.level_depth = level_depth; a.packet_samples = r->L; a.trailer = r->trailer;
     SOLO_CHECK(solo_rtp_pack_launch(a, r->d_scratch, d_dgrams, d_wire, (long long)wire_capacity, d_count, st));
     return 0;
 }
@@ -1295,6 +1319,83 @@ int32_t solo_rtp_parse(solo_rtp_t* r, solo_batch_t* b, const solo_dgram_t* d_dgr
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n_dgrams = n_dgrams; a.n_streams = r->n_rows; a.packet_samples = r->L;
     SOLO_CHECK(solo_rtp_parse_launch(a, d_arrivals, d_level_out, d_rtp_seq_out, d_count, (hipStream_t)hip_stream));
+    return 0;
+}
+
+// ---- SRTP (solo_srtp.h): the session's keys, then protect behind pack and unprotect in front of parse -----------------------------------
+int32_t solo_rtp_set_trailer(solo_rtp_t* r, int32_t trailer_bytes) {
+    if (!r || !sx_srtp_trailer_ok(r->srtp, trailer_bytes)) return -1;
+    r->trailer = trailer_bytes;
+    return 0;
+}
+int32_t solo_srtp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_rx_roc,
+                           int32_t tag_bytes, void* hip_stream) {
+    std::vector<SxSrtpKey> recs;
+    std::vector<SxSrtpRx> rx;
+    SxSrtpMirror next;
+    if (!r || !sx_srtp_set_keys_plan(r->srtp, r->n_rows, r->trailer, h_streams, n, h_tx_master, h_rx_master, h_rx_roc, tag_bytes, next, recs, rx)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!r->d_keys) {                // the first call: every record "no key", every receive record "none yet"
+        const size_t kb = 2 * (size_t)r->n_rows * sizeof(SxSrtpKey);
+        std::vector<SxSrtpRx> none((size_t)r->n_rows);
+        for (SxSrtpRx& x : none) { x.index = -1; x.pending = 0; x.roc0 = 0; x.pad[0] = x.pad[1] = x.pad[2] = 0; }
+        if (hipMalloc((void**)&r->d_keys, kb) != hipSuccess || hipMalloc((void**)&r->d_rx, none.size() * sizeof(SxSrtpRx)) != hipSuccess ||
+            hipMemset(r->d_keys, 0, kb) != hipSuccess || hipMemcpy(r->d_rx, none.data(), none.size() * sizeof(SxSrtpRx), hipMemcpyHostToDevice) != hipSuccess) {
+            dev_free(r->d_keys);
+            dev_free(r->d_rx);
+            sx_srtp_wipe(recs);
+            return -2;
+        }
+        r->srtp.tx_tag.assign((size_t)r->n_rows, 0); r->srtp.rx_tag.assign((size_t)r->n_rows, 0);
+    }
+    hipError_t e = hipSuccess;
+    for (int32_t i = 0; i < n && e == hipSuccess; i++) {
+        SxSrtpKey* d = r->d_keys + 2 * (size_t)h_streams[i];
+        if (h_tx_master) e = hipMemcpyAsync(d, &recs[2 * (size_t)i], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(d + 1, &recs[2 * (size_t)i + 1], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(r->d_rx + h_streams[i], &rx[(size_t)i], sizeof(SxSrtpRx), hipMemcpyHostToDevice, st);
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);         // (the host records go with this call: the copies must have read them)
+    sx_srtp_wipe(recs);
+    if (e != hipSuccess || e2 != hipSuccess) return -(int32_t)(e != hipSuccess ? e : e2);
+    r->srtp.tx_tag.swap(next.tx_tag); r->srtp.rx_tag.swap(next.rx_tag);
+    return 0;
+}
+int32_t solo_srtp_clear_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
+    if (!r || !sx_list_ok(h_streams, n, r->n_rows)) return -1;
+    const int32_t e = srtp_clear(r, h_streams, n, (hipStream_t)hip_stream);
+    SOLO_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
+    return e;
+}
+int32_t solo_srtp_get_rx_index(solo_rtp_t* r, const int32_t* h_streams, int32_t n, int64_t* h_index, void* hip_stream) {
+    if (!r || !h_index || !sx_list_ok(h_streams, n, r->n_rows)) return -1;
+    for (int32_t i = 0; i < n; i++) h_index[i] = -1;
+    if (!r->d_rx) return 0;
+    hipStream_t st = (hipStream_t)hip_stream;
+    for (int32_t i = 0; i < n; i++) SOLO_CHECK(hipMemcpyAsync(&h_index[i], &r->d_rx[h_streams[i]].index, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    SOLO_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+int32_t solo_srtp_protect(solo_rtp_t* r, const solo_arrival_t* d_records, const solo_send_count_t* d_send_count, int32_t max_records, solo_dgram_t* d_dgrams,
+                          uint8_t* d_wire, int64_t wire_bytes, solo_srtp_count_t* d_count, void* hip_stream) {
+    if (!r || !d_records || !d_send_count || !d_dgrams || !d_wire || !d_count || max_records <= 0 || wire_bytes < 0) return -1;
+    if (((uintptr_t)d_records | (uintptr_t)d_send_count | (uintptr_t)d_dgrams | (uintptr_t)d_count) & 3) return -1;
+    SxSrtpProtectArgs a;
+    a.records = d_records; a.send_count = d_send_count; a.dgrams = d_dgrams; a.wire = d_wire; a.cfg = (const SxRtpStream*)r->d_state; a.keys = r->d_keys;
+    a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
+    a.max_records = max_records; a.n_streams = r->n_rows;
+    SOLO_CHECK(solo_srtp_protect_launch(a, d_count, (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_srtp_unprotect(solo_rtp_t* r, const solo_dgram_t* d_dgrams, int32_t n_dgrams, uint8_t* d_wire, int64_t wire_bytes, solo_dgram_t* d_dgrams_out,
+                            solo_srtp_count_t* d_count, void* hip_stream) {
+    if (!r || n_dgrams < 0 || wire_bytes < 0 || !d_count || (n_dgrams > 0 && (!d_dgrams || !d_wire || !d_dgrams_out))) return -1;
+    if (((uintptr_t)d_dgrams | (uintptr_t)d_dgrams_out | (uintptr_t)d_count) & 3) return -1;
+    SxSrtpUnprotectArgs a;
+    a.dgrams = d_dgrams; a.out = d_dgrams_out; a.wire = d_wire; a.table = r->d_table; a.keys = r->d_keys; a.rx = r->d_rx;
+    a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
+    a.n_dgrams = n_dgrams; a.n_streams = r->n_rows;
+    SOLO_CHECK(solo_srtp_unprotect_launch(a, d_count, (hipStream_t)hip_stream));
     return 0;
 }
 

@@ -9,7 +9,8 @@
 // pure functions of their inputs.
 //
 // Pack: datagram k belongs to record k.  Offsets of the pool may repeat (fanout stores a source datagram once), so the wire offsets are
-// a prefix sum of roundup4(H + len) over the valid records, H = 12 or 20: three short launches, as in solo_send.h, none of which waits
+// a prefix sum of roundup4(H + len + T) over the valid records, H = 12 or 20, T the session's trailer (solo_rtp_set_trailer: room for the
+// SRTP tag of solo_srtp.h, written as zero; 0 unless asked for): three short launches, as in solo_send.h, none of which waits
 // for another workgroup:
 //     1. totals   one workgroup per tile of SX_RTP_TILE records (a lane per record): {valid, refused} and padded bytes of the tile
 //     2. scan     ONE wavefront walks the tile totals 64 at a time (wv_scan_incl) -> every tile's first wire offset, the call's counts
@@ -106,6 +107,7 @@ struct SxRtpPackArgs {
     const SxSendRecord* records; const SxSendCount* send_count; const u8* payload; const u8* level; const SxRtpStream* cfg; const u32* table;
     i64 payload_bytes;
     int max_records, n_streams, level_depth, packet_samples;
+    int trailer = 0;                                        // bytes kept free behind every datagram (solo_rtp_set_trailer: the SRTP tag's room), written as zero
 };
 struct SxRtpRun { i32 src, dst, len; u32 w0, ts, ssrc, ext, pad; };   // one datagram of pass 3: payload[src ..) -> wire[dst + H ..), the header's words
 static_assert(sizeof(SxRtpRun) == 32, "a run in LDS");
@@ -113,6 +115,8 @@ static_assert(sizeof(SxRtpRun) == 32, "a run in LDS");
 // records of the call, read on the device: < 0 = the list behind the records was refused
 SX_HD i32 sx_rtp_n_records(const SxRtpPackArgs& a) { return sx_min(a.send_count->records, a.max_records); }
 SX_HD int sx_rtp_header_bytes(const SxRtpPackArgs& a) { return a.level ? 20 : 12; }
+// what a datagram of wlen bytes takes of the wire: itself, the trailer and the pad bytes up to a multiple of 4 (0 for a refused record)
+SX_HD i32 sx_rtp_padded(const SxRtpPackArgs& a, i32 wlen) { return wlen > 0 ? sx_rtp_roundup4(wlen + a.trailer) : 0; }
 
 // THE record rule: record k -> bytes of its datagram, header included (0: refused; its payload is never read), and where asked for the
 // header's words as they are stored (little-endian dwords of the big-endian fields)
@@ -126,7 +130,8 @@ SX_HD i32 sx_rtp_pack_plan(const SxRtpPackArgs& a, int k, SxRtpRun* run) {
     if (run) {
         const u32 pt = (c.seq_pt >> (16 + 8 * r.desc)) & 127u;
         const u32 seq = (c.seq_pt + 2u * (u32)r.seq + (u32)r.desc) & 0xFFFFu;
-        run->src = r.offset; run->len = r.len; run->dst = 0; run->pad = 0;
+        run->src = r.offset; run->len = r.len; run->dst = 0;
+        run->pad = (u32)(sx_rtp_padded(a, sx_rtp_header_bytes(a) + r.len) - sx_rtp_header_bytes(a) - r.len);    // trailer and pad bytes
         run->w0 = (a.level ? 0x90u : 0x80u) | (pt << 8) | ((seq >> 8) << 16) | ((seq & 255u) << 24);
         run->ts = sx_rtp_bswap(c.ts_offset + (u32)r.seq * (u32)a.packet_samples);
         run->ssrc = sx_rtp_bswap(c.ssrc);
@@ -137,15 +142,16 @@ SX_HD i32 sx_rtp_pack_plan(const SxRtpPackArgs& a, int k, SxRtpRun* run) {
 // what a record adds to the tile totals: valid | refused << 10 (each at most SX_RTP_TILE per tile)
 SX_HD i32 sx_rtp_pack_counts(i32 wlen) { return wlen > 0 ? 1 : (1 << 10); }
 
-// a datagram of `wlen` bytes at wire offset `off` is written iff it and the pad bytes behind it end inside cap (<= 2^31 - 1).  The
-// offsets grow along the order, so what is written is a prefix.  d_dgrams[k] is written either way: {0, 0} for a datagram that is not
-SX_HD bool sx_rtp_pack_emit(SxRtpDgram* dgrams, int k, i32 wlen, i64 off, i64 cap) {
-    const bool w = wlen > 0 && off + (i64)sx_rtp_roundup4(wlen) <= cap;
+// a datagram of `wlen` bytes (`padded` with its trailer and pad bytes) at wire offset `off` is written iff all of that ends inside cap
+// (<= 2^31 - 1).  The offsets grow along the order, so what is written is a prefix.  d_dgrams[k] is written either way: {0, 0} for a
+// datagram that is not; its len is wlen, the RTP packet without the trailer
+SX_HD bool sx_rtp_pack_emit(SxRtpDgram* dgrams, int k, i32 wlen, i32 padded, i64 off, i64 cap) {
+    const bool w = wlen > 0 && off + (i64)padded <= cap;
     SxRtpDgram d; d.offset = w ? (i32)off : 0; d.len = w ? wlen : 0;
     dgrams[k] = d;
     return w;
 }
-// the bytes of one datagram by `nlanes` lanes, this one being `lane`: header dwords, payload, zero pad (dst is dword-aligned)
+// the bytes of one datagram by `nlanes` lanes, this one being `lane`: header dwords, payload, zero trailer and pad (dst is dword-aligned)
 SX_HD void sx_rtp_write(u8* dst, const u8* payload, const SxRtpRun& r, int H, int lane, int nlanes) {
     u32* d32 = (u32*)dst;
     if (lane == 0) d32[0] = r.w0;
@@ -157,7 +163,7 @@ SX_HD void sx_rtp_write(u8* dst, const u8* payload, const SxRtpRun& r, int H, in
     }
     sx_send_copy(dst + H, payload + r.src, r.len, lane, nlanes);
     const int end = H + r.len;
-    if (lane < sx_rtp_roundup4(end) - end) dst[end + lane] = 0;
+    for (int i = lane; i < (int)r.pad; i += nlanes) dst[end + i] = 0;
 }
 
 struct SxRtpBase { i64 bytes; };                            // where a tile's output starts
@@ -173,13 +179,13 @@ __global__ void __launch_bounds__(SX_RTP_TILE) solo_rtp_totals_kernel(const SxRt
     if (k < n) {
         const i32 wlen = sx_rtp_pack_plan(a, k, NULL);
         cnt = sx_rtp_pack_counts(wlen);
-        bytes = sx_rtp_roundup4(wlen);
+        bytes = sx_rtp_padded(a, wlen);
     }
     cnt = wg_sum(cnt, red);
     bytes = wg_sum(bytes, red);
     if (threadIdx.x == 0) { totals[blockIdx.x * 2 + 0] = cnt; totals[blockIdx.x * 2 + 1] = bytes; }
 }
-// pass 2: one wavefront; a tile holds at most 256 x 32788 bytes, so 64 of them scan in 32 bits and the running base is carried in 64
+// pass 2: one wavefront; a tile holds at most 256 x 32804 bytes, so 64 of them scan in 32 bits and the running base is carried in 64
 __global__ void __launch_bounds__(64) solo_rtp_scan_kernel(const SxRtpPackArgs a, const i32* __restrict__ totals, SxRtpBase* __restrict__ bases, int n_tiles,
                                                            SxRtpPackCount* count) {
     if (sx_rtp_n_records(a) < 0) {
@@ -215,12 +221,12 @@ __global__ void __launch_bounds__(SX_RTP_TILE) solo_rtp_scatter_kernel(const SxR
     run.src = 0; run.dst = 0; run.len = 0; run.w0 = 0; run.ts = 0; run.ssrc = 0; run.ext = 0; run.pad = 0;
     i32 wlen = 0;
     if (k < n) wlen = sx_rtp_pack_plan(a, k, &run);
-    const i32 bytes = sx_rtp_roundup4(wlen);
+    const i32 bytes = sx_rtp_padded(a, wlen);
     const i32 ibytes = wg_scan_incl(bytes, part);
     bool written = false;
     if (k < n) {
         const i64 off = bases[blockIdx.x].bytes + (i64)(ibytes - bytes);
-        written = sx_rtp_pack_emit(dgrams, k, wlen, off, cap);
+        written = sx_rtp_pack_emit(dgrams, k, wlen, bytes, off, cap);
         run.dst = (i32)off;
     }
     if (!written) run.len = 0;
@@ -267,7 +273,7 @@ static inline void sx_rtp_pack_host(const SxRtpPackArgs& a, SxRtpDgram* dgrams, 
         for (int k = t * SX_RTP_TILE; k < n && k < (t + 1) * SX_RTP_TILE; k++) {
             const i32 wlen = sx_rtp_pack_plan(a, k, NULL);
             cnt += sx_rtp_pack_counts(wlen);
-            bytes += sx_rtp_roundup4(wlen);
+            bytes += sx_rtp_padded(a, wlen);
         }
         totals[t * 2 + 0] = cnt; totals[t * 2 + 1] = bytes;
     }
@@ -281,11 +287,11 @@ static inline void sx_rtp_pack_host(const SxRtpPackArgs& a, SxRtpDgram* dgrams, 
         for (int k = t * SX_RTP_TILE; k < n && k < (t + 1) * SX_RTP_TILE; k++) {
             SxRtpRun run;
             const i32 wlen = sx_rtp_pack_plan(a, k, &run);
-            if (sx_rtp_pack_emit(dgrams, k, wlen, off, cap)) {
+            if (sx_rtp_pack_emit(dgrams, k, wlen, sx_rtp_padded(a, wlen), off, cap)) {
                 for (int lane = 0; lane < SX_RTP_ROW; lane++) sx_rtp_write(wire + off, a.payload, run, H, lane, SX_RTP_ROW);
-                c.dgrams++; c.bytes += sx_rtp_roundup4(wlen);
+                c.dgrams++; c.bytes += sx_rtp_padded(a, wlen);
             }
-            off += sx_rtp_roundup4(wlen);
+            off += sx_rtp_padded(a, wlen);
         }
     }
     *count = c;
@@ -343,26 +349,37 @@ SX_HD SxRtpParsed sx_rtp_rejected(i32 verdict) {
     o.verdict = verdict; o.level = 255u; o.rtp_seq = 0;
     return o;
 }
+// THE header walk, shared by parse and by both SRTP calls (solo_srtp.h): the datagram [lo, lo + len), len >= 12 -> bytes in front of the
+// payload (12 + 4 CC, and with X set the extension block: 4 + 4 x its length), or -1 where that reaches past len.  w0: the first header
+// word; ext_at / ext_len / profile: the extension block's body (0 without X)
+struct SxRtpHead { u32 w0, profile; i32 ext_at, ext_len; };
+SX_HD i32 sx_rtp_header_walk(const u8* lo, i32 len, SxRtpHead* h) {
+    const u8* hi = lo + len;
+    h->w0 = sx_rtp_be32(lo, lo, hi); h->profile = 0; h->ext_at = 0; h->ext_len = 0;
+    i32 hdr = 12 + 4 * (i32)((h->w0 >> 24) & 15u);
+    if (hdr > len) return -1;
+    if ((h->w0 >> 28) & 1u) {
+        if (hdr + 4 > len) return -1;
+        const u32 xw = sx_rtp_be32(lo + hdr, lo, hi);
+        h->profile = xw >> 16;
+        h->ext_at = hdr + 4; h->ext_len = 4 * (i32)(xw & 0xFFFFu);
+        hdr = h->ext_at + h->ext_len;
+        if (hdr > len) return -1;
+    }
+    return hdr;
+}
 // THE datagram rule: datagram i -> its arrival, its verdict (the first rule that fails), its level byte and its raw sequence number
 SX_HD SxRtpParsed sx_rtp_parse_one(const SxRtpParseArgs& a, int i) {
     const SxRtpDgram d = a.dgrams[i];
     if (d.len < 12 || d.offset < 0 || (i64)d.offset + (i64)d.len > a.wire_bytes) return sx_rtp_rejected(SX_RTP_MALFORMED);
     const u8* lo = a.wire + d.offset;
     const u8* hi = lo + d.len;
-    const u32 w0 = sx_rtp_be32(lo, lo, hi);
-    const u32 cc = (w0 >> 24) & 15u;
+    SxRtpHead hd;
+    const i32 hdr = sx_rtp_header_walk(lo, d.len, &hd);
+    if (hdr < 0) return sx_rtp_rejected(SX_RTP_MALFORMED);
+    const u32 w0 = hd.w0, profile = hd.profile;
+    const i32 ext_at = hd.ext_at, ext_len = hd.ext_len;
     const bool has_x = ((w0 >> 28) & 1u) != 0, has_p = ((w0 >> 29) & 1u) != 0;
-    i32 hdr = 12 + 4 * (i32)cc, ext_at = 0, ext_len = 0;
-    u32 profile = 0;
-    if (hdr > d.len) return sx_rtp_rejected(SX_RTP_MALFORMED);
-    if (has_x) {
-        if (hdr + 4 > d.len) return sx_rtp_rejected(SX_RTP_MALFORMED);
-        const u32 xw = sx_rtp_be32(lo + hdr, lo, hi);
-        profile = xw >> 16;
-        ext_at = hdr + 4; ext_len = 4 * (i32)(xw & 0xFFFFu);
-        hdr = ext_at + ext_len;
-        if (hdr > d.len) return sx_rtp_rejected(SX_RTP_MALFORMED);
-    }
     i32 pad = 0;
     if (has_p) {
         pad = (i32)hi[-1];
