@@ -933,6 +933,87 @@ int32_t solo_srtp_protect(solo_rtp_t *r, const solo_arrival_t *d_records, const 
                           solo_dgram_t *d_dgrams, uint8_t *d_wire, int64_t wire_bytes, solo_srtp_count_t *d_count, void *hip_stream);
 int32_t solo_srtp_unprotect(solo_rtp_t *r, const solo_dgram_t *d_dgrams, int32_t n_dgrams, uint8_t *d_wire, int64_t wire_bytes,
                             solo_dgram_t *d_dgrams_out, solo_srtp_count_t *d_count, void *hip_stream);
+/* Forwarding without transcoding: the middle of a forwarding server's tick.  Such a server reads its senders' RFC 6464 levels without
+ * decoding and copies a selected sender to the other members of its room; it has neither decoder nor encoder.  solo_forward_levels turns
+ * the arrivals solo_rtp_parse wrote into one level per row, which solo_vad_select takes; solo_forward_route turns the selected speakers'
+ * arrivals into records for solo_rtp_pack, under per-room slots whose packet numbers stay continuous when the speaker behind a slot
+ * changes.  No payload byte moves: a record's offset and len are the arrival's own and point into the receive buffer, which the egress
+ * solo_rtp_pack is given as its pool.
+ * The wire model: a room has K slots (K = slots, 1 .. 8, normally the max_speakers given to solo_vad_select); a selected speaker holds one
+ * slot of its room for as long as it stays selected.  Every row m of the room receives slot k as egress stream m x K + k, a stream of a
+ * second solo_rtp_t of n_rows x K streams that the caller binds with SSRCs of its own (distinct payload types: the records carry desc
+ * 0 / 1) and, for SRTP, the receivers' keys.  A row does not receive the slot it holds itself.  solo_rtp_pack derives sequence number and
+ * timestamp from the record's packet number, so a slot stays continuous across a change of speaker if the packet number does: that
+ * number is the state this object keeps, 16 bytes {int32 src, delta, start, next} per room and slot.
+ * Object and control plane -- a row-state object like solo_vad_t whose "row" is a ROOM.  solo_forward_create: NULL for n_rows <= 0 or
+ * slots outside 1 .. 8.  solo_forward_reset: every room; solo_forward_reset_rooms: a HOST list, -1 for an index outside [0, n_rows) or
+ * listed twice; a reset leaves {src = -1, delta = 0, start = 0, next = 0} in every slot.  solo_forward_get_state / _set_state: a DEVICE
+ * list of rooms or NULL, uint8 [n][16 x K], as the other row objects.  Lifecycle and state calls come before a capture.
+ * solo_forward_levels -- stateless, needs no object.  An arrival COUNTS when its stream is inside [0, n_rows) and its desc is 0 or 1 (a
+ *   rejected datagram, stream = -1, does not; nor does desc = -1, a sender bound with equal payload types: solo_rtp_pack takes only
+ *   0 / 1).  The byte of a counting arrival i is d_level_in[i] unless that is 255, otherwise default_level unless that is 255 too (255:
+ *   the datagram has no byte); d_level_in NULL: every datagram has default_level.  For row s, over its counting arrivals, d_rowinfo[s] =
+ *   {min_seq, max_seq: the smallest and largest seq, -1, -1 if there is none (an arrival's seq is 0 .. 2^31 - 1); dgrams: their number;
+ *   byte: the byte with the smallest key (byte & 127) << 1 | !(byte >> 7), i.e. the loudest, voiced before unvoiced at equal level, 0x7F
+ *   if no arrival has a byte; level = byte & 127; sa = 255 if byte & 128, else 0; pad = 0}.  d_sa_q8[s] and d_level[s] (uint8 [n_rows])
+ *   receive sa and level: what solo_vad_select takes with n_packets = 1, frames = 1.  Every row is written; the result is a pure
+ *   function of the inputs and independent of the order of the arrivals.
+ *   -1 with nothing enqueued: a NULL output; n_dgrams < 0, or n_dgrams > 0 with NULL d_arrivals; n_rows <= 0; default_level outside
+ *   0 .. 255; d_rowinfo or d_arrivals not 4-byte aligned.  Three short kernels (a clear, a lane per datagram with atomic min / max / add
+ *   on the row's words, a lane per row that turns the winning key into the bytes) on hip_stream, no allocation, no host synchronisation:
+ *   capturable with n_dgrams frozen (tests/test_gpu_forward.py: test_capture_forward_tick).
+ * solo_forward_route -- d_sel: uint8 [n] as solo_vad_select wrote it for one packet; d_room: the ids of solo_mix, -1 = in no room, the
+ *   members of room r are the rows i < n with d_room[i] == r.
+ *   Step 1, slots, per room r in this order: a slot whose src is a row x with x < n, d_room[x] == r and d_sel[x] != 0 keeps it, every
+ *   other slot becomes free (src = -1; start, next and delta stay).  The selected members of r that hold no slot AND have
+ *   d_rowinfo[x].dgrams > 0 take the free slots, in increasing row order, lowest free k first; a slot that takes row x gets src = x,
+ *   start = next, delta = next - d_rowinfo[x].min_seq, and adds 1 to `switches`.  Members left over when the slots run out hold none this
+ *   call; a selected member with no datagram this call takes no slot yet.
+ *   Step 2, the verdict of arrival i, the FIRST rule that fails, each with a counter: rejected (stream outside [0, n)), no_desc (desc not
+ *   0 / 1), no_room (the sender's room is -1), not_selected (d_sel[sender] == 0), no_slot (the sender holds no slot after step 1), stale
+ *   (q = seq + delta, computed in 64 bits, is outside [start, 2^31 - 2]); otherwise the arrival is forwarded.
+ *   Step 3, records: a forwarded arrival of sender s in slot k of room r yields one record per member m != s of r, in increasing m:
+ *   {stream = m x K + k, seq = q, desc, offset, len}, offset and len the arrival's own.  The records are ordered by arrival index, then
+ *   by m; record j is written iff j < max_records, so what is written is a prefix and max_records = 0 only counts.  d_send_count has the
+ *   form solo_rtp_pack and solo_srtp_protect read on the device: records / records_needed = written / needed, bytes / bytes_needed = the
+ *   sum of len over the same two sets, empty = refused = 0.  A DUPLICATE DATAGRAM IS FORWARDED TWICE: there is no ring here, the
+ *   receivers' rings drop it.
+ *   Step 4, after the records: for every slot with a source, next = max(next, d_rowinfo[src].max_seq + delta + 1), taken only if that
+ *   value is within [start + 1, 2^31 - 1].  d_level_fwd (uint8 [n x K], or NULL) receives, for every row m in a room and every k,
+ *   d_rowinfo[src].byte of its room's slot k, or 0x7F for a free slot (rows in no room are not written): d_level of the egress
+ *   solo_rtp_pack with level_depth = 1.  d_slot_src (int32 [n_rooms][K], or NULL) receives src of every slot: the signalling plane tells
+ *   receivers from it who a slot carries.
+ *   Refusal on the device: a room id outside [-1, n_rooms) is found ahead of everything else; then d_count->forwarded = -1,
+ *   d_send_count->records = -1 (the egress pack and protect then write nothing), and no state, record or other output is touched.
+ *   -1 with nothing enqueued: NULL f, d_rowinfo, d_sel, d_room, d_records, d_send_count or d_count; n or n_rooms outside (0, n_rows];
+ *   n_dgrams < 0, or n_dgrams > 0 with NULL d_arrivals; max_records < 0; n_dgrams x (n - 1) >= 2^31; d_arrivals, d_rowinfo, d_room,
+ *   d_records, d_slot_src or d_count not 4-byte, d_send_count not 8-byte aligned.
+ *   Every output and the state after the call are a pure function of inputs and state, independent of the order of the arrivals except
+ *   for the order of the records, which follows the arrivals by definition.  Nine short kernels on hip_stream (the room plan's four, the
+ *   counts, a wavefront per room, a lane per arrival, a scan, a lane per OUTPUT record), no host synchronisation.  What depends on n_rows
+ *   belongs to the object and is sized at create; the scratch for the scan over the arrivals (12 bytes per datagram) grows, with a stream
+ *   synchronisation, only when a call has more datagrams than every one before it: capturable with n_dgrams, n and max_records frozen
+ *   (tests/test_gpu_forward.py: test_capture_forward_tick).  Calls on one object must be ordered (same stream, or events).
+ * A row that changes room while it holds a slot loses the slot in its old room and takes a free one in the new room like any newcomer.
+ * A room id that is used again for another conference keeps its slots' packet numbers unless solo_forward_reset_rooms is called (and the
+ * egress streams rebound).  A receiver that joins mid-call: its slot streams simply begin.  INTEGRATION.md section 2 has the tick. */
+typedef struct solo_forward_obj solo_forward_t;
+typedef struct { int32_t min_seq, max_seq, dgrams; uint8_t sa, level, byte, pad; } solo_forward_row_t;      /* 16 bytes */
+typedef struct { int32_t forwarded, rejected, no_desc, no_room, not_selected, no_slot, stale, switches; } solo_forward_count_t;  /* 32 bytes; forwarded = -1: refused on the device */
+#define SOLO_FORWARD_STATE_BYTES(slots) (16 * (slots))   /* per room: {int32 src, delta, start, next} per slot */
+/* The object's lifecycle and control plane, then the two device calls. */
+solo_forward_t *solo_forward_create(int32_t n_rows, int32_t slots);
+void    solo_forward_destroy(solo_forward_t *f);
+int32_t solo_forward_reset(solo_forward_t *f, void *hip_stream);
+int32_t solo_forward_reset_rooms(solo_forward_t *f, const int32_t *h_rooms, int32_t n, void *hip_stream);
+int32_t solo_forward_get_state(solo_forward_t *f, const int32_t *d_rooms, int32_t n, uint8_t *d_blob, void *hip_stream);
+int32_t solo_forward_set_state(solo_forward_t *f, const int32_t *d_rooms, int32_t n, const uint8_t *d_blob, void *hip_stream);
+int32_t solo_forward_levels(const solo_arrival_t *d_arrivals, const uint8_t *d_level_in, int32_t n_dgrams, int32_t n_rows,
+                            int32_t default_level, solo_forward_row_t *d_rowinfo, uint8_t *d_sa_q8, uint8_t *d_level, void *hip_stream);
+int32_t solo_forward_route(solo_forward_t *f, const solo_arrival_t *d_arrivals, int32_t n_dgrams, const solo_forward_row_t *d_rowinfo,
+                           const uint8_t *d_sel, const int32_t *d_room, int32_t n, int32_t n_rooms,
+                           solo_arrival_t *d_records, int32_t max_records, solo_send_count_t *d_send_count,
+                           uint8_t *d_level_fwd, int32_t *d_slot_src, solo_forward_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "solo_agc_create", "solo_agc_destroy", "solo_agc_reset", "solo_agc_reset_rows", "solo_agc_get_state", "solo_agc_set_state", "solo_agc",
     "solo_rtp_create", "solo_rtp_destroy", "solo_rtp_bind", "solo_rtp_unbind", "solo_rtp_pack", "solo_rtp_parse",
     "solo_rtp_set_trailer", "solo_srtp_set_keys", "solo_srtp_clear_keys", "solo_srtp_get_rx_index", "solo_srtp_protect", "solo_srtp_unprotect",
+    "solo_forward_create", "solo_forward_destroy", "solo_forward_reset", "solo_forward_reset_rooms", "solo_forward_get_state",
+    "solo_forward_set_state", "solo_forward_levels", "solo_forward_route",
 ]
 
 
@@ -166,6 +168,18 @@ class solo_srtp_count_t(C.Structure):
     """datagrams per verdict of a solo_srtp_protect / solo_srtp_unprotect call (include/solo_mi355x.h); 32 bytes; ok = -1: the list behind
     protect's records was refused"""
     _fields_ = [(n, C.c_int32) for n in ("ok", "skipped", "malformed", "unknown_ssrc", "no_key", "auth_failed", "reserved0", "reserved1")]
+
+
+class solo_forward_row_t(C.Structure):
+    """what solo_forward_levels gathers per row from the arrivals of a call (include/solo_mi355x.h); 16 bytes"""
+    _fields_ = [("min_seq", C.c_int32), ("max_seq", C.c_int32), ("dgrams", C.c_int32), ("sa", C.c_uint8), ("level", C.c_uint8), ("byte", C.c_uint8),
+                ("pad", C.c_uint8)]
+
+
+class solo_forward_count_t(C.Structure):
+    """arrivals per verdict of a solo_forward_route call and the slots that changed their source (include/solo_mi355x.h); 32 bytes;
+    forwarded = -1: a room id was refused on the device"""
+    _fields_ = [(n, C.c_int32) for n in ("forwarded", "rejected", "no_desc", "no_room", "not_selected", "no_slot", "stale", "switches")]
 
 
 SRTP_MASTER_BYTES = 30
@@ -330,6 +344,17 @@ def load_library():
     lib.solo_srtp_protect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.solo_srtp_unprotect.restype = C.c_int32
     lib.solo_srtp_unprotect.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, (restype, argtypes) in {"create": (C.c_void_p, [C.c_int32, C.c_int32]), "destroy": (None, [C.c_void_p]), "reset": (C.c_int32, [C.c_void_p, C.c_void_p]),
+                                      "reset_rooms": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+                                      "get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+                                      "set_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])}.items():
+        f = getattr(lib, "solo_forward_" + name)
+        f.restype, f.argtypes = restype, argtypes
+    lib.solo_forward_levels.restype = C.c_int32
+    lib.solo_forward_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_forward_route.restype = C.c_int32
+    lib.solo_forward_route.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1815,4 +1840,100 @@ class Rtp(_RowObject):
     def close(self):
         if getattr(self, "h", None):
             self.lib.solo_rtp_destroy(self.h)
+            self.h = None
+
+
+FORWARD_MAX_SLOTS = 8
+
+
+class Forward(_RowStateObject):
+    """The middle of a forwarding server's tick (solo_forward_*, include/solo_mi355x.h): levels() turns the arrivals Rtp.parse() wrote into
+    one RFC 6464 level per row for Vad.select(), route() turns the selected speakers' arrivals into records for the egress Rtp.pack()
+    -- one per other member of the sender's room, under `slots` per-room slots whose packet numbers stay continuous when the speaker
+    behind a slot changes.  Nothing is decoded and no payload byte moves.  The state is 16 bytes per ROOM and slot: a "row" of this
+    object is a room."""
+
+    COUNT = ("forwarded", "rejected", "no_desc", "no_room", "not_selected", "no_slot", "stale", "switches")
+    PREFIX = "forward"
+
+    def __init__(self, n_rows, slots=3):
+        self.n_rows, self.slots = int(n_rows), int(slots)
+        if self.n_rows <= 0 or not 1 <= self.slots <= FORWARD_MAX_SLOTS:
+            raise ValueError("n_rows must be positive, slots 1 .. %d" % FORWARD_MAX_SLOTS)
+        self.state_bytes = 16 * self.slots
+        self._create(self.n_rows, self.slots)
+
+    def levels(self, arrivals, level_in=None, default_level=255, n_rows=None):
+        """arrivals int32 [n_dgrams,5] and level_in uint8 [n_dgrams] (or None: every datagram has default_level) as Rtp.parse() wrote
+        them; default_level 0 .. 255: the byte of a datagram that carries none (255: it has none) -> dict(rowinfo int32 [n_rows,4] =
+        solo_forward_row_t per row, what route() takes; sa uint8 [n_rows] and level uint8 [n_rows]: what Vad.select() takes as sa[:, None,
+        None] and level[:, None]).  Stateless.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        nd, _ = _tensor("arrivals", arrivals, t.int32, (None, 5))
+        _tensor("level_in", level_in, t.uint8, (nd,), optional=True)
+        n_rows, default_level = self.n_rows if n_rows is None else int(n_rows), int(default_level)
+        if n_rows <= 0 or not 0 <= default_level <= 255:
+            raise ValueError("n_rows must be positive, default_level 0 .. 255")
+        out = {"rowinfo": t.zeros((n_rows, 4), dtype=t.int32, device=arrivals.device), "sa": t.zeros((n_rows,), dtype=t.uint8, device=arrivals.device),
+               "level": t.zeros((n_rows,), dtype=t.uint8, device=arrivals.device)}
+        r = self.lib.solo_forward_levels(arrivals.data_ptr() or None, _ptr(level_in) or None, nd, n_rows, default_level, out["rowinfo"].data_ptr(),
+                                         out["sa"].data_ptr(), out["level"].data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_forward_levels -> %d" % r)
+        return out
+
+    def route(self, arrivals, rowinfo, sel, room, n_rooms=None, max_records=None, records=None):
+        """arrivals int32 [n_dgrams,5]; rowinfo int32 [n,4] as levels() wrote it; sel uint8 [n] (or [n,1]) as Vad.select() wrote it for one
+        packet; room int32 [n] (-1 = in no room; n_rooms=None: the largest id + 1, which synchronises) -> dict(records int32 [max,5] for the
+        egress Rtp.pack(records, send_count, the receive buffer, level=level_fwd): stream = receiver x slots + slot; send_count int32 [8];
+        level_fwd uint8 [n x slots, 1]; slot_src int32 [n_rooms, slots]: the row each slot carries, -1 = free; count int32 [8], read with
+        count()).  max_records=None: n_dgrams x (n - 1), never too small; records: the caller's buffer.  A room id outside [-1, n_rooms) is
+        refused on the device: forwarded == -1 in the count, records == -1 in send_count, nothing else written.  Enqueued on the
+        current stream; synchronises only when a call has more datagrams than every one before it."""
+        t = self.torch
+        nd, _ = _tensor("arrivals", arrivals, t.int32, (None, 5))
+        n, _ = _tensor("rowinfo", rowinfo, t.int32, (None, 4))
+        if not 0 < n <= self.n_rows:
+            raise ValueError("rowinfo: 1 .. %d rows" % self.n_rows)
+        if getattr(sel, "dim", None) and sel.dim() == 2:
+            _tensor("sel", sel, t.uint8, (n, 1))
+        else:
+            _tensor("sel", sel, t.uint8, (n,))
+        _tensor("room", room, t.int32, (n,))
+        if n_rooms is None:
+            n_rooms = max(int(room.max()) + 1, 1)
+        n_rooms = int(n_rooms)
+        if not 0 < n_rooms <= self.n_rows:
+            raise ValueError("n_rooms: 1 .. %d" % self.n_rows)
+        if nd * (n - 1) >= 2 ** 31:
+            raise ValueError("n_dgrams x (n - 1) must stay below 2^31")
+        if records is not None:
+            max_records, _ = _tensor("records", records, t.int32, (None, 5))
+        max_records = nd * (n - 1) if max_records is None else int(max_records)
+        if max_records < 0:
+            raise ValueError("max_records: not negative")
+        dev = rowinfo.device
+        if records is None:
+            records = t.zeros((max(max_records, 1), 5), dtype=t.int32, device=dev)
+        out = {"records": records, "send_count": t.zeros((8,), dtype=t.int32, device=dev),
+               "level_fwd": t.full((n * self.slots, 1), 0x7F, dtype=t.uint8, device=dev),
+               "slot_src": t.full((n_rooms, self.slots), -1, dtype=t.int32, device=dev), "count": t.zeros((8,), dtype=t.int32, device=dev)}
+        self._call("route", arrivals.data_ptr() or None, nd, rowinfo.data_ptr(), sel.data_ptr(), room.data_ptr(), n, n_rooms, records.data_ptr(), max_records,
+                   out["send_count"].data_ptr(), out["level_fwd"].data_ptr(), out["slot_src"].data_ptr(), out["count"].data_ptr())
+        return out
+
+    def count(self, count):
+        """the count tensor of route() as a dict (synchronises); forwarded == -1: the call was refused on the device"""
+        return _counts(solo_forward_count_t, count)
+
+    def reset(self, rooms=None):
+        """every room, or the listed rooms (a host sequence: inside [0, n_rows), none twice), back to free slots that start at packet 0"""
+        if rooms is None:
+            return self._call("reset")
+        idx = _distinct("rooms", rooms, self.n_rows)
+        self._call("reset_rooms", (C.c_int32 * len(idx))(*idx), len(idx))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.solo_forward_destroy(self.h)
             self.h = None

@@ -42,6 +42,7 @@
 #include "solo_rows.h"          // the record kernels of those four objects (reset, listed reset, state copy): likewise
 #include "solo_srtp.h"          // SRTP protection of the datagrams of solo_rtp.h (solo_srtp_protect / _unprotect): likewise
 #include "solo_rtp.h"           // RTP framing of the sender's records and parsing of received datagrams (solo_rtp_pack / _parse): likewise
+#include "solo_forward.h"       // forwarding without transcoding: levels per row from arrivals, routing under per-room slots (solo_forward_*): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -1396,6 +1397,67 @@ int32_t solo_srtp_unprotect(solo_rtp_t* r, const solo_dgram_t* d_dgrams, int32_t
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n_dgrams = n_dgrams; a.n_streams = r->n_rows;
     SOLO_CHECK(solo_srtp_unprotect_launch(a, d_count, (hipStream_t)hip_stream));
+    return 0;
+}
+
+// ---- forwarding without transcoding (solo_forward.h): a row object whose "row" is a room, K slots of four words each ----------------------
+static_assert(SX_FWD_MAX_SLOTS * SX_FWD_SLOT_WORDS <= SX_ROWS_MAX_WORDS, "solo_forward.h and solo_rows.h agree");
+struct solo_forward_obj : solo_rows {    // d_state: SxFwdSlot [n_rows][slots]; d_verdict[1]: the verdict word of the room plan
+    int32_t slots;
+    void* d_plan;                    // the room plan and the ranks (solo_forward_plan_bytes): sized at create
+    void* d_scratch;                 // what a route call keeps per arrival (solo_forward_scratch_bytes), grown on demand
+    size_t scratch_bytes;
+};
+solo_forward_t* solo_forward_create(int32_t n_rows, int32_t slots) {
+    if (n_rows <= 0 || slots < 1 || slots > SX_FWD_MAX_SLOTS || (int64_t)n_rows * SX_FWD_MAX_SLOTS >= ((int64_t)1 << 31) || !have_device()) return NULL;
+    solo_forward_obj* f = new (std::nothrow) solo_forward_obj();
+    if (!f) return NULL;
+    f->slots = slots;
+    if (hipMalloc(&f->d_plan, solo_forward_plan_bytes(n_rows)) != hipSuccess || !rows_alloc(f, n_rows, slots * SX_FWD_SLOT_WORDS, sx_fwd_init_word, 1, 0)) {
+        solo_forward_destroy(f);
+        return NULL;
+    }
+    return f;
+}
+void solo_forward_destroy(solo_forward_t* f) {
+    if (!f) return;
+    rows_free(f);
+    dev_free(f->d_plan);
+    dev_free(f->d_scratch);
+    delete f;
+}
+int32_t solo_forward_reset(solo_forward_t* f, void* hip_stream) { return rows_reset(f, (hipStream_t)hip_stream); }
+int32_t solo_forward_reset_rooms(solo_forward_t* f, const int32_t* h_rooms, int32_t n, void* hip_stream) {
+    return rows_reset_list(f, h_rooms, n, (hipStream_t)hip_stream);
+}
+int32_t solo_forward_get_state(solo_forward_t* f, const int32_t* d_rooms, int32_t n, uint8_t* d_blob, void* hip_stream) {
+    return rows_copy_state(f, d_rooms, n, d_blob, 0, (hipStream_t)hip_stream);
+}
+int32_t solo_forward_set_state(solo_forward_t* f, const int32_t* d_rooms, int32_t n, const uint8_t* d_blob, void* hip_stream) {
+    return rows_copy_state(f, d_rooms, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+}
+int32_t solo_forward_levels(const solo_arrival_t* d_arrivals, const uint8_t* d_level_in, int32_t n_dgrams, int32_t n_rows, int32_t default_level,
+                            solo_forward_row_t* d_rowinfo, uint8_t* d_sa_q8, uint8_t* d_level, void* hip_stream) {
+    if (!sx_fwd_levels_ok(d_arrivals, n_dgrams, n_rows, default_level, d_rowinfo, d_sa_q8, d_level)) return -1;
+    SxFwdLevelArgs a;
+    a.arrivals = d_arrivals; a.level_in = d_level_in; a.rowinfo = d_rowinfo; a.sa = d_sa_q8; a.level = d_level;
+    a.n_dgrams = n_dgrams; a.n_rows = n_rows; a.default_level = default_level;
+    SOLO_CHECK(solo_forward_levels_launch(a, (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_forward_route(solo_forward_t* f, const solo_arrival_t* d_arrivals, int32_t n_dgrams, const solo_forward_row_t* d_rowinfo, const uint8_t* d_sel,
+                           const int32_t* d_room, int32_t n, int32_t n_rooms, solo_arrival_t* d_records, int32_t max_records, solo_send_count_t* d_send_count,
+                           uint8_t* d_level_fwd, int32_t* d_slot_src, solo_forward_count_t* d_count, void* hip_stream) {
+    if (!sx_fwd_route_ok(f, f ? f->n_rows : 0, d_arrivals, n_dgrams, d_rowinfo, d_sel, d_room, n, n_rooms, d_records, max_records, d_send_count, d_slot_src,
+                         d_count))
+        return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(f->d_scratch, f->scratch_bytes, solo_forward_scratch_bytes(n_dgrams) + 16, st));
+    SxFwdArgs a = {};
+    a.arrivals = d_arrivals; a.rowinfo = d_rowinfo; a.sel = d_sel; a.room = d_room; a.state = (SxFwdSlot*)f->d_state;
+    a.records = d_records; a.send_count = d_send_count; a.level_fwd = d_level_fwd; a.slot_src = d_slot_src; a.count = d_count;
+    a.n_dgrams = n_dgrams; a.n = n; a.n_rooms = n_rooms; a.K = f->slots; a.max_records = max_records;
+    SOLO_CHECK(solo_forward_route_launch(a, f->d_plan, f->n_rows, f->d_scratch, f->d_verdict, st));
     return 0;
 }
 
