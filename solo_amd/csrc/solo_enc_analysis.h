@@ -1279,6 +1279,16 @@ struct SxLpcWork {
     } u;
 };
 
+// Debug builds of the host emulation with -DSX_BURG_COUNT (tools/debug/burg_branches.py): per call site, the runs of the recursion in the
+// usual scaling regime [0] and in the other one [1], the runs that left through the |num| >= den exit [2], and (second-half site) the
+// runs whose first row of correlations accumulates as the whole-frame run before them did (64-bit: rshifts > 0, or wrapping 32-bit) [3]
+#if defined(SX_BURG_COUNT) && SX_NLANES == 1
+extern "C" { inline long long sx_burg_count[3][4]; inline int sx_burg_last_regime; }
+#define SX_BURG_COUNTED(site, what) (sx_burg_count[site][what]++)
+#else
+#define SX_BURG_COUNTED(site, what)
+#endif
+
 // SKP_Silk_burg_modified, SKP_Silk_burg_modified.c:49.  The reference's scalar loops over the coefficient index k are
 // spread over lanes (all its accumulations are wrapping int32 sums of independent terms, so lane order is immaterial):
 // lane (s, k) builds the per-subframe prediction terms, lane k owns row / correlation element k.
@@ -1316,6 +1326,11 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
         rshifts += rshifts_extra;
     }
     C0 = SX_UNI(C0); rshifts = SX_UNI(rshifts);
+#if defined(SX_BURG_COUNT) && SX_NLANES == 1
+    SX_BURG_COUNTED(SITE, rshifts > -2 ? 0 : 1);
+    if (SITE == 1 && sx_burg_last_regime == (rshifts > 0)) SX_BURG_COUNTED(SITE, 3);
+    if (SITE == 0) sx_burg_last_regime = rshifts > 0;
+#endif
     // first row of the correlation matrix: lane (s, n) computes one inner product serially
     SX_PAR(sn, nb_subfr * 16) {
         const int s = sn >> 4, n = (sn & 15) + 1;
@@ -1352,69 +1367,82 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
     // 17 correlation entries and takes the LDS form below)
     // Register-resident recursion: lane (s, k) = (row, column) of the wave.  Column k of a row holds coefficient / correlation
     // element k (Af in every row; the correlation rows Cf / Cl in rows 0 - 1, CAf / CAb in rows 2 - 3), so the per-subframe terms
-    // reduce inside a row (DPP) and index reversals n-1-k are one lane gather; nothing goes through LDS but the signal.
+    // reduce inside a row (DPP) and index reversals n-1-k are one lane gather; nothing goes through LDS, the signal included:
+    // the recursion only ever touches the first and the last D + 1 samples of a subframe, and those sit in four lane registers per
+    // row that move by one column a step (profiles/burg_steps.txt).
     i32 nrg, tmp1;
     {
         const int row = SX_LANE >> 4, k = SX_LANE & 15, rowbase = SX_LANE & 48;
-        const int srow = row < nb_subfr ? row : 0;            // rows past nb_subfr compute a copy of subframe 0 and are ignored
-        const i16* xr = x + srow * L;
+        const bool live = row < nb_subfr;                     // rows past nb_subfr hold zero samples: every term of theirs is zero
+        const i16* xr = x + (live ? row : 0) * L;
         // The two correlation rows (first: Cf, last: Cl) are kept by rows 0 and 1 of the wave, the forward / backward correlations (CAf, CAb)
         // by rows 2 and 3 -- P_k = Cf | CAf, Q_k = Cl | CAb: the four per-subframe terms of step (b) then reach the rows that keep their
         // totals with three lane swaps (a transposing reduction) instead of two swaps each into every row.
         const bool upper = row >= 2;
         i32 Af_k = 0, P_k = upper ? (k == 0 ? CA0 : 0) : bw->Cf[k], Q_k = P_k;
-        // element index of step (c)'s gather, gidx_a + (n & gidx_n): rows 0, 1: n - k - 1; row 2: n - k; row 3: k + 1
-        const int gidx_a = row < 2 ? -k - 1 : (row == 2 ? -k : k + 1), gidx_n = row < 3 ? -1 : 0;
-#define SX_GATHER(v, idx) __shfl((v), rowbase | ((idx) & 15), 64)
-        // (the recursion exists twice, once per scaling regime of the input -- `hi` = rshifts > -2, the usual one -- so that the regime is
+        // The edge samples.  ef / eb: the samples still to enter, column k = xr[n + k] / xr[L - 1 - n - k] at step n (they move one column
+        // down a step, so column 0 is the entering pair xr[n], xr[L - n - 1]: one row broadcast each).  fr / bk: the samples that have
+        // entered, column k = xr[n - 1 - k] / xr[L - n + k] for k < n and ZERO from column n on (one column up a step, the entering sample
+        // into column 0) -- so every product with them vanishes in the columns the reference's loops do not reach, and no condition
+        // on k is needed around steps (a) and (b).  After the move of step n they are the operands xs[n - k], xs[L - n + k - 1] of step (b).
+        i32 ef = live ? (i32)xr[k] : 0, eb = live ? (i32)xr[L - 1 - k] : 0, fr = 0, bk = 0;
+#define SX_ROW_DOWN(v) __builtin_amdgcn_update_dpp(0, (v), 0x101, 0xF, 0xF, true)             /* row_shl:1, zero into column 15 */
+#define SX_ROW_UP_IN(in, v) __builtin_amdgcn_update_dpp((in), (v), 0x111, 0xF, 0xF, false)    /* row_shr:1, `in` into column 0 */
+#define SX_ROW_BCAST0(v) __builtin_amdgcn_update_dpp(0, (v), 0x150, 0xF, 0xF, true)           /* row_newbcast:0 */
+        // Lane gathers (ds_bpermute byte addresses, 4 x lane): ga = step (c)'s source -- rows 0, 1: column n - k - 1, row 2: n - k,
+        // row 3: k + 1; da = step (d)'s, column n - k - 1 (and n + 1 - k, eight bytes on).  Both advance by a constant a step.  They
+        // leave the row where the column is negative; those are the columns whose gathered value meets Af_k == 0 or a condition on k.
+        int ga = 4 * (SX_LANE + (row < 2 ? -2 * k - 1 : (row == 2 ? -2 * k : 1))), da = 4 * (SX_LANE - 2 * k - 1);
+        const int ga_step = row < 3 ? 4 : 0;
+        // own_at: zero in the one column of a row that carries step (c)'s summand from outside the sums -- column n of rows 0 and 1 (it
+        // counts down a step), column 0 of row 3 (it stays); never zero elsewhere
+        int own_at = upper ? (SX_LANE == 48 ? 0 : -1) : k;
+        const int own_step = upper ? 0 : 1;
+        // (the recursion exists twice, once per scaling regime of the input -- `hi` = rshifts > -2, the high band's usual one; the low
+        // band's gain-scaled residual mostly takes the other, profiles/burg_steps.txt section 4 -- so that the regime is
         // a compile-time constant inside the loop: a wave-uniform condition nested in the per-column conditions below is otherwise
         // carried as an execution mask through every step)
         auto recursion = [&](auto regime) {
         constexpr bool hi = decltype(regime)::value;
+        // x1 = -(xr[n] << s) as one 24-bit multiply by a factor formed once (s <= 17: both factors fit)
+        const i32 edge_scale = SX_UNI(sx_neg(sx_shl(1, hi ? 16 - rshifts : -rshifts)));
         for (int n = 0; n < D; n++) {
+            const i32 xn = SX_ROW_BCAST0(ef), xb = SX_ROW_BCAST0(eb);          // xr[n], xr[L - n - 1] in every column of the row
             // (a) forward / backward prediction errors at the two edges of subframe `row`
-            i32 a = 0, b = 0;
-            if (k < n) {
-                if (hi) {
-                    a = sx_smulwb(Af_k, xr[n - k - 1]);
-                    b = sx_smulwb(Af_k, xr[L - n + k]);
-                } else {
-                    const i32 Atmp1 = sx_rshift_round(Af_k, QA - 17);
-                    a = sx_mul(xr[n - k - 1], Atmp1);
-                    b = sx_mul(xr[L - n + k], Atmp1);
-                }
+            i32 a, b;
+            if (hi) {
+                a = sx_smulwb(Af_k, fr);
+                b = sx_smulwb(Af_k, bk);
+            } else {
+                const i32 Atmp1 = sx_rshift_round(Af_k, QA - 17);
+                a = sx_mul(fr, Atmp1);
+                b = sx_mul(bk, Atmp1);
             }
             a = wv_row_sum(a);
             b = wv_row_sum(b);
-            i32 t1 = sx_add(sx_shl((i32)xr[n], hi ? QA - 16 : 17), a), t2 = sx_add(sx_shl((i32)xr[L - n - 1], hi ? QA - 16 : 17), b);
+            i32 t1 = sx_add(sx_shl(xn, hi ? QA - 16 : 17), a), t2 = sx_add(sx_shl(xb, hi ? QA - 16 : 17), b);
             t1 = sx_neg(t1); t2 = sx_neg(t2);
             if (hi) { t1 = sx_shl(t1, 32 - QA - rshifts); t2 = sx_shl(t2, 32 - QA - rshifts); }
             // (b) column k: correlation rows and forward / backward correlations.  Lane (row, k) adds the terms of ITS subframe (the
             // row's own prediction errors t1 / t2 are already in its lanes), the four rows are then summed column by column
             // (wrapping adds: the order is free), which leaves the same totals in every row
             {
-                i32 dcf = 0, dcl = 0, dcaf = 0, dcab = 0;
-                if (row < nb_subfr) {
-                    const i16* xs = xr;
-                    const int kk = sx_min(k, n);                       // columns past n only feed lanes that are never read
-                    if (hi) {
-                        const i32 x1 = sx_neg(sx_shl((i32)xs[n], 16 - rshifts)), x2 = sx_neg(sx_shl((i32)xs[L - n - 1], 16 - rshifts));
-                        if (k < n) {
-                            dcf = sx_smulwb(x1, xs[n - k - 1]);
-                            dcl = sx_smulwb(x2, xs[L - n + k]);
-                        }
-                        dcaf = sx_smulwb(t1, xs[n - kk]);
-                        dcab = sx_smulwb(t2, xs[L - n + kk - 1]);
-                    } else {
-                        const i32 x1 = sx_neg(sx_shl((i32)xs[n], -rshifts)), x2 = sx_neg(sx_shl((i32)xs[L - n - 1], -rshifts));
-                        if (k < n) {
-                            dcf = sx_mul(x1, xs[n - k - 1]);
-                            dcl = sx_mul(x2, xs[L - n + k]);
-                        }
-                        dcaf = sx_smulww(t1, sx_shl((i32)xs[n - kk], -rshifts - 1));
-                        dcab = sx_smulww(t2, sx_shl((i32)xs[L - n + kk - 1], -rshifts - 1));
-                    }
+                const i32 fr1 = SX_ROW_UP_IN(xn, fr), bk1 = SX_ROW_UP_IN(xb, bk);
+                const i32 x1 = __mul24(xn, edge_scale), x2 = __mul24(xb, edge_scale);
+                i32 dcf, dcl, dcaf, dcab;
+                if (hi) {
+                    dcf = sx_smulwb(x1, fr);
+                    dcl = sx_smulwb(x2, bk);
+                    dcaf = sx_smulwb(t1, fr1);
+                    dcab = sx_smulwb(t2, bk1);
+                } else {
+                    dcf = sx_mul(x1, fr);
+                    dcl = sx_mul(x2, bk);
+                    dcaf = sx_smulww(t1, sx_shl(fr1, -rshifts - 1));
+                    dcab = sx_smulww(t2, sx_shl(bk1, -rshifts - 1));
                 }
+                fr = fr1; bk = bk1;
+                ef = SX_ROW_DOWN(ef); eb = SX_ROW_DOWN(eb);
                 {   // v_permlane32_swap(X, Y): {X.lower | Y.lower}, {X.upper | Y.upper}: their sum holds X's half-sums in rows 0, 1 and Y's in
                     // rows 2, 3; v_permlane16_swap of that with itself: the even row of each half in both of its rows, and the odd one
                     auto p_ = __builtin_amdgcn_permlane32_swap(dcf, dcaf, false, false);
@@ -1422,27 +1450,30 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
                     const i32 u_ = sx_add((i32)p_[0], (i32)p_[1]), v_ = sx_add((i32)q_[0], (i32)q_[1]);
                     auto pu_ = __builtin_amdgcn_permlane16_swap(u_, u_, false, false);
                     auto qv_ = __builtin_amdgcn_permlane16_swap(v_, v_, false, false);
-                    const i32 dP = sx_add((i32)pu_[0], (i32)pu_[1]), dQ = sx_add((i32)qv_[0], (i32)qv_[1]);
-                    if (upper ? k <= n : k < n) { P_k = sx_add(P_k, dP); Q_k = sx_add(Q_k, dQ); }
+                    // (the totals are zero from column n on in rows 0, 1 and from column n + 1 on in rows 2, 3)
+                    P_k = sx_add(P_k, sx_add((i32)pu_[0], (i32)pu_[1]));
+                    Q_k = sx_add(Q_k, sx_add((i32)qv_[0], (i32)qv_[1]));
                 }
             }
             // (c) reflection coefficient: numerator / denominator terms of column k < n.  The four sums over k (against the reversed
-            // Cl, Cf, CAb and the shifted CAb + CAf) are taken by the four rows, one each: the rows hold identical copies of the vectors
+            // Cl, Cf, CAb and the shifted CAb + CAf) are taken by the four rows, one each: the rows hold identical copies of the vectors.
+            // The terms outside the sums ride along in a column of their own: Cf[n] / Cl[n] in column n of rows 0 / 1 (its Af_k is
+            // zero), CAb[0] + CAf[0] in column 0 of row 3 -- so four row totals are all the scalar unit reads back.
             i32 s1, s2, num, den;
             {
-                const i32 src = row < 2 ? (row == 0 ? Q_k : P_k) : (row == 2 ? Q_k : sx_add(Q_k, P_k));
-                const i32 g = SX_GATHER(src, gidx_a + (n & gidx_n));
-                i32 pq = 0;
-                if (k < n) {
-                    int lz = sx_clz32(sx_abs(Af_k)) - 1;
-                    lz = sx_min(32 - QA, lz);
-                    pq = sx_shl(sx_smmul(g, sx_shl(Af_k, lz)), 32 - QA - lz);
-                }
+                const i32 both = sx_add(Q_k, P_k);
+                const i32 src = row < 3 ? (row == 1 ? P_k : Q_k) : both;
+                const i32 g = __builtin_amdgcn_ds_bpermute(ga, src);
+                int lz = sx_clz32(sx_abs(Af_k)) - 1;
+                lz = sx_min(32 - QA, lz);
+                i32 pq = sx_shl(sx_smmul(g, sx_shl(Af_k, lz)), 32 - QA - lz);     // zero from column n on: Af_k is
+                const i32 own = upper ? src : sx_sub(both, src);                  // (rows 0, 1: the vector the row does not gather)
+                pq = sx_add(pq, own_at == 0 ? own : 0);
                 const i32 tot = wv_row_sum(pq);
-                s1 = sx_add(__builtin_amdgcn_readlane(tot, 0), __builtin_amdgcn_readlane(P_k, n));
-                s2 = sx_add(__builtin_amdgcn_readlane(tot, 16), __builtin_amdgcn_readlane(Q_k, n));
+                s1 = __builtin_amdgcn_readlane(tot, 0);
+                s2 = __builtin_amdgcn_readlane(tot, 16);
                 num = __builtin_amdgcn_readlane(tot, 32);
-                den = sx_add(__builtin_amdgcn_readlane(tot, 48), sx_add(__builtin_amdgcn_readlane(Q_k, 32), __builtin_amdgcn_readlane(P_k, 32)));
+                den = __builtin_amdgcn_readlane(tot, 48);
             }
             if (upper && k == n + 1) { P_k = s1; Q_k = s2; }
             num = sx_add(num, s2);
@@ -1454,19 +1485,23 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
             const i32 rc_Q31 = sx_div32_varQ(num, den, 31);
             // (d) symmetric coefficient update and correlation update
             {
-                const i32 Af_r = SX_GATHER(Af_k, n - k - 1);
-                const i32 CAb_r = SX_GATHER(Q_k, n + 1 - k), CAf_r = SX_GATHER(P_k, n + 1 - k);
-                if (k < n) Af_k = sx_add(Af_k, sx_shl(sx_smmul(Af_r, rc_Q31), 1));
-                if (upper && k <= n + 1) {
-                    P_k = sx_add(P_k, sx_shl(sx_smmul(CAb_r, rc_Q31), 1));
-                    Q_k = sx_add(Q_k, sx_shl(sx_smmul(CAf_r, rc_Q31), 1));
-                }
-                if (k == n) Af_k = rc_Q31 >> (31 - QA);
+                const i32 Af_r = __builtin_amdgcn_ds_bpermute(da, Af_k);
+                const i32 CAb_r = __builtin_amdgcn_ds_bpermute(da + 8, Q_k), CAf_r = __builtin_amdgcn_ds_bpermute(da + 8, P_k);
+                // (Af_r is zero from column n on: the gather leaves the row there and meets columns >= n of the row before it, where Af
+                // is still zero in every row; the correlations are not, so rows 2, 3 take a zero factor past column n + 1)
+                const i32 rc_up = upper && k <= n + 1 ? rc_Q31 : 0;
+                Af_k = sx_add(Af_k, sx_shl(sx_smmul(Af_r, rc_Q31), 1));
+                P_k = sx_add(P_k, sx_shl(sx_smmul(CAb_r, rc_up), 1));
+                Q_k = sx_add(Q_k, sx_shl(sx_smmul(CAf_r, rc_up), 1));
+                Af_k = k == n ? rc_Q31 >> (31 - QA) : Af_k;
             }
+            ga += ga_step; da += 4; own_at -= own_step;
         }
         };
         if (rshifts > -2) recursion(SxConst<bool, true>{}); else recursion(SxConst<bool, false>{});
-#undef SX_GATHER
+#undef SX_ROW_DOWN
+#undef SX_ROW_UP_IN
+#undef SX_ROW_BCAST0
         SX_T(25)
         // residual energy and output
         const i32 At = k < D ? sx_rshift_round(Af_k, QA - 16) : 0;
@@ -1584,6 +1619,7 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
         if (sx_abs(num) < nrg) {
             rc_Q31 = sx_div32_varQ(num, nrg, 31);
         } else {
+            SX_BURG_COUNTED(SITE, 2);
             wv_sync();
             SX_PAR(k, D - n) bw->Af[n + k] = 0;
             wv_sync();

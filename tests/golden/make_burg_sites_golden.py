@@ -1,0 +1,19 @@
+#!/usr/bin/env python3
+"""tests/golden/burg_sites.npz: what the compiled reference (oracle/_ref) writes for the input families of tests/burg_sites_inputs.py --
+payload bytes and the two lengths of every packet, per family.  Run from the repository root after __graft_entry__.build()."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+import burg_sites_inputs as B  # noqa: E402
+
+out = {}
+for name in B.FAMILIES + (B.WB,):
+    bits, nb = B.reference(name)
+    out[name + "/bits"], out[name + "/nbytes"] = bits, nb
+    print("%-26s payload bytes %3d .. %3d" % (name, nb[:, :, 0].min(), nb[:, :, 0].max()))
+np.savez_compressed(os.path.join(ROOT, "tests", "golden", "burg_sites.npz"), **out)
