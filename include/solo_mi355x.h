@@ -1014,6 +1014,131 @@ int32_t solo_forward_route(solo_forward_t *f, const solo_arrival_t *d_arrivals, 
                            const uint8_t *d_sel, const int32_t *d_room, int32_t n, int32_t n_rooms,
                            solo_arrival_t *d_records, int32_t max_records, solo_send_count_t *d_send_count,
                            uint8_t *d_level_fwd, int32_t *d_slot_src, solo_forward_count_t *d_count, void *hip_stream);
+/* RTCP (RFC 3550 section 6.4): reception statistics per stream, kept on the device from the arrivals solo_rtp_parse wrote, the sender's
+ * packet and octet counts from the datagrams solo_rtp_pack / solo_srtp_protect left, compound SR / RR + SDES packets built from both, and
+ * the peers' compound packets parsed into round-trip time and loss feedback.  A solo_rtcp_t stands beside the solo_rtp_t sessions and never
+ * writes them: it reads their per-stream records and SSRC tables on the device.  One row per stream, 32 integer words (little-endian
+ * uint32 unless said otherwise), then the CNAME:
+ *     0 base_seq   1 max_seq   2 cycles (a multiple of 65536)   3 bad_seq   4 received   5 expected_prior   6 received_prior      (A.1)
+ *     7 transit    8 jitter (scaled by 16, A.8)    9 seen: bit 0 a datagram has counted, bit 1 transit is set, bit 2 an SR was parsed
+ *    10 lsr (the middle 32 bits of the peer's last SR's NTP stamp)    11 lsr_arrival (the middle 32 bits of the local time it was parsed at)
+ *    12 tx_packets   13 tx_octets (wrapping)   14 tx_next (1 + the highest packet number sent)   15 tx_since (datagrams since the last build)
+ *    16 .. 31 reserved, zero;   then 32 bytes: the CNAME, NUL-padded (all zero: none)
+ * Object and control plane -- a row-state object like solo_vad_t.  solo_rtcp_create: NULL for n_streams <= 0.  solo_rtcp_reset: every
+ * row; solo_rtcp_reset_rows: a HOST list, -1 for an index outside [0, n_streams) or listed twice; a reset leaves every word AND the CNAME
+ * zero.  solo_rtcp_get_state / _set_state: a DEVICE list of rows or NULL, uint8 [n][SOLO_RTCP_STATE_BYTES + SOLO_RTCP_CNAME_BYTES], as
+ * the other row objects: the hand-over of a stream to another object.  solo_rtcp_set_cname: HOST arrays, h_cname [n][32] with a name of
+ * 1 .. 31 bytes, NUL-padded; ordered on hip_stream, returns when the device holds the names; -1 and nothing changed for a NULL argument,
+ * n <= 0, an index outside [0, n_streams) or listed twice, an empty name or one without a NUL inside its 32 bytes.  Lifecycle, state
+ * and name calls come before a graph is recorded.  Calls on one object must be ordered (same stream, or events).
+ * solo_rtcp_received -- behind solo_rtp_parse: r the session that parsed, d_arrivals / d_rtp_seq / n_dgrams as parse wrote them,
+ *   d_arrival_time uint32 [n_dgrams] in RTP timestamp units of the caller's clock, NULL = every datagram arrived at now_rtp.  An arrival
+ *   COUNTS when its stream is inside [0, n_streams); desc = -1 counts (it was a datagram on the wire), a rejected datagram (stream = -1)
+ *   is not_counted.  Per stream, its counting datagrams are processed IN INCREASING DATAGRAM INDEX, each by update_seq of RFC 3550 A.1 on
+ *   the raw 16-bit sequence number (MAX_DROPOUT 3000, MAX_MISORDER 100, no probation: the bind vouched for the source), with one outcome:
+ *     first            seen bit 0 was clear: init_seq (base_seq = max_seq = seq, bad_seq = 65537, cycles = 0, received = expected_prior =
+ *                      received_prior = 0), accepted
+ *     in_order         udelta = (seq - max_seq) mod 2^16 < 3000: cycles += 65536 if seq < max_seq; max_seq = seq; accepted
+ *     dropout_pending  3000 <= udelta <= 65536 - 100 and seq != bad_seq: bad_seq = (seq + 1) mod 2^16; NOT accepted
+ *     resynced         ... and seq == bad_seq: init_seq, accepted
+ *     misordered       udelta > 65536 - 100 (reordered, or a duplicate of an older packet): accepted
+ *   An accepted datagram adds 1 to received and then updates the jitter (A.8): transit = arrival_time - (ts_offset + seq x packet_samples)
+ *   mod 2^32, from the ARRIVAL's packet number and the session's ts_offset (no wire byte is read again); if seen bit 1 is set,
+ *   d = |(int32)(transit - the row's transit)| and jitter += d - ((jitter + 8) >> 4); then the row's transit = transit, bit 1 set.
+ *   d_count: counted = first + in_order + misordered + dropout_pending + resynced, and not_counted.  The result equals this sequential
+ *   rule for any interleaving of streams and depends on nothing but the index order.  How: a histogram per stream and the workgroup scan
+ *   the bridge stages share, a scatter of the datagram indices into per-stream segments, then one wavefront per stream that puts its
+ *   segment (at most SOLO_RTCP_WALK_MAX datagrams) back into index order and walks it; a stream with more gets a workgroup of its own
+ *   that reads the arrival list tile by tile in index order: no lane loops over the call per datagram, the work is linear in n_dgrams
+ *   plus, per flooding stream (at most n_dgrams / (SOLO_RTCP_WALK_MAX + 1) of them), one pass over the arrivals.
+ *   -1 with nothing enqueued: NULL c, r or d_count; r has another stream count; n_dgrams < 0, or n_dgrams > 0 with NULL d_arrivals or
+ *   d_rtp_seq; d_arrivals, d_arrival_time or d_count not 4-byte, d_rtp_seq not 2-byte aligned.  Eight short kernels on hip_stream; the
+ *   scratch (8 bytes per datagram) grows, with a stream synchronisation, only when a call has more datagrams than every one before it;
+ *   no host synchronisation otherwise: capturable with n_dgrams frozen (tests/test_gpu_rtcp.py: test_capture_received_tick).
+ * solo_rtcp_sent -- behind solo_rtp_pack or solo_srtp_protect: r the sending session, d_records / d_send_count / max_records / d_dgrams
+ *   as those calls left them.  The records of the call are min(d_send_count->records, max_records), read on the device; a negative
+ *   count: d_count->sent = -1, nothing touched.  Every record k with d_dgrams[k].len > 0 and a stream inside [0, n_streams) is `sent`:
+ *   tx_packets += 1, tx_octets += the RECORD's len (payload octets: no header, no tag), tx_since += 1, tx_next = max(tx_next, seq + 1);
+ *   every other record is `skipped`.  Atomics, a lane per record: independent of the order.  -1: a NULL pointer, r with another stream
+ *   count, max_records <= 0, a pointer not 4-byte aligned.  Two kernels, no allocation: capturable with max_records frozen
+ *   (tests/test_gpu_rtcp.py: test_capture_sent_tick).
+ * solo_rtcp_build -- one compound packet per listed stream, d_dgrams[i] = that of d_streams[i], back to back in d_wire, every length a
+ *   multiple of 4.  d_streams: a DEVICE list under the rule of every device list (strictly increasing inside [0, n_streams), which also
+ *   means none twice); a list that breaks it refuses the whole call on the device: d_count->built = -1, nothing else is touched.
+ *   now: *d_now_ntp if that is given, else now_ntp (64 bits, 32.32 fixed point; A REPLAY OF A CAPTURED CALL REPEATS THE SCALAR, so a
+ *   caller who captures brings the time in the device word); mid32(x) = (x >> 16) mod 2^32.
+ *   refused, d_dgrams[i] = {0, 0}: the stream is not bound in r_tx, or has no CNAME (RFC 3550 makes it mandatory in every compound packet).
+ *   First packet: SR (PT 200, 28 bytes) if tx_since > 0, else RR (PT 201, 8 bytes); sender SSRC = the stream's in r_tx.  SR: NTP = now,
+ *   RTP timestamp = ts_offset + tx_next x packet_samples of r_tx -- the sampling instant of the packet the NEXT tick sends, an
+ *   approximation of "the same instant as the NTP stamp" that is off by less than one tick --, then tx_packets and tx_octets.
+ *   One report block (RC = 1, 24 bytes) iff r_rx is given, the stream is bound there and seen bit 0 is set, else RC = 0: SSRC_1 = the
+ *   stream's in r_rx; by A.3 expected = cycles + max_seq - base_seq + 1, lost = (int32)(expected - received) clamped to [-0x800000,
+ *   0x7FFFFF], expected_interval = expected - expected_prior, lost_interval = (int32)(expected_interval - (received - received_prior)),
+ *   fraction = 0 if expected_interval == 0 or lost_interval <= 0, else min(255, (lost_interval << 8) / expected_interval); then
+ *   cycles | max_seq, jitter >> 4, lsr, and DLSR = mid32(now) - lsr_arrival (both 0 while seen bit 2 is clear).
+ *   SDES (PT 202, SC = 1): the same sender SSRC, item 1 (CNAME), its length, the text, one zero octet, zero-padded to a multiple of 4.
+ *   Cap, as in solo_rtp_pack: packet i is written iff it ends inside wire_capacity; the offsets grow along the list, so what is written
+ *   is a prefix and nothing is written at or beyond the cap; wire_capacity = 0 only counts; bytes_needed is 64 bits.  A written packet
+ *   with a report block sets expected_prior = expected and received_prior = received; every written packet sets tx_since = 0.  A packet
+ *   cut by the cap or refused changes no state.  d_count: built / built_needed (packets written / not refused), bytes / bytes_needed,
+ *   refused, with_sr (written packets that begin with an SR).
+ *   -1 with nothing enqueued: NULL c, r_tx, d_streams, d_dgrams, d_wire or d_count; a session with another stream count; n outside
+ *   (0, n_streams]; wire_capacity < 0; d_streams, d_dgrams, d_wire not 4-byte, d_now_ntp or d_count not 8-byte aligned.  Four kernels
+ *   (the list check, tile totals, a scan, the packets: a lane each), scratch sized at create: capturable with n frozen
+ *   (tests/test_gpu_rtcp.py: test_capture_build_and_parse).
+ * solo_rtcp_parse -- n_dgrams received compound packets inside d_wire at any byte alignment, a lane each; r_rx has the peers' SSRCs, r_tx
+ *   (or NULL) ours.  Validity is RFC 3550 A.2 over the whole datagram; the verdict is the FIRST rule that fails, each with a counter:
+ *     malformed   the range is outside [0, min(wire_bytes, 2^31 - 1)) or len < 4
+ *     version     the first header's V is not 2
+ *     first_type  the first header has P set or a PT other than 200 / 201
+ *     then packet by packet from the first on, at byte `at`: length if at + 4 > len; version if V is not 2; length if the packet's
+ *     4 x (length field + 1) bytes reach past len, if P is set on a packet that is not the last or with a pad count (the last octet) that
+ *     is 0, no multiple of 4 or larger than the packet's body, or if the body is too short for what the header announces (SR: 24 + 24 RC,
+ *     RR: 4 + 24 RC, BYE: 4 SC bytes behind the header).
+ *   A rejected datagram changes nothing.  In an accepted one: an SR whose sender SSRC is bound in r_rx (the table search of
+ *   solo_rtp_parse) gives that stream lsr = mid32(its NTP stamp), lsr_arrival = mid32(now), seen bit 2, counted sr; an unknown sender is
+ *   counted unknown_ssrc and its SR skipped; its report blocks are still read.  Among several SRs of one stream in a call the one in the
+ *   HIGHEST DATAGRAM INDEX wins (inside one datagram the last).  A report block (of an SR or RR) whose SSRC_n is bound in r_tx is that
+ *   stream's feedback, counted blocks: d_feedback[stream] = {seen, fraction_lost, cum_lost (24 bits sign-extended), ext_high_seq, jitter,
+ *   lsr, dlsr, rtt}, rtt = mid32(now) - lsr - dlsr in 1 / 65536 s, 0 where that is negative as int32, -1 where lsr == 0; the highest
+ *   datagram index wins, inside a datagram the last such block; seen = the blocks the stream got in the call, | 1 << 30 if a BYE (PT 203)
+ *   in the call lists the stream's SSRC of r_rx (counted bye per listed SSRC found).  EVERY row of d_feedback [n_streams] is written: a
+ *   row without a block is {seen = 0 or 1 << 30, 0, 0, 0, 0, 0, 0, rtt = -1}.  SDES, APP and every other packet type are skipped by
+ *   length and counted skipped.  The result does not depend on the order of the datagrams except through the index rule.
+ *   -1 with nothing enqueued: NULL c, r_rx, d_feedback or d_count; a session with another stream count; n_dgrams < 0 or wire_bytes < 0;
+ *   n_dgrams > 0 with NULL d_dgrams or d_wire; d_dgrams, d_feedback not 4-byte, d_now_ntp or d_count not 8-byte aligned.  Three kernels;
+ *   the scratch (4 bytes per datagram) grows like that of solo_rtcp_received: capturable with n_dgrams frozen
+ *   (tests/test_gpu_rtcp.py: test_capture_build_and_parse).
+ * Not built: SRTCP, report timing and the choice of whom to report, XR, NACK / PLI / REMB, reduced-size RTCP,
+ * more than one report block per packet, source probation, RTCP state in a migration blob.  INTEGRATION.md section 2 has both ticks. */
+#define SOLO_RTCP_STATE_BYTES 128    /* a row's 32 words */
+#define SOLO_RTCP_CNAME_BYTES 32     /* ... and its CNAME behind them in a state blob */
+#define SOLO_RTCP_WALK_MAX 128       /* datagrams of one stream in one solo_rtcp_received call that a wavefront walks from its segment */
+#define SOLO_RTCP_BYE (1 << 30)      /* solo_rtcp_feedback_t.seen: a BYE named the stream */
+typedef struct solo_rtcp_obj solo_rtcp_t;
+typedef struct { int32_t counted, first, in_order, misordered, dropout_pending, resynced, not_counted, reserved; } solo_rtcp_received_count_t;  /* 32 bytes */
+typedef struct { int32_t sent, skipped, reserved[6]; } solo_rtcp_sent_count_t;                     /* 32 bytes; sent = -1: the records were refused */
+typedef struct { int32_t built, built_needed; int64_t bytes, bytes_needed; int32_t refused, with_sr; } solo_rtcp_build_count_t;   /* 32 bytes; built = -1: list refused */
+typedef struct { int32_t accepted, malformed, version, first_type, length, sr, blocks, unknown_ssrc, bye, skipped, reserved[6]; } solo_rtcp_parse_count_t;  /* 64 bytes */
+typedef struct { int32_t seen, fraction_lost, cum_lost; uint32_t ext_high_seq, jitter, lsr, dlsr; int32_t rtt; } solo_rtcp_feedback_t;    /* 32 bytes */
+/* The object's lifecycle and control plane, then its four device calls. */
+solo_rtcp_t *solo_rtcp_create(int32_t n_streams);
+void    solo_rtcp_destroy(solo_rtcp_t *c);
+int32_t solo_rtcp_reset(solo_rtcp_t *c, void *hip_stream);
+int32_t solo_rtcp_reset_rows(solo_rtcp_t *c, const int32_t *h_rows, int32_t n, void *hip_stream);
+int32_t solo_rtcp_get_state(solo_rtcp_t *c, const int32_t *d_rows, int32_t n, uint8_t *d_blob, void *hip_stream);
+int32_t solo_rtcp_set_state(solo_rtcp_t *c, const int32_t *d_rows, int32_t n, const uint8_t *d_blob, void *hip_stream);
+int32_t solo_rtcp_set_cname(solo_rtcp_t *c, const int32_t *h_streams, int32_t n, const char *h_cname, void *hip_stream);
+int32_t solo_rtcp_received(solo_rtcp_t *c, const solo_rtp_t *r, const solo_arrival_t *d_arrivals, const uint16_t *d_rtp_seq, int32_t n_dgrams,
+                           const uint32_t *d_arrival_time, uint32_t now_rtp, solo_rtcp_received_count_t *d_count, void *hip_stream);
+int32_t solo_rtcp_sent(solo_rtcp_t *c, const solo_rtp_t *r, const solo_arrival_t *d_records, const solo_send_count_t *d_send_count,
+                       int32_t max_records, const solo_dgram_t *d_dgrams, solo_rtcp_sent_count_t *d_count, void *hip_stream);
+int32_t solo_rtcp_build(solo_rtcp_t *c, const solo_rtp_t *r_tx, const solo_rtp_t *r_rx, const int32_t *d_streams, int32_t n, uint64_t now_ntp,
+                        const uint64_t *d_now_ntp, solo_dgram_t *d_dgrams, uint8_t *d_wire, int64_t wire_capacity,
+                        solo_rtcp_build_count_t *d_count, void *hip_stream);
+int32_t solo_rtcp_parse(solo_rtcp_t *c, const solo_rtp_t *r_rx, const solo_rtp_t *r_tx, const solo_dgram_t *d_dgrams, int32_t n_dgrams,
+                        const uint8_t *d_wire, int64_t wire_bytes, uint64_t now_ntp, const uint64_t *d_now_ntp,
+                        solo_rtcp_feedback_t *d_feedback, solo_rtcp_parse_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

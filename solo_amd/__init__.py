@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "solo_rtp_set_trailer", "solo_srtp_set_keys", "solo_srtp_clear_keys", "solo_srtp_get_rx_index", "solo_srtp_protect", "solo_srtp_unprotect",
     "solo_forward_create", "solo_forward_destroy", "solo_forward_reset", "solo_forward_reset_rooms", "solo_forward_get_state",
     "solo_forward_set_state", "solo_forward_levels", "solo_forward_route",
+    "solo_rtcp_create", "solo_rtcp_destroy", "solo_rtcp_reset", "solo_rtcp_reset_rows", "solo_rtcp_get_state", "solo_rtcp_set_state",
+    "solo_rtcp_set_cname", "solo_rtcp_received", "solo_rtcp_sent", "solo_rtcp_build", "solo_rtcp_parse",
 ]
 
 
@@ -168,6 +170,34 @@ class solo_srtp_count_t(C.Structure):
     """datagrams per verdict of a solo_srtp_protect / solo_srtp_unprotect call (include/solo_mi355x.h); 32 bytes; ok = -1: the list behind
     protect's records was refused"""
     _fields_ = [(n, C.c_int32) for n in ("ok", "skipped", "malformed", "unknown_ssrc", "no_key", "auth_failed", "reserved0", "reserved1")]
+
+
+class solo_rtcp_received_count_t(C.Structure):
+    """datagrams per outcome of a solo_rtcp_received call (include/solo_mi355x.h); 32 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("counted", "first", "in_order", "misordered", "dropout_pending", "resynced", "not_counted", "reserved")]
+
+
+class solo_rtcp_sent_count_t(C.Structure):
+    """records of a solo_rtcp_sent call; 32 bytes; sent = -1: the records were refused"""
+    _fields_ = [(n, C.c_int32) for n in ("sent", "skipped") + tuple("reserved%d" % k for k in range(6))]
+
+
+class solo_rtcp_build_count_t(C.Structure):
+    """packets and bytes of a solo_rtcp_build call, written and needed; 32 bytes; built = -1: the list was refused on the device"""
+    _fields_ = [("built", C.c_int32), ("built_needed", C.c_int32), ("bytes", C.c_int64), ("bytes_needed", C.c_int64), ("refused", C.c_int32),
+                ("with_sr", C.c_int32)]
+
+
+class solo_rtcp_parse_count_t(C.Structure):
+    """datagrams per verdict of a solo_rtcp_parse call, then what the accepted ones held; 64 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("accepted", "malformed", "version", "first_type", "length", "sr", "blocks", "unknown_ssrc", "bye",
+                                         "skipped") + tuple("reserved%d" % k for k in range(6))]
+
+
+class solo_rtcp_feedback_t(C.Structure):
+    """what a peer's report block says about one of our streams (solo_rtcp_parse); 32 bytes"""
+    _fields_ = [("seen", C.c_int32), ("fraction_lost", C.c_int32), ("cum_lost", C.c_int32), ("ext_high_seq", C.c_uint32), ("jitter", C.c_uint32),
+                ("lsr", C.c_uint32), ("dlsr", C.c_uint32), ("rtt", C.c_int32)]
 
 
 class solo_forward_row_t(C.Structure):
@@ -355,6 +385,20 @@ def load_library():
     lib.solo_forward_route.restype = C.c_int32
     lib.solo_forward_route.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, (restype, argtypes) in {"create": (C.c_void_p, [C.c_int32]), "destroy": (None, [C.c_void_p]), "reset": (C.c_int32, [C.c_void_p, C.c_void_p]),
+                                      "reset_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+                                      "get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+                                      "set_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+                                      "set_cname": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+                                      "received": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                               C.c_void_p]),
+                                      "sent": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                      "build": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+                                      "parse": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])}.items():
+        f = getattr(lib, "solo_rtcp_" + name)
+        f.restype, f.argtypes = restype, argtypes
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1936,4 +1980,135 @@ class Forward(_RowStateObject):
     def close(self):
         if getattr(self, "h", None):
             self.lib.solo_forward_destroy(self.h)
+            self.h = None
+
+
+RTCP_STATE_BYTES = 128
+RTCP_CNAME_BYTES = 32
+RTCP_WALK_MAX = 128
+RTCP_BYE = 1 << 30
+
+
+class Rtcp(_RowStateObject):
+    """RTCP beside the Rtp sessions of n_streams streams (solo_rtcp_*, include/solo_mi355x.h): received() keeps the reception statistics
+    of RFC 3550 A.1 / A.8 from the arrivals Rtp.parse() wrote, sent() the sender's counts from what Rtp.pack() / protect() left, build()
+    writes one compound SR / RR + SDES packet per listed stream and parse() turns the peers' packets into round-trip time and loss
+    feedback.  The state is 128 bytes a row; a state blob carries the row's CNAME (32 bytes) behind them."""
+
+    COUNT = {"received": solo_rtcp_received_count_t, "sent": solo_rtcp_sent_count_t, "build": solo_rtcp_build_count_t, "parse": solo_rtcp_parse_count_t}
+    PREFIX = "rtcp"
+    state_bytes = RTCP_STATE_BYTES + RTCP_CNAME_BYTES
+
+    def __init__(self, n_streams):
+        self.n_rows = self.n_streams = int(n_streams)
+        if self.n_streams <= 0:
+            raise ValueError("n_streams must be positive")
+        self._create(self.n_streams)
+
+    def _session(self, name, r, optional=False):
+        if r is None and optional:
+            return None
+        if not isinstance(r, Rtp) or r.n_streams != self.n_streams or not r.h:
+            raise ValueError("%s: an Rtp session of %d streams%s" % (name, self.n_streams, " or None" if optional else ""))
+        return r.h
+
+    def _now(self, now_ntp):
+        """the time of a build() / parse() call: an int (64 bits, 32.32) or a CUDA int64 tensor [1] -> (scalar, pointer)"""
+        if getattr(now_ntp, "is_cuda", False):
+            _tensor("now_ntp", now_ntp, self.torch.int64, (1,))
+            return 0, now_ntp.data_ptr()
+        now_ntp = int(now_ntp)
+        if not 0 <= now_ntp < 2 ** 64:
+            raise ValueError("now_ntp: 0 .. 2^64 - 1, or an int64 CUDA tensor [1]")
+        return now_ntp, None
+
+    def set_cname(self, streams, names):
+        """the CNAME of the listed streams (a host sequence inside [0, n_streams), none twice): one str / bytes of 1 .. 31 bytes, or one per
+        listed stream.  Ordered on the current stream; synchronises; not capturable."""
+        idx = _distinct("streams", streams, self.n_streams)
+        if isinstance(names, (str, bytes)):
+            names = [names] * len(idx)
+        raw = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in names]
+        if len(raw) != len(idx) or any(not 1 <= len(x) <= RTCP_CNAME_BYTES - 1 or 0 in x for x in raw):
+            raise ValueError("names: one name of 1 .. %d bytes without a zero byte, or %d of them" % (RTCP_CNAME_BYTES - 1, len(idx)))
+        buf = b"".join(x.ljust(RTCP_CNAME_BYTES, b"\0") for x in raw)
+        self._call("set_cname", (C.c_int32 * len(idx))(*idx), len(idx), buf)
+
+    def received(self, rtp, arrivals, rtp_seq, arrival_time=None, now_rtp=0):
+        """behind rtp.parse(..., rtp_seq=True): arrivals int32 [n,5] and rtp_seq int16 [n] as it wrote them; arrival_time int32 [n] (the 32
+        bits of the caller's clock in RTP timestamp units) or None = every datagram arrived at now_rtp -> count int32 [8] on the device,
+        read with count("received", c).  Enqueued on the current stream; synchronises only when a call has more datagrams than every
+        one before it."""
+        t = self.torch
+        n, _ = _tensor("arrivals", arrivals, t.int32, (None, 5))
+        _tensor("rtp_seq", rtp_seq, t.int16, (n,))
+        _tensor("arrival_time", arrival_time, t.int32, (n,), optional=True)
+        now_rtp = int(now_rtp)
+        if not 0 <= now_rtp < 2 ** 32:
+            raise ValueError("now_rtp: 0 .. 2^32 - 1")
+        count = t.zeros((8,), dtype=t.int32, device=arrivals.device)
+        self._call("received", self._session("rtp", rtp), arrivals.data_ptr() or None, rtp_seq.data_ptr() or None, n, _ptr(arrival_time) or None, now_rtp,
+                   count.data_ptr())
+        return count
+
+    def sent(self, rtp, records, send_count, dgrams):
+        """behind rtp.pack() or rtp.protect(): records int32 [max,5], send_count int32 [8] and dgrams int32 [max,2] as they left them ->
+        count int32 [8] on the device, read with count("sent", c).  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        m, _ = _tensor("records", records, t.int32, (None, 5))
+        _tensor("send_count", send_count, t.int32, (8,))
+        _tensor("dgrams", dgrams, t.int32, (m, 2))
+        if m < 1:
+            raise ValueError("records: at least one")
+        count = t.zeros((8,), dtype=t.int32, device=records.device)
+        self._call("sent", self._session("rtp", rtp), records.data_ptr(), send_count.data_ptr(), m, dgrams.data_ptr(), count.data_ptr())
+        return count
+
+    def build(self, rtp_tx, rtp_rx, streams, now_ntp, dgrams=None, wire=None):
+        """one compound packet (SR or RR, with a report block where rtp_rx is given and the stream has received, then SDES CNAME) per listed
+        stream: streams a strictly increasing host sequence or an int32 CUDA tensor [n]; now_ntp an int (32.32) or an int64 CUDA tensor
+        [1], which a captured call reads at every replay -> (dgrams int32 [n,2], wire uint8 [cap], count int32 [8], read with
+        count("build", c)).  The default wire, 96 bytes a packet, is never too small.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        rows = self._rows(streams)
+        if rows is None:
+            raise ValueError("streams: a list")
+        n = int(rows.shape[0])
+        now, d_now = self._now(now_ntp)
+        _tensor("dgrams", dgrams, t.int32, (n, 2), optional=True)
+        _tensor("wire", wire, t.uint8, (None,), optional=True)
+        if dgrams is None:
+            dgrams = t.zeros((n, 2), dtype=t.int32, device=self.device)
+        if wire is None:
+            wire = t.zeros((96 * n,), dtype=t.uint8, device=self.device)
+        count = t.zeros((8,), dtype=t.int32, device=self.device)
+        self._call("build", self._session("rtp_tx", rtp_tx), self._session("rtp_rx", rtp_rx, optional=True), rows.data_ptr(), n, now, d_now, dgrams.data_ptr(),
+                   wire.data_ptr() or count.data_ptr(), wire.shape[0], count.data_ptr())
+        return dgrams, wire, count
+
+    def parse(self, rtp_rx, rtp_tx, dgrams, wire, now_ntp, feedback=None):
+        """dgrams int32 [n,2] = (offset, len) of received compound packets inside wire uint8 [bytes]; rtp_rx: the session with the peers'
+        SSRCs, rtp_tx (or None): ours -> (feedback int32 [n_streams,8] = solo_rtcp_feedback_t per stream, count int32 [16], read with
+        count("parse", c)).  Enqueued on the current stream; synchronises only when a call has more datagrams than every one before it."""
+        t = self.torch
+        n, _ = _tensor("dgrams", dgrams, t.int32, (None, 2))
+        nbytes, = _tensor("wire", wire, t.uint8, (None,))
+        _tensor("feedback", feedback, t.int32, (self.n_streams, 8), optional=True)
+        now, d_now = self._now(now_ntp)
+        if feedback is None:
+            feedback = t.zeros((self.n_streams, 8), dtype=t.int32, device=self.device)
+        count = t.zeros((16,), dtype=t.int32, device=self.device)
+        self._call("parse", self._session("rtp_rx", rtp_rx), self._session("rtp_tx", rtp_tx, optional=True), dgrams.data_ptr() or None, n,
+                   wire.data_ptr() or None, nbytes, now, d_now, feedback.data_ptr(), count.data_ptr())
+        return feedback, count
+
+    def count(self, which, count):
+        """the count tensor of received() / sent() / build() / parse() as a dict (synchronises)"""
+        if which not in self.COUNT:
+            raise ValueError("which: one of %s" % ", ".join(sorted(self.COUNT)))
+        return {k: v for k, v in _counts(self.COUNT[which], count).items() if not k.startswith("reserved")}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.solo_rtcp_destroy(self.h)
             self.h = None

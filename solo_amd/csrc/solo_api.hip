@@ -43,6 +43,7 @@
 #include "solo_srtp.h"          // SRTP protection of the datagrams of solo_rtp.h (solo_srtp_protect / _unprotect): likewise
 #include "solo_rtp.h"           // RTP framing of the sender's records and parsing of received datagrams (solo_rtp_pack / _parse): likewise
 #include "solo_forward.h"       // forwarding without transcoding: levels per row from arrivals, routing under per-room slots (solo_forward_*): likewise
+#include "solo_rtcp.h"          // RTCP beside the RTP sessions: reception statistics, sender counts, compound packets out and in (solo_rtcp_*): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -1458,6 +1459,109 @@ int32_t solo_forward_route(solo_forward_t* f, const solo_arrival_t* d_arrivals, 
     a.records = d_records; a.send_count = d_send_count; a.level_fwd = d_level_fwd; a.slot_src = d_slot_src; a.count = d_count;
     a.n_dgrams = n_dgrams; a.n = n; a.n_rooms = n_rooms; a.K = f->slots; a.max_records = max_records;
     SOLO_CHECK(solo_forward_route_launch(a, f->d_plan, f->n_rows, f->d_scratch, f->d_verdict, st));
+    return 0;
+}
+
+// ---- RTCP (solo_rtcp.h): a row object beside the RTP sessions; d_extra: the CNAMEs, 8 words a row ------------------------------------------
+static_assert(SX_RTCP_WORDS <= SX_ROWS_MAX_WORDS, "solo_rtcp.h and solo_rows.h agree");
+struct solo_rtcp_obj : solo_rows {   // d_state: SxRtcpRow [n_rows]; d_verdict[2]: the verdict words of received's plan and of build's list
+    void* d_plan;                    // what depends on the rows (solo_rtcp_plan_words): sized at create
+    void* d_scratch;                 // what received and parse keep per datagram (solo_rtcp_scratch_bytes), grown on demand
+    size_t scratch_bytes;
+};
+solo_rtcp_t* solo_rtcp_create(int32_t n_streams) {
+    if (n_streams <= 0 || !have_device()) return NULL;
+    solo_rtcp_obj* c = new (std::nothrow) solo_rtcp_obj();
+    if (!c) return NULL;
+    if (hipMalloc(&c->d_plan, solo_rtcp_plan_words(n_streams) * sizeof(i32)) != hipSuccess || !rows_alloc(c, n_streams, SX_RTCP_WORDS, NULL, 2, SX_RTCP_CNAME_WORDS)) {
+        solo_rtcp_destroy(c);
+        return NULL;
+    }
+    return c;
+}
+void solo_rtcp_destroy(solo_rtcp_t* c) {
+    if (!c) return;
+    rows_free(c);
+    dev_free(c->d_plan);
+    dev_free(c->d_scratch);
+    delete c;
+}
+int32_t solo_rtcp_reset(solo_rtcp_t* c, void* hip_stream) { return rows_reset(c, (hipStream_t)hip_stream); }
+int32_t solo_rtcp_reset_rows(solo_rtcp_t* c, const int32_t* h_rows, int32_t n, void* hip_stream) { return rows_reset_list(c, h_rows, n, (hipStream_t)hip_stream); }
+int32_t solo_rtcp_get_state(solo_rtcp_t* c, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
+    return rows_copy_state(c, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+}
+int32_t solo_rtcp_set_state(solo_rtcp_t* c, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
+    return rows_copy_state(c, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+}
+int32_t solo_rtcp_set_cname(solo_rtcp_t* c, const int32_t* h_streams, int32_t n, const char* h_cname, void* hip_stream) {
+    if (!c || !sx_rtcp_cname_ok(h_streams, n, h_cname, c->n_rows)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipError_t e = hipSuccess;
+    for (int32_t i = 0; i < n && e == hipSuccess; i++)
+        e = hipMemcpyAsync(c->d_extra + (size_t)h_streams[i] * SX_RTCP_CNAME_WORDS, h_cname + (size_t)i * SOLO_RTCP_CNAME_BYTES, SOLO_RTCP_CNAME_BYTES,
+                           hipMemcpyHostToDevice, st);
+    const hipError_t e2 = hipStreamSynchronize(st);         // (the caller's array goes with this call: the copies must have read it)
+    SOLO_CHECK(e);
+    SOLO_CHECK(e2);
+    return 0;
+}
+int32_t solo_rtcp_received(solo_rtcp_t* c, const solo_rtp_t* r, const solo_arrival_t* d_arrivals, const uint16_t* d_rtp_seq, int32_t n_dgrams,
+                           const uint32_t* d_arrival_time, uint32_t now_rtp, solo_rtcp_received_count_t* d_count, void* hip_stream) {
+    if (!r || !sx_rtcp_received_ok(c, c ? c->n_rows : 0, r->n_rows, d_arrivals, d_rtp_seq, n_dgrams, d_arrival_time, d_count)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(c->d_scratch, c->scratch_bytes, solo_rtcp_scratch_bytes(n_dgrams), st));
+    const SxRtcpPlanMem pm = sx_rtcp_plan_mem(c->d_plan, c->n_rows);
+    SxRtcpRecvArgs a;
+    a.arrivals = d_arrivals; a.rtp_seq = d_rtp_seq; a.arrival_time = d_arrival_time; a.cfg = (const SxRtpStream*)r->d_state; a.state = (SxRtcpRow*)c->d_state;
+    a.key = (i32*)c->d_scratch; a.members = a.key + n_dgrams;
+    a.counts = pm.counts; a.starts = pm.starts; a.cursor = pm.cursor; a.big = pm.big; a.count = (i32*)d_count;
+    a.now_rtp = now_rtp; a.n_dgrams = n_dgrams; a.n_streams = c->n_rows; a.packet_samples = r->L;
+    SOLO_CHECK(solo_rtcp_received_launch(a, c->d_verdict, st));
+    return 0;
+}
+int32_t solo_rtcp_sent(solo_rtcp_t* c, const solo_rtp_t* r, const solo_arrival_t* d_records, const solo_send_count_t* d_send_count, int32_t max_records,
+                       const solo_dgram_t* d_dgrams, solo_rtcp_sent_count_t* d_count, void* hip_stream) {
+    if (!r || !sx_rtcp_sent_ok(c, c ? c->n_rows : 0, r->n_rows, d_records, d_send_count, max_records, d_dgrams, d_count)) return -1;
+    SxRtcpSentArgs a;
+    a.records = d_records; a.send_count = d_send_count; a.dgrams = d_dgrams; a.state = (SxRtcpRow*)c->d_state; a.count = (i32*)d_count;
+    a.max_records = max_records; a.n_streams = c->n_rows;
+    SOLO_CHECK(solo_rtcp_sent_launch(a, (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_rtcp_build(solo_rtcp_t* c, const solo_rtp_t* r_tx, const solo_rtp_t* r_rx, const int32_t* d_streams, int32_t n, uint64_t now_ntp,
+                        const uint64_t* d_now_ntp, solo_dgram_t* d_dgrams, uint8_t* d_wire, int64_t wire_capacity, solo_rtcp_build_count_t* d_count,
+                        void* hip_stream) {
+    if (!r_tx || !sx_rtcp_build_ok(c, c ? c->n_rows : 0, r_tx->n_rows, r_rx != NULL, r_rx ? r_rx->n_rows : 0, d_streams, n, d_now_ntp, d_dgrams, d_wire,
+                                   wire_capacity, d_count))
+        return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const SxRtcpPlanMem pm = sx_rtcp_plan_mem(c->d_plan, c->n_rows);
+    SxRtcpBuildArgs a;
+    a.streams = d_streams; a.cfg_tx = (const SxRtpStream*)r_tx->d_state; a.cfg_rx = r_rx ? (const SxRtpStream*)r_rx->d_state : NULL;
+    a.state = (SxRtcpRow*)c->d_state; a.cname = (const u32*)c->d_extra; a.d_now = (const unsigned long long*)d_now_ntp; a.now = now_ntp;
+    a.dgrams = d_dgrams; a.wire = d_wire; a.cap = wire_capacity; a.count = d_count; a.totals = pm.totals; a.bases = pm.bases;
+    a.n = n; a.n_streams = c->n_rows; a.packet_samples = r_tx->L;
+    SOLO_CHECK(launch_list_check(d_streams, n, c->n_rows, c->d_verdict + 1, NULL, st));
+    SOLO_CHECK(solo_rtcp_build_launch(a, c->d_verdict + 1, st));
+    return 0;
+}
+int32_t solo_rtcp_parse(solo_rtcp_t* c, const solo_rtp_t* r_rx, const solo_rtp_t* r_tx, const solo_dgram_t* d_dgrams, int32_t n_dgrams, const uint8_t* d_wire,
+                        int64_t wire_bytes, uint64_t now_ntp, const uint64_t* d_now_ntp, solo_rtcp_feedback_t* d_feedback, solo_rtcp_parse_count_t* d_count,
+                        void* hip_stream) {
+    if (!r_rx || !sx_rtcp_parse_ok(c, c ? c->n_rows : 0, r_rx->n_rows, r_tx != NULL, r_tx ? r_tx->n_rows : 0, d_dgrams, n_dgrams, d_wire, wire_bytes, d_now_ntp,
+                                   d_feedback, d_count))
+        return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    SOLO_CHECK(grow_scratch(c->d_scratch, c->scratch_bytes, solo_rtcp_scratch_bytes(n_dgrams), st));
+    const SxRtcpPlanMem pm = sx_rtcp_plan_mem(c->d_plan, c->n_rows);
+    SxRtcpParseArgs a;
+    a.dgrams = d_dgrams; a.wire = d_wire; a.table_rx = r_rx->d_table; a.table_tx = r_tx ? r_tx->d_table : NULL; a.state = (SxRtcpRow*)c->d_state;
+    a.win = pm.win; a.ok = (i32*)c->d_scratch; a.feedback = d_feedback; a.count = (i32*)d_count;
+    a.d_now = (const unsigned long long*)d_now_ntp; a.now = now_ntp;
+    a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
+    a.n_dgrams = n_dgrams; a.n_streams = c->n_rows;
+    SOLO_CHECK(solo_rtcp_parse_launch(a, st));
     return 0;
 }
 
