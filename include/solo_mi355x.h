@@ -920,7 +920,7 @@ int32_t solo_rtp_parse(solo_rtp_t *r, solo_batch_t *b, const solo_dgram_t *d_dgr
  *   THERE IS NO REPLAY LIST: a replayed datagram reaches the ring, which drops it as duplicate or late.
  *   -1 with nothing enqueued: NULL r or d_count; n_dgrams < 0 or wire_bytes < 0; with n_dgrams > 0 a NULL d_dgrams, d_wire or
  *   d_dgrams_out; d_dgrams, d_dgrams_out or d_count not 4-byte aligned.  Three kernels on hip_stream, no allocation, no host
- *   synchronisation: capturable with n_dgrams frozen.  Not built: SRTCP, MKI, RFC 6904, AES-GCM, AES-256. */
+ *   synchronisation: capturable with n_dgrams frozen.  Not built: MKI, RFC 6904, AES-GCM, AES-256. */
 #define SOLO_SRTP_MASTER_BYTES 30   /* master key (16) || master salt (14): one direction's SDES / DTLS-SRTP keying material */
 typedef struct { int32_t ok, skipped, malformed, unknown_ssrc, no_key, auth_failed, reserved[2]; } solo_srtp_count_t;   /* 32 bytes */
 /* The trailer switch and the key calls of the session, then its two SRTP device calls. */
@@ -1109,7 +1109,7 @@ int32_t solo_forward_route(solo_forward_t *f, const solo_arrival_t *d_arrivals, 
  *   n_dgrams > 0 with NULL d_dgrams or d_wire; d_dgrams, d_feedback not 4-byte, d_now_ntp or d_count not 8-byte aligned.  Three kernels;
  *   the scratch (4 bytes per datagram) grows like that of solo_rtcp_received: capturable with n_dgrams frozen
  *   (tests/test_gpu_rtcp.py: test_capture_build_and_parse).
- * Not built: SRTCP, report timing and the choice of whom to report, XR, NACK / PLI / REMB, reduced-size RTCP,
+ * Not built: report timing and the choice of whom to report, XR, NACK / PLI / REMB, reduced-size RTCP,
  * more than one report block per packet, source probation, RTCP state in a migration blob.  INTEGRATION.md section 2 has both ticks. */
 #define SOLO_RTCP_STATE_BYTES 128    /* a row's 32 words */
 #define SOLO_RTCP_CNAME_BYTES 32     /* ... and its CNAME behind them in a state blob */
@@ -1139,6 +1139,80 @@ int32_t solo_rtcp_build(solo_rtcp_t *c, const solo_rtp_t *r_tx, const solo_rtp_t
 int32_t solo_rtcp_parse(solo_rtcp_t *c, const solo_rtp_t *r_rx, const solo_rtp_t *r_tx, const solo_dgram_t *d_dgrams, int32_t n_dgrams,
                         const uint8_t *d_wire, int64_t wire_bytes, uint64_t now_ntp, const uint64_t *d_now_ntp,
                         solo_rtcp_feedback_t *d_feedback, solo_rtcp_parse_count_t *d_count, void *hip_stream);
+/* SRTCP (RFC 3711 section 3.4): solo_srtcp_protect stands behind solo_rtcp_build and turns the compound packets into SRTCP in place,
+ * solo_srtcp_unprotect stands in front of solo_rtcp_parse and turns the peers' SRTCP datagrams back into RTCP in place, so that a secured
+ * session sends no RTCP in the clear and still walks no packet on the host.  An SRTCP datagram is the compound packet with its first 8
+ * bytes (first header, sender SSRC) in the clear and everything from byte 8 on under AES-128 in counter mode, then ONE big-endian word
+ * E << 31 | index (index: 31 bits; E = 1: encrypted), then the tag.  No MKI.  THE TAG IS ALWAYS 10 BYTES: RFC 3711 section 5.2 and RFC 4568
+ * keep HMAC_SHA1_80 for SRTCP in the _32 suite as well, so there is no tag_bytes argument and the trailer is always
+ * SOLO_SRTCP_TRAILER_BYTES = 4 + 10.  IV = (k_s << 16) ^ (SSRC << 64) ^ (index << 16) with SSRC = bytes 4 .. 8 and index without E;
+ * keystream block j = AES(k_e, IV + j) XORed over bytes [8, len); tag = the first 10 bytes of HMAC-SHA1(k_a, bytes [0, len) as sent ||
+ * the E || index word).  Session keys: the PRF of section 4.3 with rate 0 and index 0 over one direction's 30 bytes of master key ||
+ * master salt, labels 3 (cipher key), 4 (authentication key), 5 (salt).
+ * solo_rtcp_set_trailer -- a host switch on the RTCP object like solo_rtp_set_trailer, 0 .. 16, default 0, read when a solo_rtcp_build call
+ *   is issued: with a trailer T build plans every packet that is not refused as roundup4(len + T), writes the T bytes and the pad behind
+ *   the packet as zero, leaves d_dgrams[i].len = len, counts the trailer in bytes and bytes_needed, and writes a packet iff all of it,
+ *   trailer included, ends inside wire_capacity.  T = 0: every byte, count and state word as without the call.  -1: NULL c, or a value
+ *   outside 0 .. 16.
+ * Control plane, on the solo_rtp_t session beside solo_srtp_* (it has the SSRC table) -- HOST arrays, ordered on hip_stream, the calls
+ * return when the device holds the records.  Per stream: two 256-byte key records as those of SRTP (tag = 10), a send record {uint32
+ * next: the index the next protected packet gets} and a receive record {int64 index: the highest authenticated, -1 = none yet; uint64
+ * pending}.  They are ONE device allocation of their own, made by the first solo_srtcp_set_keys: a session without SRTCP pays nothing,
+ * and solo_srtp_* allocates nothing more than before.  The host keeps "has tx / has rx" per stream and never the keys.
+ *   solo_srtcp_set_keys   h_tx_master / h_rx_master: [n][30] or NULL = that direction keeps what it had; h_tx_index: [n], 0 .. 2^31, NULL
+ *                    = 0 (the RFC's first index); h_rx_index: [n], -1 .. 2^31 - 1, the highest index already authenticated, NULL = -1.
+ *                    Setting a tx key sets the send index, setting an rx key sets the receive record.  -1, nothing changed: NULL r or
+ *                    list; n <= 0, an index outside [0, n_streams) or listed twice; both masters NULL; an initial index outside its range
+ *   solo_srtcp_clear_keys  both keys of the listed streams and their send index are zeroed on the device, the receive record goes back
+ *                    to "none yet".  solo_rtp_unbind does the same for its streams, solo_rtp_destroy zeroes the allocation;
+ *                    solo_srtp_clear_keys does not touch it
+ *   solo_srtcp_get_index  h_tx_next[i] / h_rx_index[i] = send index / receive record of listed stream i (0 / -1 without SRTCP); either may
+ *                    be NULL.  With solo_srtcp_set_keys' two index arrays this is the hand-over to another session
+ * solo_srtcp_protect -- datagram i belongs to d_streams[i], the list the build call had (c: the object that built; its trailer switch
+ *   must stand at 14 or more).  d_build_count->built < 0 (the list was refused on the device): d_count->ok = -1 and no datagram, index
+ *   or byte is touched -- which is also what keeps two lanes from sharing a send index.  d_dgrams[i].len == 0 (refused, or cut by the
+ *   cap): skipped.  Then the FIRST rule that fails, each with a counter: malformed (len < 8; len no multiple of 4; the range or its 14
+ *   trailer bytes outside [0, min(wire_bytes, 2^31 - 1)); a listed stream outside [0, n_streams)), no_key (no tx SRTCP key), exhausted
+ *   (the stream's next is 2^31: the key has protected 2^31 packets and must be changed, RFC 3711 section 9.2).  A datagram that fails
+ *   becomes {0, 0} and does not advance the index: NOTHING OF A SESSION'S LEAVES IN THE CLEAR THROUGH THIS CALL.  Otherwise index = next:
+ *   [8, len) is encrypted, 0x80000000 | index goes to [len, len + 4) and the tag to [len + 4, len + 14), d_dgrams[i].len += 14,
+ *   next += 1.  -1 with nothing enqueued: a NULL pointer; n outside (0, n_streams]; wire_bytes < 0; a session with another stream count;
+ *   a trailer switch of c below 14; d_streams, d_dgrams, d_wire or d_count not 4-byte, d_build_count not 8-byte aligned.  Two kernels (the
+ *   clear of the count, a workgroup per 256 datagrams), no allocation, no host synchronisation: capturable with n frozen, and every
+ *   replay advances the indices, as it must (tests/test_gpu_srtcp.py: test_capture_rtcp_build_and_srtcp_protect).
+ * solo_srtcp_unprotect -- n_dgrams datagrams inside d_wire at any byte alignment, their ranges disjoint.  The FIRST rule that fails:
+ *   malformed (the range outside [0, min(wire_bytes, 2^31 - 1)), or len < 8 + 14), unknown_ssrc (bytes 4 .. 8 are not in r_rx's table:
+ *   the search of solo_rtp_parse), no_key (no rx SRTCP key), replayed, auth_failed.  AUTHENTICATE FIRST: only an accepted datagram
+ *   with E = 1 is decrypted, one with E = 0 is authenticated and left as it is; d_dgrams_out[i] = {offset, len - 14}, ready for
+ *   solo_rtcp_parse (d_dgrams_out may be d_dgrams).  A rejected datagram keeps every wire byte and yields {0, 0}, which parse counts as
+ *   malformed.
+ *   THE REPLAY RULE: A DATAGRAM IS ACCEPTED ONLY IF ITS INDEX IS STRICTLY NEWER THAN EVERYTHING AUTHENTICATED FOR ITS STREAM BEFORE THIS
+ *   CALL -- replayed: index <= the stream's receive record as it stood when the call began.  This is NOT the RFC's 64-packet window:
+ *   RTCP has no ring behind it that would drop a replay, and a report that arrives after a newer one of the same sender is dropped,
+ *   which costs nothing because the newer report supersedes it.  The verdict kernel only reads the record and raises `pending` with a
+ *   64-bit atomic max; a second short kernel, a lane per stream, folds pending into index: the result does not depend on the order
+ *   inside the call.  Two copies of one datagram inside one call both pass (solo_rtcp_parse's highest-index-wins rule makes the second
+ *   harmless, except that `seen` counts it); the result equals a packet-by-packet receiver under the same rule whenever each stream's
+ *   datagrams stand in increasing index order in the call -- so whenever a call holds at most one datagram per stream.  A newer datagram
+ *   IN FRONT of an older one of the same stream lets both pass, where that receiver would drop the older.
+ *   -1 with nothing enqueued: NULL r_rx or d_count; n_dgrams < 0 or wire_bytes < 0; with n_dgrams > 0 a NULL d_dgrams, d_wire or
+ *   d_dgrams_out; d_dgrams, d_dgrams_out or d_count not 4-byte aligned.  Three kernels, no allocation, no host synchronisation:
+ *   capturable with n_dgrams frozen (tests/test_gpu_srtcp.py: test_capture_srtcp_unprotect_and_rtcp_parse).
+ * Not built: the MKI, sending with E = 0, the 64-packet replay window, AES-GCM and AES-256, SRTCP keys and indices
+ * in a migration blob. */
+#define SOLO_SRTCP_TRAILER_BYTES 14  /* the E || index word (4) and the tag (10) behind every SRTCP datagram */
+typedef struct { int32_t ok, skipped, malformed, unknown_ssrc, no_key, auth_failed, replayed, exhausted; } solo_srtcp_count_t;   /* 32 bytes; ok = -1: the list was refused */
+/* The trailer switch of the RTCP object, the key calls of the session, then the two SRTCP device calls. */
+int32_t solo_rtcp_set_trailer(solo_rtcp_t *c, int32_t trailer_bytes);
+int32_t solo_srtcp_set_keys(solo_rtp_t *r, const int32_t *h_streams, int32_t n, const uint8_t *h_tx_master, const uint8_t *h_rx_master,
+                            const uint32_t *h_tx_index, const int64_t *h_rx_index, void *hip_stream);
+int32_t solo_srtcp_clear_keys(solo_rtp_t *r, const int32_t *h_streams, int32_t n, void *hip_stream);
+int32_t solo_srtcp_get_index(solo_rtp_t *r, const int32_t *h_streams, int32_t n, uint32_t *h_tx_next, int64_t *h_rx_index, void *hip_stream);
+int32_t solo_srtcp_protect(const solo_rtcp_t *c, solo_rtp_t *r_tx, const int32_t *d_streams, int32_t n,
+                           const solo_rtcp_build_count_t *d_build_count, solo_dgram_t *d_dgrams, uint8_t *d_wire, int64_t wire_bytes,
+                           solo_srtcp_count_t *d_count, void *hip_stream);
+int32_t solo_srtcp_unprotect(solo_rtp_t *r_rx, const solo_dgram_t *d_dgrams, int32_t n_dgrams, uint8_t *d_wire, int64_t wire_bytes,
+                             solo_dgram_t *d_dgrams_out, solo_srtcp_count_t *d_count, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

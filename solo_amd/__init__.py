@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "solo_forward_set_state", "solo_forward_levels", "solo_forward_route",
     "solo_rtcp_create", "solo_rtcp_destroy", "solo_rtcp_reset", "solo_rtcp_reset_rows", "solo_rtcp_get_state", "solo_rtcp_set_state",
     "solo_rtcp_set_cname", "solo_rtcp_received", "solo_rtcp_sent", "solo_rtcp_build", "solo_rtcp_parse",
+    "solo_rtcp_set_trailer", "solo_srtcp_set_keys", "solo_srtcp_clear_keys", "solo_srtcp_get_index", "solo_srtcp_protect", "solo_srtcp_unprotect",
 ]
 
 
@@ -172,6 +173,12 @@ class solo_srtp_count_t(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("ok", "skipped", "malformed", "unknown_ssrc", "no_key", "auth_failed", "reserved0", "reserved1")]
 
 
+class solo_srtcp_count_t(C.Structure):
+    """datagrams per verdict of a solo_srtcp_protect / solo_srtcp_unprotect call (include/solo_mi355x.h); 32 bytes; ok = -1: the list
+    behind protect's datagrams was refused"""
+    _fields_ = [(n, C.c_int32) for n in ("ok", "skipped", "malformed", "unknown_ssrc", "no_key", "auth_failed", "replayed", "exhausted")]
+
+
 class solo_rtcp_received_count_t(C.Structure):
     """datagrams per outcome of a solo_rtcp_received call (include/solo_mi355x.h); 32 bytes"""
     _fields_ = [(n, C.c_int32) for n in ("counted", "first", "in_order", "misordered", "dropout_pending", "resynced", "not_counted", "reserved")]
@@ -213,6 +220,7 @@ class solo_forward_count_t(C.Structure):
 
 
 SRTP_MASTER_BYTES = 30
+SRTCP_TRAILER_BYTES = 14
 RECV_REPORT_CLEAR_MARGIN = 1
 
 _lib = None
@@ -399,6 +407,18 @@ def load_library():
                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])}.items():
         f = getattr(lib, "solo_rtcp_" + name)
         f.restype, f.argtypes = restype, argtypes
+    lib.solo_rtcp_set_trailer.restype = C.c_int32
+    lib.solo_rtcp_set_trailer.argtypes = [C.c_void_p, C.c_int32]
+    lib.solo_srtcp_set_keys.restype = C.c_int32
+    lib.solo_srtcp_set_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_srtcp_clear_keys.restype = C.c_int32
+    lib.solo_srtcp_clear_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_srtcp_get_index.restype = C.c_int32
+    lib.solo_srtcp_get_index.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_srtcp_protect.restype = C.c_int32
+    lib.solo_srtcp_protect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.solo_srtcp_unprotect.restype = C.c_int32
+    lib.solo_srtcp_unprotect.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_resample_rows.restype = C.c_int32
     lib.solo_resample_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_batch_set_async_join.restype = C.c_int32
@@ -1873,6 +1893,87 @@ class Rtp(_RowObject):
         """the count tensor of protect() / unprotect() as a dict (synchronises); ok == -1: the list behind protect's records was refused"""
         return _counts(solo_srtp_count_t, count)
 
+    # ---- SRTCP (solo_srtcp_*): RTCP keys and indices per stream, protect_rtcp() behind Rtcp.build(), unprotect_rtcp() in front of Rtcp.parse() ----
+    def set_rtcp_keys(self, streams, tx=None, rx=None, tx_index=None, rx_index=None):
+        """SRTCP keys of the listed streams (a host sequence inside [0, n_streams), none twice): tx / rx = 30 bytes of keying material per
+        listed stream (master key || master salt) or None = that direction keeps what it had; tx_index: the index the next protected
+        packet gets, 0 .. 2^31, a scalar or one per listed stream (None: 0); rx_index: the highest index already authenticated, -1 ..
+        2^31 - 1, likewise (None: -1, none yet).  The tag is always 10 bytes.  Ordered on the current stream; synchronises; not
+        capturable."""
+        idx = _distinct("streams", streams, self.n_streams)
+        n = len(idx)
+        txa, rxa = self._masters("tx", tx, n), self._masters("rx", rx, n)
+        if txa is None and rxa is None:
+            raise ValueError("at least one of tx and rx")
+        ti = None if tx_index is None else (C.c_uint32 * n)(*self._per_stream(tx_index, n, "tx_index", 2 ** 31))
+        ri = None if rx_index is None else (C.c_int64 * n)(*[v - 1 for v in self._per_stream(self._plus_one(rx_index), n, "rx_index + 1", 2 ** 31)])
+        self._call("set_keys", (C.c_int32 * n)(*idx), n, txa, rxa, ti, ri, prefix="srtcp")
+
+    @staticmethod
+    def _plus_one(v):
+        """rx_index (-1 = none yet) moved to 0 .. 2^31 for the range check of _per_stream; what is no integer goes through and is refused there"""
+        try:
+            return [int(x) + 1 for x in (v.tolist() if hasattr(v, "tolist") else v)] if hasattr(v, "__len__") else int(v) + 1
+        except (TypeError, ValueError):
+            return None
+
+    def clear_rtcp_keys(self, streams):
+        """both SRTCP keys, the send index and the receive index of the listed streams go; unbind() does the same"""
+        idx = _distinct("streams", streams, self.n_streams)
+        self._call("clear_keys", (C.c_int32 * len(idx))(*idx), len(idx), prefix="srtcp")
+
+    def rtcp_index(self, streams=None):
+        """(tx_next, rx_index) of the listed streams (None: all): the index the next protected packet gets, and the highest authenticated
+        one, -1 = none yet (synchronises).  With set_rtcp_keys(tx_index=, rx_index=) the hand-over to another session."""
+        idx = list(range(self.n_streams)) if streams is None else _distinct("streams", streams, self.n_streams)
+        tx, rx = (C.c_uint32 * len(idx))(), (C.c_int64 * len(idx))()
+        self._call("get_index", (C.c_int32 * len(idx))(*idx), len(idx), tx, rx, prefix="srtcp")
+        return list(tx), list(rx)
+
+    def protect_rtcp(self, rtcp, streams, build_count, dgrams, wire):
+        """behind rtcp.build(self, ..., streams, ...) -> (dgrams, wire, build_count) with rtcp.set_trailer(14) or more: the compound
+        packets become SRTCP in place (bytes from 8 on encrypted, E || index and the tag in the trailer, dgrams[i].len grown by 14, the
+        stream's send index advanced); a packet of a stream without a tx key, or whose key is used up, becomes (0, 0).  streams: the int32
+        CUDA tensor [n] the build call had -> count int32 [8] on the device, read with srtcp_count().  Enqueued on the current stream,
+        no synchronisation."""
+        t = self.torch
+        if not isinstance(rtcp, Rtcp) or rtcp.n_streams != self.n_streams or not rtcp.h:
+            raise ValueError("rtcp: an Rtcp object of %d streams" % self.n_streams)
+        if rtcp.trailer < SRTCP_TRAILER_BYTES:
+            raise ValueError("rtcp: set_trailer(%d) or more before the build call" % SRTCP_TRAILER_BYTES)
+        n, = _tensor("streams", streams, t.int32, (None,))
+        if not 0 < n <= self.n_streams:
+            raise ValueError("streams: 1 .. %d indices" % self.n_streams)
+        _tensor("build_count", build_count, t.int32, (8,))
+        _tensor("dgrams", dgrams, t.int32, (n, 2))
+        nbytes, = _tensor("wire", wire, t.uint8, (None,))
+        count = t.zeros((8,), dtype=t.int32, device=dgrams.device)
+        r = self.lib.solo_srtcp_protect(rtcp.h, self.h, streams.data_ptr(), n, build_count.data_ptr(), dgrams.data_ptr(), wire.data_ptr() or count.data_ptr(),
+                                        nbytes, count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_srtcp_protect -> %d" % r)
+        return count
+
+    def unprotect_rtcp(self, dgrams, wire, dgrams_out=None):
+        """in front of Rtcp.parse(self, ...): dgrams int32 [n,2] of received SRTCP datagrams inside wire -> (dgrams_out int32 [n,2] for
+        parse(): the compound packet of an accepted datagram, decrypted in place, (0, 0) for a rejected one, whose bytes stay as they
+        were; count int32 [8] on the device, read with srtcp_count()).  A datagram is accepted only if its index is newer than everything
+        authenticated for its stream before this call.  dgrams_out may be dgrams.  Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        n, _ = _tensor("dgrams", dgrams, t.int32, (None, 2))
+        nbytes, = _tensor("wire", wire, t.uint8, (None,))
+        _tensor("dgrams_out", dgrams_out, t.int32, (n, 2), optional=True)
+        if dgrams_out is None:
+            dgrams_out = t.zeros((n, 2), dtype=t.int32, device=dgrams.device)
+        count = t.zeros((8,), dtype=t.int32, device=dgrams.device)
+        self._call("unprotect", dgrams.data_ptr() or count.data_ptr(), n, wire.data_ptr() or count.data_ptr(), nbytes,
+                   dgrams_out.data_ptr() or count.data_ptr(), count.data_ptr(), prefix="srtcp")
+        return dgrams_out, count
+
+    def srtcp_count(self, count):
+        """the count tensor of protect_rtcp() / unprotect_rtcp() as a dict (synchronises); ok == -1: the list behind the build was refused"""
+        return _counts(solo_srtcp_count_t, count)
+
     def pack_count(self, count):
         """the count tensor of pack() as a dict (synchronises); dgrams == -1: the list behind the records was refused on the device"""
         return _counts(solo_rtp_pack_count_t, count)
@@ -2001,9 +2102,21 @@ class Rtcp(_RowStateObject):
 
     def __init__(self, n_streams):
         self.n_rows = self.n_streams = int(n_streams)
+        self.trailer = 0
         if self.n_streams <= 0:
             raise ValueError("n_streams must be positive")
         self._create(self.n_streams)
+
+    def set_trailer(self, trailer_bytes):
+        """bytes build() keeps free (and zero) behind every packet: the room of the SRTCP trailer (Rtp.protect_rtcp() needs 14), 0 .. 16;
+        dgrams[i].len stays the compound packet's, the offsets and byte counts include the trailer.  Read by the next build()."""
+        trailer_bytes = int(trailer_bytes)
+        if not 0 <= trailer_bytes <= 16:
+            raise ValueError("trailer_bytes: 0 .. 16")
+        r = self.lib.solo_rtcp_set_trailer(self.h, trailer_bytes)
+        if r:
+            raise RuntimeError("solo_rtcp_set_trailer -> %d" % r)
+        self.trailer = trailer_bytes
 
     def _session(self, name, r, optional=False):
         if r is None and optional:
@@ -2068,7 +2181,7 @@ class Rtcp(_RowStateObject):
         """one compound packet (SR or RR, with a report block where rtp_rx is given and the stream has received, then SDES CNAME) per listed
         stream: streams a strictly increasing host sequence or an int32 CUDA tensor [n]; now_ntp an int (32.32) or an int64 CUDA tensor
         [1], which a captured call reads at every replay -> (dgrams int32 [n,2], wire uint8 [cap], count int32 [8], read with
-        count("build", c)).  The default wire, 96 bytes a packet, is never too small.  Enqueued on the current stream, no synchronisation."""
+        count("build", c)).  The default wire, 96 bytes a packet and the trailer of set_trailer(), is never too small.  Enqueued on the current stream, no synchronisation."""
         t = self.torch
         rows = self._rows(streams)
         if rows is None:
@@ -2080,7 +2193,7 @@ class Rtcp(_RowStateObject):
         if dgrams is None:
             dgrams = t.zeros((n, 2), dtype=t.int32, device=self.device)
         if wire is None:
-            wire = t.zeros((96 * n,), dtype=t.uint8, device=self.device)
+            wire = t.zeros(((96 + 4 * ((getattr(self, "trailer", 0) + 3) // 4)) * n,), dtype=t.uint8, device=self.device)
         count = t.zeros((8,), dtype=t.int32, device=self.device)
         self._call("build", self._session("rtp_tx", rtp_tx), self._session("rtp_rx", rtp_rx, optional=True), rows.data_ptr(), n, now, d_now, dgrams.data_ptr(),
                    wire.data_ptr() or count.data_ptr(), wire.shape[0], count.data_ptr())

@@ -43,6 +43,7 @@
 #include "solo_srtp.h"          // SRTP protection of the datagrams of solo_rtp.h (solo_srtp_protect / _unprotect): likewise
 #include "solo_rtp.h"           // RTP framing of the sender's records and parsing of received datagrams (solo_rtp_pack / _parse): likewise
 #include "solo_forward.h"       // forwarding without transcoding: levels per row from arrivals, routing under per-room slots (solo_forward_*): likewise
+#include "solo_srtcp.h"         // SRTCP protection of the compound packets of solo_rtcp.h (solo_srtcp_protect / _unprotect): likewise
 #include "solo_rtcp.h"          // RTCP beside the RTP sessions: reception statistics, sender counts, compound packets out and in (solo_rtcp_*): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
@@ -1226,6 +1227,9 @@ struct solo_rtp_obj : solo_rows {    // d_state: SxRtpStream [n_rows]
     SxSrtpKey* d_keys;               // [n_rows][2]: tx, rx
     SxSrtpRx* d_rx;                  // [n_rows]
     SxSrtpMirror srtp;
+    // SRTCP (solo_srtcp.h): ONE allocation (SxSrtcpMem) made by the first solo_srtcp_set_keys.  The mirror holds "has tx / has rx"
+    void* d_srtcp;
+    SxSrtcpMirror srtcp;
 };
 solo_rtp_t* solo_rtp_create(int32_t n_streams, int32_t packet_samples) {
     if (n_streams <= 0 || (packet_samples != 320 && packet_samples != 640 && packet_samples != 1280) || !have_device()) return NULL;
@@ -1248,8 +1252,13 @@ void solo_rtp_destroy(solo_rtp_t* r) {
         (void)hipMemset(r->d_keys, 0, 2 * (size_t)r->n_rows * sizeof(SxSrtpKey));
         (void)hipDeviceSynchronize();
     }
+    if (r->d_srtcp) {
+        (void)hipMemset(r->d_srtcp, 0, sx_srtcp_bytes(r->n_rows));
+        (void)hipDeviceSynchronize();
+    }
     dev_free(r->d_keys);
     dev_free(r->d_rx);
+    dev_free(r->d_srtcp);
     rows_free(r);
     dev_free(r->d_table);
     dev_free(r->d_scratch);
@@ -1286,12 +1295,26 @@ static int32_t srtp_clear(solo_rtp_obj* r, const int32_t* h_streams, int32_t n, 
     }
     return 0;
 }
+// SRTCP likewise: both keys and the send index to zero, the receive record to "none yet"
+static int32_t srtcp_clear(solo_rtp_obj* r, const int32_t* h_streams, int32_t n, hipStream_t st) {
+    if (!r->d_srtcp) return 0;
+    const SxSrtcpMem m = sx_srtcp_mem(r->d_srtcp, r->n_rows);
+    for (int32_t i = 0; i < n; i++) {
+        SOLO_CHECK(hipMemsetAsync(m.keys + 2 * (size_t)h_streams[i], 0, 2 * sizeof(SxSrtpKey), st));
+        SOLO_CHECK(hipMemsetAsync(m.tx + h_streams[i], 0, sizeof(SxSrtcpTx), st));
+        SOLO_CHECK(hipMemsetAsync(&m.rx[h_streams[i]].index, 0xFF, sizeof(i64), st));                                // index = -1
+        SOLO_CHECK(hipMemsetAsync(&m.rx[h_streams[i]].pending, 0, sizeof(u64), st));
+        r->srtcp.has_tx[(size_t)h_streams[i]] = 0; r->srtcp.has_rx[(size_t)h_streams[i]] = 0;
+    }
+    return 0;
+}
 int32_t solo_rtp_unbind(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
     std::vector<u32> table;
     SxRtpMirror next;
     if (!r || !sx_rtp_unbind_plan(r->mirror, h_streams, n, next, table)) return -1;
     int32_t e = rows_reset_list(r, h_streams, n, (hipStream_t)hip_stream);
     if (e == 0) e = srtp_clear(r, h_streams, n, (hipStream_t)hip_stream);             // (a slot taken by the next bind inherits no key)
+    if (e == 0) e = srtcp_clear(r, h_streams, n, (hipStream_t)hip_stream);
     if (e == 0) e = rtp_upload_table(r, table, (hipStream_t)hip_stream);
     if (e == 0) r->mirror.cfg.swap(next.cfg);
     return e;
@@ -1468,6 +1491,7 @@ struct solo_rtcp_obj : solo_rows {   // d_state: SxRtcpRow [n_rows]; d_verdict[2
     void* d_plan;                    // what depends on the rows (solo_rtcp_plan_words): sized at create
     void* d_scratch;                 // what received and parse keep per datagram (solo_rtcp_scratch_bytes), grown on demand
     size_t scratch_bytes;
+    int32_t trailer;                 // solo_rtcp_set_trailer
 };
 solo_rtcp_t* solo_rtcp_create(int32_t n_streams) {
     if (n_streams <= 0 || !have_device()) return NULL;
@@ -1541,7 +1565,7 @@ int32_t solo_rtcp_build(solo_rtcp_t* c, const solo_rtp_t* r_tx, const solo_rtp_t
     a.streams = d_streams; a.cfg_tx = (const SxRtpStream*)r_tx->d_state; a.cfg_rx = r_rx ? (const SxRtpStream*)r_rx->d_state : NULL;
     a.state = (SxRtcpRow*)c->d_state; a.cname = (const u32*)c->d_extra; a.d_now = (const unsigned long long*)d_now_ntp; a.now = now_ntp;
     a.dgrams = d_dgrams; a.wire = d_wire; a.cap = wire_capacity; a.count = d_count; a.totals = pm.totals; a.bases = pm.bases;
-    a.n = n; a.n_streams = c->n_rows; a.packet_samples = r_tx->L;
+    a.n = n; a.n_streams = c->n_rows; a.packet_samples = r_tx->L; a.trailer = c->trailer;
     SOLO_CHECK(launch_list_check(d_streams, n, c->n_rows, c->d_verdict + 1, NULL, st));
     SOLO_CHECK(solo_rtcp_build_launch(a, c->d_verdict + 1, st));
     return 0;
@@ -1562,6 +1586,93 @@ int32_t solo_rtcp_parse(solo_rtcp_t* c, const solo_rtp_t* r_rx, const solo_rtp_t
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n_dgrams = n_dgrams; a.n_streams = c->n_rows;
     SOLO_CHECK(solo_rtcp_parse_launch(a, st));
+    return 0;
+}
+
+// ---- SRTCP (solo_srtcp.h): the session's RTCP keys and indices, protect behind solo_rtcp_build, unprotect in front of solo_rtcp_parse -------
+int32_t solo_rtcp_set_trailer(solo_rtcp_t* c, int32_t trailer_bytes) {
+    if (!c || !sx_srtcp_trailer_ok(trailer_bytes)) return -1;
+    c->trailer = trailer_bytes;
+    return 0;
+}
+int32_t solo_srtcp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_tx_index,
+                            const int64_t* h_rx_index, void* hip_stream) {
+    std::vector<SxSrtpKey> recs;
+    std::vector<SxSrtcpTx> tx;
+    std::vector<SxSrtcpRx> rx;
+    SxSrtcpMirror next;
+    if (!r || !sx_srtcp_set_keys_plan(r->srtcp, r->n_rows, h_streams, n, h_tx_master, h_rx_master, h_tx_index, (const i64*)h_rx_index, next, recs, tx, rx)) return -1;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!r->d_srtcp) {               // the first call: every record "no key", every send index 0, every receive record "none yet"
+        const size_t bytes = sx_srtcp_bytes(r->n_rows);
+        std::vector<u8> init(bytes);
+        sx_srtcp_mem_init(init.data(), r->n_rows);
+        if (hipMalloc(&r->d_srtcp, bytes) != hipSuccess || hipMemcpy(r->d_srtcp, init.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            dev_free(r->d_srtcp);
+            sx_srtp_wipe(recs);
+            return -2;
+        }
+        r->srtcp.has_tx.assign((size_t)r->n_rows, 0); r->srtcp.has_rx.assign((size_t)r->n_rows, 0);
+    }
+    const SxSrtcpMem m = sx_srtcp_mem(r->d_srtcp, r->n_rows);
+    hipError_t e = hipSuccess;
+    for (int32_t i = 0; i < n && e == hipSuccess; i++) {
+        const size_t s = (size_t)h_streams[i];
+        if (h_tx_master) e = hipMemcpyAsync(m.keys + 2 * s, &recs[2 * (size_t)i], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (h_tx_master && e == hipSuccess) e = hipMemcpyAsync(m.tx + s, &tx[(size_t)i], sizeof(SxSrtcpTx), hipMemcpyHostToDevice, st);
+        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(m.keys + 2 * s + 1, &recs[2 * (size_t)i + 1], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(m.rx + s, &rx[(size_t)i], sizeof(SxSrtcpRx), hipMemcpyHostToDevice, st);
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);         // (the host records go with this call: the copies must have read them)
+    sx_srtp_wipe(recs);
+    if (e != hipSuccess || e2 != hipSuccess) return -(int32_t)(e != hipSuccess ? e : e2);
+    r->srtcp.has_tx.swap(next.has_tx); r->srtcp.has_rx.swap(next.has_rx);
+    return 0;
+}
+int32_t solo_srtcp_clear_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
+    if (!r || !sx_list_ok(h_streams, n, r->n_rows)) return -1;
+    const int32_t e = srtcp_clear(r, h_streams, n, (hipStream_t)hip_stream);
+    SOLO_CHECK(hipStreamSynchronize((hipStream_t)hip_stream));
+    return e;
+}
+int32_t solo_srtcp_get_index(solo_rtp_t* r, const int32_t* h_streams, int32_t n, uint32_t* h_tx_next, int64_t* h_rx_index, void* hip_stream) {
+    if (!r || !sx_list_ok(h_streams, n, r->n_rows)) return -1;
+    for (int32_t i = 0; i < n; i++) {
+        if (h_tx_next) h_tx_next[i] = 0;
+        if (h_rx_index) h_rx_index[i] = -1;
+    }
+    if (!r->d_srtcp) return 0;
+    const SxSrtcpMem m = sx_srtcp_mem(r->d_srtcp, r->n_rows);
+    hipStream_t st = (hipStream_t)hip_stream;
+    for (int32_t i = 0; i < n; i++) {
+        if (h_tx_next) SOLO_CHECK(hipMemcpyAsync(&h_tx_next[i], &m.tx[h_streams[i]].next, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (h_rx_index) SOLO_CHECK(hipMemcpyAsync(&h_rx_index[i], &m.rx[h_streams[i]].index, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    }
+    SOLO_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+int32_t solo_srtcp_protect(const solo_rtcp_t* c, solo_rtp_t* r_tx, const int32_t* d_streams, int32_t n, const solo_rtcp_build_count_t* d_build_count,
+                           solo_dgram_t* d_dgrams, uint8_t* d_wire, int64_t wire_bytes, solo_srtcp_count_t* d_count, void* hip_stream) {
+    if (!sx_srtcp_protect_ok(c, c ? c->n_rows : 0, c ? c->trailer : 0, r_tx, r_tx ? r_tx->n_rows : 0, d_streams, n, d_build_count, d_dgrams, d_wire, wire_bytes,
+                             d_count))
+        return -1;
+    const SxSrtcpMem m = sx_srtcp_mem(r_tx->d_srtcp, r_tx->n_rows);
+    SxSrtcpProtectArgs a;
+    a.streams = d_streams; a.build_count = d_build_count; a.dgrams = d_dgrams; a.wire = d_wire; a.keys = m.keys; a.tx = m.tx;
+    a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
+    a.n = n; a.n_streams = r_tx->n_rows;
+    SOLO_CHECK(solo_srtcp_protect_launch(a, d_count, (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_srtcp_unprotect(solo_rtp_t* r_rx, const solo_dgram_t* d_dgrams, int32_t n_dgrams, uint8_t* d_wire, int64_t wire_bytes, solo_dgram_t* d_dgrams_out,
+                             solo_srtcp_count_t* d_count, void* hip_stream) {
+    if (!sx_srtcp_unprotect_ok(r_rx, d_dgrams, n_dgrams, d_wire, wire_bytes, d_dgrams_out, d_count)) return -1;
+    const SxSrtcpMem m = sx_srtcp_mem(r_rx->d_srtcp, r_rx->n_rows);
+    SxSrtcpUnprotectArgs a;
+    a.dgrams = d_dgrams; a.out = d_dgrams_out; a.wire = d_wire; a.table = r_rx->d_table; a.keys = m.keys; a.rx = m.rx;
+    a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
+    a.n_dgrams = n_dgrams; a.n_streams = r_rx->n_rows;
+    SOLO_CHECK(solo_srtcp_unprotect_launch(a, d_count, (hipStream_t)hip_stream));
     return 0;
 }
 

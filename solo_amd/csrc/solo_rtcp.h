@@ -23,7 +23,8 @@
 // Linear in the datagrams; a flooding stream costs one more pass over the keys and a serial walk of its own datagrams.
 //
 // Sent: a clear, then a lane per record with atomic add / max on the row.  Build: the list check of every device list, then the three
-// passes of solo_rtp_pack (tile totals, one wavefront scans them, the tile again: a lane writes its packet, at most 96 bytes).  Parse:
+// passes of solo_rtp_pack (tile totals, one wavefront scans them, the tile again: a lane writes its packet, at most 96 bytes, and behind it
+// the zeroed room solo_rtcp_set_trailer asked for: that of the SRTCP trailer, solo_srtcp.h).  Parse:
 // a lane per datagram validates (A.2) and votes -- atomicMax of the datagram index per stream for SRs and for report blocks --, then the
 // same walk again in which the winners write; a lane per row fills the feedback rows nobody won.
 //
@@ -390,6 +391,7 @@ struct SxRtcpBuildArgs {
     SxRtpDgram* dgrams; u8* wire; i64 cap; SxRtcpBuildCount* count;
     i32* totals; i64* bases;                                                             // [tiles][3], [tiles]: the object's
     int n, n_streams, packet_samples;
+    int trailer = 0;                                        // bytes kept free behind every packet (solo_rtcp_set_trailer: the SRTCP trailer's room), written as zero
 };
 static inline bool sx_rtcp_build_ok(const void* c, int n_streams, int tx_streams, bool has_rx, int rx_streams, const void* streams, int n, const void* d_now,
                                     const void* dgrams, const void* wire, long long cap, const void* count) {
@@ -418,6 +420,8 @@ SX_HD SxRtcpPlan sx_rtcp_build_plan(const SxRtcpBuildArgs& a, int i) {
     p.len = (p.sr ? 28 : 8) + 24 * p.rb + sx_rtcp_sdes_bytes(p.name_len);
     return p;
 }
+// what a packet of len bytes takes of the wire: itself, the trailer and the pad bytes up to a multiple of 4 (0 for a refused stream)
+SX_HD i32 sx_rtcp_padded(const SxRtcpBuildArgs& a, i32 len) { return len > 0 ? sx_rtp_roundup4(len + a.trailer) : 0; }
 SX_HD unsigned long long sx_rtcp_now(const unsigned long long* d_now, unsigned long long now) { return d_now ? *d_now : now; }
 // ... second half: the bytes at dst (4-byte aligned), and the row's state behind a written packet
 SX_HD void sx_rtcp_build_write(const SxRtcpBuildArgs& a, int i, const SxRtcpPlan& p, u8* dst) {
@@ -464,6 +468,7 @@ SX_HD void sx_rtcp_build_write(const SxRtcpBuildArgs& a, int i, const SxRtcpPlan
     b[0] = 1; b[1] = (u8)p.name_len;
     for (int k = 0; k < p.name_len; k++) b[2 + k] = name[k];
     for (int k = 2 + p.name_len; k < sdes - 8; k++) b[k] = 0;
+    for (int k = p.len / 4; k < sx_rtcp_padded(a, p.len) / 4; k++) d[k] = 0;     // (the trailer and its pad: whole dwords, none without a trailer)
     r.tx_since = 0;
 }
 #if defined(__HIPCC__)
@@ -473,7 +478,7 @@ __global__ void __launch_bounds__(SX_RTCP_TILE) solo_rtcp_build_totals_kernel(co
     const int i = (int)blockIdx.x * SX_RTCP_TILE + (int)threadIdx.x;
     i32 len = 0, listed = 0;
     if (i < a.n) { len = sx_rtcp_build_plan(a, i).len; listed = 1; }
-    const i32 valid = wg_sum(len > 0 ? 1 : 0, red), refused = wg_sum(listed && len == 0 ? 1 : 0, red), bytes = wg_sum(len, red);
+    const i32 valid = wg_sum(len > 0 ? 1 : 0, red), refused = wg_sum(listed && len == 0 ? 1 : 0, red), bytes = wg_sum(sx_rtcp_padded(a, len), red);
     if (threadIdx.x == 0) { a.totals[blockIdx.x * 3 + 0] = valid; a.totals[blockIdx.x * 3 + 1] = refused; a.totals[blockIdx.x * 3 + 2] = bytes; }
 }
 __global__ void __launch_bounds__(64) solo_rtcp_build_scan_kernel(const SxRtcpBuildArgs a, int n_tiles, const u32* verdict) {
@@ -503,14 +508,15 @@ __global__ void __launch_bounds__(SX_RTCP_TILE) solo_rtcp_build_kernel(const SxR
     const int i = (int)blockIdx.x * SX_RTCP_TILE + (int)threadIdx.x;
     SxRtcpPlan p; p.len = 0; p.sr = 0; p.rb = 0; p.name_len = 0;
     if (i < a.n) p = sx_rtcp_build_plan(a, i);
-    const i32 incl = wg_scan_incl(p.len, part);
+    const i32 padded = sx_rtcp_padded(a, p.len);
+    const i32 incl = wg_scan_incl(padded, part);
     bool written = false;
     if (i < a.n) {
-        const i64 off = a.bases[blockIdx.x] + (i64)(incl - p.len);
-        written = sx_rtp_pack_emit(a.dgrams, i, p.len, p.len, off, a.cap);
+        const i64 off = a.bases[blockIdx.x] + (i64)(incl - padded);
+        written = sx_rtp_pack_emit(a.dgrams, i, p.len, padded, off, a.cap);
         if (written) sx_rtcp_build_write(a, i, p, a.wire + off);
     }
-    const i32 n_written = wg_sum(written ? 1 : 0, red), n_sr = wg_sum(written && p.sr ? 1 : 0, red), bytes = wg_sum(written ? p.len : 0, red);
+    const i32 n_written = wg_sum(written ? 1 : 0, red), n_sr = wg_sum(written && p.sr ? 1 : 0, red), bytes = wg_sum(written ? padded : 0, red);
     if (threadIdx.x == 0 && n_written) {
         atomicAdd(&a.count->built, n_written);
         if (n_sr) atomicAdd(&a.count->with_sr, n_sr);
@@ -540,11 +546,12 @@ static inline bool sx_rtcp_build_host(SxRtcpBuildArgs a) {
     }
     for (int i = 0; i < a.n; i++) {
         const SxRtcpPlan& p = plans[i];
-        if (sx_rtp_pack_emit(a.dgrams, i, p.len, p.len, c.bytes_needed, a.cap)) {
+        const i32 padded = sx_rtcp_padded(a, p.len);
+        if (sx_rtp_pack_emit(a.dgrams, i, p.len, padded, c.bytes_needed, a.cap)) {
             sx_rtcp_build_write(a, i, p, a.wire + c.bytes_needed);
-            c.built++; c.bytes += p.len; c.with_sr += p.sr;
+            c.built++; c.bytes += padded; c.with_sr += p.sr;
         }
-        c.bytes_needed += p.len;
+        c.bytes_needed += padded;
     }
     *a.count = c;
     return true;

@@ -223,14 +223,15 @@ static inline void sx_hmac_midstates(const u8* key, int n, u32* mid_i, u32* mid_
         sx_sha1_compress(h, w);
     }
 }
-// one direction's 30 bytes of keying material (master key || master salt) -> its record; ke / ks / ka: where the test wants the session keys
-static inline void sx_srtp_make_key(const u8* master, int tag_bytes, SxSrtpKey* rec, u8* ke_out, u8* ks_out, u8* ka_out) {
+// one direction's 30 bytes of keying material (master key || master salt) -> its record; ke / ks / ka: where the test wants the session keys.
+// label: that of the cipher key, with the authentication key and the salt behind it (0, 1, 2 for SRTP; 3, 4, 5 for SRTCP, solo_srtcp.h)
+static inline void sx_srtp_make_key_at(const u8* master, int label, int tag_bytes, SxSrtpKey* rec, u8* ke_out, u8* ks_out, u8* ka_out) {
     u32 mrk[44];
     u8 ke[16], ks[16], ka[20];
     sx_aes_expand(master, mrk);
-    sx_srtp_prf(mrk, master + 16, 0, ke, 16);
-    sx_srtp_prf(mrk, master + 16, 1, ka, 20);
-    sx_srtp_prf(mrk, master + 16, 2, ks, 14);
+    sx_srtp_prf(mrk, master + 16, label, ke, 16);
+    sx_srtp_prf(mrk, master + 16, label + 1, ka, 20);
+    sx_srtp_prf(mrk, master + 16, label + 2, ks, 14);
     ks[14] = ks[15] = 0;
     memset(rec, 0, sizeof(*rec));
     sx_aes_expand(ke, rec->rk);
@@ -246,6 +247,9 @@ static inline void sx_srtp_make_key(const u8* master, int tag_bytes, SxSrtpKey* 
     for (int k = 0; k < 20; k++) z[k] = 0;
     volatile u32* zr = mrk;
     for (int k = 0; k < 44; k++) zr[k] = 0;
+}
+static inline void sx_srtp_make_key(const u8* master, int tag_bytes, SxSrtpKey* rec, u8* ke_out, u8* ks_out, u8* ka_out) {
+    sx_srtp_make_key_at(master, 0, tag_bytes, rec, ke_out, ks_out, ka_out);
 }
 
 // the host mirror: per stream the tag of its tx and of its rx key (0: none) -- never the keys
@@ -392,8 +396,8 @@ SX_HD i32 sx_srtp_unprotect_one(const SxSrtpUnprotectArgs& a, int i, SxSrtpRun* 
 SX_HD void sx_srtp_unprotect_cipher(const SxSrtpUnprotectArgs& a, const SxSrtpRun& r, const u32* te, int lane, int nlanes) {
     sx_srtp_cipher(a.wire + r.off, r.hdr, r.len, sx_srtp_key(a.keys, r.stream, 1), te, r.ssrc, r.roc, r.seq, lane, nlanes);
 }
-// the second kernel's lane: stream s takes the call's highest accepted index
-SX_HD void sx_srtp_rx_fold(SxSrtpRx* rx, int s) {
+// the second kernel's lane: stream s takes the call's highest accepted index (Rx: SxSrtpRx, or the SxSrtcpRx of solo_srtcp.h)
+template <typename Rx> SX_HD void sx_srtp_rx_fold(Rx* rx, int s) {
     const u64 p = rx[s].pending;
     if (p) {
         if ((i64)(p - 1) > rx[s].index) rx[s].index = (i64)(p - 1);
