@@ -447,15 +447,18 @@ SX_HD void sx_sum_sqr_shift_wv_inl(i32* energy, i32* shift, const i16* x, int le
 //   out[k] = sat16( rshift_round( sub_sat32( in[k] << 12, sum_j B[j] * in[k-1-j] ), 12 ) ),  in[<0] = 0
 // (the reference's delay-line update is a plain shift, and its SMLABB accumulation wraps, so the
 // tap order is irrelevant).  Wave-parallel over k; caller must wv_sync() afterwards.
-SX_HD void sx_lpc_analysis_filter_zero_state(const i16* in, const i16* B, i16* out, int len, int order) {
+// The taps are taken two at a time on packed pairs (sx_fir_dot2; `in` is 4-byte aligned, len even).  The first ORDER outputs, the only
+// ones the zero state shows in, are NOT computed: they are written as 0, and no caller reads them (the residual energies start
+// ORDER samples into a block).
+template <int ORDER>
+SX_HD void sx_lpc_analysis_filter_zero_state(const i16* in, const i16* B, i16* out, int len) {
+    u32 B2[ORDER / 2];
+    sx_fir_pack<ORDER>(B2, B);
     SX_PAR(k, len) {
-        i32 acc = 0;
-        for (int j = 0; j < order; j++) {
-            int t = k - 1 - j;
-            if (t >= 0) acc = sx_smlabb(acc, in[t], B[j]);
-        }
-        i32 o = sx_sub_sat32(sx_shl((i32)in[k], 12), acc);
-        out[k] = (i16)sx_sat16(sx_rshift_round(o, 12));
+        i32 xk;
+        const i32 acc = sx_fir_dot2<ORDER>(in, k, B2, &xk);
+        i32 o = sx_sub_sat32(sx_shl(xk, 12), acc);
+        out[k] = k < ORDER ? (i16)0 : (i16)sx_sat16(sx_rshift_round(o, 12));
     }
 }
 

@@ -58,6 +58,9 @@ struct SxFrontWork {                 // LDS scratch of the per-frame analysis ch
     } u;
 };
 
+static_assert(alignof(SxFrontWork) >= 4 && offsetof(SxFrontWork, x_buf) % 4 == 0 && alignof(SxPredWork) >= 4 && offsetof(SxPredWork, LPC_in_pre) % 4 == 0,
+              "int16 arrays that the packed FIRs read as dwords (sx_fir_dot2)");
+
 struct SxHbWork {                    // LDS scratch of the high-band encoder
     i16 x_hb_buf[SX_HB_XBUF];
     i16 lpc_in[4 * (10 * SX_FS_KHZ + SX_HB_LPC)];

@@ -1332,6 +1332,7 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
     if (SITE == 0) sx_burg_last_regime = rshifts > 0;
 #endif
     // first row of the correlation matrix: lane (s, n) computes one inner product serially
+    const bool dwords = SX_UNI((int)((((u32)(uintptr_t)x >> 1) | (u32)L) & 1u)) == 0;      // every subframe starts on a 4-byte boundary (all three sites)
     SX_PAR(sn, nb_subfr * 16) {
         const int s = sn >> 4, n = (sn & 15) + 1;
         i32 v = 0;
@@ -1341,6 +1342,24 @@ SX_FN void sx_burg_modified(i32* res_nrg, i32* res_nrg_Q, i32* A_Q16, const i16*
                 i64 acc = 0;
                 for (int i = 0; i < L - n; i++) acc += (i64)((i32)xs[i] * (i32)xs[i + n]);
                 v = (i32)(acc >> rshifts);
+            } else if (dwords) {
+                // the wrapping sum two terms at a time: the subframe's dwords as they lie against the pairs n samples on (either
+                // parity: sx_pair).  P whole pairs whose upper dword is still the subframe's own, then the last term (n odd) or
+                // the last two (n even), which the carried dword holds: no read leaves the subframe.
+                const sx_u32a *aw = sx_dwords(xs), *bw = sx_dwords(xs) + (n >> 1);
+                const int sh = (n & 1) << 4, P = (L - 1 - n) >> 1;
+                u32 lo = bw[0];
+                i32 acc = 0;
+#if defined(__clang__)
+#pragma unroll 8
+#endif
+                for (int m = 0; m < P; m++) {
+                    const u32 hi = bw[m + 1];
+                    acc = sx_dot2(acc, aw[m], sx_pair(lo, hi, sh));
+                    lo = hi;
+                }
+                acc = sx_dot2(acc, aw[P], sx_pair(lo, 0u, sh));
+                v = sx_shl(acc, -rshifts);
             } else {
                 i32 acc = 0;
                 for (int i = 0; i < L - n; i++) acc = sx_smlabb(acc, xs[i], xs[i + n]);
@@ -1892,6 +1911,7 @@ SX_FN1 void sx_find_LPC(i32* NLSF_Q15, i32* interpIndex, const i32* prev_NLSFq_Q
     wv_sync();
     SX_T_BEGIN
     if (useInterp == 1) {
+        SX_DOT_COUNTED(10);
         sx_burg_modified<1>(&res_tmp_nrg, &res_tmp_nrg_Q, a_tmp_Q16, x + 2 * subfr_length, subfr_length, 2, K_FIND_LPC_COND_FAC_Q32, order, &lw->burg);
         sx_bwexpander_32(a_tmp_Q16, order, K_FIND_LPC_CHIRP_Q16);
         wv_sync();
@@ -1933,14 +1953,14 @@ SX_FN1 void sx_find_LPC(i32* NLSF_Q15, i32* interpIndex, const i32* prev_NLSFq_Q
             const int len = 2 * (SX_SUBFR + SX_LPC);
             SX_PAR(t, 4 * len) {
                 const int k = t / len, n = t - k * len;
-                const i16* B = lw->u.it.a_Q12[k];
-                i32 acc = 0;
-                for (int j = 0; j < order; j++) {
-                    const int u = n - 1 - j;
-                    if (u >= 0) acc = sx_smlabb(acc, x[u], B[j]);
-                }
-                const i32 o = sx_sub_sat32(sx_shl((i32)x[n], 12), acc);
-                lw->u.it.res[k][n] = (i16)sx_sat16(sx_rshift_round(o, 12));
+                // (packed pairs, sx_fir_dot2: x is SxPredWork::LPC_in_pre, 4-byte aligned, len even; the first `order` outputs of a
+                // candidate -- its zero-state start -- are written as 0: the energies below start `order` samples into a block)
+                u32 B2[SX_LPC / 2];
+                sx_fir_pack<SX_LPC>(B2, lw->u.it.a_Q12[k]);
+                i32 xn;
+                const i32 acc = sx_fir_dot2<SX_LPC>(x, n, B2, &xn);
+                const i32 o = sx_sub_sat32(sx_shl(xn, 12), acc);
+                lw->u.it.res[k][n] = n < SX_LPC ? (i16)0 : (i16)sx_sat16(sx_rshift_round(o, 12));
             }
         }
         wv_sync();
@@ -2396,7 +2416,7 @@ SX_FN1 void sx_residual_energy(i32* nrgs, i32* nrgsQ, const i16* x, i16 a_Q12[2]
     const int offset = SX_LPC + SX_SUBFR;
     const i16* x_ptr = x;
     for (int i = 0; i < 2; i++) {
-        sx_lpc_analysis_filter_zero_state(x_ptr, a_Q12[i], LPC_res, 2 * offset, SX_LPC);
+        sx_lpc_analysis_filter_zero_state<SX_LPC>(x_ptr, a_Q12[i], LPC_res, 2 * offset);      // (x: SxPredWork::LPC_in_pre, 4-byte aligned; offset even)
         wv_sync();
         for (int j = 0; j < 2; j++) {
             i32 rshift;

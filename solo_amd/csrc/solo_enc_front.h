@@ -665,6 +665,7 @@ SX_FN1 int sx_pitch_analysis_core(const i16* signal, i32* pitch_out, i32* lagInd
     if (shift > 0) {
         SX_PAR(i, 160) w->sig4[i] = (i16)(w->sig4[i] >> shift);
         wv_sync();
+        SX_DOT_COUNTED(6);
     }
     SX_S(34)
     // ---- first stage (4 kHz): normalised correlation of two 10 ms targets against lags 8..72 ----
@@ -684,10 +685,12 @@ SX_FN1 int sx_pitch_analysis_core(const i16* signal, i32* pitch_out, i32* lagInd
         const int nlag = max_lag_4 - min_lag_4 + 1;
         SX_PAR(t, 2 * nlag) {
             const int k = t / nlag, d = min_lag_4 + (t - k * nlag);
-            const i16* target = &w->sig4[80 + k * sf8];
-            const i16* b = target - d;
-            i32 cc = 0, E = 0;
-            for (int n = 0; n < sf8; n++) { cc = sx_smlabb(cc, target[n], b[n]); E = sx_smlabb(E, b[n], b[n]); }
+            // sample pairs: the target's dwords as they lie, the basis (even or odd lag) through sx_pair; the last dword read ends at
+            // sample 80 + 40 - 8 + 41 of sig4 at most
+            static_assert(offsetof(SxPitchWork, sig4) % 4 == 0 && alignof(SxPitchWork) >= 4 && 80 + 40 - 8 + 41 < 160 && 80 - 72 >= 0, "stage-1 windows read as dwords");
+            i32 cc, E;
+            sx_corr_dot2<40, false>(w->sig4, 80 + k * sf8, 80 + k * sf8 - d, &cc, &E, nullptr);
+            SX_DOT_COUNTED(0 + (d & 1));
             i32 normalizer = sx_add(k ? N8k[1] : N8k[0], sx_sub(E, k ? E8k[1] : E8k[0]));
             i32 tq = cc / (sx_sqrt_approx(normalizer) + 1);
             w->C[k][d] = (i16)sx_sat16(tq);
@@ -825,20 +828,18 @@ SX_FN1 int sx_pitch_analysis_core(const i16* signal, i32* pitch_out, i32* lagInd
     shift = sx_pitch_find_scaling(w->sig8, 320, sf8);
     if (shift > 0) {
         SX_PAR(i, 320) w->sig8[i] = (i16)(w->sig8[i] >> shift);
+        SX_DOT_COUNTED(7);
     }
     SX_PAR(i, 4 * 221) (&w->C[0][0])[i] = 0;
     wv_sync();
     SX_PAR(t, 4 * length_d_comp) {
         int k = t / length_d_comp, j = t - k * length_d_comp;
-        const i16* tp = &w->sig8[160 + k * sf8];
         int d = w->d_comp[j];
-        const i16* bp = tp - d;
-        i32 cross = 0, eb = 0, et = 0;
-        for (int n = 0; n < sf8; n++) {
-            cross = sx_smlabb(cross, tp[n], bp[n]);
-            eb = sx_smlabb(eb, bp[n], bp[n]);
-            et = sx_smlabb(et, tp[n], tp[n]);
-        }
+        // (d_comp holds lags 14 .. 145 of either parity: the basis starts at sample 15 or later, its last dword ends at sample 307 at most)
+        static_assert(offsetof(SxPitchWork, sig8) % 4 == 0 && 160 + 3 * 40 - (16 - 2) + 41 < 320 && 160 - (144 + 3 - 2) >= 0, "stage-2 windows read as dwords");
+        i32 cross, eb, et;
+        sx_corr_dot2<40, true>(w->sig8, 160 + k * sf8, 160 + k * sf8 - d, &cross, &eb, &et);
+        SX_DOT_COUNTED(2 + (d & 1));
         i32 r = 0;
         if (cross > 0) {
             i32 en = sx_max(et, eb);
@@ -926,6 +927,7 @@ SX_FN1 int sx_pitch_analysis_core(const i16* signal, i32* pitch_out, i32* lagInd
         }
     }
 #endif
+    if (lag != -1) { SX_DOT_COUNTED(4 + (lag & 1)); }
     if (lag == -1) {
         for (int k = 0; k < 4; k++) pitch_out[k] = 0;
         *LTPCorr_Q15 = 0; *lagIndex = 0; *contourIndex = 0;
@@ -1128,13 +1130,15 @@ SX_FN1 void sx_find_pitch_lags(SxEncState* st, SxEncCtrl* c, const i16* x_buf, i
     sx_bwexpander(A_Q12, SX_PITCH_LPC_ORDER, K_FIND_PITCH_BANDWITH_EXPANSION_Q16);
 #endif
     // MA_Prediction with zero state over the whole buffer (SKP_Silk_MA.c:40), FIR form, then zero the first `order` outputs
+    // (the taps two at a time on packed pairs; the zero state only shows in the first `order` outputs, which are replaced anyway.
+    // x_buf is the first, 4-byte aligned member of the work area and buf_len is even: no dword read leaves it)
+    static_assert(buf_len % 2 == 0 && buf_len <= SX_XBUF && SX_PITCH_LPC_ORDER % 2 == 0, "x_buf read as dwords");
+    u32 A2[SX_PITCH_LPC_ORDER / 2];
+    sx_fir_pack<SX_PITCH_LPC_ORDER>(A2, A_Q12);
     SX_PAR(k, buf_len) {
-        i32 acc = 0;
-        for (int d = 0; d < SX_PITCH_LPC_ORDER; d++) {
-            int t = k - 1 - d;
-            if (t >= 0) acc = sx_smlabb(acc, x_buf[t], A_Q12[d]);
-        }
-        i32 o = sx_rshift_round(sx_sub(sx_shl((i32)x_buf[k], 12), acc), 12);
+        i32 xk;
+        const i32 acc = sx_fir_dot2<SX_PITCH_LPC_ORDER>(x_buf, k, A2, &xk);
+        i32 o = sx_rshift_round(sx_sub(sx_shl(xk, 12), acc), 12);
         res[k] = k < SX_PITCH_LPC_ORDER ? (i16)0 : (i16)sx_sat16(o);
     }
     wv_sync();
@@ -1147,4 +1151,5 @@ SX_FN1 void sx_find_pitch_lags(SxEncState* st, SxEncCtrl* c, const i16* x_buf, i
     SX_S(33)
     c->sigtype = sx_pitch_analysis_core(res, c->pitchL, &c->lagIndex, &c->contourIndex, &st->LTPCorr_Q15, st->prevLag,
                                         K_FIND_PITCH_CORRELATION_THRESHOLD_HC_MODE_Q16, (i16)thr, pw);
+    SX_DOT_COUNTED(c->sigtype == 0 ? 8 : 9);
 }

@@ -99,6 +99,92 @@ SX_HD i32 sx_smulwt(i32 a, i32 b) { return (i32)(((i64)a * (i64)(i32)((u32)b & 0
 SX_HD i32 sx_smlawt(i32 acc, i32 a, i32 b) { return sx_add(acc, sx_smulwt(a, b)); }
 SX_HD i32 sx_smulbb(i32 a, i32 b) { return (i32)(i16)a * (i32)(i16)b; }
 SX_HD i32 sx_smlabb(i32 acc, i32 a, i32 b) { return sx_add(acc, sx_smulbb(a, b)); }
+// Two SMLABB steps on packed pairs of 16-bit samples: acc + a.lo * b.lo + a.hi * b.hi, all of it wrapping.  The reference sums such
+// products with wrapping 32-bit additions (SMLABB chains, SKP_Silk_inner_prod_aligned), which are associative, so taking the terms
+// two at a time changes no bit.  gfx950: one v_dot2_i32_i16 without clamp (tests/test_gpu_dot2_primitive.py pins that it wraps).
+SX_HD i32 sx_dot2(i32 acc, u32 a2, u32 b2) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short sx_v2i16_ __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_sdot2(__builtin_bit_cast(sx_v2i16_, a2), __builtin_bit_cast(sx_v2i16_, b2), acc, false);
+#else
+    return (i32)((u32)acc + (u32)((i32)(i16)a2 * (i32)(i16)b2) + (u32)((i32)(i16)(a2 >> 16) * (i32)(i16)(b2 >> 16)));
+#endif
+}
+// the pair of samples that starts `sh` bits (0 or 16) into the dword `lo`, continued in its upper neighbour `hi`: one v_alignbit_b32
+// with a per-lane shift, so a lane's first sample may be even or odd without a branch
+SX_HD u32 sx_pair(u32 lo, u32 hi, int sh) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, (u32)sh);
+#else
+    return (u32)(((((u64)hi) << 32) | (u64)lo) >> (sh & 31));
+#endif
+}
+// Debug builds of the host emulation with -DSX_DOT_COUNT (tools/debug/dot_branches.py): what the packed sums met -- (target, lag) pairs of
+// pitch stage 1 with an even [0] / odd [1] lag, of stage 2 [2] / [3], winning 8 kHz lags even [4] / odd [5], frames whose 4 kHz [6] / 8 kHz
+// [7] signal was scaled down (shift > 0), frames that came out voiced [8] / unvoiced [9], runs of the interpolation search [10]
+#if defined(SX_DOT_COUNT) && !defined(__HIPCC__)
+extern "C" { inline long long sx_dot_count[16]; }
+#define SX_DOT_COUNTED(what) (sx_dot_count[what]++)
+#else
+#define SX_DOT_COUNTED(what)
+#endif
+SX_HD u32 sx_pack2(i32 lo, i32 hi) { return ((u32)lo & 0xFFFFu) | ((u32)hi << 16); }
+// an int16 array read a dword at a time, as it lies (little endian: the even sample is the low half); the array is 4-byte aligned
+typedef u32 __attribute__((may_alias)) sx_u32a;
+SX_HD const sx_u32a* sx_dwords(const i16* p) { return (const sx_u32a*)(const void*)p; }
+
+// sum_{j < ORDER} B[j] * in[k - 1 - j] (wrapping) of a direct-form FIR, k >= ORDER: the lane reads the ORDER samples before sample k
+// of the 4-byte aligned array `in` as ORDER / 2 + 1 dwords and pairs them with cp[q] = sx_pack2(B[ORDER - 1 - 2q], B[ORDER - 2 - 2q]),
+// the coefficients of samples k - ORDER + 2q and + 2q + 1.  The highest dword read holds sample k, so no read leaves an array of
+// an even length > k; for k < ORDER the reads start at sample 0 and the sum means nothing (the caller masks those outputs).
+template <int ORDER>
+SX_HD i32 sx_fir_dot2(const i16* in, int k, const u32* cp, i32* in_k) {      // *in_k = in[k], which the last dword holds
+    static_assert(ORDER % 2 == 0, "coefficient pairs");
+    const int s0 = k >= ORDER ? k - ORDER : 0;
+    const sx_u32a* w = sx_dwords(in) + (s0 >> 1);
+    const int sh = (k & 1) << 4;
+    u32 dw[ORDER / 2 + 1];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int q = 0; q <= ORDER / 2; q++) dw[q] = w[q];
+    i32 acc = 0;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int q = 0; q < ORDER / 2; q++) acc = sx_dot2(acc, sx_pair(dw[q], dw[q + 1], sh), cp[q]);
+    *in_k = (i32)(i16)(dw[ORDER / 2] >> sh);
+    return acc;
+}
+template <int ORDER>
+SX_HD void sx_fir_pack(u32* cp, const i16* B) {
+    for (int q = 0; q < ORDER / 2; q++) cp[q] = sx_pack2(B[ORDER - 1 - 2 * q], B[ORDER - 2 - 2 * q]);
+}
+
+// cc = sum_{n < N} t[n] * b[n], eb = sum b[n]^2, et = sum t[n]^2 (wrapping) over two windows of the 4-byte aligned array `sig`: the target
+// starts at the EVEN sample ti, the basis at sample bi >= 0 of either parity.  N / 2 + 1 dwords of the basis are read, the last of
+// which ends at sample bi + N + 1 at most.
+template <int N, bool WITH_ET>
+SX_HD void sx_corr_dot2(const i16* sig, int ti, int bi, i32* cc, i32* eb, i32* et) {
+    static_assert(N % 2 == 0, "sample pairs");
+    const sx_u32a *tw = sx_dwords(sig) + (ti >> 1), *bw = sx_dwords(sig) + (bi >> 1);
+    const int sh = (bi & 1) << 4;
+    i32 c_ = 0, b_ = 0, t_ = 0;
+    u32 lo = bw[0];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int n = 0; n < N / 2; n++) {
+        const u32 hi = bw[n + 1], tp = tw[n], bp = sx_pair(lo, hi, sh);
+        c_ = sx_dot2(c_, tp, bp);
+        b_ = sx_dot2(b_, bp, bp);
+        if (WITH_ET) t_ = sx_dot2(t_, tp, tp);
+        lo = hi;
+    }
+    *cc = c_; *eb = b_;
+    if (WITH_ET) *et = t_;
+}
+
 SX_HD i32 sx_smulbt(i32 a, i32 b) { return sx_mul((i32)(i16)a, b >> 16); }
 SX_HD i32 sx_smultt(i32 a, i32 b) { return sx_mul(a >> 16, b >> 16); }
 // SKP_RSHIFT_ROUND (SigProc_FIX.h:592); shift >= 1

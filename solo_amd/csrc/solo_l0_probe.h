@@ -50,6 +50,9 @@ SX_HD i32 sx_l0_probe(int op, i32 a, i32 b, i32 c) {
         case 43: return sx_smulbb(c, (i32)(i16)((i16)a - (i16)b));     // MULT16_16(c, SUB16(a, b))
         case 44: return sx_smulbb(a, b);
         case 45: return sx_smlabb(c, a, b);
+        // packed pairs (tests/test_gpu_dot2_primitive.py, tests/test_dot2_primitive.py)
+        case 50: return sx_dot2(c, (u32)a, (u32)b);
+        case 51: return (i32)sx_pair((u32)a, (u32)b, (c & 1) << 4);
     }
     return 0;
 }
