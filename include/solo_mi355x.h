@@ -1304,6 +1304,15 @@ int32_t solo_debug_dec_synth(int32_t samplerate, int32_t useMDIndex, int32_t joi
                              int32_t n_packets, int32_t chunk, int32_t slot_bytes, const uint8_t *h_bits, const int16_t *h_nbytes,
                              const uint8_t *h_recv, const void *h_recs, int16_t *h_pcm, int32_t *h_status, void *h_state, int32_t state_bytes);
 int32_t solo_debug_clock(double *mhz_out);
+/* solo_debug_fn: function-level probe of the encoder's LPC / NLSF stage functions (solo_amd/csrc/solo_fn_probe.h, which lists the
+ * functions and the int32 record of each; tests/test_gpu_fn_probe.py): ONE call of stage function `fn` (4 * unit + site: a2nlsf,
+ * nlsf2a_stable, msvq, burg, find_lpc at the product's call sites) per case, one wavefront per case, in the build of `samplerate`
+ * (16000 / 32000).  d_in int32 [n_cases][in_words], d_out int32 [n_cases][out_words]: DEVICE pointers; runs on hip_stream and waits
+ * for it.  Returns 0, -1 for an fn that does not exist, record sizes that are not the fn's, n_cases outside 0 .. 65536 or a missing
+ * pointer, -2 when the launch failed.  It runs the function's device body as compiled for the probe's call, in a translation unit of its
+ * own; the product kernels' specialised copies are reached by whole-encoder inputs only. */
+int32_t solo_debug_fn(int32_t samplerate, int32_t fn, int32_t n_cases, const int32_t *d_in, int32_t in_words, int32_t *d_out,
+                      int32_t out_words, void *hip_stream);
 /* Library version string. */
 const char *solo_version(void);
 

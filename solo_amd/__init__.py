@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "solo_batch_n_streams", "solo_batch_slot_bytes", "solo_kernel_name", "solo_version", "solo_batch_set_timing",
     "solo_batch_last_kernel_ms", "solo_batch_last_encode_chunks", "solo_batch_decode_split", "solo_batch_set_async_join",
     "solo_batch_wait_encode", "solo_debug_l0", "solo_debug_sum_sqr_shift", "solo_debug_rowops", "solo_debug_clock", "solo_debug_nsq",
-    "solo_debug_waveops", "solo_debug_nsq_ex", "solo_debug_analysis", "solo_debug_coding", "solo_debug_dec_extract", "solo_debug_dec_synth",
+    "solo_debug_waveops", "solo_debug_fn", "solo_debug_nsq_ex", "solo_debug_analysis", "solo_debug_coding", "solo_debug_dec_extract", "solo_debug_dec_synth",
     "solo_recv_create", "solo_recv_insert", "solo_recv_decode", "solo_recv_stats",
     "solo_batch_reset_streams", "solo_recv_reset_streams", "solo_batch_update_streams",
     "solo_batch_encode_streams", "solo_batch_decode_streams", "solo_recv_decode_streams",
@@ -431,6 +431,8 @@ def load_library():
     lib.solo_debug_rowops.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_debug_waveops.restype = C.c_int32
     lib.solo_debug_waveops.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_debug_fn.restype = C.c_int32
+    lib.solo_debug_fn.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     lib.solo_debug_nsq.restype = C.c_int32
     lib.solo_debug_nsq.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     # stage probes of the encoder: (samplerate, silk_rate_bps, useMDIndex, joint, dtx, frames_per_packet, n_streams, n_packets, ...)
@@ -530,6 +532,20 @@ def _distinct(name, rows, n):
     if not 0 < len(idx) <= n or any(v < 0 or v >= n for v in idx) or len(set(idx)) != len(idx):
         raise ValueError("%s: 1 .. %d indices inside [0, %d), none twice" % (name, n, n))
     return idx
+
+
+def debug_fn(samplerate, fn, records, out):
+    """Function-level probe of the encoder's LPC / NLSF stage functions (solo_debug_fn, include/solo_mi355x.h; the functions and their
+    records: solo_amd/csrc/solo_fn_probe.h): one call of stage function `fn` per row of `records` (int32 [n_cases, in_words]) into the
+    same row of `out` (int32 [n_cases, out_words]), in the build of `samplerate`; runs on the current stream and waits for it.  -> out"""
+    import torch
+    n, _ = _tensor("records", records, torch.int32, (None, None))
+    _tensor("out", out, torch.int32, (n, None))
+    r = load_library().solo_debug_fn(int(samplerate), int(fn), n, _ptr(records), records.shape[1], _ptr(out), out.shape[1],
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    if r:
+        raise ValueError("solo_debug_fn -> %d (no such fn, or not its record sizes)" % r if r == -1 else "solo_debug_fn -> %d" % r)
+    return out
 
 
 class SoloBatch:

@@ -1918,9 +1918,9 @@ SX_FN1 void sx_find_LPC(i32* NLSF_Q15, i32* interpIndex, const i32* prev_NLSFq_Q
         SX_T(22)
         int shift = res_tmp_nrg_Q - res_nrg_Q;
         if (shift >= 0) {
-            if (shift < 32) res_nrg = res_nrg - (res_tmp_nrg >> shift);
+            SX_DOT_COUNTED(11); if (shift < 32) res_nrg = res_nrg - (res_tmp_nrg >> shift);
         } else {
-            res_nrg = (res_nrg >> (-shift)) - res_tmp_nrg;
+            SX_DOT_COUNTED(12); res_nrg = (res_nrg >> (-shift)) - res_tmp_nrg;
             res_nrg_Q = res_tmp_nrg_Q;
         }
         sx_a2nlsf<1>(NLSF_Q15, a_tmp_Q16, order, lw->P, lw->Q, &lw->u.grid);
@@ -1978,10 +1978,10 @@ SX_FN1 void sx_find_LPC(i32* NLSF_Q15, i32* interpIndex, const i32* prev_NLSFq_Q
             const i32 rshift0 = lw->u.it.rsh[k][0], rshift1 = lw->u.it.rsh[k][1];
             shift = rshift0 - rshift1;
             if (shift >= 0) {
-                res_nrg1 = res_nrg1 >> shift;
+                SX_DOT_COUNTED(13); res_nrg1 = res_nrg1 >> shift;
                 res_nrg_interp_Q = -rshift0;
             } else {
-                res_nrg0 = res_nrg0 >> (-shift);
+                SX_DOT_COUNTED(14); res_nrg0 = res_nrg0 >> (-shift);
                 res_nrg_interp_Q = -rshift1;
             }
             res_nrg_interp = sx_add(res_nrg0, res_nrg1);

@@ -121,7 +121,8 @@ SX_HD u32 sx_pair(u32 lo, u32 hi, int sh) {
 }
 // Debug builds of the host emulation with -DSX_DOT_COUNT (tools/debug/dot_branches.py): what the packed sums met -- (target, lag) pairs of
 // pitch stage 1 with an even [0] / odd [1] lag, of stage 2 [2] / [3], winning 8 kHz lags even [4] / odd [5], frames whose 4 kHz [6] / 8 kHz
-// [7] signal was scaled down (shift > 0), frames that came out voiced [8] / unvoiced [9], runs of the interpolation search [10]
+// [7] signal was scaled down (shift > 0), frames that came out voiced [8] / unvoiced [9], runs of the interpolation search [10],
+// the interpolation search's first energy shift >= 0 [11] / < 0 [12], a candidate's two residual shifts rshift0 >= rshift1 [13] / < [14]
 #if defined(SX_DOT_COUNT) && !defined(__HIPCC__)
 extern "C" { inline long long sx_dot_count[16]; }
 #define SX_DOT_COUNTED(what) (sx_dot_count[what]++)

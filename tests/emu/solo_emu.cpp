@@ -18,6 +18,7 @@ static void emu_tap(int stage, const SxEncState* st, const SxEncWork* w, const i
 #include "../../solo_amd/csrc/solo_recv.h"
 #ifndef EMU_DEC_ONLY
 #include "../../solo_amd/csrc/solo_enc.h"
+#include "../../solo_amd/csrc/solo_fn_probe.h"
 #endif
 
 extern "C" {
@@ -287,6 +288,27 @@ int emu_write_desc(int nframes, int useMDIndex, const void* syms, const int32_t*
     memcpy(out, buf, (size_t)nb);
     return nb;
 }
+// the function-level probe of the LPC / NLSF stage functions (solo_amd/csrc/solo_fn_probe.h; tests/test_fn_probe_reference.py): the host twin
+// of solo_debug_fn over the same records, one call of the stage function per case.  -> 0, -1: no such fn / not the fn's record sizes
+int emu_fn(int fn, int n_cases, const int32_t* in, int in_words, int32_t* out, int out_words) {
+    int iw = 0, ow = 0;
+    if (!sx_fn_probe_words(fn, &iw, &ow) || iw != in_words || ow != out_words || n_cases < 0) return -1;
+    static SxFnProbeWork w;
+    for (int c = 0; c < n_cases; c++) {
+        memset(&w, 0, sizeof(w));
+        const int32_t* ic = in + (size_t)c * iw;
+        int32_t* oc = out + (size_t)c * ow;
+        switch (fn >> 2) {
+        case SX_FNP_A2NLSF: sx_fn_probe_case<SX_FNP_A2NLSF>(&w, fn & 3, ic, oc); break;
+        case SX_FNP_NLSF2A: sx_fn_probe_case<SX_FNP_NLSF2A>(&w, fn & 3, ic, oc); break;
+        case SX_FNP_MSVQ: sx_fn_probe_case<SX_FNP_MSVQ>(&w, fn & 3, ic, oc); break;
+        case SX_FNP_BURG: sx_fn_probe_case<SX_FNP_BURG>(&w, fn & 3, ic, oc); break;
+        default: sx_fn_probe_case<SX_FNP_FIND_LPC>(&w, fn & 3, ic, oc); break;
+        }
+    }
+    return 0;
+}
+int emu_fn_x_words() { return SX_FNP_X; }
 int emu_frame_samples() { return SX_FRAME; }
 int emu_sizeof_nsq_in() { return (int)sizeof(SxNsqIn); }
 int emu_sizeof_enc_state() { return (int)sizeof(SxEncStream); }
