@@ -920,7 +920,7 @@ int32_t solo_rtp_parse(solo_rtp_t *r, solo_batch_t *b, const solo_dgram_t *d_dgr
  *   THERE IS NO REPLAY LIST: a replayed datagram reaches the ring, which drops it as duplicate or late.
  *   -1 with nothing enqueued: NULL r or d_count; n_dgrams < 0 or wire_bytes < 0; with n_dgrams > 0 a NULL d_dgrams, d_wire or
  *   d_dgrams_out; d_dgrams, d_dgrams_out or d_count not 4-byte aligned.  Three kernels on hip_stream, no allocation, no host
- *   synchronisation: capturable with n_dgrams frozen.  Not built: MKI, RFC 6904, AES-GCM, AES-256. */
+ *   synchronisation: capturable with n_dgrams frozen.  Not built: MKI, RFC 6904, AES-256. */
 #define SOLO_SRTP_MASTER_BYTES 30   /* master key (16) || master salt (14): one direction's SDES / DTLS-SRTP keying material */
 typedef struct { int32_t ok, skipped, malformed, unknown_ssrc, no_key, auth_failed, reserved[2]; } solo_srtp_count_t;   /* 32 bytes */
 /* The trailer switch and the key calls of the session, then its two SRTP device calls. */
@@ -1149,11 +1149,11 @@ int32_t solo_rtcp_parse(solo_rtcp_t *c, const solo_rtp_t *r_rx, const solo_rtp_t
  * keystream block j = AES(k_e, IV + j) XORed over bytes [8, len); tag = the first 10 bytes of HMAC-SHA1(k_a, bytes [0, len) as sent ||
  * the E || index word).  Session keys: the PRF of section 4.3 with rate 0 and index 0 over one direction's 30 bytes of master key ||
  * master salt, labels 3 (cipher key), 4 (authentication key), 5 (salt).
- * solo_rtcp_set_trailer -- a host switch on the RTCP object like solo_rtp_set_trailer, 0 .. 16, default 0, read when a solo_rtcp_build call
+ * solo_rtcp_set_trailer -- a host switch on the RTCP object like solo_rtp_set_trailer, 0 .. 16 or exactly 20, default 0, read when a solo_rtcp_build call
  *   is issued: with a trailer T build plans every packet that is not refused as roundup4(len + T), writes the T bytes and the pad behind
  *   the packet as zero, leaves d_dgrams[i].len = len, counts the trailer in bytes and bytes_needed, and writes a packet iff all of it,
  *   trailer included, ends inside wire_capacity.  T = 0: every byte, count and state word as without the call.  -1: NULL c, or a value
- *   outside 0 .. 16.
+ *   outside 0 .. 16 other than 20.
  * Control plane, on the solo_rtp_t session beside solo_srtp_* (it has the SSRC table) -- HOST arrays, ordered on hip_stream, the calls
  * return when the device holds the records.  Per stream: two 256-byte key records as those of SRTP (tag = 10), a send record {uint32
  * next: the index the next protected packet gets} and a receive record {int64 index: the highest authenticated, -1 = none yet; uint64
@@ -1198,7 +1198,7 @@ int32_t solo_rtcp_parse(solo_rtcp_t *c, const solo_rtp_t *r_rx, const solo_rtp_t
  *   -1 with nothing enqueued: NULL r_rx or d_count; n_dgrams < 0 or wire_bytes < 0; with n_dgrams > 0 a NULL d_dgrams, d_wire or
  *   d_dgrams_out; d_dgrams, d_dgrams_out or d_count not 4-byte aligned.  Three kernels, no allocation, no host synchronisation:
  *   capturable with n_dgrams frozen (tests/test_gpu_srtcp.py: test_capture_srtcp_unprotect_and_rtcp_parse).
- * Not built: the MKI, sending with E = 0, the 64-packet replay window, AES-GCM and AES-256, SRTCP keys and indices
+ * Not built: the MKI, sending with E = 0, the 64-packet replay window, AES-256, SRTCP keys and indices
  * in a migration blob. */
 #define SOLO_SRTCP_TRAILER_BYTES 14  /* the E || index word (4) and the tag (10) behind every SRTCP datagram */
 typedef struct { int32_t ok, skipped, malformed, unknown_ssrc, no_key, auth_failed, replayed, exhausted; } solo_srtcp_count_t;   /* 32 bytes; ok = -1: the list was refused */
@@ -1213,6 +1213,50 @@ int32_t solo_srtcp_protect(const solo_rtcp_t *c, solo_rtp_t *r_tx, const int32_t
                            solo_srtcp_count_t *d_count, void *hip_stream);
 int32_t solo_srtcp_unprotect(solo_rtp_t *r_rx, const solo_dgram_t *d_dgrams, int32_t n_dgrams, uint8_t *d_wire, int64_t wire_bytes,
                              solo_dgram_t *d_dgrams_out, solo_srtcp_count_t *d_count, void *hip_stream);
+/* AEAD_AES_128_GCM (RFC 7714) as a second transform of the SRTP and the SRTCP stage, for peers that negotiate SRTP_AEAD_AES_128_GCM
+ * (DTLS-SRTP).  It is selected per stream and direction by the key that was set: a stream and direction has ONE key, the last set call
+ * wins whichever transform it names, and a session may hold streams of both transforms side by side in one call.  The four device
+ * calls (solo_srtp_protect / _unprotect, solo_srtcp_protect / _unprotect) keep their signatures, their -1 rules, their verdict order
+ * and their count structures; every datagram of a call is counted once.  A session that never sets a GCM key allocates and enqueues
+ * exactly what it did; one that holds a GCM key in a call's direction enqueues one more kernel (a workgroup per 64 datagrams) behind
+ * the older transform's, in front of the fold kernel, which takes the datagrams of GCM-keyed streams and adds to the same count.
+ *   The transform: tag 16 bytes, 12-byte IV, J0 = IV || 00 00 00 01, keystream block j = AES(k, IV || be32(j + 2)), tag = AES(k, J0) ^
+ *   GHASH(AES(k, 0^128), AAD, ciphertext).  Keying material per direction: SOLO_SRTP_GCM_MASTER_BYTES = master key (16) || master salt
+ *   (12); session key and salt by the PRF of RFC 3711 section 4.3 (rate 0, index 0) with the salt padded on the right to 14 bytes, labels
+ *   0 / 2 for SRTP and 3 / 5 for SRTCP; there is no authentication key.  The 256-byte key record keeps its layout: round keys, the 12
+ *   salt bytes, H where the HMAC states were, tag = 16, and a word that names the transform (0 for the older one).
+ *   SRTP: IV = (00 00 || SSRC || ROC || SEQ) ^ salt; the associated data is the RTP header, 12 + 4 CC bytes and the extension block --
+ *   what AES-CM leaves in the clear, so the RFC 6464 level stays readable; the plaintext is everything behind it.  On the wire: header,
+ *   ciphertext, tag; d_dgrams[k].len += 16 on protect (solo_rtp_set_trailer(16) is its room), len - 16 on unprotect.  unprotect's
+ *   malformed rule uses tag = 16 for a stream under a GCM rx key (and 4, as before, where stream or key is not known); the rollover
+ *   estimate, the pending index and the fold kernel are those of the older transform.  The ROC is neither sent nor associated data.
+ *   SRTCP: IV = (00 00 || SSRC || 00 00 || index) ^ salt.  E = 1: associated data = bytes [0, 8) || the word 0x80000000 | index, plaintext
+ *   = bytes [8, len).  On the wire: bytes [0, 8), ciphertext, tag (16), and the E || index word as the LAST four bytes -- not the HMAC
+ *   layout, where the word stands in front of the tag.  E = 0 (accepted, never written): associated data = the packet || the word,
+ *   nothing is encrypted; on the wire packet, tag, word.  The trailer is SOLO_SRTCP_GCM_TRAILER_BYTES = 20: solo_rtcp_set_trailer(20),
+ *   and solo_srtcp_protect returns -1 with nothing enqueued while c's trailer is below 20 and the session holds any GCM SRTCP tx key.
+ *   unprotect: len < 8 + 14 stays the first rule; a datagram of a stream under a GCM rx key with len < 8 + 20 is malformed; the replay
+ *   rule, the exhausted rule and their counters are unchanged.  d_dgrams[i].len += 20 on protect, len - 20 on unprotect.
+ *   AUTHENTICATE FIRST and NOTHING OF A SESSION'S LEAVES IN THE CLEAR hold as for the older transform: a rejected datagram keeps every byte.
+ * solo_srtp_set_keys_gcm / solo_srtcp_set_keys_gcm -- the semantics and refusals of solo_srtp_set_keys / solo_srtcp_set_keys with masters
+ *   of [n][28] bytes and no tag_bytes argument; a tx SRTP key is refused while the session's trailer is below 16.  solo_srtp_set_keys keeps
+ *   refusing every tag_bytes but 4 and 10; solo_rtp_set_trailer never goes below the tag of a keyed sender, which may now be 16.
+ *   solo_srtp_clear_keys / solo_srtcp_clear_keys, solo_rtp_unbind and the get_*index calls keep their meaning for both kinds of key.
+ * Graph capture: the four device calls stay capturable under GCM keys with the same frozen arguments (tests/test_gpu_srtp_gcm.py:
+ *   test_capture_srtp_gcm_protect_and_unprotect, test_capture_srtcp_gcm_protect_and_unprotect).  The extra kernel is part of the
+ *   captured sequence.  A graph captured before the session's first GCM key in the call's direction does not hold it and FAILS CLOSED: a
+ *   datagram of a GCM-keyed stream is no_key to such a replay -- voided by protect, rejected with every byte kept by unprotect -- until
+ *   the call is captured again.
+ * Not built: AEAD_AES_256_GCM, the 8-byte-tag variants, MKI, RFC 6904, GCM keys in a migration blob, constant-time
+ * table access. */
+#define SOLO_SRTP_GCM_MASTER_BYTES 28    /* master key (16) || master salt (12): one direction's DTLS-SRTP keying material */
+#define SOLO_SRTP_GCM_TAG_BYTES 16
+#define SOLO_SRTCP_GCM_TRAILER_BYTES 20  /* the tag (16), then the E || index word (4) */
+/* The two key calls of the transform; the device calls are those above. */
+int32_t solo_srtp_set_keys_gcm(solo_rtp_t *r, const int32_t *h_streams, int32_t n, const uint8_t *h_tx_master, const uint8_t *h_rx_master,
+                               const uint32_t *h_rx_roc, void *hip_stream);
+int32_t solo_srtcp_set_keys_gcm(solo_rtp_t *r, const int32_t *h_streams, int32_t n, const uint8_t *h_tx_master, const uint8_t *h_rx_master,
+                                const uint32_t *h_tx_index, const int64_t *h_rx_index, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

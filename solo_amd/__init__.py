@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "solo_agc_create", "solo_agc_destroy", "solo_agc_reset", "solo_agc_reset_rows", "solo_agc_get_state", "solo_agc_set_state", "solo_agc",
     "solo_rtp_create", "solo_rtp_destroy", "solo_rtp_bind", "solo_rtp_unbind", "solo_rtp_pack", "solo_rtp_parse",
     "solo_rtp_set_trailer", "solo_srtp_set_keys", "solo_srtp_clear_keys", "solo_srtp_get_rx_index", "solo_srtp_protect", "solo_srtp_unprotect",
+    "solo_srtp_set_keys_gcm", "solo_srtcp_set_keys_gcm",
     "solo_forward_create", "solo_forward_destroy", "solo_forward_reset", "solo_forward_reset_rooms", "solo_forward_get_state",
     "solo_forward_set_state", "solo_forward_levels", "solo_forward_route",
     "solo_rtcp_create", "solo_rtcp_destroy", "solo_rtcp_reset", "solo_rtcp_reset_rows", "solo_rtcp_get_state", "solo_rtcp_set_state",
@@ -221,6 +222,9 @@ class solo_forward_count_t(C.Structure):
 
 SRTP_MASTER_BYTES = 30
 SRTCP_TRAILER_BYTES = 14
+SRTP_GCM_MASTER_BYTES = 28      # AEAD_AES_128_GCM (RFC 7714): master key (16) || master salt (12)
+SRTP_GCM_TAG_BYTES = 16
+SRTCP_GCM_TRAILER_BYTES = 20    # the tag, then the E || index word
 RECV_REPORT_CLEAR_MARGIN = 1
 
 _lib = None
@@ -374,6 +378,10 @@ def load_library():
     lib.solo_rtp_set_trailer.argtypes = [C.c_void_p, C.c_int32]
     lib.solo_srtp_set_keys.restype = C.c_int32
     lib.solo_srtp_set_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.solo_srtp_set_keys_gcm.restype = C.c_int32
+    lib.solo_srtp_set_keys_gcm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.solo_srtcp_set_keys_gcm.restype = C.c_int32
+    lib.solo_srtcp_set_keys_gcm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_srtp_clear_keys.restype = C.c_int32
     lib.solo_srtp_clear_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.solo_srtp_get_rx_index.restype = C.c_int32
@@ -1833,16 +1841,16 @@ class Rtp(_RowObject):
         self.trailer = trailer_bytes
 
     @staticmethod
-    def _masters(name, v, n):
-        """None, or n x 30 bytes of keying material (bytes, a sequence of bytes objects, or a uint8 array [n,30]) -> ctypes array"""
+    def _masters(name, v, n, each=SRTP_MASTER_BYTES):
+        """None, or n x `each` bytes of keying material (bytes, a sequence of bytes objects, or a uint8 array [n,each]) -> ctypes array"""
         if v is None:
             return None
         try:
             raw = bytes(v) if isinstance(v, (bytes, bytearray)) else v.tobytes() if hasattr(v, "tobytes") else b"".join(bytes(x) for x in v)
         except (TypeError, ValueError):
             raw = b""
-        if len(raw) != SRTP_MASTER_BYTES * n:
-            raise ValueError("%s: %d x %d bytes (master key || master salt per listed stream) or None" % (name, n, SRTP_MASTER_BYTES))
+        if len(raw) != each * n:
+            raise ValueError("%s: %d x %d bytes (master key || master salt per listed stream) or None" % (name, n, each))
         return (C.c_uint8 * len(raw)).from_buffer_copy(raw)
 
     def set_keys(self, streams, tx=None, rx=None, rx_roc=None, tag_bytes=10):
@@ -1861,6 +1869,20 @@ class Rtp(_RowObject):
             raise ValueError("a tx key needs set_trailer(%d) or more first" % tag_bytes)
         roc = None if rx_roc is None else (C.c_uint32 * n)(*self._per_stream(rx_roc, n, "rx_roc", 2 ** 32 - 1))
         self._call("set_keys", (C.c_int32 * n)(*idx), n, txa, rxa, roc, tag_bytes, prefix="srtp")
+
+    def set_keys_gcm(self, streams, tx=None, rx=None, rx_roc=None):
+        """set_keys() for AEAD_AES_128_GCM (RFC 7714): tx / rx = 28 bytes of keying material per listed stream (master key || 12-byte
+        master salt, as DTLS-SRTP gives them for SRTP_AEAD_AES_128_GCM); the tag is always 16 bytes, so a tx key needs set_trailer(16).
+        A stream and direction has one key: the last set call wins, whichever transform it names."""
+        idx = _distinct("streams", streams, self.n_streams)
+        n = len(idx)
+        txa, rxa = self._masters("tx", tx, n, SRTP_GCM_MASTER_BYTES), self._masters("rx", rx, n, SRTP_GCM_MASTER_BYTES)
+        if txa is None and rxa is None:
+            raise ValueError("at least one of tx and rx")
+        if txa is not None and self.trailer < SRTP_GCM_TAG_BYTES:
+            raise ValueError("a tx key needs set_trailer(%d) first" % SRTP_GCM_TAG_BYTES)
+        roc = None if rx_roc is None else (C.c_uint32 * n)(*self._per_stream(rx_roc, n, "rx_roc", 2 ** 32 - 1))
+        self._call("set_keys_gcm", (C.c_int32 * n)(*idx), n, txa, rxa, roc, prefix="srtp")
 
     def clear_keys(self, streams):
         """both keys and the receive index of the listed streams go; unbind() does the same"""
@@ -1925,6 +1947,19 @@ class Rtp(_RowObject):
         ri = None if rx_index is None else (C.c_int64 * n)(*[v - 1 for v in self._per_stream(self._plus_one(rx_index), n, "rx_index + 1", 2 ** 31)])
         self._call("set_keys", (C.c_int32 * n)(*idx), n, txa, rxa, ti, ri, prefix="srtcp")
 
+    def set_rtcp_keys_gcm(self, streams, tx=None, rx=None, tx_index=None, rx_index=None):
+        """set_rtcp_keys() for AEAD_AES_128_GCM (RFC 7714): tx / rx = 28 bytes of keying material per listed stream (master key || 12-byte
+        master salt).  The trailer of such a stream's packets is 20 bytes (the 16-byte tag, then E || index): protect_rtcp() needs
+        rtcp.set_trailer(20) while the session holds a GCM tx key."""
+        idx = _distinct("streams", streams, self.n_streams)
+        n = len(idx)
+        txa, rxa = self._masters("tx", tx, n, SRTP_GCM_MASTER_BYTES), self._masters("rx", rx, n, SRTP_GCM_MASTER_BYTES)
+        if txa is None and rxa is None:
+            raise ValueError("at least one of tx and rx")
+        ti = None if tx_index is None else (C.c_uint32 * n)(*self._per_stream(tx_index, n, "tx_index", 2 ** 31))
+        ri = None if rx_index is None else (C.c_int64 * n)(*[v - 1 for v in self._per_stream(self._plus_one(rx_index), n, "rx_index + 1", 2 ** 31)])
+        self._call("set_keys_gcm", (C.c_int32 * n)(*idx), n, txa, rxa, ti, ri, prefix="srtcp")
+
     @staticmethod
     def _plus_one(v):
         """rx_index (-1 = none yet) moved to 0 .. 2^31 for the range check of _per_stream; what is no integer goes through and is refused there"""
@@ -1966,6 +2001,9 @@ class Rtp(_RowObject):
         count = t.zeros((8,), dtype=t.int32, device=dgrams.device)
         r = self.lib.solo_srtcp_protect(rtcp.h, self.h, streams.data_ptr(), n, build_count.data_ptr(), dgrams.data_ptr(), wire.data_ptr() or count.data_ptr(),
                                         nbytes, count.data_ptr(), self._stream())
+        if r == -1 and rtcp.trailer < SRTCP_GCM_TRAILER_BYTES:
+            # every other refusal of the call is checked above: the library, which alone knows the session's keys, holds a GCM tx key
+            raise ValueError("rtcp: set_trailer(%d) before the build call: the session holds a GCM tx key" % SRTCP_GCM_TRAILER_BYTES)
         if r:
             raise RuntimeError("solo_srtcp_protect -> %d" % r)
         return count
@@ -2124,11 +2162,12 @@ class Rtcp(_RowStateObject):
         self._create(self.n_streams)
 
     def set_trailer(self, trailer_bytes):
-        """bytes build() keeps free (and zero) behind every packet: the room of the SRTCP trailer (Rtp.protect_rtcp() needs 14), 0 .. 16;
-        dgrams[i].len stays the compound packet's, the offsets and byte counts include the trailer.  Read by the next build()."""
+        """bytes build() keeps free (and zero) behind every packet: the room of the SRTCP trailer (Rtp.protect_rtcp() needs 14, and 20
+        with GCM keys), 0 .. 16 or 20; dgrams[i].len stays the compound packet's, the offsets and byte counts include the trailer.
+        Read by the next build()."""
         trailer_bytes = int(trailer_bytes)
-        if not 0 <= trailer_bytes <= 16:
-            raise ValueError("trailer_bytes: 0 .. 16")
+        if not 0 <= trailer_bytes <= 16 and trailer_bytes != SRTCP_GCM_TRAILER_BYTES:
+            raise ValueError("trailer_bytes: 0 .. 16, or 20")
         r = self.lib.solo_rtcp_set_trailer(self.h, trailer_bytes)
         if r:
             raise RuntimeError("solo_rtcp_set_trailer -> %d" % r)

@@ -43,6 +43,7 @@
 #include "solo_srtp.h"          // SRTP protection of the datagrams of solo_rtp.h (solo_srtp_protect / _unprotect): likewise
 #include "solo_rtp.h"           // RTP framing of the sender's records and parsing of received datagrams (solo_rtp_pack / _parse): likewise
 #include "solo_forward.h"       // forwarding without transcoding: levels per row from arrivals, routing under per-room slots (solo_forward_*): likewise
+#include "solo_srtp_gcm.h"      // AEAD_AES_128_GCM for both (RFC 7714): the kernels behind theirs, the two key calls
 #include "solo_srtcp.h"         // SRTCP protection of the compound packets of solo_rtcp.h (solo_srtcp_protect / _unprotect): likewise
 #include "solo_rtcp.h"          // RTCP beside the RTP sessions: reception statistics, sender counts, compound packets out and in (solo_rtcp_*): likewise
 
@@ -1230,7 +1231,14 @@ struct solo_rtp_obj : solo_rows {    // d_state: SxRtpStream [n_rows]
     // SRTCP (solo_srtcp.h): ONE allocation (SxSrtcpMem) made by the first solo_srtcp_set_keys.  The mirror holds "has tx / has rx"
     void* d_srtcp;
     SxSrtcpMirror srtcp;
+    // streams that hold a GCM key (solo_srtp_gcm.h): SRTP tx, SRTP rx, SRTCP tx, SRTCP rx -- counted wherever a mirror changes, so that a
+    // device call asks "is the GCM kernel needed" without walking the mirror
+    int32_t n_gcm[4];
 };
+static void rtp_count_gcm(solo_rtp_obj* r) {
+    r->n_gcm[0] = sx_srtp_gcm_count(r->srtp.tx_tag); r->n_gcm[1] = sx_srtp_gcm_count(r->srtp.rx_tag);
+    r->n_gcm[2] = sx_srtcp_gcm_count(r->srtcp.has_tx); r->n_gcm[3] = sx_srtcp_gcm_count(r->srtcp.has_rx);
+}
 solo_rtp_t* solo_rtp_create(int32_t n_streams, int32_t packet_samples) {
     if (n_streams <= 0 || (packet_samples != 320 && packet_samples != 640 && packet_samples != 1280) || !have_device()) return NULL;
     solo_rtp_obj* r = new (std::nothrow) solo_rtp_obj();
@@ -1293,6 +1301,7 @@ static int32_t srtp_clear(solo_rtp_obj* r, const int32_t* h_streams, int32_t n, 
         SOLO_CHECK(hipMemsetAsync((uint8_t*)(r->d_rx + h_streams[i]) + sizeof(i64), 0, sizeof(SxSrtpRx) - sizeof(i64), st));
         r->srtp.tx_tag[(size_t)h_streams[i]] = 0; r->srtp.rx_tag[(size_t)h_streams[i]] = 0;
     }
+    rtp_count_gcm(r);
     return 0;
 }
 // SRTCP likewise: both keys and the send index to zero, the receive record to "none yet"
@@ -1306,6 +1315,7 @@ static int32_t srtcp_clear(solo_rtp_obj* r, const int32_t* h_streams, int32_t n,
         SOLO_CHECK(hipMemsetAsync(&m.rx[h_streams[i]].pending, 0, sizeof(u64), st));
         r->srtcp.has_tx[(size_t)h_streams[i]] = 0; r->srtcp.has_rx[(size_t)h_streams[i]] = 0;
     }
+    rtp_count_gcm(r);
     return 0;
 }
 int32_t solo_rtp_unbind(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
@@ -1353,13 +1363,9 @@ int32_t solo_rtp_set_trailer(solo_rtp_t* r, int32_t trailer_bytes) {
     r->trailer = trailer_bytes;
     return 0;
 }
-int32_t solo_srtp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_rx_roc,
-                           int32_t tag_bytes, void* hip_stream) {
-    std::vector<SxSrtpKey> recs;
-    std::vector<SxSrtpRx> rx;
-    SxSrtpMirror next;
-    if (!r || !sx_srtp_set_keys_plan(r->srtp, r->n_rows, r->trailer, h_streams, n, h_tx_master, h_rx_master, h_rx_roc, tag_bytes, next, recs, rx)) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
+// the planned records of a set_keys call of either transform (has_tx / has_rx: the directions it sets) -> the device, then the mirror
+static int32_t srtp_put_keys(solo_rtp_obj* r, const int32_t* h_streams, int32_t n, bool has_tx, bool has_rx, std::vector<SxSrtpKey>& recs, const std::vector<SxSrtpRx>& rx,
+                             SxSrtpMirror& next, hipStream_t st) {
     if (!r->d_keys) {                // the first call: every record "no key", every receive record "none yet"
         const size_t kb = 2 * (size_t)r->n_rows * sizeof(SxSrtpKey);
         std::vector<SxSrtpRx> none((size_t)r->n_rows);
@@ -1376,15 +1382,32 @@ int32_t solo_srtp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, c
     hipError_t e = hipSuccess;
     for (int32_t i = 0; i < n && e == hipSuccess; i++) {
         SxSrtpKey* d = r->d_keys + 2 * (size_t)h_streams[i];
-        if (h_tx_master) e = hipMemcpyAsync(d, &recs[2 * (size_t)i], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
-        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(d + 1, &recs[2 * (size_t)i + 1], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
-        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(r->d_rx + h_streams[i], &rx[(size_t)i], sizeof(SxSrtpRx), hipMemcpyHostToDevice, st);
+        if (has_tx) e = hipMemcpyAsync(d, &recs[2 * (size_t)i], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (has_rx && e == hipSuccess) e = hipMemcpyAsync(d + 1, &recs[2 * (size_t)i + 1], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (has_rx && e == hipSuccess) e = hipMemcpyAsync(r->d_rx + h_streams[i], &rx[(size_t)i], sizeof(SxSrtpRx), hipMemcpyHostToDevice, st);
     }
     const hipError_t e2 = hipStreamSynchronize(st);         // (the host records go with this call: the copies must have read them)
     sx_srtp_wipe(recs);
     if (e != hipSuccess || e2 != hipSuccess) return -(int32_t)(e != hipSuccess ? e : e2);
     r->srtp.tx_tag.swap(next.tx_tag); r->srtp.rx_tag.swap(next.rx_tag);
+    rtp_count_gcm(r);
     return 0;
+}
+int32_t solo_srtp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_rx_roc,
+                           int32_t tag_bytes, void* hip_stream) {
+    std::vector<SxSrtpKey> recs;
+    std::vector<SxSrtpRx> rx;
+    SxSrtpMirror next;
+    if (!r || !sx_srtp_set_keys_plan(r->srtp, r->n_rows, r->trailer, h_streams, n, h_tx_master, h_rx_master, h_rx_roc, tag_bytes, next, recs, rx)) return -1;
+    return srtp_put_keys(r, h_streams, n, h_tx_master != NULL, h_rx_master != NULL, recs, rx, next, (hipStream_t)hip_stream);
+}
+int32_t solo_srtp_set_keys_gcm(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_rx_roc,
+                               void* hip_stream) {
+    std::vector<SxSrtpKey> recs;
+    std::vector<SxSrtpRx> rx;
+    SxSrtpMirror next;
+    if (!r || !sx_srtp_gcm_set_keys_plan(r->srtp, r->n_rows, r->trailer, h_streams, n, h_tx_master, h_rx_master, h_rx_roc, next, recs, rx)) return -1;
+    return srtp_put_keys(r, h_streams, n, h_tx_master != NULL, h_rx_master != NULL, recs, rx, next, (hipStream_t)hip_stream);
 }
 int32_t solo_srtp_clear_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
     if (!r || !sx_list_ok(h_streams, n, r->n_rows)) return -1;
@@ -1409,7 +1432,7 @@ int32_t solo_srtp_protect(solo_rtp_t* r, const solo_arrival_t* d_records, const 
     a.records = d_records; a.send_count = d_send_count; a.dgrams = d_dgrams; a.wire = d_wire; a.cfg = (const SxRtpStream*)r->d_state; a.keys = r->d_keys;
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.max_records = max_records; a.n_streams = r->n_rows;
-    SOLO_CHECK(solo_srtp_protect_launch(a, d_count, (hipStream_t)hip_stream));
+    SOLO_CHECK(solo_srtp_protect_launch_all(a, d_count, r->n_gcm[0] > 0, (hipStream_t)hip_stream));
     return 0;
 }
 int32_t solo_srtp_unprotect(solo_rtp_t* r, const solo_dgram_t* d_dgrams, int32_t n_dgrams, uint8_t* d_wire, int64_t wire_bytes, solo_dgram_t* d_dgrams_out,
@@ -1420,7 +1443,7 @@ int32_t solo_srtp_unprotect(solo_rtp_t* r, const solo_dgram_t* d_dgrams, int32_t
     a.dgrams = d_dgrams; a.out = d_dgrams_out; a.wire = d_wire; a.table = r->d_table; a.keys = r->d_keys; a.rx = r->d_rx;
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n_dgrams = n_dgrams; a.n_streams = r->n_rows;
-    SOLO_CHECK(solo_srtp_unprotect_launch(a, d_count, (hipStream_t)hip_stream));
+    SOLO_CHECK(solo_srtp_unprotect_launch_all(a, d_count, r->n_gcm[1] > 0, (hipStream_t)hip_stream));
     return 0;
 }
 
@@ -1595,14 +1618,9 @@ int32_t solo_rtcp_set_trailer(solo_rtcp_t* c, int32_t trailer_bytes) {
     c->trailer = trailer_bytes;
     return 0;
 }
-int32_t solo_srtcp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_tx_index,
-                            const int64_t* h_rx_index, void* hip_stream) {
-    std::vector<SxSrtpKey> recs;
-    std::vector<SxSrtcpTx> tx;
-    std::vector<SxSrtcpRx> rx;
-    SxSrtcpMirror next;
-    if (!r || !sx_srtcp_set_keys_plan(r->srtcp, r->n_rows, h_streams, n, h_tx_master, h_rx_master, h_tx_index, (const i64*)h_rx_index, next, recs, tx, rx)) return -1;
-    hipStream_t st = (hipStream_t)hip_stream;
+// the planned records of a set_keys call of either transform -> the device, then the mirror
+static int32_t srtcp_put_keys(solo_rtp_obj* r, const int32_t* h_streams, int32_t n, bool has_tx, bool has_rx, std::vector<SxSrtpKey>& recs, const std::vector<SxSrtcpTx>& tx,
+                              const std::vector<SxSrtcpRx>& rx, SxSrtcpMirror& next, hipStream_t st) {
     if (!r->d_srtcp) {               // the first call: every record "no key", every send index 0, every receive record "none yet"
         const size_t bytes = sx_srtcp_bytes(r->n_rows);
         std::vector<u8> init(bytes);
@@ -1618,16 +1636,35 @@ int32_t solo_srtcp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, 
     hipError_t e = hipSuccess;
     for (int32_t i = 0; i < n && e == hipSuccess; i++) {
         const size_t s = (size_t)h_streams[i];
-        if (h_tx_master) e = hipMemcpyAsync(m.keys + 2 * s, &recs[2 * (size_t)i], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
-        if (h_tx_master && e == hipSuccess) e = hipMemcpyAsync(m.tx + s, &tx[(size_t)i], sizeof(SxSrtcpTx), hipMemcpyHostToDevice, st);
-        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(m.keys + 2 * s + 1, &recs[2 * (size_t)i + 1], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
-        if (h_rx_master && e == hipSuccess) e = hipMemcpyAsync(m.rx + s, &rx[(size_t)i], sizeof(SxSrtcpRx), hipMemcpyHostToDevice, st);
+        if (has_tx) e = hipMemcpyAsync(m.keys + 2 * s, &recs[2 * (size_t)i], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (has_tx && e == hipSuccess) e = hipMemcpyAsync(m.tx + s, &tx[(size_t)i], sizeof(SxSrtcpTx), hipMemcpyHostToDevice, st);
+        if (has_rx && e == hipSuccess) e = hipMemcpyAsync(m.keys + 2 * s + 1, &recs[2 * (size_t)i + 1], sizeof(SxSrtpKey), hipMemcpyHostToDevice, st);
+        if (has_rx && e == hipSuccess) e = hipMemcpyAsync(m.rx + s, &rx[(size_t)i], sizeof(SxSrtcpRx), hipMemcpyHostToDevice, st);
     }
     const hipError_t e2 = hipStreamSynchronize(st);         // (the host records go with this call: the copies must have read them)
     sx_srtp_wipe(recs);
     if (e != hipSuccess || e2 != hipSuccess) return -(int32_t)(e != hipSuccess ? e : e2);
     r->srtcp.has_tx.swap(next.has_tx); r->srtcp.has_rx.swap(next.has_rx);
+    rtp_count_gcm(r);
     return 0;
+}
+int32_t solo_srtcp_set_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_tx_index,
+                            const int64_t* h_rx_index, void* hip_stream) {
+    std::vector<SxSrtpKey> recs;
+    std::vector<SxSrtcpTx> tx;
+    std::vector<SxSrtcpRx> rx;
+    SxSrtcpMirror next;
+    if (!r || !sx_srtcp_set_keys_plan(r->srtcp, r->n_rows, h_streams, n, h_tx_master, h_rx_master, h_tx_index, (const i64*)h_rx_index, next, recs, tx, rx)) return -1;
+    return srtcp_put_keys(r, h_streams, n, h_tx_master != NULL, h_rx_master != NULL, recs, tx, rx, next, (hipStream_t)hip_stream);
+}
+int32_t solo_srtcp_set_keys_gcm(solo_rtp_t* r, const int32_t* h_streams, int32_t n, const uint8_t* h_tx_master, const uint8_t* h_rx_master, const uint32_t* h_tx_index,
+                                const int64_t* h_rx_index, void* hip_stream) {
+    std::vector<SxSrtpKey> recs;
+    std::vector<SxSrtcpTx> tx;
+    std::vector<SxSrtcpRx> rx;
+    SxSrtcpMirror next;
+    if (!r || !sx_srtcp_gcm_set_keys_plan(r->srtcp, r->n_rows, h_streams, n, h_tx_master, h_rx_master, h_tx_index, (const i64*)h_rx_index, next, recs, tx, rx)) return -1;
+    return srtcp_put_keys(r, h_streams, n, h_tx_master != NULL, h_rx_master != NULL, recs, tx, rx, next, (hipStream_t)hip_stream);
 }
 int32_t solo_srtcp_clear_keys(solo_rtp_t* r, const int32_t* h_streams, int32_t n, void* hip_stream) {
     if (!r || !sx_list_ok(h_streams, n, r->n_rows)) return -1;
@@ -1654,14 +1691,15 @@ int32_t solo_srtcp_get_index(solo_rtp_t* r, const int32_t* h_streams, int32_t n,
 int32_t solo_srtcp_protect(const solo_rtcp_t* c, solo_rtp_t* r_tx, const int32_t* d_streams, int32_t n, const solo_rtcp_build_count_t* d_build_count,
                            solo_dgram_t* d_dgrams, uint8_t* d_wire, int64_t wire_bytes, solo_srtcp_count_t* d_count, void* hip_stream) {
     if (!sx_srtcp_protect_ok(c, c ? c->n_rows : 0, c ? c->trailer : 0, r_tx, r_tx ? r_tx->n_rows : 0, d_streams, n, d_build_count, d_dgrams, d_wire, wire_bytes,
-                             d_count))
+                             d_count) ||
+        !sx_srtcp_gcm_protect_ok(r_tx->n_gcm[2] > 0, c->trailer))
         return -1;
     const SxSrtcpMem m = sx_srtcp_mem(r_tx->d_srtcp, r_tx->n_rows);
     SxSrtcpProtectArgs a;
     a.streams = d_streams; a.build_count = d_build_count; a.dgrams = d_dgrams; a.wire = d_wire; a.keys = m.keys; a.tx = m.tx;
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n = n; a.n_streams = r_tx->n_rows;
-    SOLO_CHECK(solo_srtcp_protect_launch(a, d_count, (hipStream_t)hip_stream));
+    SOLO_CHECK(solo_srtcp_protect_launch_all(a, d_count, r_tx->n_gcm[2] > 0, (hipStream_t)hip_stream));
     return 0;
 }
 int32_t solo_srtcp_unprotect(solo_rtp_t* r_rx, const solo_dgram_t* d_dgrams, int32_t n_dgrams, uint8_t* d_wire, int64_t wire_bytes, solo_dgram_t* d_dgrams_out,
@@ -1672,7 +1710,7 @@ int32_t solo_srtcp_unprotect(solo_rtp_t* r_rx, const solo_dgram_t* d_dgrams, int
     a.dgrams = d_dgrams; a.out = d_dgrams_out; a.wire = d_wire; a.table = r_rx->d_table; a.keys = m.keys; a.rx = m.rx;
     a.wire_bytes = wire_bytes > 0x7FFFFFFFLL ? 0x7FFFFFFFLL : wire_bytes;
     a.n_dgrams = n_dgrams; a.n_streams = r_rx->n_rows;
-    SOLO_CHECK(solo_srtcp_unprotect_launch(a, d_count, (hipStream_t)hip_stream));
+    SOLO_CHECK(solo_srtcp_unprotect_launch_all(a, d_count, r_rx->n_gcm[3] > 0, (hipStream_t)hip_stream));
     return 0;
 }
 

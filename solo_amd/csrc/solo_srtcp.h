@@ -33,6 +33,7 @@
 // what became of a datagram == its word of solo_srtcp_count_t; 0 .. 5 are those of solo_srtp.h
 #define SX_SRTCP_REPLAYED 6
 #define SX_SRTCP_EXHAUSTED 7
+#define SX_SRTCP_ELSEWHERE 8    // as SX_SRTP_ELSEWHERE: the datagram is solo_srtp_gcm.h's; a word of the workgroup's counters that is never flushed
 
 typedef solo_srtcp_count_t SxSrtcpCount;
 static_assert(sizeof(SxSrtcpCount) == 32, "solo_srtcp_count_t layout");
@@ -59,7 +60,7 @@ static inline void sx_srtcp_mem_init(void* at, int n_streams) {
 }
 
 // ---- the control plane (host) ---------------------------------------------------------------------------------------------------------------
-static inline bool sx_srtcp_trailer_ok(int32_t trailer) { return trailer >= 0 && trailer <= 16; }        // solo_rtcp_set_trailer
+static inline bool sx_srtcp_trailer_ok(int32_t trailer) { return (trailer >= 0 && trailer <= 16) || trailer == 20; }        // solo_rtcp_set_trailer; 20: the GCM trailer
 // the host mirror: per stream "has a tx key" and "has an rx key" -- never the keys
 struct SxSrtcpMirror { std::vector<u8> has_tx, has_rx; };
 // A set_keys call: validated before anything changes.  true: recs[2 i + d] is the record of direction d (0 tx, 1 rx) of listed stream i
@@ -89,6 +90,7 @@ struct SxSrtcpProtectArgs {
     const i32* streams; const SxRtcpBuildCount* build_count; SxRtpDgram* dgrams; u8* wire; const SxSrtpKey* keys; SxSrtcpTx* tx;     // keys, tx: NULL = no stream has a key
     i64 wire_bytes;                                          // (at most 2^31 - 1)
     int n, n_streams;
+    int gcm = 0;                                             // the GCM kernel follows this one (solo_srtp_gcm.h): see SX_SRTP_ELSEWHERE
 };
 static inline bool sx_srtcp_protect_ok(const void* c, int n_streams, int trailer, const void* r, int session_streams, const void* streams, int n, const void* build_count,
                                        const void* dgrams, const void* wire, long long wire_bytes, const void* count) {
@@ -109,12 +111,14 @@ SX_HD i32 sx_srtcp_protect_plan(const SxSrtcpProtectArgs& a, int i, SxSrtpRun* r
     const SxRtpDgram d = a.dgrams[i];
     sx_srtcp_run_clear(run);
     if (d.len == 0) return run->verdict = SX_SRTP_SKIPPED;
+    const i32 s = a.streams[i];
+    const bool other = a.keys && s >= 0 && s < a.n_streams && sx_srtp_key(a.keys, s, 0)->transform != SX_SRTP_CM;
+    if (other && a.gcm) return run->verdict = SX_SRTCP_ELSEWHERE;
     const SxRtpDgram none = {0, 0};
     a.dgrams[i] = none;                                     // (written again behind the MAC)
-    const i32 s = a.streams[i];
     if (d.len < SX_SRTCP_HEAD || (d.len & 3) || d.offset < 0 || (i64)d.offset + (i64)d.len + SX_SRTCP_TRAILER > a.wire_bytes || s < 0 || s >= a.n_streams)
         return run->verdict = SX_SRTP_MALFORMED;
-    if (!a.keys || !sx_srtp_key(a.keys, s, 0)->has) return run->verdict = SX_SRTP_NO_KEY;
+    if (!a.keys || !sx_srtp_key(a.keys, s, 0)->has || other) return run->verdict = SX_SRTP_NO_KEY;
     const u32 index = a.tx[s].next;
     if (index >= SX_SRTCP_INDEX_END) return run->verdict = SX_SRTCP_EXHAUSTED;
     a.tx[s].next = index + 1u;
@@ -146,6 +150,7 @@ struct SxSrtcpUnprotectArgs {
     const SxRtpDgram* dgrams; SxRtpDgram* out; u8* wire; const u32* table; const SxSrtpKey* keys; SxSrtcpRx* rx;      // keys, rx: NULL = no stream has a key
     i64 wire_bytes;                                          // (at most 2^31 - 1)
     int n_dgrams, n_streams;
+    int gcm = 0;                                             // the GCM kernel follows this one (solo_srtp_gcm.h): see SX_SRTP_ELSEWHERE
 };
 // THE receive rule: datagram i -> its run and its verdict, the first rule that fails; authenticated here, by this lane.  d_dgrams_out[i]
 // is written either way, and the stream's pending index is raised for an accepted datagram.  A run with E = 0 has hdr = len: no cipher
@@ -162,6 +167,11 @@ SX_HD i32 sx_srtcp_unprotect_one(const SxSrtcpUnprotectArgs& a, int i, SxSrtpRun
     if (stream < 0 || stream >= a.n_streams) return run->verdict = SX_SRTP_UNKNOWN_SSRC;
     if (!a.keys || !a.rx || !sx_srtp_key(a.keys, stream, 1)->has) return run->verdict = SX_SRTP_NO_KEY;
     const SxSrtpKey* key = sx_srtp_key(a.keys, stream, 1);
+    if (key->transform != SX_SRTP_CM) {
+        if (!a.gcm) return run->verdict = SX_SRTP_NO_KEY;   // (no kernel behind this one: no key this call can use)
+        if (a.out == a.dgrams) a.out[i] = d;                // the kernel behind reads dgrams[i]: where out IS dgrams the entry goes back
+        return run->verdict = SX_SRTCP_ELSEWHERE;
+    }
     const i32 body = d.len - SX_SRTCP_TRAILER;               // what the tag covers, with the word behind it
     const u32 word = sx_rtp_be32(lo + body, lo, hi), index = word & 0x7FFFFFFFu;
     if ((i64)index <= a.rx[stream].index) return run->verdict = SX_SRTCP_REPLAYED;
@@ -191,7 +201,7 @@ __device__ __forceinline__ void sx_srtcp_count_flush(const i32* cnt, i32* count)
 // The count is zeroed by solo_rtp_clear_kernel ahead of either kernel, as in solo_srtp.h
 __global__ void __launch_bounds__(SX_RTP_TILE) solo_srtcp_protect_kernel(const SxSrtcpProtectArgs a, i32* count) {
     __shared__ u32 te[256];
-    __shared__ i32 cnt[8];
+    __shared__ i32 cnt[16];                                 // (8 .. : SX_SRTCP_ELSEWHERE)
     __shared__ SxSrtpRun runs[SX_RTP_TILE];
     if (sx_srtcp_refused(a)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) count[0] = -1;
@@ -200,7 +210,7 @@ __global__ void __launch_bounds__(SX_RTP_TILE) solo_srtcp_protect_kernel(const S
     const int tid = (int)threadIdx.x;
     const int i = (int)blockIdx.x * SX_RTP_TILE + tid;
     te[tid] = SX_AES_TE0_DEV[tid];
-    if (tid < 8) cnt[tid] = 0;
+    if (tid < 16) cnt[tid] = 0;
     __syncthreads();
     SxSrtpRun run;
     sx_srtcp_run_clear(&run); run.verdict = -1;
@@ -218,12 +228,12 @@ __global__ void __launch_bounds__(SX_RTP_TILE) solo_srtcp_protect_kernel(const S
 }
 __global__ void __launch_bounds__(SX_RTP_TILE) solo_srtcp_unprotect_kernel(const SxSrtcpUnprotectArgs a, i32* count) {
     __shared__ u32 te[256];
-    __shared__ i32 cnt[8];
+    __shared__ i32 cnt[16];                                 // (8 .. : SX_SRTCP_ELSEWHERE)
     __shared__ SxSrtpRun runs[SX_RTP_TILE];
     const int tid = (int)threadIdx.x;
     const int i = (int)blockIdx.x * SX_RTP_TILE + tid;
     te[tid] = SX_AES_TE0_DEV[tid];
-    if (tid < 8) cnt[tid] = 0;
+    if (tid < 16) cnt[tid] = 0;
     __syncthreads();
     SxSrtpRun run;
     sx_srtcp_run_clear(&run); run.verdict = -1;
@@ -246,17 +256,26 @@ static inline hipError_t solo_srtcp_protect_launch(const SxSrtcpProtectArgs& a, 
     hipLaunchKernelGGL(solo_srtcp_protect_kernel, dim3((a.n + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a, (i32*)count);
     return hipGetLastError();
 }
-static inline hipError_t solo_srtcp_unprotect_launch(const SxSrtcpUnprotectArgs& a, SxSrtcpCount* count, hipStream_t s) {
+// the two halves of an unprotect call, as in solo_srtp.h
+static inline hipError_t solo_srtcp_unprotect_launch_verdicts(const SxSrtcpUnprotectArgs& a, SxSrtcpCount* count, hipStream_t s) {
     hipLaunchKernelGGL(solo_rtp_clear_kernel, dim3(1), dim3(64), 0, s, (i32*)count);
     if (a.n_dgrams == 0) return hipGetLastError();
     hipLaunchKernelGGL(solo_srtcp_unprotect_kernel, dim3((a.n_dgrams + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a, (i32*)count);
-    if (a.rx) hipLaunchKernelGGL(solo_srtcp_rx_fold_kernel, dim3((a.n_streams + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a.rx, a.n_streams);
     return hipGetLastError();
+}
+static inline hipError_t solo_srtcp_unprotect_launch_fold(const SxSrtcpUnprotectArgs& a, hipStream_t s) {
+    if (a.n_dgrams == 0 || !a.rx) return hipSuccess;
+    hipLaunchKernelGGL(solo_srtcp_rx_fold_kernel, dim3((a.n_streams + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a.rx, a.n_streams);
+    return hipGetLastError();
+}
+static inline hipError_t solo_srtcp_unprotect_launch(const SxSrtcpUnprotectArgs& a, SxSrtcpCount* count, hipStream_t s) {
+    const hipError_t e = solo_srtcp_unprotect_launch_verdicts(a, count, s);
+    return e != hipSuccess ? e : solo_srtcp_unprotect_launch_fold(a, s);
 }
 #else
 // Host forms (tests): tile by tile, phase by phase, lane by lane through the per-datagram functions above.
 static inline void sx_srtcp_protect_host(const SxSrtcpProtectArgs& a, SxSrtcpCount* count) {
-    i32 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    i32 c[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (sx_srtcp_refused(a)) { c[0] = -1; memcpy(count, c, sizeof(*count)); return; }
     SxSrtpRun* runs = new SxSrtpRun[SX_RTP_TILE];
     for (int t0 = 0; t0 < a.n; t0 += SX_RTP_TILE) {
@@ -271,7 +290,7 @@ static inline void sx_srtcp_protect_host(const SxSrtcpProtectArgs& a, SxSrtcpCou
     memcpy(count, c, sizeof(*count));
 }
 static inline void sx_srtcp_unprotect_host(const SxSrtcpUnprotectArgs& a, SxSrtcpCount* count) {
-    i32 c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    i32 c[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     SxSrtpRun* runs = new SxSrtpRun[SX_RTP_TILE];
     for (int t0 = 0; t0 < a.n_dgrams; t0 += SX_RTP_TILE) {
         const int m = sx_min(a.n_dgrams - t0, SX_RTP_TILE);

@@ -43,11 +43,18 @@
 #define SX_SRTP_UNKNOWN_SSRC 3
 #define SX_SRTP_NO_KEY 4
 #define SX_SRTP_AUTH_FAILED 5
+// a datagram whose key names another transform (solo_srtp_gcm.h) is left as it is and counted by that transform's kernel: this word of
+// the workgroup's counters is never flushed.  ONLY where the call's arguments say that this kernel follows (`gcm`, set at launch from the
+// host mirror): a call issued -- or a graph captured -- before the session held such a key has no kernel behind it that could take the
+// datagram, and judges it no_key, so that it is voided on the way out and rejected on the way in: the hand-over fails closed
+#define SX_SRTP_ELSEWHERE 6
+#define SX_SRTP_CM 0            // SxSrtpKey.transform: AES-CM with HMAC-SHA1, the records made here
+#define SX_SRTP_GCM 1           //                      AEAD_AES_128_GCM (RFC 7714), the records of solo_srtp_gcm.h
 
 typedef solo_srtp_count_t SxSrtpCount;
 static_assert(sizeof(SxSrtpCount) == 32, "solo_srtp_count_t layout");
 
-struct SxSrtpKey { u32 rk[44], salt[4], mid_i[5], mid_o[5], tag, has, pad[4]; };   // big-endian words throughout
+struct SxSrtpKey { u32 rk[44], salt[4], mid_i[5], mid_o[5], tag, has, transform, pad[3]; };   // big-endian words throughout
 static_assert(sizeof(SxSrtpKey) == 4 * SOLO_SRTP_KEY_WORDS && sizeof(SxSrtpKey) == 256, "a key record");
 struct SxSrtpRx { i64 index; u64 pending; u32 roc0, pad[3]; };   // index: -1 = none yet; pending: 1 + the call's highest accepted index, 0 = none
 static_assert(sizeof(SxSrtpRx) == 32, "a receive record");
@@ -288,6 +295,7 @@ struct SxSrtpProtectArgs {
     const SxSendRecord* records; const SxSendCount* send_count; SxRtpDgram* dgrams; u8* wire; const SxRtpStream* cfg; const SxSrtpKey* keys;   // keys: [n_streams][2] or NULL
     i64 wire_bytes;                                          // (at most 2^31 - 1)
     int max_records, n_streams;
+    int gcm = 0;                                             // the GCM kernel follows this one (solo_srtp_gcm.h)
 };
 struct SxSrtpRun { i32 off, len, hdr, stream; u32 roc, seq, ssrc; i32 verdict; };   // one datagram of a tile: wire[off .. off + len) is what the MAC covers
 static_assert(sizeof(SxSrtpRun) == 32, "a run in LDS");
@@ -300,13 +308,15 @@ SX_HD i32 sx_srtp_protect_plan(const SxSrtpProtectArgs& a, int k, SxSrtpRun* run
     const SxRtpDgram d = a.dgrams[k];
     run->off = 0; run->len = 0; run->hdr = 0; run->stream = -1; run->roc = 0; run->seq = 0; run->ssrc = 0;
     if (d.len == 0) return run->verdict = SX_SRTP_SKIPPED;
+    const SxSendRecord r = a.records[k];
+    const bool other = a.keys && r.stream >= 0 && r.stream < a.n_streams && sx_srtp_key(a.keys, r.stream, 0)->transform != SX_SRTP_CM;
+    if (other && a.gcm) return run->verdict = SX_SRTP_ELSEWHERE;
     const SxRtpDgram none = {0, 0};
     a.dgrams[k] = none;                                     // (written again behind the MAC)
-    const SxSendRecord r = a.records[k];
     if (d.len < 12 || d.offset < 0 || (i64)d.offset + (i64)d.len > a.wire_bytes || r.stream < 0 || r.stream >= a.n_streams || r.seq < 0 ||
         r.desc < 0 || r.desc > 1)
         return run->verdict = SX_SRTP_MALFORMED;
-    if (!a.keys || !sx_srtp_key(a.keys, r.stream, 0)->has) return run->verdict = SX_SRTP_NO_KEY;
+    if (!a.keys || !sx_srtp_key(a.keys, r.stream, 0)->has || other) return run->verdict = SX_SRTP_NO_KEY;
     SxRtpHead hd;
     const i32 hdr = sx_rtp_header_walk(a.wire + d.offset, d.len, &hd);
     if (hdr < 0 || (i64)d.offset + (i64)d.len + (i64)sx_srtp_key(a.keys, r.stream, 0)->tag > a.wire_bytes) return run->verdict = SX_SRTP_MALFORMED;
@@ -342,6 +352,7 @@ struct SxSrtpUnprotectArgs {
     const SxRtpDgram* dgrams; SxRtpDgram* out; u8* wire; const u32* table; const SxSrtpKey* keys; SxSrtpRx* rx;      // keys, rx: NULL = no stream has a key
     i64 wire_bytes;                                          // (at most 2^31 - 1)
     int n_dgrams, n_streams;
+    int gcm = 0;                                             // the GCM kernel follows this one (solo_srtp_gcm.h)
 };
 // the packet index of a datagram with sequence number seq against a receive record (RFC 3711 section 3.3.1, appendix A)
 SX_HD i64 sx_srtp_guess_index(const SxSrtpRx& x, u32 seq) {
@@ -368,6 +379,13 @@ SX_HD i32 sx_srtp_unprotect_one(const SxSrtpUnprotectArgs& a, int i, SxSrtpRun* 
     i32 stream = sx_rtp_find_ssrc(a.table, ssrc);
     if (stream >= a.n_streams) stream = -1;
     const SxSrtpKey* key = (stream >= 0 && a.keys && a.rx && sx_srtp_key(a.keys, stream, 1)->has) ? sx_srtp_key(a.keys, stream, 1) : NULL;
+    if (key && key->transform != SX_SRTP_CM) {
+        if (a.gcm) {                                        // the kernel behind reads dgrams[i]: where out IS dgrams the entry goes back, elsewhere out stays {0, 0}
+            if (a.out == a.dgrams) a.out[i] = d;
+            return run->verdict = SX_SRTP_ELSEWHERE;
+        }
+        key = NULL;                                         // (no kernel behind this one: no key this call can use)
+    }
     const i32 T = key ? (i32)key->tag : SX_SRTP_MIN_TAG;
     SxRtpHead hd;
     const i32 body = d.len - T;                              // what the tag covers
@@ -469,12 +487,21 @@ static inline hipError_t solo_srtp_protect_launch(const SxSrtpProtectArgs& a, Sx
     hipLaunchKernelGGL(solo_srtp_protect_kernel, dim3((a.max_records + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a, (i32*)count);
     return hipGetLastError();
 }
-static inline hipError_t solo_srtp_unprotect_launch(const SxSrtpUnprotectArgs& a, SxSrtpCount* count, hipStream_t s) {
+// the two halves of an unprotect call: the clear and the verdicts, then the fold (solo_srtp_gcm.h puts its kernel between them)
+static inline hipError_t solo_srtp_unprotect_launch_verdicts(const SxSrtpUnprotectArgs& a, SxSrtpCount* count, hipStream_t s) {
     hipLaunchKernelGGL(solo_rtp_clear_kernel, dim3(1), dim3(64), 0, s, (i32*)count);
     if (a.n_dgrams == 0) return hipGetLastError();
     hipLaunchKernelGGL(solo_srtp_unprotect_kernel, dim3((a.n_dgrams + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a, (i32*)count);
-    if (a.rx) hipLaunchKernelGGL(solo_srtp_rx_fold_kernel, dim3((a.n_streams + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a.rx, a.n_streams);
     return hipGetLastError();
+}
+static inline hipError_t solo_srtp_unprotect_launch_fold(const SxSrtpUnprotectArgs& a, hipStream_t s) {
+    if (a.n_dgrams == 0 || !a.rx) return hipSuccess;
+    hipLaunchKernelGGL(solo_srtp_rx_fold_kernel, dim3((a.n_streams + SX_RTP_TILE - 1) / SX_RTP_TILE), dim3(SX_RTP_TILE), 0, s, a.rx, a.n_streams);
+    return hipGetLastError();
+}
+static inline hipError_t solo_srtp_unprotect_launch(const SxSrtpUnprotectArgs& a, SxSrtpCount* count, hipStream_t s) {
+    const hipError_t e = solo_srtp_unprotect_launch_verdicts(a, count, s);
+    return e != hipSuccess ? e : solo_srtp_unprotect_launch_fold(a, s);
 }
 #else
 // Host forms (tests): tile by tile, phase by phase, lane by lane through the per-datagram functions above.
@@ -492,6 +519,7 @@ static inline void sx_srtp_protect_host(const SxSrtpProtectArgs& a, SxSrtpCount*
             if (runs[t].verdict == SX_SRTP_OK) sx_srtp_protect_mac(a, t0 + t, runs[t]);
     }
     delete[] runs;
+    c[SX_SRTP_ELSEWHERE] = 0;
     memcpy(count, c, sizeof(*count));
 }
 static inline void sx_srtp_unprotect_host(const SxSrtpUnprotectArgs& a, SxSrtpCount* count) {
@@ -506,6 +534,7 @@ static inline void sx_srtp_unprotect_host(const SxSrtpUnprotectArgs& a, SxSrtpCo
     if (a.rx)
         for (int s = 0; s < a.n_streams; s++) sx_srtp_rx_fold(a.rx, s);
     delete[] runs;
+    c[SX_SRTP_ELSEWHERE] = 0;
     memcpy(count, c, sizeof(*count));
 }
 #endif
