@@ -1257,6 +1257,92 @@ int32_t solo_srtp_set_keys_gcm(solo_rtp_t *r, const int32_t *h_streams, int32_t 
                                const uint32_t *h_rx_roc, void *hip_stream);
 int32_t solo_srtcp_set_keys_gcm(solo_rtp_t *r, const int32_t *h_streams, int32_t n, const uint8_t *h_tx_master, const uint8_t *h_rx_master,
                                 const uint32_t *h_tx_index, const int64_t *h_rx_index, void *hip_stream);
+/* The sender's feedback loop (solo_rate): what the peers report about our sending sets each stream's bitrate without a per-stream value
+ * reaching the host.  solo_rtcp_parse leaves solo_rtcp_feedback_t [n_streams] on the device; solo_rate_update, a controller with a state
+ * record per row, turns it into a target per stream; solo_batch_update_rates applies the targets to the running encoders from device
+ * memory; solo_rate_send_mask turns the controller's mode into the d_send mask of solo_send_pack.  The sender's RTCP tick is
+ * solo_srtcp_unprotect -> solo_rtcp_parse -> solo_rate_update -> solo_batch_update_rates -> solo_batch_encode -> solo_rate_send_mask ->
+ * solo_send_pack, captured as one graph (tests/test_gpu_rate.py: test_capture_closed_loop).
+ * solo_batch_update_rates -- a running stream's rate from DEVICE memory.  d_target_bps int32 [n]; position i belongs to stream
+ *   d_streams[i] under the rule of every device list (strictly increasing inside [0, N)); a list that breaks it refuses the whole call
+ *   on the device: d_count->applied = -1, nothing else is touched.  d_streams == NULL: n must be N, position i is stream i.  A value
+ *   <= 0 means "keep": counted kept, not one byte of that stream changes.  A positive value means exactly what the same targetRate_bps
+ *   means to solo_batch_update_streams on this handle: minus 1600 (800 with joint_mode 1), clamped to [5000, 100000], then setup_rate
+ *   (the two SNR targets); useDTX, useMDIndex and every other word of the state stay bit for bit; counted applied.  On a 32 kHz handle a
+ *   value that leaves SILK below 14000 is not built (solo_batch_update_streams refuses the whole call for it): HERE, where the host
+ *   does not know the values, that position is counted refused and its stream is left untouched.  listed = n.  One lane per position.
+ *   Ordering exactly as solo_batch_update_streams: hip_stream first waits for the handle's work in flight (the analysis kernels write a
+ *   stream's whole state back when they end: an update that overtook them would be undone); the new rate applies from the first packet
+ *   encoded after the call on hip_stream.  No allocation, no host synchronisation: capturable with n frozen.
+ *   -1 with nothing enqueued: NULL b, d_target_bps or d_count; a handle without an encoder; n outside (0, N], or d_streams NULL with
+ *   n != N; a pointer not 4-byte aligned.
+ * solo_rate_t -- an object of its own like solo_agc_t: n_rows state records of SOLO_RATE_STATE_BYTES, the lifecycle calls of every
+ *   row-state object (reset_rows: a HOST list; get_state / set_state: a device list or NULL, the blob is the records as they are).
+ *   The record: int32 flags (1 started, 2 has used a report, 4 thin), target_bps, uint32 last_ehs, int32 min_rtt (2^31 - 1: none yet),
+ *   idle, over, under, uint32 reports used, targets changed (both since the reset, mod 2^32), int32 the last fraction_lost and rtt
+ *   used, five words the stage never writes.  The reset record is zero but for min_rtt.
+ * solo_rate_update -- d_feedback [n_rows] exactly as solo_rtcp_parse wrote it; every row advances by one step and writes
+ *   d_target_bps[row] = the row's new target if it changed in this call, else 0 (the input format of solo_batch_update_rates: only
+ *   changed streams are touched), and d_mode[row] = 0 (both descriptions) or 1 (one description per packet, alternating).  Integers
+ *   only, products in 64 bits; tests/rate_model.py is this rule in plain Python integers and the normative text where the two differ.
+ *   A row, in this order, with t = target_bps:
+ *   1. not started: the live words go to the reset record, t = start_bps, started is set (counted started) and the row reports a
+ *      change even where nothing below moves t, so that the encoder takes the controller's start rate.
+ *   2. seen has SOLO_RTCP_BYE: the live words go back to the reset record, d_target_bps = 0, d_mode = 0, counted bye; nothing below.
+ *   3. the report is USED iff (seen & 0xFFFF) > 0 and (the row has used no report yet or (int32)(ext_high_seq - last_ehs) > 0): a
+ *      wrap-safe test.  A row with blocks whose ext_high_seq does not advance got the same interval again: counted repeated.
+ *   4. not used: idle = min(idle + 1, 2^31 - 1); in the call in which idle reaches stale_calls (> 0): t = min(t, start_bps), thin is
+ *      cleared, over = under = 0, counted stale -- once, as idle goes on counting: a sender without feedback does not keep an
+ *      escalated rate.
+ *   5. used (counted used): idle = 0, last_ehs = ext_high_seq, p = fraction_lost clamped to 0 .. 255; rtt > 0: min_rtt = min(min_rtt,
+ *      rtt); delayed = rtt_guard > 0 and rtt > 0 and rtt - min_rtt > rtt_guard (rtt -1 and 0 say nothing).  Then, counted by branch:
+ *        p > hi_q8           decreased: over = over + 1 if t <= min_bps (consecutive such reports at the floor) else 0;
+ *                            t = min(t - (t p >> 9), t - quantum_bps): the factor 1 - p / 512, at least a quantum
+ *        p < lo_q8, not delayed, not thin
+ *                            increased: over = 0; t = t + max(quantum_bps, t inc_q8 >> 8)
+ *        otherwise           held: over = 0; also counted delayed where p < lo_q8 and not thin, the delay guard being what held it
+ *   6. thinning, on used reports only, with thin as it stood when the step began: while thin, under = under + 1 if p < lo_q8 else 0,
+ *      and under >= thin_release clears thin, over and under (counted thin_off; increases resume with the next report); while not
+ *      thin, thin_after > 0 and over >= thin_after sets thin (counted thin_on).
+ *   Then, on every path but BYE: t is clamped to [min_bps, max_bps] and floored to a multiple of quantum_bps; changed = the row started
+ *   or t differs from the target the step began with (counted changed); thin_rows = the rows that leave the call thin; rows = n_rows.
+ *   Parameters, refused (-1) unless: 1 <= min_bps <= start_bps <= max_bps <= 1000000, quantum_bps >= 1 and divides all three,
+ *   0 <= lo_q8 <= hi_q8 <= 255, 0 <= inc_q8 <= 256, rtt_guard (1 / 65536 s), stale_calls, thin_after, thin_release >= 0, reserved = 0.
+ *   The binding's defaults are POLICY, NOT MEASUREMENTS: lo_q8 5, hi_q8 26 and inc_q8 13 are the 2 % and 10 % thresholds and the 5 % step
+ *   of the loss-based controller of the RMCAT "Google Congestion Control" draft; quantum_bps 200, rtt_guard 0, stale_calls
+ *   250, thin_after 0 (thinning is opt-in), thin_release 3.  Thinning is what a multiple-description codec can do below its floor rate:
+ *   one description per packet halves the wire rate, and the receiver decodes from one description as it does under loss.
+ *   -1 with nothing enqueued: a NULL pointer, refused parameters, d_feedback not 16-byte, d_target_bps or d_count not 4-byte aligned.
+ *   Two kernels (the clear of the count, a lane per row), the parameters travel as kernel arguments, no allocation, no host
+ *   synchronisation: capturable.
+ * solo_rate_send_mask -- stateless, a lane per (i, p): position i is row d_streams[i] of d_mode [n_rows], or i where d_streams is NULL;
+ *   seq = first_seq + (d_seq_base ? d_seq_base[i] : 0) + p mod 2^32, as solo_send_pack numbers packets.  d_send[i][p] = 3 in mode 0; in
+ *   mode 1 it is 1 (MD1) on even seq and 2 (MD2 || HB) on odd seq; ANDed with d_send_in[i][p] where that is given, so a caller's own mask
+ *   (silent rooms) survives; d_send may be d_send_in.  A list that is not strictly increasing inside [0, n_rows) writes nothing (every
+ *   workgroup checks it itself: the call has no object to keep a verdict in).  -1 with nothing enqueued: NULL d_mode or d_send; n_rows,
+ *   n or n_packets <= 0; n > n_rows; n * n_packets >= 2^31; d_streams or d_seq_base not 4-byte aligned.  One kernel: capturable.
+ * Not built: a delay-gradient / transport-wide estimator, REMB, pacing, a change of rate inside a multi-packet
+ * encode call, the decoder side, controller state in a migration blob (solo_rate_get_state / _set_state is the hand-over). */
+/* The records, the handle's call, the object's lifecycle, then its two device calls. */
+#define SOLO_RATE_STATE_BYTES 64
+typedef struct solo_rate_obj solo_rate_t;
+typedef struct { int32_t applied, kept, refused, listed; } solo_rate_apply_count_t;   /* 16 bytes; applied = -1: list refused on the device */
+typedef struct { int32_t min_bps, max_bps, start_bps, quantum_bps, lo_q8, hi_q8, inc_q8, rtt_guard,
+                 stale_calls, thin_after, thin_release, reserved; } solo_rate_params_t;              /* 48 bytes, reserved = 0 */
+typedef struct { int32_t rows, started, used, repeated, increased, decreased, held, delayed,
+                 stale, bye, thin_on, thin_off, thin_rows, changed, reserved[2]; } solo_rate_count_t; /* 64 bytes */
+int32_t solo_batch_update_rates(solo_batch_t *b, const int32_t *d_streams, int32_t n, const int32_t *d_target_bps,
+                                solo_rate_apply_count_t *d_count, void *hip_stream);
+solo_rate_t *solo_rate_create(int32_t n_rows);
+void    solo_rate_destroy(solo_rate_t *rc);
+int32_t solo_rate_reset(solo_rate_t *rc, void *hip_stream);
+int32_t solo_rate_reset_rows(solo_rate_t *rc, const int32_t *h_rows, int32_t n, void *hip_stream);
+int32_t solo_rate_get_state(solo_rate_t *rc, const int32_t *d_rows, int32_t n, uint8_t *d_blob, void *hip_stream);
+int32_t solo_rate_set_state(solo_rate_t *rc, const int32_t *d_rows, int32_t n, const uint8_t *d_blob, void *hip_stream);
+int32_t solo_rate_update(solo_rate_t *rc, const solo_rtcp_feedback_t *d_feedback, const solo_rate_params_t *params,
+                         int32_t *d_target_bps, uint8_t *d_mode, solo_rate_count_t *d_count, void *hip_stream);
+int32_t solo_rate_send_mask(const uint8_t *d_mode, int32_t n_rows, const int32_t *d_streams, int32_t n, int32_t n_packets,
+                            const int32_t *d_seq_base, int32_t first_seq, const uint8_t *d_send_in, uint8_t *d_send, void *hip_stream);
 /* Pipelining consecutive encode calls: with on = 1 solo_batch_encode returns without making `hip_stream` wait for the handle's
  * internal streams, so the next encode call starts while the tail of this one still runs (the caller passes different output
  * buffers to calls in flight).  Before consuming the outputs of an encode call on some stream, call

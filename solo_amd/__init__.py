@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "solo_rtcp_create", "solo_rtcp_destroy", "solo_rtcp_reset", "solo_rtcp_reset_rows", "solo_rtcp_get_state", "solo_rtcp_set_state",
     "solo_rtcp_set_cname", "solo_rtcp_received", "solo_rtcp_sent", "solo_rtcp_build", "solo_rtcp_parse",
     "solo_rtcp_set_trailer", "solo_srtcp_set_keys", "solo_srtcp_clear_keys", "solo_srtcp_get_index", "solo_srtcp_protect", "solo_srtcp_unprotect",
+    "solo_batch_update_rates", "solo_rate_create", "solo_rate_destroy", "solo_rate_reset", "solo_rate_reset_rows", "solo_rate_get_state",
+    "solo_rate_set_state", "solo_rate_update", "solo_rate_send_mask",
 ]
 
 
@@ -206,6 +208,23 @@ class solo_rtcp_feedback_t(C.Structure):
     """what a peer's report block says about one of our streams (solo_rtcp_parse); 32 bytes"""
     _fields_ = [("seen", C.c_int32), ("fraction_lost", C.c_int32), ("cum_lost", C.c_int32), ("ext_high_seq", C.c_uint32), ("jitter", C.c_uint32),
                 ("lsr", C.c_uint32), ("dlsr", C.c_uint32), ("rtt", C.c_int32)]
+
+
+class solo_rate_apply_count_t(C.Structure):
+    """what a solo_batch_update_rates call did (include/solo_mi355x.h); 16 bytes; applied = -1: list refused on the device"""
+    _fields_ = [(n, C.c_int32) for n in ("applied", "kept", "refused", "listed")]
+
+
+class solo_rate_params_t(C.Structure):
+    """the policy of a solo_rate_update call (include/solo_mi355x.h); 48 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("min_bps", "max_bps", "start_bps", "quantum_bps", "lo_q8", "hi_q8", "inc_q8", "rtt_guard", "stale_calls", "thin_after",
+                                         "thin_release", "reserved")]
+
+
+class solo_rate_count_t(C.Structure):
+    """what a solo_rate_update call did (include/solo_mi355x.h); 64 bytes"""
+    _fields_ = [(n, C.c_int32) for n in ("rows", "started", "used", "repeated", "increased", "decreased", "held", "delayed", "stale", "bye", "thin_on",
+                                         "thin_off", "thin_rows", "changed", "reserved0", "reserved1")]
 
 
 class solo_forward_row_t(C.Structure):
@@ -415,6 +434,17 @@ def load_library():
                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])}.items():
         f = getattr(lib, "solo_rtcp_" + name)
         f.restype, f.argtypes = restype, argtypes
+    for name, (restype, argtypes) in {"create": (C.c_void_p, [C.c_int32]), "destroy": (None, [C.c_void_p]), "reset": (C.c_int32, [C.c_void_p, C.c_void_p]),
+                                      "reset_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+                                      "get_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+                                      "set_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+                                      "update": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+                                      "send_mask": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p])}.items():
+        f = getattr(lib, "solo_rate_" + name)
+        f.restype, f.argtypes = restype, argtypes
+    lib.solo_batch_update_rates.restype = C.c_int32
+    lib.solo_batch_update_rates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.solo_rtcp_set_trailer.restype = C.c_int32
     lib.solo_rtcp_set_trailer.argtypes = [C.c_void_p, C.c_int32]
     lib.solo_srtcp_set_keys.restype = C.c_int32
@@ -693,6 +723,31 @@ class SoloBatch:
         r = self.lib.solo_batch_update_streams(self.h, (C.c_int32 * n)(*idx), n, w, enc_arr, dec_arr, self._stream())
         if r:
             raise RuntimeError("solo_batch_update_streams -> %d" % r)
+
+    RATES_COUNT = tuple(n for n, _ in solo_rate_apply_count_t._fields_)
+
+    def update_rates(self, target, streams=None):
+        """The rate of RUNNING streams from device memory (solo_batch_update_rates): target int32 [n] on the device, one value per stream
+        (streams=None: n = N) or per listed stream (streams: a strictly increasing sequence or int32 CUDA tensor, as in encode()).  A
+        value <= 0 keeps the stream as it is; a positive one is the `rate` of update_streams(), and nothing but the rate changes; on a
+        32 kHz handle a value that leaves SILK below 14000 bps is refused for that stream alone.  This is what Rate.update() writes.
+        -> count int32 [4] on the device, read with rates_count().  The new rate applies from the next packet encoded on the current
+        stream; no synchronisation."""
+        t = self.torch
+        if self._enc is None:
+            raise ValueError("the handle has no encoder")
+        smap, n = self._rows_of(streams)
+        _tensor("target", target, t.int32, (n,))
+        count = t.zeros((4,), dtype=t.int32, device=target.device)
+        r = self.lib.solo_batch_update_rates(self.h, _ptr(smap), n, target.data_ptr(), count.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_batch_update_rates -> %d" % r)
+        return count
+
+    def rates_count(self, count):
+        """the count tensor of update_rates() as a dict (synchronises): applied, kept, refused, listed; applied == -1: the stream list
+        was refused on the device"""
+        return _counts(solo_rate_apply_count_t, count)
 
     def encode(self, pcm, bits=None, nbytes=None, status=None, streams=None):
         """pcm: int16 CUDA tensor [N, P, 640] -> (bits uint8 [N,P,slot], nbytes int16 [N,P,2], status int32 [N]).
@@ -1256,7 +1311,7 @@ class SoloBatch:
 
 
 class _RowObject:
-    """What Resampler, Vad, Playout and Agc share: a library object solo_<PREFIX>_* of n_rows state records on the current HIP device,
+    """What Resampler, Vad, Playout, Agc and Rate share: a library object solo_<PREFIX>_* of n_rows state records on the current HIP device,
     carried from call to call, with its create / destroy / reset / reset_rows calls."""
 
     PREFIX = None
@@ -1706,6 +1761,81 @@ class Agc(_RowStateObject):
     def count(self, count):
         """a count tensor of run() as a dict (synchronises); rows == -1: the list was refused on the device"""
         return _counts(solo_agc_count_t, count)
+
+
+RATE_STATE_BYTES = 64
+
+
+class Rate(_RowStateObject):
+    """n_rows loss-based rate controllers on the current HIP device (solo_rate_*, include/solo_mi355x.h): update() turns the feedback rows
+    of Rtcp.parse() into a target per stream for SoloBatch.update_rates() and a mode per stream, send_mask() turns the mode into the
+    send= mask of SoloBatch.send_pack().  State carries from call to call."""
+
+    COUNT = tuple(n for n, _ in solo_rate_count_t._fields_ if not n.startswith("reserved"))
+    PREFIX, state_bytes = "rate", RATE_STATE_BYTES
+
+    def __init__(self, n_rows):
+        self.n_rows = int(n_rows)
+        if self.n_rows <= 0:
+            raise ValueError("n_rows must be positive")
+        self._create(self.n_rows)
+
+    def update(self, feedback, min_bps, max_bps, start_bps, quantum_bps=200, lo_q8=5, hi_q8=26, inc_q8=13, rtt_guard=0, stale_calls=250, thin_after=0,
+               thin_release=3, target=None, mode=None):
+        """feedback int32 [n_rows, 8] as Rtcp.parse() wrote it -> (target int32 [n_rows]: a row's new target in bps where it changed in
+        this call, else 0; mode uint8 [n_rows]: 1 = one description per packet; count int32 [16] on the device, read with count()).
+        The rates stay inside [min_bps, max_bps], multiples of quantum_bps, and begin at start_bps.  The other defaults are policy, not
+        measurements: lo_q8 / hi_q8 / inc_q8 are the 2 % and 10 % loss thresholds and the 5 % step of the loss-based controller of the
+        RMCAT "Google Congestion Control" draft; rtt_guard (1 / 65536 s above the smallest round trip seen; 0: off) holds increases;
+        stale_calls without a report take the rate back to start_bps; thin_after (0: off) reports of loss at min_bps switch a row to one
+        description per packet, thin_release clean ones switch it back.  target= / mode=: the caller's buffers (a captured call).
+        Enqueued on the current stream, no synchronisation."""
+        t = self.torch
+        _tensor("feedback", feedback, t.int32, (self.n_rows, 8))
+        _tensor("target", target, t.int32, (self.n_rows,), optional=True)
+        _tensor("mode", mode, t.uint8, (self.n_rows,), optional=True)
+        prm = solo_rate_params_t(int(min_bps), int(max_bps), int(start_bps), int(quantum_bps), int(lo_q8), int(hi_q8), int(inc_q8), int(rtt_guard),
+                                 int(stale_calls), int(thin_after), int(thin_release), 0)
+        q = prm.quantum_bps
+        if not (q >= 1 and 1 <= prm.min_bps <= prm.start_bps <= prm.max_bps <= 1000000 and not (prm.min_bps % q or prm.max_bps % q or prm.start_bps % q) and
+                0 <= prm.lo_q8 <= prm.hi_q8 <= 255 and 0 <= prm.inc_q8 <= 256 and min(prm.rtt_guard, prm.stale_calls, prm.thin_after, prm.thin_release) >= 0):
+            raise ValueError("1 <= min_bps <= start_bps <= max_bps <= 1000000, all multiples of quantum_bps >= 1; 0 <= lo_q8 <= hi_q8 <= 255; inc_q8 0 .. 256; "
+                             "rtt_guard, stale_calls, thin_after, thin_release >= 0")
+        if feedback.data_ptr() & 15:
+            raise ValueError("feedback: 16-byte aligned")
+        if target is None:
+            target = t.empty((self.n_rows,), dtype=t.int32, device=feedback.device)
+        if mode is None:
+            mode = t.empty((self.n_rows,), dtype=t.uint8, device=feedback.device)
+        count = t.empty((16,), dtype=t.int32, device=feedback.device)
+        self._call("update", feedback.data_ptr(), C.byref(prm), target.data_ptr(), mode.data_ptr(), count.data_ptr())
+        return target, mode, count
+
+    def send_mask(self, mode, n_packets, streams=None, seq_base=None, first_seq=0, send=None, out=None):
+        """mode uint8 [n_rows] as update() wrote it -> the send= mask of SoloBatch.send_pack(), uint8 [n, n_packets]: 3 for a row in mode
+        0; for a row in mode 1, 1 (MD1) where the packet's sequence number first_seq + seq_base[i] + p is even and 2 (MD2 || HB) where
+        it is odd.  streams: position i is row streams[i] (None: row i, n = n_rows); send uint8 [n, n_packets]: the caller's own mask,
+        ANDed in; out=: where the mask goes (out=send works in place).  A bad list writes nothing.  Enqueued on the current stream."""
+        t = self.torch
+        rows = self._rows(streams)
+        n, P = self._n(rows), int(n_packets)
+        _tensor("mode", mode, t.uint8, (self.n_rows,))
+        _tensor("seq_base", seq_base, t.int32, (n,), optional=True)
+        _tensor("send", send, t.uint8, (n, P), optional=True)
+        _tensor("out", out, t.uint8, (n, P), optional=True)
+        first_seq = int(first_seq)
+        if P < 1 or n * P >= 2 ** 31 or not -2 ** 31 <= first_seq < 2 ** 31:
+            raise ValueError("n_packets >= 1, n * n_packets below 2^31, first_seq inside int32")
+        if out is None:
+            out = t.zeros((n, P), dtype=t.uint8, device=mode.device)
+        r = self.lib.solo_rate_send_mask(mode.data_ptr(), self.n_rows, _ptr(rows), n, P, _ptr(seq_base), first_seq, _ptr(send), out.data_ptr(), self._stream())
+        if r:
+            raise RuntimeError("solo_rate_send_mask -> %d" % r)
+        return out
+
+    def count(self, count):
+        """the count tensor of update() as a dict (synchronises)"""
+        return {k: v for k, v in _counts(solo_rate_count_t, count).items() if not k.startswith("reserved")}
 
 
 class Rtp(_RowObject):

@@ -46,6 +46,7 @@
 #include "solo_srtp_gcm.h"      // AEAD_AES_128_GCM for both (RFC 7714): the kernels behind theirs, the two key calls
 #include "solo_srtcp.h"         // SRTCP protection of the compound packets of solo_rtcp.h (solo_srtcp_protect / _unprotect): likewise
 #include "solo_rtcp.h"          // RTCP beside the RTP sessions: reception statistics, sender counts, compound packets out and in (solo_rtcp_*): likewise
+#include "solo_rate.h"          // the sender's feedback loop: rate controller per row, its mode as a send mask (solo_rate_*): likewise
 
 // conformance probe of the L0 fixed-point vocabulary as compiled for gfx950 (solo_debug_l0 below): out[i] = op(a[i], b[i], c[i])
 __global__ void __launch_bounds__(64) solo_l0_probe_kernel(int op, int n, const i32* a, const i32* b, const i32* c, i32* out) {
@@ -202,7 +203,8 @@ enum {
     SOLO_VERDICT_MIX,                // solo_mix, solo_mix_shared, solo_mix_selected (their room ids, slots, picks per room and packet)
     SOLO_VERDICT_REPORT,             // solo_recv_report
     SOLO_VERDICT_EXPORT,             // solo_batch_export_streams
-    SOLO_VERDICT_IMPORT,             // [8, 9] solo_batch_import_streams (its list, its records)
+    SOLO_VERDICT_RATES,              // solo_batch_update_rates
+    SOLO_VERDICT_IMPORT,             // [9, 10] solo_batch_import_streams (its list, its records)
     SOLO_N_VERDICTS = SOLO_VERDICT_IMPORT + 2
 };
 // an environment knob that is a number
@@ -479,6 +481,27 @@ int32_t solo_batch_reset_streams(solo_batch_t* b, const int32_t* h_streams, int3
 int32_t solo_batch_update_streams(solo_batch_t* b, const int32_t* h_streams, int32_t n, int32_t which, const USER_Ctrl_enc* h_enc,
                                   const USER_Ctrl_dec* h_dec, void* hip_stream) {
     return stream_ctl_apply(b, false, h_streams, n, which, h_enc, h_dec, (hipStream_t)hip_stream);
+}
+
+// A running stream's rate from DEVICE memory (include/solo_mi355x.h; the kernel: solo_enc_rate_list_kernel of the handle's build).  The
+// wait is that of solo_batch_update_streams, for its reason; the values are judged on the device (sx_enc_apply_target), the list by the
+// list check kernel.
+int32_t solo_batch_update_rates(solo_batch_t* b, const int32_t* d_streams, int32_t n, const int32_t* d_target_bps, solo_rate_apply_count_t* d_count,
+                                void* hip_stream) {
+    if (!b || !sx_rate_apply_call_ok(b->n_streams, b->have_enc != 0, d_streams, n, d_target_bps, d_count)) return -1;
+#ifdef SOLO_WITH_ENCODER
+    hipStream_t st = (hipStream_t)hip_stream;
+    {
+        const int32_t r = solo_wait_in_flight(b, st);
+        if (r) return r;
+    }
+    uint32_t* verdict = b->d_verdict + SOLO_VERDICT_RATES;
+    SOLO_CHECK(launch_list_check(d_streams, n, b->n_streams, verdict, NULL, st));
+    SOLO_CHECK(b->eops->rate_list(b->d_enc_state, d_streams, d_target_bps, n, enc_hb_joint(b), d_count, verdict, st));
+    return 0;
+#else
+    return -1;
+#endif
 }
 
 solo_batch_t* solo_batch_create(int32_t n_streams, const USER_Ctrl_enc* enc, const USER_Ctrl_dec* dec, int32_t slot_bytes) {
@@ -882,7 +905,7 @@ int32_t solo_timescale(solo_batch_t* b, const int16_t* d_pcm_in, int32_t n, int3
     return 0;
 }
 
-// ---- the row-state objects: Resampler, Vad, Agc, Playout ------------------------------------------------------------------------------
+// ---- the row-state objects: Resampler, Vad, Agc, Rate, Playout ------------------------------------------------------------------------------
 // Each sits beside a handle, holds one state record per row, carries it from call to call and derives from solo_rows; what is written
 // here once is their whole lifecycle (solo_rows.h has the kernels).  The entry points keep their own argument checks.
 struct solo_rows {
@@ -1087,6 +1110,51 @@ int32_t solo_agc(solo_agc_t* g, const int32_t* d_rows, int32_t n, const int16_t*
     a.n = n; a.n_packets = n_packets; a.packet_samples = packet_samples; a.frames = d_sa_q8 ? frames : 0; a.prm = *params;
     SOLO_CHECK(launch_list_check(d_rows, n, g->n_rows, g->d_verdict, NULL, st));
     SOLO_CHECK(solo_agc_launch(a, d_count, g->d_acc, g->d_verdict, st));
+    return 0;
+}
+
+// ---- the sender's rate controller (solo_rate.h): an object of its own, with a state record per row; the send mask is stateless ---------
+static_assert(SOLO_RATE_STATE_BYTES == SX_RATE_STATE_WORDS * 4 && SX_RATE_STATE_WORDS <= SX_ROWS_MAX_WORDS, "include/solo_mi355x.h, solo_rate.h and solo_rows.h agree");
+struct solo_rate_obj : solo_rows {};
+solo_rate_t* solo_rate_create(int32_t n_rows) {
+    if (n_rows <= 0 || (int64_t)n_rows * SX_RATE_STATE_WORDS >= ((int64_t)1 << 31) || !have_device()) return NULL;
+    solo_rate_obj* rc = new (std::nothrow) solo_rate_obj();
+    if (!rc) return NULL;
+    if (!rows_alloc(rc, n_rows, SX_RATE_STATE_WORDS, sx_rate_init_word, 1, 0)) {
+        solo_rate_destroy(rc);
+        return NULL;
+    }
+    return rc;
+}
+void solo_rate_destroy(solo_rate_t* rc) {
+    if (!rc) return;
+    rows_free(rc);
+    delete rc;
+}
+int32_t solo_rate_reset(solo_rate_t* rc, void* hip_stream) { return rows_reset(rc, (hipStream_t)hip_stream); }
+int32_t solo_rate_reset_rows(solo_rate_t* rc, const int32_t* h_rows, int32_t n, void* hip_stream) { return rows_reset_list(rc, h_rows, n, (hipStream_t)hip_stream); }
+int32_t solo_rate_get_state(solo_rate_t* rc, const int32_t* d_rows, int32_t n, uint8_t* d_blob, void* hip_stream) {
+    return rows_copy_state(rc, d_rows, n, d_blob, 0, (hipStream_t)hip_stream);
+}
+int32_t solo_rate_set_state(solo_rate_t* rc, const int32_t* d_rows, int32_t n, const uint8_t* d_blob, void* hip_stream) {
+    return rows_copy_state(rc, d_rows, n, (uint8_t*)d_blob, 1, (hipStream_t)hip_stream);
+}
+int32_t solo_rate_update(solo_rate_t* rc, const solo_rtcp_feedback_t* d_feedback, const solo_rate_params_t* params, int32_t* d_target_bps, uint8_t* d_mode,
+                         solo_rate_count_t* d_count, void* hip_stream) {
+    if (!rc || !sx_rate_update_call_ok(rc->n_rows, d_feedback, params, d_target_bps, d_mode, d_count)) return -1;
+    SxRateArgs a;
+    a.feedback = (const u32*)d_feedback; a.state = rc->d_state; a.target = d_target_bps; a.mode = d_mode; a.count = (i32*)d_count;
+    a.p = *params; a.n_rows = rc->n_rows;
+    SOLO_CHECK(solo_rate_update_launch(a, (hipStream_t)hip_stream));
+    return 0;
+}
+int32_t solo_rate_send_mask(const uint8_t* d_mode, int32_t n_rows, const int32_t* d_streams, int32_t n, int32_t n_packets, const int32_t* d_seq_base,
+                            int32_t first_seq, const uint8_t* d_send_in, uint8_t* d_send, void* hip_stream) {
+    if (!sx_rate_mask_call_ok(d_mode, n_rows, d_streams, n, n_packets, d_seq_base, d_send)) return -1;
+    SxRateMaskArgs a;
+    a.mode = d_mode; a.map = d_streams; a.seq_base = d_seq_base; a.send_in = d_send_in; a.send = d_send;
+    a.n_rows = n_rows; a.n = n; a.n_packets = n_packets; a.first_seq = first_seq;
+    SOLO_CHECK(solo_rate_send_mask_launch(a, (hipStream_t)hip_stream));
     return 0;
 }
 

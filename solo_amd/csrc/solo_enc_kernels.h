@@ -5,8 +5,9 @@
 #include <hip/hip_runtime.h>
 #include "solo_enc.h"
 #include "solo_stream_ctl.h"
+#include "../../include/solo_mi355x.h"      // solo_rate_apply_count_t
 
-#ifndef SX_TU_FRONT       // (the front kernel lives in a translation unit of its own, solo_enc_front_k.hip: see there)
+#ifndef SX_TU_FRONT      // (the front kernel lives in a translation unit of its own, solo_enc_front_k.hip: see there)
 __global__ void __launch_bounds__(64) SX_K(solo_enc_init_kernel)(SxEncStream* states, int n_streams, int silk_rate_bps, int useMDIndex, int hb_joint, int useDTX, int fpp) {
     const int s = blockIdx.x;
     if (s >= n_streams) return;
@@ -28,6 +29,30 @@ __global__ void __launch_bounds__(64) SX_K(solo_enc_ctl_list_kernel)(SxEncStream
     sx_enc_setup_rate(st, r.a);
     st->useMDIndex = r.b;
     st->useDTX = r.c;
+}
+// solo_batch_update_rates: the same setup_rate with the value read from device memory.  ONE LANE per listed position, 256 a workgroup;
+// position i is stream map[i] (NULL: i) and takes target[i] under sx_enc_apply_target (solo_enc_state.h): useDTX, useMDIndex and every
+// other word stay.  The clear kernel in front leaves {0, 0, 0, n}; the counts go through wg_sum and one atomic instruction per workgroup
+// (lane k adds field k).  A list the check kernel refused: applied = -1, nothing else.
+__global__ void __launch_bounds__(64) SX_K(solo_enc_rate_clear_kernel)(solo_rate_apply_count_t* count, int n) {
+    if (threadIdx.x == 0) { solo_rate_apply_count_t c; c.applied = 0; c.kept = 0; c.refused = 0; c.listed = n; *count = c; }
+}
+__global__ void __launch_bounds__(256) SX_K(solo_enc_rate_list_kernel)(SxEncStream* states, const i32* __restrict__ map, const i32* __restrict__ target, int n,
+                                                                        int hb_joint, solo_rate_apply_count_t* count, const u32* verdict) {
+    __shared__ i32 red[4];
+    if (sx_map_refused(map, verdict)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) count->applied = -1;
+        return;
+    }
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    int r = -1;
+    if (i < n) r = sx_enc_apply_target(&states[map ? map[i] : i].core, target[i], hb_joint, SX_ENC_MIN_SILK_BPS);
+    const i32 applied = wg_sum(r == SX_RATE_APPLIED ? 1 : 0, red), kept = wg_sum(r == SX_RATE_KEPT ? 1 : 0, red),
+              refused = wg_sum(r == SX_RATE_REFUSED ? 1 : 0, red);
+    if (threadIdx.x < 3) {
+        const i32 v = threadIdx.x == 0 ? applied : (threadIdx.x == 1 ? kept : refused);
+        if (v) atomicAdd(&count->applied + threadIdx.x, v);
+    }
 }
 
 // Encoder, rows E0-E9, over HBM hand-over records.  Two schedules of the same stage functions (solo_api.hip picks one per call):
@@ -443,6 +468,13 @@ static hipError_t SX_K(solo_enc_launch_init_list)(void* states, const SxStreamCt
 static hipError_t SX_K(solo_enc_launch_ctl_list)(void* states, const SxStreamCtl* recs, int n, hipStream_t s) {
     return sx_launch_ctl_batches(recs, n, [&](const SxStreamCtlList& l, int k) { hipLaunchKernelGGL(SX_K(solo_enc_ctl_list_kernel), dim3(k), dim3(64), 0, s, (SxEncStream*)states, l, k); });
 }
+static hipError_t SX_K(solo_enc_launch_rate_list)(void* states, const int32_t* map, const int32_t* target_bps, int n, int hb_joint,
+                                                  solo_rate_apply_count_t* count, const uint32_t* verdict, hipStream_t s) {
+    hipLaunchKernelGGL(SX_K(solo_enc_rate_clear_kernel), dim3(1), dim3(64), 0, s, count, n);
+    hipLaunchKernelGGL(SX_K(solo_enc_rate_list_kernel), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (SxEncStream*)states, map, target_bps, n, hb_joint, count,
+                       verdict);
+    return hipGetLastError();
+}
 static hipError_t SX_K(solo_enc_launch_analysis)(void* states, const int16_t* pcm, int n_streams, int n_packets, int p0, int pc, void* nsq_in,
                                                  void* code_in, const int32_t* map, const uint32_t* verdict, hipStream_t s) {
     hipLaunchKernelGGL(SX_K(solo_enc_analysis_kernel), dim3(n_streams), dim3(64), 0, s, (SxEncStream*)states, pcm, n_streams, n_packets, p0, pc,
@@ -523,6 +555,7 @@ static const solo_enc_ops SX_K(solo_enc_ops_table) = {
     sizeof(SxEncStream), sizeof(SxNsqIn), sizeof(SxNsqOut), sizeof(SxCodeIn), SX_PACKET,
     SX_K(solo_enc_launch_init), SX_K(solo_enc_launch_init_list), SX_K(solo_enc_launch_ctl_list), SX_K(solo_enc_launch_analysis), SX_K(solo_launch_nsq), SX_K(solo_enc_launch_coding), SX_K(solo_enc_rc_scratch_bytes),
     SX_K(solo_nsq_workgroups), SX_K(solo_nsq_ring_bytes), SX_K(solo_enc_launch_front), SX_K(solo_launch_nsq_persist), SX_K(solo_enc_front_scratch_bytes), SX_K(solo_nsq_persist_workgroups), SX_K(solo_nsq_stage_bytes),
-    SX_FRONT_WAVES, SX_FRONT_PER_CU, SX_K(solo_enc_launch_hb), SX_K(solo_enc_launch_rc_batch), SX_RC_LANES / 2};
+    SX_FRONT_WAVES, SX_FRONT_PER_CU, SX_K(solo_enc_launch_hb), SX_K(solo_enc_launch_rc_batch), SX_RC_LANES / 2,
+    SX_K(solo_enc_launch_rate_list)};
 
 #endif

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "solo_stream_ctl.h"
+#include "../../include/solo_mi355x.h"      // solo_rate_apply_count_t
 #ifndef SOLO_ENC_OPS_DEFINED
 #define SOLO_ENC_OPS_DEFINED
 struct solo_enc_ops {
@@ -46,5 +47,10 @@ struct solo_enc_ops {
     hipError_t (*rc_batch)(void* states, const void* code_in, const void* nsq_out, int n_streams, int n_packets, int pb, int kb, int kb_cap, int cp, int slot,
                            uint8_t* bits, int16_t* nbytes, int32_t* status, void* rc_scratch, const int32_t* map, const uint32_t* verdict, hipStream_t s);
     int rc_batch_max;                                                    // packets one rc_batch launch takes at most (a stream's lanes share a wavefront)
+    // ---- solo_batch_update_rates: the rate of RUNNING streams from DEVICE memory (solo_enc_kernels.h: solo_enc_rate_list_kernel) ----
+    // position i: stream map[i] (NULL: i) takes target_bps[i] under sx_enc_apply_target; nothing else of the state changes.  count: what
+    // the n positions came to; a refused list (verdict) leaves applied = -1 and touches nothing
+    hipError_t (*rate_list)(void* states, const int32_t* map, const int32_t* target_bps, int n, int hb_joint, solo_rate_apply_count_t* count,
+                            const uint32_t* verdict, hipStream_t s);
 };
 #endif

@@ -175,6 +175,23 @@ SX_HD void sx_enc_setup_rate(SxEncState* st, i32 silk_rate_bps) {
     }
 }
 
+// solo_batch_update_rates (solo_enc_rate_list_kernel): one value of d_target_bps on a running stream.  <= 0 keeps the stream as it is;
+// a positive value is the targetRate_bps of solo_batch_update_streams on the same handle -- minus the high-band share (1600, or 800
+// with the 40 ms high-band frame of joint_mode 1), then setup_rate, which clamps to [5000, 100000]; nothing else of the state is
+// written.  min_silk_bps: the SILK rate below which the build does not code (14000 at the 32 kHz API rate, where the reference
+// switches to an internal rate that is not built; 0: no floor): such a value is refused and the stream stays as it is.
+#define SX_RATE_KEPT 0
+#define SX_RATE_APPLIED 1
+#define SX_RATE_REFUSED 2
+#define SX_ENC_MIN_SILK_BPS (SX_FS_KHZ == 16 ? 14000 : 0)
+SX_HD int sx_enc_apply_target(SxEncState* st, i32 target_bps, i32 hb_joint, i32 min_silk_bps) {
+    if (target_bps <= 0) return SX_RATE_KEPT;
+    const i32 silk_rate_bps = target_bps - (hb_joint ? 800 : 1600);
+    if (min_silk_bps > 0 && silk_rate_bps < min_silk_bps) return SX_RATE_REFUSED;
+    sx_enc_setup_rate(st, silk_rate_bps);
+    return SX_RATE_APPLIED;
+}
+
 // SKP_Silk_init_encoder_FIX (SKP_Silk_init_encoder_FIX.c:33) + the first SKP_Silk_control_encoder_FIX
 // pass (control_codec_FIX.c:56-130: setup_fs(8), setup_rate, ...) + AGR_Sate_Encoder_Init
 // (libBWE/AGR_BWE_SDK_API.c:11-126).  `silk_rate_bps` = targetRate_bps - 1600.
